@@ -17,7 +17,16 @@ Inputs are resident in HBM before the timed region.
 Scaling (``--scaling``): ``strong`` (default, what BASELINE config C4 names: the SAME global batch
 of 256 windows sharded by rows over the ranks) or ``weak`` (256 windows per rank).
 
-Objects on the JSON line beside the contract fields:
+A plain run does only what the headline needs: set-up, ``--warmup`` steps, ``--steps`` timed steps, the outputs of the
+last timed step if ``--dump-outputs DIR`` is given, and one JSON line with the contract fields (``metric``, ``value``,
+``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step``, ...) and ``config``.  Everything else - the objects listed
+below, the first step's loss against the committed value, the replica checks and the exchange timing of a data-parallel
+run - is measured only under ``--full``; ``--no-cpu-baseline``, ``--no-kernel-timers``, ``--timer-steps`` and
+``--no-extras`` trim that full run.
+
+``--dump-outputs DIR`` writes, after the timed steps, what the timed path computed in its last step (dump_outputs).
+
+Objects on the JSON line of a ``--full`` run beside the contract fields:
   roofline     the dominant kernel family of the step (largest total time; one rocprofv3 kernel name
                covers its conv2 and conv3 launches).  ``achieved`` = MFMA FLOPs the kernel ISSUES per
                launch (the Winograd forms need 1/2 or 2/3 of the direct convolution's multiplies) /
@@ -53,6 +62,7 @@ import statistics
 import subprocess
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -93,7 +103,16 @@ def parse_args(argv=None):
     ap.add_argument("--model", choices=["full", "lite"], default="full",
                     help="full = SynthesisModelCNN (headline, C3); lite = SynthesisLite (use --channels 32 "
                          "--timepoints 200 --batch 64 for BASELINE config C2)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: CPU baseline, per-kernel roofline timers, "
+                         "C2 / C5 / signal sub-results, first-step loss against the committed value, data-parallel replica "
+                         "checks and exchange timing (off: set-up, warm-up, the timed steps and the result line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------
@@ -647,6 +666,55 @@ def step0_record(step0, args, C, T, GB, drop):
     return rec
 
 
+DUMP_CAP = 1 << 20           # elements: a larger array is dumped as a fixed, seeded sample of this many
+DUMP_LIMIT = 64 << 20        # bytes of all dumped arrays together
+
+
+def dump_sample(name: str, t):
+    """``t`` as a float32 array, or - above DUMP_CAP elements - DUMP_CAP of its elements (flattened) at sorted positions drawn
+    from a seed fixed by ``name``: the same positions in every run of the same shapes."""
+    import numpy as np
+    import torch
+    t = t.detach().float()
+    if t.numel() <= DUMP_CAP:
+        return t.cpu().numpy()
+    idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(t.numel(), DUMP_CAP, replace=False))
+    return t.reshape(-1)[torch.from_numpy(idx).to(t.device)].cpu().numpy()
+
+
+def dump_outputs(out_dir: str, trainer, model, GB: int, rank: int, world: int) -> None:
+    """--dump-outputs: what the timed path hands its caller after its last step, one ``.npy`` file per array in ``out_dir``:
+      out.npy             the model output of the last step, global batch x mel bins (float32; computed before that step's update)
+      loss_mcd.npy        L1 loss and MCD of the last step over its global batch (float64)
+      param.<name>.npy    every parameter of the synthesis model after the last update (float32; dump_sample above DUMP_CAP)
+    Data parallel: every rank takes part (the row-sharded W_hh is re-assembled, the output rows gathered), rank 0 writes."""
+    import numpy as np
+    import torch
+    from decode_tonal_langauge_amd import parallel
+    trainer.sync_parameters()
+    out = trainer._last_out.detach().float()
+    stats = trainer._stats[2:4].detach().double()
+    if world > 1:
+        stats = parallel.all_reduce_(stats.clone())        # per-rank statistics carry their weight in the global mean
+        rows = [len(range(*parallel.shard_rows(GB, r, world).indices(GB))) for r in range(world)]
+        mine = torch.zeros(max(rows), out.shape[1], dtype=out.dtype, device=out.device)
+        mine[:out.shape[0]] = out
+        every = torch.empty((world,) + tuple(mine.shape), dtype=out.dtype, device=out.device)
+        parallel.all_gather_blocks(every, mine)
+        out = torch.cat([every[r, :n] for r, n in enumerate(rows)])
+    if rank != 0:
+        return
+    arrays = {"out": dump_sample("out", out), "loss_mcd": stats.cpu().numpy()}
+    for name, p in model.named_parameters():
+        arrays[f"param.{name}"] = dump_sample(name, p)
+    nbytes = sum(a.nbytes for a in arrays.values())
+    if nbytes > DUMP_LIMIT:
+        raise SystemExit(f"bench.py: --dump-outputs would write {nbytes / 2 ** 20:.1f} MB, more than {DUMP_LIMIT >> 20} MB")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 # ------------------------------------------------------------------------------------------------
 def main():
     args = parse_args()
@@ -709,7 +777,7 @@ def main():
         parallel.broadcast_parameters_(trainer.syllable_model, src=0)
     eng = model._engine
     dp_check = None
-    if world > 1:
+    if world > 1 and args.full:
         # every rank must start from the same bits (model AND classifiers), whichever way they were initialised
         spread0 = replica_spread([model, trainer.tone_model, trainer.syllable_model], parallel, dist)
         dp_check = {"init_checksum_spread": spread0}
@@ -739,19 +807,19 @@ def main():
     lstm_mode = None
     for i in range(args.warmup):
         trainer.train_step(*data[i % nb])
-        if i == 0:
+        if i == 0 and args.full:
             # loss / MCD of the first step on the seeded first global batch: under strong scaling the same number whatever
             # the rank count (rows sharded, masks hashed by the global element) - checked against the committed 1-GPU value
             s0 = trainer._stats[2:4].detach().clone().double()
             if dist.is_initialized():
                 parallel.all_reduce_(s0)               # per-rank statistics carry their weight in the global mean
             step0 = [float(v) for v in s0.tolist()]
-            if world > 1 and args.model == "full":
-                lstm_mode = choose_lstm_mode(trainer, data, args.lstm_shard, sync, parallel, dist, dev)
-    if world > 1:
+        if i == 0 and world > 1 and args.model == "full":
+            lstm_mode = choose_lstm_mode(trainer, data, args.lstm_shard, sync, parallel, dist, dev)
+    if world > 1 and args.full:
         trainer.exchange_events = []
         trainer.exchange_wait_events = []
-    state0 = gpu_state(local if world > 1 else 0)
+    state0 = gpu_state(local if world > 1 else 0) if args.full else None
     sync()
     # ---- the timed region: exactly args.steps train steps, nothing else (no per-kernel instrumentation) ----
     t0 = time.perf_counter()
@@ -759,24 +827,27 @@ def main():
         trainer.train_step(*data[(args.warmup + i) % nb])
     sync()
     dt = time.perf_counter() - t0
-    state1 = gpu_state(local if world > 1 else 0)
+    state1 = gpu_state(local if world > 1 else 0) if args.full else None
     exch_ms = exposed_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         ev = trainer.exchange_events
         trainer.exchange_events = None
         exch_ms = sum(a.elapsed_time(b) for a, b in ev) / max(args.steps, 1)
         wev = getattr(trainer, "exchange_wait_events", None) or []
         trainer.exchange_wait_events = None
         exposed_ms = sum(a.elapsed_time(b) for a, b in wev) / max(args.steps, 1) if wev else None
+    if args.dump_outputs:
+        # before anything below runs further train steps on the model
+        dump_outputs(args.dump_outputs, trainer, model, GB, rank, world)
     # ---- second, UNTIMED pass: per-launch HIP-event timers of the conv kernels (roofline / families) ----
     tsum = {}
-    if not args.no_kernel_timers and args.model == "full":
+    if args.full and not args.no_kernel_timers and args.model == "full":
         eng.enable_timers(True)
         for i in range(max(1, args.timer_steps)):
             trainer.train_step(*data[(args.warmup + args.steps + i) % nb])
         tsum = eng.timer_summary()
         eng.enable_timers(False)
-    if world > 1:
+    if world > 1 and args.full:
         # Self-check of the data-parallel run: after re-assembling the shard-wise updated W_hh every rank must hold the same
         # bits (the replicas see identical reduced gradients and run deterministic kernels) - a spread means the ranks did
         # not stay in lockstep and the throughput above is not that of the single-process computation.
@@ -879,7 +950,7 @@ def main():
                     "frac": round(fl * iss / (ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4),
                     "per_stage_frac": {k: round(v[0] * iss / (v[1] * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4) for k, v in sorted(ops.items())}}}
         extras = {}
-        if world == 1 and args.model == "full" and not args.no_extras:
+        if args.full and world == 1 and args.model == "full" and not args.no_extras:
             for key, fn in (("rank_batch_probe", lambda: rank_batch_probe(trainer, data)),
                             ("c2_lite", lambda: lite_subresult(dev)),
                             ("signal_c5", lambda: signal_subresult(dev, not args.no_cpu_baseline)),
@@ -889,12 +960,12 @@ def main():
                 except Exception as e:      # noqa: BLE001 - a sub-result must not kill the headline line
                     extras[key] = {"error": repr(e)}
         cpu = None
-        if not args.no_cpu_baseline and world == 1:      # the LIVE CPU leg runs on rank 0 of the 1-GPU run only
+        if args.full and not args.no_cpu_baseline and world == 1:      # the LIVE CPU leg runs on rank 0 of the 1-GPU run only
             try:
                 cpu = cpu_baseline(model, args.cpu_batch, C, T, D, budget_s=args.cpu_budget)
             except Exception as e:      # noqa: BLE001 - the baseline leg must not kill the bench line
                 cpu = {"value": None, "error": repr(e)}
-        static256 = cpu_baseline_at_256()
+        static256 = cpu_baseline_at_256() if args.full else None
         if static256 is not None and args.model == "full" and not args.no_cpu_baseline:
             # the same oracle timed ONCE at the metric's own batch on a GPU box's host (static, committed file): carried on every
             # line, multi-GPU ones included (the live leg is skipped there)
@@ -919,18 +990,19 @@ def main():
                        "exchange_ms_per_step": None if exch_ms is None else round(exch_ms, 3),
                        "exchange_exposed_ms_per_step": None if exposed_ms is None else round(exposed_ms, 3),
                        "init": ("broadcast from rank 0" if bcast_init else "drawn on every rank")},
-            "gpu_state": {"before_timed_region": state0, "after_timed_region": state1,
-                          "note": "sysfs pp_dpm_sclk / hwmon power of this rank's card, one read each"},
-            "roofline": roof, "cpu_baseline": cpu,
         }
-        if roof is not None:
-            roof["timers_from"] = f"a second, untimed pass of {max(1, args.timer_steps)} steps (the timed region carries no instrumentation)"
-        line["step0"] = step0_record(step0, args, C, T, GB, drop)
-        if dp_check is not None:
-            dp_check["loss_step0_vs_dp1_golden"] = line["step0"]
-            dp_check["ok"] = dp_check["param_checksum_spread"] == 0.0 and dp_check["init_checksum_spread"] == 0.0
-            line["dp_check"] = dp_check
-        line.update(extras)
+        if args.full:
+            line.update({"gpu_state": {"before_timed_region": state0, "after_timed_region": state1,
+                                       "note": "sysfs pp_dpm_sclk / hwmon power of this rank's card, one read each"},
+                         "roofline": roof, "cpu_baseline": cpu})
+            if roof is not None:
+                roof["timers_from"] = f"a second, untimed pass of {max(1, args.timer_steps)} steps (the timed region carries no instrumentation)"
+            line["step0"] = step0_record(step0, args, C, T, GB, drop)
+            if dp_check is not None:
+                dp_check["loss_step0_vs_dp1_golden"] = line["step0"]
+                dp_check["ok"] = dp_check["param_checksum_spread"] == 0.0 and dp_check["init_checksum_spread"] == 0.0
+                line["dp_check"] = dp_check
+            line.update(extras)
         print(json.dumps(line), flush=True)
     bad = dp_check is not None and not (dp_check.get("param_checksum_spread") == 0.0)
     if dist.is_initialized():

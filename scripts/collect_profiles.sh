@@ -17,7 +17,7 @@ for sec in "$@"; do
     c2)      rocprofv3 --kernel-trace --stats --output-format csv -d $O/c2 -o l -- python3 $R/bench.py --model lite --channels 32 --timepoints 200 --batch 64 --steps 200 --warmup 20 --no-extras > $O/c2_run.log 2>&1 ;;
     c5)      rocprofv3 --kernel-trace --stats --output-format csv -d $O/c5 -o c5 -- python3 $R/scripts/bench_c5.py --train-classifiers --no-stock-compare > $O/c5_run.log 2>&1 ;;
     signal)  rocprofv3 --kernel-trace --stats --output-format csv -d $O/sig -o s -- python3 $R/scripts/bench_signal.py > $O/sig_run.log 2>&1 ;;
-    bench)   python3 $R/bench.py --steps 20 --warmup 5 > $O/bench_line.log 2> $O/bench_line.err ;;
+    bench)   python3 $R/bench.py --steps 20 --warmup 5 --full > $O/bench_line.log 2> $O/bench_line.err ;;
     *) echo "unknown section $sec"; exit 2 ;;
   esac
   echo "section $sec done ($?)"

@@ -20,7 +20,7 @@ out = [f"# Round {int(TAG[1:3])} - C3 train step, 1x MI355X, rocprofv3 --kernel-
        "`rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o r3 -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline "
        "--no-kernel-timers --no-extras`\n",
        f"4 train steps (1 warm-up incl. the one-time zero-fills + 3 timed) of SynthesisModelCNN 128ch x 400t, batch 256, fp32.  Total kernel time "
-       f"{tot/1e6:.1f} ms = {tot/1e6/4:.1f} ms/step under the profiler; the un-profiled default run of the same call (`python bench.py --steps 20 --warmup 5`, "
+       f"{tot/1e6:.1f} ms = {tot/1e6/4:.1f} ms/step under the profiler; the un-profiled full run of the same call (`python bench.py --steps 20 --warmup 5 --full`, "
        f"`{TAG}_c3_bench_line.log`) **{line['ms_per_step']:.1f} ms/step = {line['value']:.0f} mel-frames/s**, `roofline.frac` {roof['frac']:.4f} "
        f"({roof['kernel'][:40]}..., {roof['avg_launch_ms']} ms per launch by HIP events), `step_mfma_issued_frac` {roof['step_mfma_issued_frac']:.4f}; "
        f"`cpu_baseline` {line['cpu_baseline']['value']} mel-frames/s measured live at micro-batch 16 over 5 timed steps on {line['cpu_baseline']['cores']} threads"

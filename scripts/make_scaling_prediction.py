@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """profiles/scaling_prediction.json: the strong-scaling curve the first real `bench.py --gpus N` run should show, from the
-single-GPU `rank_batch_probe` of a default bench line (train-step time at the per-rank batches 128 / 64 / 32, whole LSTM on the
+single-GPU `rank_batch_probe` of a `bench.py --full` line (train-step time at the per-rank batches 128 / 64 / 32, whole LSTM on the
 rank, no exchange) - machine-readable form of DESIGN.md section 7 (review item 9c).  NOTHING here is measured on N > 1 GPUs.
 
     python scripts/make_scaling_prediction.py profiles/r06_c3_bench_line.log

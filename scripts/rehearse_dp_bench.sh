@@ -4,4 +4,4 @@
 # Small shapes; prints the JSON line (parallelism dp2, backend gloo, exchange_ms_per_step).
 set -e
 cd "$(dirname "$0")/.."
-TONAL_BENCH_SHARE_GPU=1 python bench.py --gpus 2 --steps 3 --warmup 1 --batch 16 --channels 16 --timepoints 200 --no-cpu-baseline
+TONAL_BENCH_SHARE_GPU=1 python bench.py --gpus 2 --steps 3 --warmup 1 --batch 16 --channels 16 --timepoints 200 --full --no-cpu-baseline

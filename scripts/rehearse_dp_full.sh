@@ -4,4 +4,4 @@
 # timings are not meaningful (the ranks time-share the device).
 set -e
 cd "$(dirname "$0")/.."
-TONAL_BENCH_SHARE_GPU=1 python bench.py --gpus 2 --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timers
+TONAL_BENCH_SHARE_GPU=1 python bench.py --gpus 2 --steps 2 --warmup 1 --full --no-cpu-baseline --no-kernel-timers

@@ -371,7 +371,7 @@ def test_bench_two_rank_launch_at_the_headline_shape():
     (TONAL_BENCH_SHARE_GPU=1; RCCL refuses two ranks per device): the launcher starts the ranks, the global batch of
     256 is sharded 128 + 128, the exchange step is timed, and rank 0 prints the one JSON line of the contract."""
     import math
-    r, line = _bench({"TONAL_BENCH_SHARE_GPU": "1"}, "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    r, line = _bench({"TONAL_BENCH_SHARE_GPU": "1"}, "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
                      "--no-extras")
     assert r.returncode == 0, r.stderr[-2000:]
     assert line is not None and line["n_gpus"] == 2 and line["steps"] == 2 and line["warmup"] == 1
@@ -406,7 +406,7 @@ def test_bench_under_torch_distributed_run():
     env["TONAL_BENCH_SHARE_GPU"] = "1"
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3", "--master-addr",
                         "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "3", "--steps", "2",
-                        "--warmup", "1", "--batch", "9", "--channels", "8", "--timepoints", "100", "--no-cpu-baseline",
+                        "--warmup", "1", "--batch", "9", "--channels", "8", "--timepoints", "100", "--full", "--no-cpu-baseline",
                         "--no-extras"], env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -45,7 +45,7 @@ def test_g2_lite_forward():
     assert sum(v.numel() for v in p.values()) == 919312
 
 
-def _check_train(kind, gname, B, C, T):
+def _check_train(kind, gname, B, C, T, f64name=None):
     g = np.load(os.path.join(GOLD, gname))
     xs, _t, _s, labs, tg = gi.train_batches(3, B, C, T)
     assert abs(gi.checksum(*xs, *labs, *tg) - float(g["in_checksum"])) < 1e-6 * float(g["in_checksum"])
@@ -72,12 +72,29 @@ def _check_train(kind, gname, B, C, T):
                 else:
                     assert rel(v.numpy().reshape(-1)[::97], g["grad1." + k + "@s97"]) < 1e-4, k
     assert rel(losses, g["losses"]) < 1e-5 and rel(mcds, g["mcds"]) < 1e-5
-    for k, v in p.items():
-        fin = v.numpy()
-        if "final." + k in g:
-            assert gi.update_rel_l2(fin, g["final." + k], init[k]) < 1e-3, k
-        else:
-            assert gi.update_rel_l2(fin.reshape(-1)[::97], g["final." + k + "@s97"], init[k].reshape(-1)[::97]) < 1e-3, k
+    if f64name is None:
+        for k, v in p.items():
+            fin = v.numpy()
+            if "final." + k in g:
+                assert gi.update_rel_l2(fin, g["final." + k], init[k]) < 1e-3, k
+            else:
+                assert gi.update_rel_l2(fin.reshape(-1)[::97], g["final." + k + "@s97"], init[k].reshape(-1)[::97]) < 1e-3, k
+    else:
+        # G4's conv biases with cancelling fp32 gradient sums: their fp32 three-step update moves by up to 3e-3 with the
+        # summation order of the host (oracle/make_golden_f64.py) - the update is pinned with both sides in float64
+        g64 = np.load(os.path.join(GOLD, f64name))
+        torch.manual_seed(0)
+        p64 = {k: v.double() for k, v in so.init_cnn_params(80, C, T).items()}
+        st64 = so.NAdamState(p64)
+        for s in range(3):
+            so.train_step(kind, p64, None, st64, xs[s].double(), labs[s].double(), tg[s].double())
+        for k, v in p64.items():
+            upd = v.numpy() - init[k]
+            ref = g64["upd." + k] if "upd." + k in g64 else None
+            if ref is None:
+                upd, ref = upd.reshape(-1)[::97], g64["upd." + k + "@s97"]
+            assert upd.shape == ref.shape, k
+            assert np.linalg.norm(upd - ref) / np.linalg.norm(ref) < 1e-6, k
     return b, g
 
 
@@ -89,7 +106,7 @@ def test_g3_lite_train_steps():
 
 
 def test_g4_cnn_train_steps():
-    _check_train("cnn", "g4_cnn_train.npz", 8, 16, 200)
+    _check_train("cnn", "g4_cnn_train.npz", 8, 16, 200, f64name="g4f64_cnn_update.npz")
 
 
 def test_g5_tone_dynamics():
