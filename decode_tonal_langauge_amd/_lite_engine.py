@@ -24,6 +24,12 @@ class LiteEngine:
             raise ValueError("the MI355X path needs negative_slope >= 0")
         if label_dim > 8:
             raise ValueError("label_dim > 8 is not supported by the LSTM input-gradient kernel")
+        # the direct conv kernels stage a 64-sample time tile plus the k - 1 halo of every input channel (forward) / output
+        # channel (input gradient) in 64 KB of LDS (csrc/tonal_lite.hip): refuse here, before any launch
+        if n_channels * (64 + 4) * 4 > 64 * 1024:
+            raise ValueError(f"n_channels = {n_channels}: at most 240 ECoG channels fit the conv kernel's LDS tile")
+        if conv_channels * (64 + 2) * 4 > 64 * 1024:
+            raise ValueError(f"conv_channels = {conv_channels}: at most 248 fit the conv kernel's LDS tile")
         self.seed_dev = None          # set by the trainer's HIP-graph mode: dropout seed (int64 tensor) in device memory
         self.lib = _lib.load()
         self.out_dim, self.C, self.T, self.in_dim = output_dim, n_channels, n_timepoints, label_dim
@@ -95,7 +101,7 @@ class LiteEngine:
                                    ptr(part), B, Cn, CC, T, 5, 2, st), "tl_lite_conv_fwd")
         self.m1, self.r1 = torch.empty(CC, **f32), torch.empty(CC, **f32)
         check(lib.tl_lite_bn_finalize(ptr(part), ptr(self.m1), ptr(self.r1), ptr(t["ecog_conv.1.running_mean"]),
-                                      ptr(t["ecog_conv.1.running_var"]), B * nt1, CC, B * T, 0.1, 1e-5, int(training),
+                                      ptr(t["ecog_conv.1.running_var"]), B * nt1, CC, B * T, T, 0.1, 1e-5, int(training),
                                       ptr(t["ecog_conv.1.num_batches_tracked"]), st), "tl_lite_bn_finalize")
         self.y1 = torch.empty(B, CC, T1, **f32)
         check(lib.tl_lite_bn_act_pool_fwd(ptr(self.z1), ptr(self.m1), ptr(self.r1), ptr(t["ecog_conv.1.weight"]),
@@ -108,7 +114,7 @@ class LiteEngine:
                                    ptr(self.z2), ptr(part2), B, CC, CC, T1, 3, 1, st), "tl_lite_conv_fwd")
         self.m2, self.r2 = torch.empty(CC, **f32), torch.empty(CC, **f32)
         check(lib.tl_lite_bn_finalize(ptr(part2), ptr(self.m2), ptr(self.r2), ptr(t["ecog_conv.5.running_mean"]),
-                                      ptr(t["ecog_conv.5.running_var"]), B * nt2, CC, B * T1, 0.1, 1e-5,
+                                      ptr(t["ecog_conv.5.running_var"]), B * nt2, CC, B * T1, T1, 0.1, 1e-5,
                                       int(training), ptr(t["ecog_conv.5.num_batches_tracked"]), st), "tl_lite_bn_finalize")
         y2 = torch.empty(B, CC, T2, **f32)
         check(lib.tl_lite_bn_act_pool_fwd(ptr(self.z2), ptr(self.m2), ptr(self.r2), ptr(t["ecog_conv.5.weight"]),

@@ -12,7 +12,8 @@ namespace tl {
 constexpr int LT = 64;   // time tile of the direct conv kernels
 
 // z[b][o][t] = bias[o] + sum_{i,j} w[o][i][j] * x[b][i][t + j - pad]   (zero padding)
-// part[(b*ntile + tile)][o][0..1] = (sum_t z, sum_t z^2) over the tile
+// part[(b*ntile + tile)][o][0..1] = (sum_t z, sum_t (z - tile mean)^2) over the tile: centred per tile, so that a channel
+// whose mean is many standard deviations (a DC offset on the input) keeps its variance instead of losing it to E[z^2] - m^2
 __global__ __launch_bounds__(512) void lite_conv_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                             const float* __restrict__ bias, float* __restrict__ z,
                                                             float* __restrict__ part, int Cin, int Cout, int T, int k,
@@ -31,12 +32,14 @@ __global__ __launch_bounds__(512) void lite_conv_fwd_kernel(const float* __restr
   const bool ok = t < T;
   auto finish = [&](int o, float acc) {
     if (ok) z[((long long)b * Cout + o) * T + t] = acc;
-    float s1 = ok ? acc : 0.f, s2 = ok ? acc * acc : 0.f;
+    float s1 = ok ? acc : 0.f;
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      s1 += __shfl_down(s1, off);
-      s2 += __shfl_down(s2, off);
-    }
+    for (int off = 32; off > 0; off >>= 1) s1 += __shfl_down(s1, off);
+    s1 = __shfl(s1, 0);
+    const float dev = ok ? acc - s1 / (float)min(LT, T - t0) : 0.f;
+    float s2 = dev * dev;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s2 += __shfl_down(s2, off);
     if (lane == 0 && part) {
       float* pp = part + (((long long)b * gridDim.x + tile) * Cout + o) * 2;
       pp[0] = s1;
@@ -83,29 +86,33 @@ __global__ __launch_bounds__(512) void lite_conv_fwd_kernel(const float* __restr
   }
 }
 
-// mean / rstd from the partial sums (fixed order), running-stat update (momentum, unbiased var)
+// mean / rstd from the per-tile partials (fixed order; Chan's combination of tile sums and centred squares: the tiles of a
+// row hold LT samples, its last one T - (ntile - 1) LT), running-stat update (momentum, unbiased var)
 __global__ __launch_bounds__(64) void lite_bn_finalize_kernel(const float* __restrict__ part, float* __restrict__ mean,
                                                               float* __restrict__ rstd, float* __restrict__ run_mean,
                                                               float* __restrict__ run_var, int nparts, int C, long long count,
-                                                              float momentum, float eps, int training,
+                                                              int T, float momentum, float eps, int training,
                                                               long long* __restrict__ tracked) {
   const int c = blockIdx.x;                      // one wave per channel, lanes stride over the partials
   const int lane = threadIdx.x;
+  const int ntile = (T + LT - 1) / LT;
   if (training && tracked != nullptr && c == 0 && lane == 0) tracked[0] += 1;     // BatchNorm's num_batches_tracked
   if (training) {
-    double s1 = 0.0, s2 = 0.0;
+    double s1 = 0.0;
+    for (int i = lane; i < nparts; i += 64) s1 += part[((long long)i * C + c) * 2];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s1 += __shfl_down(s1, o);
+    const double m = __shfl(s1, 0) / (double)count;
+    double s2 = 0.0;                             // sum of squares about m: within-tile + between-tile parts
     for (int i = lane; i < nparts; i += 64) {
-      s1 += part[((long long)i * C + c) * 2];
-      s2 += part[((long long)i * C + c) * 2 + 1];
+      const double n = (double)min(LT, T - (i % ntile) * LT);
+      const double d = (double)part[((long long)i * C + c) * 2] - n * m;
+      s2 += (double)part[((long long)i * C + c) * 2 + 1] + d * d / n;
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      s1 += __shfl_down(s1, o);
-      s2 += __shfl_down(s2, o);
-    }
+    for (int o = 32; o > 0; o >>= 1) s2 += __shfl_down(s2, o);
     if (lane == 0) {
-      const double m = s1 / (double)count;
-      double var = s2 / (double)count - m * m;
+      double var = s2 / (double)count;
       if (var < 0.0) var = 0.0;
       mean[c] = (float)m;
       rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
@@ -524,10 +531,13 @@ extern "C" int tl_lite_conv_fwd(const float* x, const float* w, const float* bia
   return check_launch("lite_conv_fwd");
 }
 extern "C" int tl_lite_bn_finalize(const float* part, float* mean, float* rstd, float* run_mean, float* run_var,
-                                   int nparts, int C, int64_t count, float momentum, float eps, int training, int64_t* tracked, void* stream) {
+                                   int nparts, int C, int64_t count, int T, float momentum, float eps, int training,
+                                   int64_t* tracked, void* stream) {
   TL_REQUIRE(mean && rstd && run_mean && run_var && C > 0 && (part || !training), "lite_bn_finalize: bad arguments");
+  TL_REQUIRE(!training || (T > 0 && nparts % ((T + LT - 1) / LT) == 0 && count == (int64_t)(nparts / ((T + LT - 1) / LT)) * T),
+             "lite_bn_finalize: partials do not match (rows, T)");
   hipLaunchKernelGGL(lite_bn_finalize_kernel, dim3(C), dim3(64), 0, (hipStream_t)stream, part, mean, rstd,
-                     run_mean, run_var, nparts, C, (long long)count, momentum, eps, training, (long long*)tracked);
+                     run_mean, run_var, nparts, C, (long long)count, T, momentum, eps, training, (long long*)tracked);
   return check_launch("lite_bn_finalize");
 }
 extern "C" int tl_lite_bn_act_pool_fwd(const float* z, const float* mean, const float* rstd, const float* gamma,

@@ -407,13 +407,14 @@ int tl_labels_from_scores(const float* tone_scores, const float* syl_scores, con
 
 /* ---- SynthesisLite blocks (models/synthesis_models.py:236-263,265-296) ----------------------
  * x (B,Cin,T) channels-first like the reference's Conv1d; 'same' padding (2*pad == k-1).       */
-/* z = conv1d(x,w)+bias; part[(b*ntile+tile)][Cout][2] = per-tile (sum z, sum z^2), ntile=ceil(T/64) */
+/* z = conv1d(x,w)+bias; part[(b*ntile+tile)][Cout][2] = per-tile (sum z, sum (z - tile mean)^2),
+ * ntile=ceil(T/64); Cin * (64 + k - 1) floats must fit 64 KB of LDS                            */
 int tl_lite_conv_fwd(const float* x, const float* w, const float* bias, float* z, float* part,
                      int B, int Cin, int Cout, int T, int k, int pad, void* stream);
 /* BatchNorm1d statistics: training -> batch mean / rstd from `part` (+ running-stat update,
  * unbiased variance); eval -> from the running buffers                                        */
 int tl_lite_bn_finalize(const float* part, float* mean, float* rstd, float* run_mean, float* run_var,
-                        int nparts, int C, int64_t count, float momentum, float eps, int training,
+                        int nparts, int C, int64_t count /* = rows * T */, int T, float momentum, float eps, int training,
                         int64_t* tracked /* optional: BatchNorm's num_batches_tracked, += 1 in training */, void* stream);
 /* y (B,C,T/2) = MaxPool1d(2)(LeakyReLU(BN(z)))                                                 */
 int tl_lite_bn_act_pool_fwd(const float* z, const float* mean, const float* rstd, const float* gamma,

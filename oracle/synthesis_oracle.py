@@ -163,10 +163,20 @@ def own_decisions(z: torch.Tensor, pool: bool) -> Dict[str, torch.Tensor]:
     return {"pos": torch.maximum(a, b) > 0, "odd": b > a}
 
 
+def own_margins(z: torch.Tensor, pool: bool) -> Dict[str, torch.Tensor]:
+    """How far the decisions of ``own_decisions`` are from flipping, in their layout: ``pos`` |z| (|max(a, b)| for a pooled
+    stage), ``odd`` |b - a|."""
+    if not pool:
+        return {"pos": z.abs()}
+    n = z.shape[2] // 2
+    a, b = z[:, :, 0:2 * n:2], z[:, :, 1:2 * n:2]
+    return {"pos": torch.maximum(a, b).abs(), "odd": (b - a).abs()}
+
+
 def cnn_forward(p: Dict[str, torch.Tensor], inputs_ecog: torch.Tensor, inputs_labels: torch.Tensor,
                 dropout_mask: Optional[torch.Tensor] = None, negative_slope: float = 0.01,
                 return_intermediates: bool = False, decisions: Optional[Dict[str, torch.Tensor]] = None,
-                own: Optional[Dict[str, torch.Tensor]] = None):
+                own: Optional[Dict[str, torch.Tensor]] = None, margins: Optional[dict] = None):
     """``SynthesisModelCNN.forward`` (models/synthesis_models.py:137-176).
 
     ``dropout_mask`` (B, conv_channels, latent, C) holds the already scaled keep mask
@@ -175,7 +185,9 @@ def cnn_forward(p: Dict[str, torch.Tensor], inputs_ecog: torch.Tensor, inputs_la
     ``decisions`` (test infrastructure): ``{"ecog<i>.pos", "ecog<i>.odd" (i = 1..4), "ecog5.pos", "concat<i>.pos"}`` bool
     tensors in the layout of the activation they belong to - the LeakyReLU' / arg-max branches the BACKWARD pass takes
     (``_ActPoolDecided``); forward values are unchanged.  Layers without an entry decide for themselves.  ``own``: a dict
-    that receives the decisions this forward pass would take by itself (for counting how many differ).
+    that receives the decisions this forward pass would take by itself (for counting how many differ).  ``margins``: a dict
+    that receives, under the same keys and in the same layout, how far this pass's own pre-activations are from flipping
+    each decision (``own_margins``), plus ``"<layer>.scale"`` = max |z| of that layer (a float): tests/branch_planes.py.
     """
     B, C, T = inputs_ecog.shape
     x = inputs_ecog.unsqueeze(1).permute(0, 1, 3, 2)        # (B, 1, T, C)  :157-158
@@ -187,6 +199,11 @@ def cnn_forward(p: Dict[str, torch.Tensor], inputs_ecog: torch.Tensor, inputs_la
             with torch.no_grad():
                 for k, v in own_decisions(z, pool).items():
                     own[f"{key}.{k}"] = v
+        if margins is not None:
+            with torch.no_grad():
+                for k, v in own_margins(z, pool).items():
+                    margins[f"{key}.{k}"] = v
+                margins[f"{key}.scale"] = float(z.abs().max())
         if f"{key}.pos" in dec:
             return _ActPoolDecided.apply(z, slope, dec[f"{key}.pos"], dec[f"{key}.odd"] if pool else None)
         y = F.leaky_relu(z, slope)

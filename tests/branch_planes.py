@@ -5,7 +5,8 @@ pre-activations agree to 2e-6 still take a handful of those branches differently
 conv-stack gradient by O(1) of one element: 1e-3 relative L2 at batch 2.  ``hip_decisions`` reads the branches the HIP path
 took (1-bit planes of the pooling epilogues, the sign of the stored stage-5 / 1x1-stack outputs); handed to
 ``oracle.synthesis_oracle.cnn_forward(decisions=...)`` they make the oracle's backward take the same ones, so that what is
-left between the two gradients is arithmetic (held to a few 1e-6)."""
+left between the two gradients is arithmetic (held to a few 1e-6).  Shared branches would also hide a wrong plane, so the planes
+are not trusted: ``check_flips`` holds them to the oracle's own decisions and their margins."""
 import torch
 
 
@@ -41,3 +42,34 @@ def hip_decisions(eng, B: int, Cn: int) -> dict:
 def count_differing(dec: dict, own: dict):
     """({plane: branches that differ}, {plane: branches})"""
     return ({k: int((dec[k] != own[k]).sum()) for k in sorted(dec)}, {k: int(dec[k].numel()) for k in sorted(dec)})
+
+
+def check_flips(dec: dict, own: dict, margins: dict, tau: float = 1e-4, max_frac: float = 1e-4, slack: int = 4) -> dict:
+    """The planes ``dec`` (``hip_decisions``) checked against the oracle's own decisions ``own`` and their ``margins``
+    (``cnn_forward(own=, margins=)``) instead of trusted: HIP and oracle pre-activations agree to about 1e-6 relative, so a
+    branch may only differ where the oracle's own pre-activations were within ``tau * scale`` of flipping it (a near-tie),
+    and only a few may differ at all (``max_frac`` of a plane's branches plus ``slack``).  A plane written with the wrong
+    channel, row, word or a stale tile flips about half its bits at O(1) margins.  Returns {plane: (branches that differ,
+    largest margin among them / scale)}; raises AssertionError if a plane breaks either rule."""
+    out = {}
+    for k in sorted(dec):
+        d, o = dec[k].cpu(), own[k].cpu()
+        assert d.shape == o.shape, (k, tuple(d.shape), tuple(o.shape))
+        m = margins[k].cpu()
+        scale = max(float(margins[k.rsplit(".", 1)[0] + ".scale"]), 1e-30)
+        diff = d != o
+        n = int(diff.sum())
+        worst = float(m[diff].max()) / scale if n else 0.0
+        out[k] = (n, worst)
+        assert worst <= tau, f"{k}: a branch that differs from the oracle's sits {worst:.2e} x max|z| from a tie (> {tau:g})"
+        assert n <= max_frac * d.numel() + slack, f"{k}: {n} of {d.numel()} branches differ from the oracle's"
+    return out
+
+
+def flip_record(flips: dict) -> dict:
+    """``check_flips``' result as flat numbers for tests/parity_record.py."""
+    rec = {}
+    for k, (n, worst) in flips.items():
+        rec["differ." + k] = n
+        rec["worst_margin." + k] = worst
+    return rec

@@ -22,7 +22,7 @@ import pytest
 import torch
 
 from tests import golden_inputs as gi
-from tests.branch_planes import count_differing, hip_decisions
+from tests.branch_planes import check_flips, count_differing, flip_record, hip_decisions
 from tests.parity_record import record
 from tests.test_gpu_parity import rel, rel_l2, _trainer
 
@@ -217,8 +217,9 @@ def test_c3_gradients_match_the_oracle_given_the_same_branches(dev, c3):
     dec = hip_decisions(eng, B, Cn)
     # ---- the oracle on the reference's parameters (host copy of the seeded state), its backward on the HIP path's branches ----
     leaves = {k: _INIT["state"][k].clone().requires_grad_(True) for k, _ in model.named_parameters()}
-    own = {}
-    ref = so.cnn_forward(leaves, x, lab, decisions=dec, own=own)
+    own, margins = {}, {}
+    ref = so.cnn_forward(leaves, x, lab, decisions=dec, own=own, margins=margins)
+    flips = check_flips(dec, own, margins)                          # every differing branch is a near-tie of the oracle's
     ref_loss = so.l1_loss(ref, tgt.long())
     ref_grads = dict(zip(leaves, torch.autograd.grad(ref_loss, list(leaves.values()))))
     obs = {"loss": abs(float(tr._stats[2]) - float(ref_loss)) / float(ref_loss)}
@@ -239,7 +240,7 @@ def test_c3_gradients_match_the_oracle_given_the_same_branches(dev, c3):
     print("gradients against the oracle on shared branches: worst", f"{worst:.2e}", "branches that differ from the oracle's own:",
           {k: v for k, v in differ.items() if v})
     record("G11 gradients, oracle backward on the HIP path's sign / arg-max planes",
-           dict(obs, **{"differ." + k: v for k, v in differ.items()}, **{"of." + k: v for k, v in total.items()}))
+           dict(obs, **flip_record(flips), **{"of." + k: v for k, v in total.items()}))
     for k, v in obs.items():
         assert v < 2e-5, (k, v)
     # near-ties only: a handful of branches out of 10^8
@@ -557,7 +558,9 @@ def test_train_mode_dropout_mask_forward_and_gradients_against_oracle(dev):
     assert eng._seed_used != seed and not torch.equal(read_mask(eng._seed_used), mask)
     # oracle with the HIP-generated mask
     leaves = {k: v.clone().requires_grad_(True) for k, v in params.items()}
-    ref = so.cnn_forward(leaves, xs[0], labs[0], dropout_mask=mask.cpu(), decisions=dec)
+    own, margins = {}, {}
+    ref = so.cnn_forward(leaves, xs[0], labs[0], dropout_mask=mask.cpu(), decisions=dec, own=own, margins=margins)
+    record("decided branches: train-mode dropout, 6x8x200", flip_record(check_flips(dec, own, margins)))
     ref_loss = so.l1_loss(ref, tg[0].long())
     ref_grads = dict(zip(leaves, torch.autograd.grad(ref_loss, list(leaves.values()))))
     assert rel(out.detach().cpu().numpy(), ref.detach().numpy()) < 1e-4

@@ -12,7 +12,8 @@ import pytest
 import torch
 
 from tests import golden_inputs as gi
-from tests.branch_planes import hip_decisions
+from tests.branch_planes import check_flips, flip_record, hip_decisions
+from tests.parity_record import record
 
 pytestmark = pytest.mark.gpu
 
@@ -137,7 +138,10 @@ def test_cnn_autograd_path_equals_fused_path(dev):
     loss.backward()
     leaves = {k: v.clone().requires_grad_(True) for k, v in params.items()}
     # (the oracle's backward takes the LeakyReLU' / arg-max branches the HIP path took: tests/branch_planes.py)
-    ref = so.cnn_forward(leaves, xs[0], labs[0], decisions=hip_decisions(model._engine, 5, 4))
+    dec, own, margins = hip_decisions(model._engine, 5, 4), {}, {}
+    ref = so.cnn_forward(leaves, xs[0], labs[0], decisions=dec, own=own, margins=margins)
+    flips = check_flips(dec, own, margins)               # the planes are checked against the oracle's, not trusted
+    record("decided branches: autograd path, 5x4x100", flip_record(flips))
     ref_loss = so.l1_loss(ref, tg[0].long())
     ref_grads = dict(zip(leaves, torch.autograd.grad(ref_loss, list(leaves.values()))))
     assert rel(out.detach().cpu().numpy(), ref.detach().numpy()) < 1e-4
@@ -158,7 +162,9 @@ def test_cnn_random_labels_no_dedup(dev):
     out = model(x.to(dev), lab.to(dev))
     out.square().mean().backward()
     leaves = {k: v.clone().requires_grad_(True) for k, v in params.items()}
-    ref = so.cnn_forward(leaves, x, lab, decisions=hip_decisions(model._engine, 70, 8))
+    dec, own, margins = hip_decisions(model._engine, 70, 8), {}, {}
+    ref = so.cnn_forward(leaves, x, lab, decisions=dec, own=own, margins=margins)
+    record("decided branches: random labels, 70x8x60", flip_record(check_flips(dec, own, margins)))
     ref_grads = dict(zip(leaves, torch.autograd.grad(ref.square().mean(), list(leaves.values()))))
     assert rel(out.detach().cpu().numpy(), ref.detach().numpy()) < 1e-4
     for k, p in model.named_parameters():
@@ -447,21 +453,30 @@ def test_trainer_with_deep_classifiers(dev):
     assert syl._drop_calls == s0 + 2 and tone._drop_calls == t0 + 2 and all(np.isfinite(v) for h in hist for v in h)
 
 
-@pytest.mark.parametrize("cfg", [
+EDGE_SHAPES = [
     # (B, C, T, out_dim, lstm_channels, conv_channels, L)
     (1, 4, 100, 80, 6, 64, 5),        # batch of one
     (3, 2, 61, 12, 2, 8, 1),          # L = 1 (no recurrence), odd T, tiny widths
     (5, 6, 77, 7, 2, 10, 4),          # output_dim and conv_channels not multiples of 4
     (9, 3, 130, 33, 4, 20, 3),        # odd channel count, odd output_dim
     (130, 1, 64, 8, 4, 4, 2),         # one ECoG channel, batch > one row tile
-])
-def test_cnn_edge_shapes_against_oracle(dev, cfg):
-    """Ragged / minimal shapes: forward and every parameter gradient against the CPU oracle."""
+]
+
+
+# (the default kernels keep the ids cfg0..cfg4 these cases always had; the other two forms are cfgN-wino4 / cfgN-wino0)
+@pytest.mark.parametrize("cfg,wino", [pytest.param(c, w, id=f"cfg{i}" + ("" if w == "6" else f"-wino{w}"))
+                                      for w in "640" for i, c in enumerate(EDGE_SHAPES)])
+def test_cnn_edge_shapes_against_oracle(dev, cfg, wino, monkeypatch):
+    """Ragged / minimal shapes: forward and every parameter gradient against the CPU oracle, for the default kernels
+    (F(6,3)), the F(4,3) V form and the direct MFMA kernels (TONAL_WINO=6 / 4 / 0).  The oracle's backward takes the HIP
+    path's sign / arg-max branches, and those planes are checked against the oracle's own decisions and margins."""
     from decode_tonal_langauge_amd.models.synthesis_models import SynthesisModelCNN
     from oracle import synthesis_oracle as so
     B, C, T, D, lc, cc, L = cfg
+    monkeypatch.setenv("TONAL_WINO", wino)
     torch.manual_seed(B * 1000 + T)
     model = SynthesisModelCNN(D, C, T, lstm_channels=lc, conv_channels=cc, dropout=0.0)
+    assert model._engine.wino43 == (wino in "46") and (wino == "6" or not model._engine.wino63)
     params = {k: v.detach().clone() for k, v in model.named_parameters()}
     g = torch.Generator().manual_seed(T)
     x = torch.randn(B, C, T, generator=g)
@@ -472,15 +487,23 @@ def test_cnn_edge_shapes_against_oracle(dev, cfg):
     ((out - tgt.to(dev)) ** 2).mean().backward()
     leaves = {k: v.clone().requires_grad_(True) for k, v in params.items()}
     # oracle with the model's widths (its helper assumes the reference's names/shapes only)
-    ref = so.cnn_forward(leaves, x, lab, decisions=hip_decisions(model._engine, B, C))
+    dec, own, margins = hip_decisions(model._engine, B, C), {}, {}
+    ref = so.cnn_forward(leaves, x, lab, decisions=dec, own=own, margins=margins)
+    flips = check_flips(dec, own, margins)
     ref_grads = dict(zip(leaves, torch.autograd.grad(((ref - tgt) ** 2).mean(), list(leaves.values()))))
-    assert rel(out.detach().cpu().numpy(), ref.detach().numpy()) < 1e-4
+    obs = {"out": rel(out.detach().cpu().numpy(), ref.detach().numpy())}
+    for k, p in model.named_parameters():
+        gref = ref_grads[k].numpy()
+        obs["grad." + k] = (float(p.grad.abs().max()) if np.abs(gref).max() < 1e-12
+                            else rel_l2(p.grad.cpu().numpy(), gref))
+    record(f"edge shape {cfg} (TONAL_WINO={wino})", dict(obs, **flip_record(flips)))
+    assert obs["out"] < 1e-4
     for k, p in model.named_parameters():
         gref = ref_grads[k].numpy()
         if np.abs(gref).max() < 1e-12:
-            assert float(p.grad.abs().max()) < 1e-9, k
+            assert obs["grad." + k] < 1e-9, k
         else:                                         # (shared LeakyReLU' / arg-max branches: tests/branch_planes.py)
-            assert rel_l2(p.grad.cpu().numpy(), gref) < 5e-5, k
+            assert obs["grad." + k] < 5e-5, k
 
 
 def test_cnn_rejects_bad_inputs(dev):

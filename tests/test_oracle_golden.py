@@ -1,5 +1,6 @@
 """CPU: the oracle (oracle/*.py) against the committed golden vectors of the real reference."""
 import os
+import re
 from argparse import Namespace
 
 import numpy as np
@@ -377,3 +378,54 @@ def test_decided_backward_is_torchs_own_given_torchs_own_branches():
     for k in g1:
         upstream = k.startswith("ecog_conv_block.") and int(k.split(".")[1]) <= 6
         assert torch.equal(g1[k], g3[k]) != upstream, k
+
+
+def test_flip_checker_rejects_corrupted_planes_and_accepts_a_near_tie():
+    """tests/branch_planes.check_flips (the GPU tests check the HIP path's sign / arg-max planes with it instead of trusting
+    them): the oracle's own planes pass, one flip at the smallest margin passes (a near-tie), and each corruption a pooling
+    epilogue could make - channels shifted by one, one 32-bit word inverted, the last row tile left zero - is rejected."""
+    import pytest
+    from tests.branch_planes import check_flips
+    torch.manual_seed(0)
+    p = so.init_cnn_params(80, 4, 100)
+    x, lab = torch.randn(3, 4, 100), torch.randn(3, 2, 5)
+    own, margins = {}, {}
+    with torch.no_grad():
+        so.cnn_forward(p, x, lab, own=own, margins=margins)
+    assert sorted(k for k in margins if not k.endswith(".scale")) == sorted(own)
+    for k, v in own.items():
+        assert margins[k].shape == v.shape, k
+    flips = check_flips({k: v.clone() for k, v in own.items()}, own, margins)
+    assert all(n == 0 for n, _ in flips.values()), flips
+    # one flip where the oracle's own pre-activations are closest to a tie: what two correct fp32 implementations may differ by
+    rel_min = {k: float(margins[k].min()) / margins[k.rsplit(".", 1)[0] + ".scale"] for k in own}
+    k_tie = min(rel_min, key=rel_min.get)
+    assert rel_min[k_tie] < 1e-6, rel_min                # (else the shape is too small to hold a near-tie)
+    dec = {k: v.clone() for k, v in own.items()}
+    flat = dec[k_tie].view(-1)
+    i = int(margins[k_tie].reshape(-1).argmin())
+    flat[i] = ~flat[i]
+    flips = check_flips(dec, own, margins)
+    assert flips[k_tie][0] == 1 and flips[k_tie][1] == rel_min[k_tie]
+    assert sum(n for n, _ in flips.values()) == 1
+
+    def corrupted(k, fn):
+        dec = {q: v.clone() for q, v in own.items()}
+        dec[k] = fn(dec[k].clone())
+        assert not torch.equal(dec[k], own[k]), k
+        return dec
+
+    def invert_word(v):                                  # channels 32 w .. 32 w + 31 of one (window, ECoG channel, t)
+        v[1, 32:64, v.shape[2] // 2, 2] = ~v[1, 32:64, v.shape[2] // 2, 2]
+        return v
+
+    def zero_last_row_tile(v):                           # rows (window, ECoG channel, t) x channels, as the epilogue writes them
+        B, ch, t, C = v.shape
+        rows = v.permute(0, 3, 2, 1).reshape(B * C * t, ch).clone()
+        rows[-128:] = False
+        return rows.view(B, C, t, ch).permute(0, 3, 2, 1).contiguous()
+
+    for k in own:
+        for fn in (lambda v: torch.roll(v, 1, dims=1), invert_word, zero_last_row_tile):     # shifted, inverted, zero tile
+            with pytest.raises(AssertionError, match=re.escape(k + ":")):
+                check_flips(corrupted(k, fn), own, margins)
