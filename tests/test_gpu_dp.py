@@ -10,24 +10,12 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+from tests import dp_harness as dp
+
 pytestmark = pytest.mark.gpu
 
-
-LONG_TONE_MAP = {"0": [3] * 10, "1": list(range(1, 11)), "2": [3, 2, 1, 2, 4, 3, 2, 1, 2, 4], "3": list(range(10, 0, -1))}
-
-
-def _build(dev, sizes=(8, 8), dropout=0.0, tone_map=None):
-    from decode_tonal_langauge_amd.models import LogisticRegressionClassifier, SynthesisModelCNN, SynthesisTrainer
-    from tests import golden_inputs as gi
-    torch.manual_seed(0)
-    model = SynthesisModelCNN(80, 8, 100, dropout=dropout)
-    tone = LogisticRegressionClassifier(4 * 100, 4)
-    syl = LogisticRegressionClassifier(4 * 100, 2)
-    tr = SynthesisTrainer(model, tone, syl, tone_map or gi.TONE_MAP, device=dev, verbose=False)
-    g = torch.Generator().manual_seed(11)
-    batches = [(torch.randn(n, 8, 100, generator=g), torch.randn(n, 4, 100, generator=g),
-                torch.randn(n, 4, 100, generator=g), 10 * torch.randn(n, 80, generator=g)) for n in sizes]
-    return model, tr, batches
+_build = dp.build
+LONG_TONE_MAP = dp.LONG_TONE_MAP
 
 
 def _worker(rank, world, port, q, sizes=(8, 8), dropout=0.0, shard="1", tone_map=None, switch=None):
@@ -123,6 +111,26 @@ def test_two_rank_training_ragged_batches_with_dropout():
     assert abs(loss_dp - float(ref_stats[0])) < 1e-3 * abs(float(ref_stats[0]))
 
 
+def _step_grads(model, tr) -> dict:
+    """The gradients of the step just taken as the optimiser consumed them (exchanged, under data parallelism), with
+    ``weight_hh_l0`` formed from its factors (or its dense fallback) in float64."""
+    torch.cuda.synchronize()
+    out = {k: v.detach().cpu().numpy().copy() for k, v in tr._grads.items() if k != dp.WHH}
+    form, g, r0, _kr = dp.whh_gradient(model._engine, tr._grads)
+    assert r0 == 0 and g.shape[0] == 4 * model._engine.H, (form, r0, g.shape)          # one rank: every row
+    out[dp.WHH] = g
+    return out
+
+
+def _assert_same_grads(grads, ref):
+    """A world-1 exchange is the identity: the exchanged gradients of the first step (same initial parameters) are those of
+    the trainer without data parallelism, to 1e-6 relative L2 per tensor."""
+    assert sorted(grads) == sorted(ref)
+    for k in ref:
+        e = dp.rel_l2(grads[k], ref[k])
+        assert e < 1e-6, (k, e)
+
+
 def _rccl_worker(port, q):
     """One rank on the RCCL ("nccl") backend with the exchange step forced on: the same
     all_reduce / all_gather_into_tensor / barrier calls the multi-GPU run issues, on device tensors."""
@@ -138,11 +146,13 @@ def _rccl_worker(port, q):
     model, tr, batches = _build(dev)
     assert tr.dp and tr.world == 1
     model.train()
+    grads = None
     for b in batches:
         tr.train_step(*b)
+        grads = grads or _step_grads(model, tr)
     dist.barrier()
     torch.cuda.synchronize()
-    q.put(({k: v.detach().cpu().numpy() for k, v in model.named_parameters()}, tr._stats.cpu().numpy()))
+    q.put(({k: v.detach().cpu().numpy() for k, v in model.named_parameters()}, tr._stats.cpu().numpy(), grads))
     dist.destroy_process_group()
 
 
@@ -161,10 +171,12 @@ def _tl_worker(port, q):
     model, tr, batches = _build(dev)
     assert tr.dp and tr.world == 1
     model.train()
+    grads = None
     for b in batches:
         tr.train_step(*b)
+        grads = grads or _step_grads(model, tr)
     torch.cuda.synchronize()
-    out = ({k: v.detach().cpu().numpy() for k, v in model.named_parameters()}, tr._stats.cpu().numpy())
+    out = ({k: v.detach().cpu().numpy() for k, v in model.named_parameters()}, tr._stats.cpu().numpy(), grads)
     # ---- the entry points themselves (one rank: every collective is the identity)
     lib, comm, _ = parallel._TL
     st = torch.cuda.current_stream().cuda_stream
@@ -209,14 +221,16 @@ def test_exchange_step_over_the_c_abi_rccl_handle_single_rank():
     dev = torch.device("cuda:0")
     model, tr, batches = _build(dev)
     model.train()
+    ref_grads = None
     for b in batches:
         tr.train_step(*b)
+        ref_grads = ref_grads or _step_grads(model, tr)
     ref = {k: v.detach().cpu() for k, v in model.named_parameters()}
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     p = ctx.Process(target=_tl_worker, args=(31500 + (os.getpid() % 1000), q))
     p.start()
-    params, stats = q.get(timeout=300)
+    params, stats, grads = q.get(timeout=300)
     p.join(timeout=60)
     assert p.exitcode == 0
     torch.manual_seed(0)
@@ -227,20 +241,23 @@ def test_exchange_step_over_the_c_abi_rccl_handle_single_rank():
         err = float((torch.from_numpy(params[k]).double() - ref[k].double()).norm() / max(float(upd.norm()), 1e-30))
         assert err < 2e-2, (k, err)
     assert abs(float(stats[0]) - float(tr._stats[0])) < 1e-3 * abs(float(tr._stats[0]))
+    _assert_same_grads(grads, ref_grads)
 
 
 def test_exchange_step_over_rccl_single_rank():
     dev = torch.device("cuda:0")
     model, tr, batches = _build(dev)
     model.train()
+    ref_grads = None
     for b in batches:
         tr.train_step(*b)
+        ref_grads = ref_grads or _step_grads(model, tr)
     ref = {k: v.detach().cpu() for k, v in model.named_parameters()}
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     p = ctx.Process(target=_rccl_worker, args=(30500 + (os.getpid() % 1000), q))
     p.start()
-    params, stats = q.get(timeout=300)
+    params, stats, grads = q.get(timeout=300)
     p.join(timeout=60)
     assert p.exitcode == 0
     torch.manual_seed(0)
@@ -251,6 +268,7 @@ def test_exchange_step_over_rccl_single_rank():
         err = float((torch.from_numpy(params[k]).double() - ref[k].double()).norm() / max(float(upd.norm()), 1e-30))
         assert err < 2e-2, (k, err)
     assert abs(float(stats[0]) - float(tr._stats[0])) < 1e-3 * abs(float(tr._stats[0]))
+    _assert_same_grads(grads, ref_grads)
 
 
 def test_two_rank_training_unsharded_lstm_reduces_the_factor_rows():

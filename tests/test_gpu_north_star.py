@@ -23,6 +23,7 @@ import torch
 
 from tests import golden_inputs as gi
 from tests.branch_planes import check_flips, count_differing, flip_record, hip_decisions
+from tests.dp_harness import read_dropout_mask
 from tests.parity_record import record
 from tests.test_gpu_parity import rel, rel_l2, _trainer
 
@@ -517,7 +518,6 @@ def test_f63_kernels_at_the_timed_batch_match_direct_kernels(dev, monkeypatch):
 
 
 def test_train_mode_dropout_mask_forward_and_gradients_against_oracle(dev):
-    from decode_tonal_langauge_amd._lib import check, ptr
     from decode_tonal_langauge_amd.models.synthesis_models import SynthesisModelCNN
     from oracle import synthesis_oracle as so
     B, Cn, T = 6, 8, 200
@@ -535,14 +535,7 @@ def test_train_mode_dropout_mask_forward_and_gradients_against_oracle(dev):
     dec = hip_decisions(eng, B, Cn)
 
     def read_mask(seed_, row0=0, nb=B):
-        # keep mask * 1/(1-p): the concat kernel applied to an all-ones stage-5 activation
-        ones = torch.ones(nb * Cn * eng.tp5, eng.ld5, device=dev)
-        xc = torch.empty(nb * Cn * eng.tp5, eng.ldx, device=dev)
-        uid = torch.zeros(nb, dtype=torch.int32, device=dev)
-        check(eng.lib.tl_concat_pack(ptr(ones), ptr(eng._h[-1]), ptr(uid), ptr(xc), nb, Cn, eng.tp5, eng.lat, eng.Cc,
-                                     eng.Lc, eng.ld5, eng.H, eng.ldx, 0.5, seed_, row0 * Cn * eng.tp5,
-                                     torch.cuda.current_stream().cuda_stream), "tl_concat_pack")
-        return xc.view(nb, Cn, eng.tp5, eng.ldx)[:, :, :eng.lat, :eng.Cc].permute(0, 3, 2, 1).contiguous()
+        return read_dropout_mask(eng, seed_, 0.5, row0, nb)
 
     mask = read_mask(seed)                                   # (B, Cc, lat, C) like the reference's dropout input
     vals = torch.unique(mask).cpu().tolist()
