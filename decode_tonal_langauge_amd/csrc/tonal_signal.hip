@@ -607,9 +607,11 @@ constexpr int MAX_TAPS = 17;
 
 template <typename TIN>
 __device__ __forceinline__ double ext_sample(const void* x, long long cbase, long long T, int edge, long long i) {
-  // odd extension of scipy.signal.filtfilt (padtype='odd'); same roundings (2*x0 - x[k])
-  if (i < edge) return 2.0 * ld_as_f64<TIN>(x, cbase) - ld_as_f64<TIN>(x, cbase + (edge - i));
-  if (i >= edge + T) return 2.0 * ld_as_f64<TIN>(x, cbase + T - 1) - ld_as_f64<TIN>(x, cbase + T - 2 - (i - edge - T));
+  // odd extension of scipy.signal.filtfilt (padtype='odd'); same roundings: numpy forms 2*x0 - x[k] in the input's own
+  // precision (a float32 recording is extended in float32) before lfilter promotes it to float64
+  const TIN* p = reinterpret_cast<const TIN*>(x);
+  if (i < edge) return (double)((TIN)2 * p[cbase] - p[cbase + (edge - i)]);
+  if (i >= edge + T) return (double)((TIN)2 * p[cbase + T - 1] - p[cbase + T - 2 - (i - edge - T)]);
   return ld_as_f64<TIN>(x, cbase + (i - edge));
 }
 

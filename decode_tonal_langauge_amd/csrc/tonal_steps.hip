@@ -67,45 +67,111 @@ __global__ __launch_bounds__(256) void car_kernel(const void* __restrict__ x, co
 }
 
 // pandas rolling(window=W, min_periods=1): mean and sample std (ddof=1) over the non-NaN values of
-// x[c][max(0,t-W+1) .. t]; z = (x - mean)/std.  Two-pass per output on an LDS-staged window.
+// x[c][max(0,t-W+1) .. t]; z = (x - mean)/std.  Two-pass per output on an LDS-staged window: the block's RZ_TB
+// outputs read the RZ_TB + W - 1 samples x[c][t0-W+1 .. t0+RZ_TB-1].  When those exceed one LDS tile (RZ_CHUNK
+// samples) they stream through it chunk by chunk, once per pass; each output still adds its window in time order, so
+// the result does not depend on whether its window was resident or streamed.
+// Like pandas, a window whose non-NaN values are all equal has mean = that value and std 0 exactly, so z = 0/0 = NaN;
+// the plain sum leaves s/n an ulp off a non-dyadic constant and would turn a flat stretch into +-sqrt((n-1)/n).  Such a
+// window has every deviation equal to x[t] - mean, i.e. q == n (x[t] - mean)^2 up to the rounding of the sum; only
+// outputs that meet that test (rare off a flat stretch) scan their window a third time to compare every value with x[t].
 constexpr int RZ_TB = 256;
+constexpr int RZ_CHUNK = 8192;                                   // 64 KiB of fp64
+template <typename T>
+__device__ __forceinline__ void rz_stage(const void* __restrict__ x, double* xs, long long row, long long Tn, long long src0,
+                                         int len, double nan) {
+  for (int j = threadIdx.x; j < len; j += blockDim.x) {
+    const long long src = src0 + j;
+    xs[j] = (src >= 0 && src < Tn) ? ldd<T>(x, row + src) : nan;
+  }
+}
+// f(v) on window samples in time order.  The trip counts are block-uniform so that the loops stay scalar (and unrolled):
+// rz_each walks a resident window p[0 .. W); rz_each_in_chunk walks the part of output i's window that lies in the chunk
+// of tile positions [c0, c0 + len) staged in xs, over a window-offset range that covers every lane of the block.
+template <typename F>
+__device__ __forceinline__ void rz_each(const double* p, int W, F f) {
+  for (int k = 0; k < W; ++k) f(p[k]);
+}
+template <typename F>
+__device__ __forceinline__ void rz_each_in_chunk(const double* xs, int i, int c0, int len, int W, F f) {
+  const int kb = c0 - (RZ_TB - 1) > 0 ? c0 - (RZ_TB - 1) : 0, ke = c0 + len < W ? c0 + len : W;
+  for (int k = kb; k < ke; ++k) {
+    const int j = i + k - c0;
+    if (j >= 0 && j < len) f(xs[j]);
+  }
+}
 template <typename T>
 __global__ __launch_bounds__(256) void rolling_zscore_kernel(const void* __restrict__ x, double* __restrict__ y, long long Tn,
                                                              int W, int zero_nans) {
-  extern __shared__ __attribute__((aligned(16))) double xs[];     // [RZ_TB + W - 1]
+  extern __shared__ __attribute__((aligned(16))) double xs[];     // [min(RZ_TB + W - 1, RZ_CHUNK)]
   const int c = blockIdx.y;
+  const long long row = (long long)c * Tn;
   const long long t0 = (long long)blockIdx.x * RZ_TB;
+  const long long src0 = t0 - (W - 1);
   const int win = RZ_TB + W - 1;
   const double nan = __longlong_as_double(0x7ff8000000000000LL);
-  for (int i = threadIdx.x; i < win; i += blockDim.x) {
-    const long long src = t0 - (W - 1) + i;
-    xs[i] = (src >= 0 && src < Tn) ? ldd<T>(x, (long long)c * Tn + src) : nan;
-  }
-  __syncthreads();
-  const long long t = t0 + threadIdx.x;
-  if (t >= Tn) return;
-  double s = 0.0;
+  const int i = threadIdx.x;                                     // window of this output: tile positions [i, i + W)
+  const long long t = t0 + i;
+  const double xv = t < Tn ? ldd<T>(x, row + t) : nan;
+  double s = 0.0, q = 0.0, mean = nan;
   int n = 0;
-  for (int k = 0; k < W; ++k) {
-    const double v = xs[threadIdx.x + k];
+  bool need, flat = true;
+  auto add = [&](double v) {
     if (v == v) {
       s += v;
       ++n;
     }
-  }
-  const double xv = xs[threadIdx.x + W - 1];
-  double out = nan;
-  if (n >= 1) {
-    const double mean = s / n;
-    double q = 0.0;
-    for (int k = 0; k < W; ++k) {
-      const double v = xs[threadIdx.x + k];
-      if (v == v) q += (v - mean) * (v - mean);
+  };
+  auto sq = [&](double v) {
+    if (v == v) q += (v - mean) * (v - mean);
+  };
+  auto same = [&](double v) { flat = flat && !(v == v && v != xv); };
+  if (win <= RZ_CHUNK) {                                         // the whole window resident in LDS
+    rz_stage<T>(x, xs, row, Tn, src0, win, nan);
+    __syncthreads();
+    if (t >= Tn) return;
+    rz_each(xs + i, W, add);
+    mean = s / n;
+    need = n >= 2;
+    if (need) rz_each(xs + i, W, sq);
+    const double d = xv - mean;
+    if (need && fabs(q - n * d * d) <= 1e-6 * q)
+      rz_each(xs + i, W, same);
+    else
+      flat = false;
+  } else {
+    for (int c0 = 0; c0 < win; c0 += RZ_CHUNK) {
+      const int len = win - c0 < RZ_CHUNK ? win - c0 : RZ_CHUNK;
+      if (c0 > 0) __syncthreads();
+      rz_stage<T>(x, xs, row, Tn, src0 + c0, len, nan);
+      __syncthreads();
+      rz_each_in_chunk(xs, i, c0, len, W, add);
     }
-    if (n >= 2) out = (xv - mean) / sqrt(q / (n - 1));
+    mean = s / n;
+    need = t < Tn && n >= 2;
+    const double d = xv - mean;
+    for (int pass = 0; pass < 2; ++pass) {                       // q, then (where flagged) the flat test
+      const bool act = pass == 0 ? need : (need && fabs(q - n * d * d) <= 1e-6 * q);
+      if (pass == 1 && !act) flat = false;
+      if (!__syncthreads_or(act)) break;
+      for (int c0 = 0; c0 < win; c0 += RZ_CHUNK) {
+        const int len = win - c0 < RZ_CHUNK ? win - c0 : RZ_CHUNK;
+        __syncthreads();
+        rz_stage<T>(x, xs, row, Tn, src0 + c0, len, nan);
+        __syncthreads();
+        if (!act) continue;
+        if (pass == 0)
+          rz_each_in_chunk(xs, i, c0, len, W, sq);
+        else
+          rz_each_in_chunk(xs, i, c0, len, W, same);
+      }
+    }
+    if (t >= Tn) return;
   }
+  double out = nan;
+  if (need && !flat) out = (xv - mean) / sqrt(q / (n - 1));
   if (zero_nans && out != out) out = 0.0;
-  y[(long long)c * Tn + t] = out;
+  y[row + t] = out;
 }
 
 
@@ -289,14 +355,16 @@ extern "C" int tl_car(const void* x, int is_f64, const int32_t* include, void* y
 extern "C" int tl_rolling_zscore(const void* x, int is_f64, double* y, int C, int64_t T, int window, int zero_nans, void* stream) {
   TL_REQUIRE(x && y && C > 0 && C <= 65535 && T > 0, "rolling_zscore: bad arguments");
   TL_REQUIRE(window > 1, "rolling_zscore: window_size must be greater than 1.");
-  const size_t lds = (size_t)(RZ_TB + window - 1) * sizeof(double);
-  TL_REQUIRE(lds <= 64 * 1024, "rolling_zscore: window of %d samples exceeds the LDS tile", window);
+  TL_REQUIRE(T <= INT32_MAX - RZ_TB, "rolling_zscore: recording too long");
+  // a window wider than the recording holds the same samples as one of length T (the rest lies before t = 0)
+  const int W = window < T ? window : (int)T;
+  const size_t lds = (size_t)(RZ_TB + W - 1 < RZ_CHUNK ? RZ_TB + W - 1 : RZ_CHUNK) * sizeof(double);
   dim3 grid((unsigned)((T + RZ_TB - 1) / RZ_TB), (unsigned)C);
   hipStream_t st = (hipStream_t)stream;
   if (is_f64)
-    hipLaunchKernelGGL((rolling_zscore_kernel<double>), grid, dim3(256), lds, st, x, y, (long long)T, window, zero_nans);
+    hipLaunchKernelGGL((rolling_zscore_kernel<double>), grid, dim3(256), lds, st, x, y, (long long)T, W, zero_nans);
   else
-    hipLaunchKernelGGL((rolling_zscore_kernel<float>), grid, dim3(256), lds, st, x, y, (long long)T, window, zero_nans);
+    hipLaunchKernelGGL((rolling_zscore_kernel<float>), grid, dim3(256), lds, st, x, y, (long long)T, W, zero_nans);
   return check_launch("rolling_zscore");
 }
 

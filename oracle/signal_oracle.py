@@ -269,17 +269,20 @@ def car_rereference(data: np.ndarray, exclude_channels=()) -> np.ndarray:
 
 def rolling_zscore(data: np.ndarray, window_size: int, preserve_nans: bool = True) -> np.ndarray:
     """preprocess/signal/rolling_zscore.py:36-49 restated without pandas: trailing window of
-    ``window_size`` samples, min_periods=1, mean and *sample* std (ddof=1) of the non-NaN values."""
+    ``window_size`` samples, min_periods=1, mean and *sample* std (ddof=1) of the non-NaN values.
+    Like pandas' rolling kernels, a window whose non-NaN values are all equal has that value as its
+    mean and std 0 exactly, so its z-score is 0/0 = NaN (not the residue of an inexact sum / n)."""
     x = np.asarray(data, dtype=np.float64)
     C, T = x.shape
     out = np.full((C, T), np.nan)
     for t in range(T):
         w = x[:, max(0, t - window_size + 1):t + 1]
         n = np.sum(~np.isnan(w), axis=1)
+        flat = np.fmin.reduce(w, axis=1) == np.fmax.reduce(w, axis=1)      # NaN-skipping; False when n == 0
         with np.errstate(invalid="ignore", divide="ignore"):
             mean = np.nansum(w, axis=1) / n
             var = np.nansum((w - mean[:, None]) ** 2, axis=1) / (n - 1)
-            out[:, t] = np.where(n >= 2, (x[:, t] - mean) / np.sqrt(var), np.nan)
+            out[:, t] = np.where((n >= 2) & ~flat, (x[:, t] - mean) / np.sqrt(var), np.nan)
     if not preserve_nans:
         out[np.isnan(out)] = 0
     return out

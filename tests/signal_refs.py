@@ -1,0 +1,62 @@
+"""Plain CPU references of the preprocess/signal steps for the tests - TEST INFRASTRUCTURE ONLY.
+
+``pandas_rolling_zscore`` is the reference's own call (preprocess/signal/rolling_zscore.py:36-49): pandas
+updates its window sums as the window moves, so on long windows it carries a rounding drift of its own.
+``two_pass_rolling_zscore`` is the exact float64 statement of the same quantity - mean, then the sum of squared
+deviations from it, over each trailing window - with pandas' rule for a window whose non-NaN values are all
+equal (mean = that value, std = 0)."""
+import numpy as np
+import pandas as pd
+from numpy.lib.stride_tricks import sliding_window_view
+
+
+def pandas_rolling_zscore(x: np.ndarray, window: int, preserve_nans: bool = True) -> np.ndarray:
+    df = pd.DataFrame(np.asarray(x).T)
+    rolling = df.rolling(window=window, min_periods=1, center=False)
+    z = (df - rolling.mean()) / rolling.std()
+    if not preserve_nans:
+        z = z.fillna(0)
+    return z.T.to_numpy()
+
+
+def two_pass_rolling_zscore(x: np.ndarray, window: int, preserve_nans: bool = True,
+                            max_elems: int = 1 << 24) -> np.ndarray:
+    x = np.asarray(x, dtype=np.float64)
+    C, T = x.shape
+    W = min(window, T)
+    pad = np.concatenate([np.full((C, W - 1), np.nan), x], axis=1)
+    view = sliding_window_view(pad, W, axis=1)                  # (C, T, W): window of output t
+    out = np.empty((C, T))
+    step = max(1, max_elems // (C * W))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for a in range(0, T, step):
+            w = view[:, a:a + step]
+            n = np.sum(~np.isnan(w), axis=2)
+            mean = np.nansum(w, axis=2) / n
+            var = np.nansum((w - mean[..., None]) ** 2, axis=2) / (n - 1)
+            flat = np.fmin.reduce(w, axis=2) == np.fmax.reduce(w, axis=2)
+            z = (x[:, a:a + step] - mean) / np.sqrt(var)
+            out[:, a:a + step] = np.where((n >= 2) & ~flat, z, np.nan)
+    if not preserve_nans:
+        out[np.isnan(out)] = 0
+    return out
+
+
+def rolling_cases(rng: np.random.Generator, C: int, T: int, W: int) -> np.ndarray:
+    """(C, T) float64: noise with a DC offset, NaN stretches shorter and longer than W (windows holding 0 and 1
+    valid values), constant stretches of 0.1 and 1/3 longer than W - one of them from t = 0 - and an exact zero run."""
+    x = rng.standard_normal((C, T)) * 2.0 + 1.5
+    L = W + 37
+    for c in range(C):
+        k = c % 4
+        if k == 0:
+            x[c, :L] = 0.1                                      # flat from the first sample
+            x[c, T // 2:T // 2 + max(1, W // 3)] = np.nan       # shorter than the window
+        elif k == 1:
+            x[c, T // 3:T // 3 + L] = 1.0 / 3.0                 # flat mid-recording
+            x[c, T // 2 + L:T // 2 + L + W + 5] = np.nan        # longer: empty windows, then single-valued ones
+        elif k == 2:
+            x[c, T // 4:T // 4 + L] = 0.1
+            x[c, T // 4 + L + 3:T // 4 + L + 4] = np.nan
+            x[c, -min(T // 5, L):] = 0.0
+    return x

@@ -202,6 +202,40 @@ def test_g7_other_signal_steps():
     assert rel(sg.downsample(x[:, :601], 300, 400)[0], g["downsample_up"]) < 1e-12
 
 
+RESAMPLE_GRID = [(900, 1200), (901, 1200), (900, 1201), (1000, 1000), (1001, 1001), (1200, 900), (1201, 900), (2, 5),
+                 (7, 1)]
+
+
+def test_resample_oracle_is_scipy_resample_bit_for_bit():
+    from scipy.signal import resample
+    rng = np.random.default_rng(11)
+    for nx, num in RESAMPLE_GRID:
+        x = rng.standard_normal((3, nx)) * 2.0 + 0.5
+        assert np.array_equal(sg.resample_fft(x, num), resample(x, num, axis=1)), (nx, num)
+
+
+def test_rolling_zscore_oracle_matches_pandas_on_edge_windows():
+    """Constant stretches (pandas: mean = the value, std = 0, so NaN), NaN stretches giving windows with 0 and 1
+    valid values, W > T and W = 2: the NaN pattern is pandas' exactly; finite values agree with the exact two-pass
+    statement to 1e-10 and with pandas to 1e-7 (pandas moves its window sums sample by sample; at W = 2 that drift
+    reaches 1.2e-8 here, on a pair of samples 1e-3 apart)."""
+    from tests.signal_refs import pandas_rolling_zscore, rolling_cases, two_pass_rolling_zscore
+    rng = np.random.default_rng(5)
+    for C, T, W in ((4, 700, 10), (4, 700, 50), (4, 301, 2), (4, 300, 450), (3, 250, 120)):
+        x = rolling_cases(rng, C, T, W)
+        for keep in (True, False):
+            o = sg.rolling_zscore(x, W, preserve_nans=keep)
+            p = pandas_rolling_zscore(x, W, preserve_nans=keep)
+            assert np.array_equal(np.isnan(o), np.isnan(p)), (C, T, W, keep)
+            assert rel(np.nan_to_num(o), np.nan_to_num(two_pass_rolling_zscore(x, W, keep))) < 1e-10, (C, T, W, keep)
+            assert rel(np.nan_to_num(o), np.nan_to_num(p)) < 1e-7, (C, T, W, keep)
+    # the reported case: N(0,1), then a flat 0.1 - pandas gives NaN on the whole flat stretch
+    x = np.concatenate([np.random.default_rng(0).standard_normal(40), np.full(60, 0.1)])[None]
+    for W in (10, 50):
+        assert np.isnan(sg.rolling_zscore(x, W)[0, 40 + W - 1:]).all()
+        assert np.array_equal(np.isnan(sg.rolling_zscore(x, W)), np.isnan(pandas_rolling_zscore(x, W)))
+
+
 def _g_sample(g, full):
     if full in g.files:
         return g[full], None
