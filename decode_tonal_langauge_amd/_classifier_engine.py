@@ -121,6 +121,8 @@ class CnnClassifierEngine(CnnEngine):
         self.S = S
         self._buf63 = {}
         self.V = {}
+        self._gy_A = None
+        self._vhalo = {}
         z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
         zi = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
         self.P = {1: z(S * self.tp1, self.c1)}

@@ -69,10 +69,10 @@ class CnnEngine:
             raise ValueError("first stage must pool")
         align = 1 << npool_after
         self.tp1 = max(align, (self.tout1 + align - 1) // align * align)
-        # TONAL_WINO=6: Winograd F(6,3) on pre-transformed operands for stages 2 and 3 (csrc/tonal_wino63.hip; 8 products per
+        # wino 6: Winograd F(6,3) on pre-transformed operands for stages 2 and 3 (csrc/tonal_wino63.hip; 8 products per
         # 6 conv rows).  A sequence of stage 2 holds a multiple of 12 rows (hexes of 6 rows, pooled into hexes of stage 3);
         # the pooled output of stage 3 keeps the row stride of the default geometry (tl_nt_params.out_tp), so everything from
-        # stage 4 on is unchanged.  Shapes the form does not cover fall back to TONAL_WINO=4 as a whole.
+        # stage 4 on is unchanged.  Shapes the form does not cover fall back to wino 4 as a whole.
         _kernels.validate()                    # TONAL_KERNELS: unknown keys / values raise here, not on the hot path
         self.wino63 = (self.F63_CAPABLE and _kernels.get("wino") == "6"
                        and self._f63_covers(stage_defs, n_timepoints))
@@ -86,7 +86,7 @@ class CnnEngine:
         self.f63_yprod = (self.wino63 and _kernels.get("f63_yprod") != "0" and stage_defs[0][0] % 256 == 0
                           and self.tp1 >= 12)
         # ... and stage 3's (whose gradient rows no Winograd epilogue produces) from a kernel of its own, tl_wino63_unpool_yvd
-        # (TONAL_F63_YPROD3=0: its weight-gradient kernel un-pools and transforms G3 itself and writes Vd3)
+        # (f63_yprod 0: its weight-gradient kernel un-pools and transforms G3 itself and writes Vd3)
         self.f63_yprod3 = (self.wino63 and _kernels.get("f63_yprod") != "0" and stage_defs[1][0] % 256 == 0)
         self.stages: List[_Stage] = []
         cin, tin, tp = self.c1, self.tout1, self.tp1
@@ -135,7 +135,8 @@ class CnnEngine:
         # stage transforms its own input; tn_bm 64 / 127 / 128 - force a C_in tile of the weight-gradient kernel (0: auto)
         self.wino_vout = True
         self.tn_bm = 0
-        self._side = None
+        self._gy_A = None      # per-batch / per-device scratch of the NT63 input-gradient paths (_alloc resets both)
+        self._vhalo = {}
         self._B = None
         self.generation = 0
         self._saved_generation = -1
@@ -198,11 +199,6 @@ class CnnEngine:
         self.GY = [z(self.rows5, d[3]) for d in self.concat_dims]
         self.dXc = z(self.rows5, self.ldx)
 
-    def _side_stream(self, dev):
-        if self._side is None or self._side.device != dev:
-            self._side = torch.cuda.Stream(device=dev)
-        return self._side
-
     # ------------------------------------------------------------------ ABI helpers
     def _stream(self):
         return torch.cuda.current_stream().cuda_stream
@@ -213,7 +209,7 @@ class CnnEngine:
         self.timers = {} if on else None
 
     def _tick(self, name):
-        if getattr(self, "timers", None) is None or name is None:
+        if self.timers is None or name is None:
             return None
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         self.timers.setdefault(name, []).append(ev)
@@ -327,6 +323,13 @@ class CnnEngine:
             V = store[idx] = torch.zeros(nh_pad, 8, cin, dtype=torch.float32, device=self._dev)
         return V
 
+    def _halo_buffer(self, key, ntm, cout):
+        """The halo rows a V / Vd-writing epilogue leaves for its fix-up kernel: two per row tile."""
+        halo = self._vhalo.get(key)
+        if halo is None or halo.shape[0] != ntm or halo.shape[2] != cout:
+            halo = self._vhalo[key] = torch.zeros(ntm, 2, cout, dtype=torch.float32, device=self._dev)
+        return halo
+
     def _pack_wino63(self, w, forward: bool):
         O, I = w.shape[0], w.shape[1]
         dst = torch.empty(8, O, I, dtype=torch.float32, device=w.device) if forward else \
@@ -355,11 +358,7 @@ class CnnEngine:
             rows_out = S * st.tp_out
             Vn = self._v_hex_buffer(self.V, 2, rows_out, st.cout)
             ntm = -(-(S * st.tp_in) // self._nt63_rows())
-            if not hasattr(self, "_vhalo"):
-                self._vhalo = {}
-            halo = self._vhalo.get(2)
-            if halo is None or halo.shape[0] != ntm or halo.shape[2] != st.cout:
-                halo = self._vhalo[2] = torch.zeros(ntm, 2, st.cout, dtype=torch.float32, device=self._dev)
+            halo = self._halo_buffer(2, ntm, st.cout)
             kw.update(epilogue=EPI_POOLV, vout=ptr(Vn), vhalo=ptr(halo), vout_quads=Vn.shape[0], ld_vout=Vn.shape[2])
             self._nt(tag="conv2_fwd", fn="tl_conv3_wino63v_nt", **kw)
             check(self.lib.tl_wino63_v_fixup(ptr(Vn), ptr(halo), rows_out // 6, ntm, st.tp_out, st.cout, Vn.shape[2],
@@ -443,7 +442,7 @@ class CnnEngine:
         f32 = dict(dtype=torch.float32, device=self._dev)
         nh = -(-rows // 6)
         nh_pad = (nh + 127) // 128 * 128
-        A = getattr(self, "_gy_A", None)
+        A = self._gy_A
         if A is None or A.shape[0] != nh_pad or A.shape[2] != st.cout:
             A = self._gy_A = torch.zeros(nh_pad, 8, st.cout, **f32)   # slots 6, 7 and the pad hexes stay zero
         Gs = self.G[st.idx]
@@ -457,11 +456,7 @@ class CnnEngine:
         Y3 = self._v_hex_buffer(self.Yt, below.idx, rows3, below.cout)
         Vd3 = self._v_hex_buffer(self.Vd, below.idx, rows3, below.cout)
         ntm = -(-rows // self._nt63_rows())
-        if not hasattr(self, "_vhalo"):
-            self._vhalo = {}
-        halo = self._vhalo.get("d3")
-        if halo is None or halo.shape[0] != ntm or halo.shape[2] != below.cout:
-            halo = self._vhalo["d3"] = torch.zeros(ntm, 2, below.cout, **f32)
+        halo = self._halo_buffer("d3", ntm, below.cout)
         self._nt(tag=None, fn="tl_conv1_wino63v_dgrad_nt", A=ptr(A), A_rows=A.shape[0], lda=A.shape[2], loader=LOAD_V,
                  Bw=ptr(taps), M=rows, N=st.cin, K=st.cout, ldb=st.cout, ldo=st.cin, J=1, row_shift=0, Tp=tpg, slope=self.slope,
                  auxbits=ptr(self.sbits[below.idx]), ld_auxbits=self.sbits[below.idx].shape[1], abits=ptr(self.bits[below.idx]),
@@ -492,11 +487,7 @@ class CnnEngine:
             Y2 = self._v_hex_buffer(self.Yt, 2, rows2, below.cout)
             Vd2 = self._v_hex_buffer(self.Vd, 2, rows2, below.cout)
             ntm = -(-rows_in // self._nt63_rows())
-            if not hasattr(self, "_vhalo"):
-                self._vhalo = {}
-            halo = self._vhalo.get("d2")
-            if halo is None or halo.shape[0] != ntm or halo.shape[2] != below.cout:
-                halo = self._vhalo["d2"] = torch.zeros(ntm, 2, below.cout, dtype=torch.float32, device=self._dev)
+            halo = self._halo_buffer("d2", ntm, below.cout)
             self._nt(tag="conv3_dgrad", fn="tl_conv3_wino63v_nt", epilogue=EPI_MASKY, out=None, vout=ptr(Y2), vout2=ptr(Vd2),
                      vhalo=ptr(halo), vout_quads=Y2.shape[0], ld_vout=Y2.shape[2], abits=ptr(self.bits[2]),
                      ld_abits=below.cout // 32, Tvalid_in=2 * below.tout, **kw)
@@ -687,9 +678,7 @@ class CnnEngine:
             rows_out = S * st.tp_out
             Vn = self._v_buffer(st.idx, rows_out, st.cout)
             ntm = (S * st.tp_in + 511) // 512
-            halo = self._vhalo.get(st.idx)
-            if halo is None or halo.shape[0] != ntm or halo.shape[2] != st.cout:
-                halo = self._vhalo[st.idx] = torch.zeros(ntm, 2, st.cout, dtype=torch.float32, device=self._dev)
+            halo = self._halo_buffer(st.idx, ntm, st.cout)
             kw.update(epilogue=EPI_POOLV, vout=ptr(Vn), vhalo=ptr(halo), vout_quads=Vn.shape[0], ld_vout=Vn.shape[2])
             self._nt(tag=f"conv{st.idx}_fwd", fn="tl_conv3_wino43v_nt", **kw)
             check(self.lib.tl_wino43_v_fixup(ptr(Vn), ptr(halo), rows_out // 4, ntm, st.tp_out, st.cout, Vn.shape[2],
@@ -855,8 +844,8 @@ class CnnEngine:
         return part
 
     def _lstm_forward(self, prm, xu, U, L, dev, training, label_table) -> None:
-        """The label LSTM on the U distinct label rows (torch's current stream: the forward runs it on a side stream beside
-        the convolution stack, which it does not depend on - four 5.4 GB streams of W_hh next to MFMA-bound kernels)."""
+        """The label LSTM on the U distinct label rows (torch's current stream; it does not depend on the convolution stack -
+        four 5.4 GB streams of W_hh)."""
         lib, st_ = self.lib, self._stream()
         H = self.H
         f32 = dict(dtype=torch.float32, device=dev)
@@ -970,20 +959,11 @@ class CnnEngine:
         xu = uniq.reshape(U, 2, L).permute(2, 0, 1).contiguous()          # (L, U, 2) time-major
         self._xu = xu
         f32 = dict(dtype=torch.float32, device=dev)
-        # the LSTM does not depend on the convolution stack: it runs on a side stream beside it (HBM-bound next to
-        # MFMA-bound), joined in front of the concat kernel.  Not under the row-sharded data-parallel LSTM (collectives).
-        side = None         # (a side stream for the LSTM beside the convolutions measured equal to one stream - round 3; retired)
-        if side is not None:
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._lstm_forward(prm, xu, U, L, dev, training, label_table)
+        # (a side stream for the LSTM beside the convolutions measured equal to one stream - round 3; retired)
         # ---- stages 2..5: windowed implicit GEMM on fp32 MFMA ----
         for st in self.stages:
             self.stage_forward(st, prm[self.STAGE_NAMES[st.idx] + ".weight"], prm[self.STAGE_NAMES[st.idx] + ".bias"])
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side)
-        else:
-            self._lstm_forward(prm, xu, U, L, dev, training, label_table)
+        self._lstm_forward(prm, xu, U, L, dev, training, label_table)
         # ---- dropout + concat ----
         check(lib.tl_concat_pack(ptr(self.P[5]), ptr(self._h[L - 1]), ptr(self._uid), ptr(self.Xc), B, self.C,
                                  self.tp5, self.lat, self.Cc, self.Lc, self.ld5, H, self.ldx, p_drop, seed,
@@ -1244,16 +1224,10 @@ class CnnEngine:
                                        ptr(dh_ext), B, U, self.C, self.tp5, self.lat, self.Cc, self.Lc, self.ld5, H,
                                        self.ldx, self.slope, self._p_drop_used, self._seed_used, self._drop_row0,
                                        st_), "tl_concat_unpack_bwd")
-        # ---- LSTM BPTT on the distinct rows: independent of the convolution backward below - on the side stream beside it
-        # when nothing in it is a collective (single process); the trainer's W_hh update rides along (on_factors) ----
-        side = None         # (the same for the BPTT beside the convolution backward)
-        if side is not None:
-            dh_ext.record_stream(side)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._lstm_backward(prm, grads, dh_ext, gather_whh, whh_factors, reduce_rows, on_factors)
-        else:
-            self._lstm_backward(prm, grads, dh_ext, gather_whh, whh_factors, reduce_rows, on_factors)
+        # ---- LSTM BPTT on the distinct rows: independent of the convolution backward below; the trainer's W_hh update
+        # rides along (on_factors) ----
+        # (a side stream for the BPTT beside the convolution backward measured equal to one stream - round 3; retired)
+        self._lstm_backward(prm, grads, dh_ext, gather_whh, whh_factors, reduce_rows, on_factors)
         # ---- ecog stages 5..2 ----
         for st in reversed(self.stages):
             name = self.STAGE_NAMES[st.idx]
@@ -1266,5 +1240,3 @@ class CnnEngine:
             check(lib.tl_conv1_wgrad(ptr(self._x), ptr(self.G[1]), ptr(self.bits[1]), ptr(part), nblk, S, self.T, self.k1,
                                      self.c1, self.tp1, self.tout1, st_), "tl_conv1_wgrad")
         self._reduce_c1_partials(part, grads["ecog_conv_block.0.weight"], grads["ecog_conv_block.0.bias"])
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side)

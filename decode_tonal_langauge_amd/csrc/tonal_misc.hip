@@ -149,9 +149,6 @@ __global__ __launch_bounds__(256) void conv1_fwd_v4_kernel(const float* __restri
 // next stage's forward / weight-gradient GEMMs read V by LDS-DMA and the 13 GB of P1 need not exist at all (P is
 // optional: tests and the direct-form kernels want it).  Thread = 4 channels x one quad; the two halo rows of a quad
 // are recomputed (3 MACs per element from the LDS-resident signal) rather than exchanged.  HBM-write bound.
-#ifndef CONV1_NT
-#define CONV1_NT 1      // same-box A/B under rocprofv3: 4.79 -> 4.65 ms per launch (20 GB written once, read by the next kernel)
-#endif
 template <int KT>
 __global__ __launch_bounds__(256) void conv1_fwd_vq_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                            const float* __restrict__ b, float* __restrict__ P,
@@ -233,13 +230,9 @@ __global__ __launch_bounds__(256) void conv1_fwd_vq_kernel(const float* __restri
       }
       const f32x4 s1 = d[4] - 4.f * d[2], s2 = d[3] - 4.f * d[1], s3 = d[4] - d[2], t = d[3] - d[1];
       float* dst = V + (seq * Tq + q) * 6LL * C1 + o;
-      // V1 (20 GB at the north-star shape) is written once and read by a later kernel: CONV1_NT streams it past the L2
+      // V1 (20 GB at the north-star shape) is written once and read by a later kernel: stream it past the L2 (4.79 -> 4.65 ms per launch)
       auto stv = [](float* p_, const f32x4 v) {
-#if CONV1_NT
         __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p_));
-#else
-        *reinterpret_cast<f32x4*>(p_) = v;
-#endif
       };
       stv(dst, 4.f * d[0] + (d[4] - 5.f * d[2]));
       stv(dst + C1, s1 + s2);

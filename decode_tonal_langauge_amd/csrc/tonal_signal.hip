@@ -601,9 +601,6 @@ __global__ __launch_bounds__(256) void gauss_envelope_generic_kernel(const void*
 // |p| = 0.998 and an fp32 recurrence diverges.
 // ------------------------------------------------------------------------------------------
 constexpr int MAX_TAPS = 17;
-#ifndef FF_LANES8
-#define FF_LANES8 1       // filtfilt with ntaps <= 9: the state over 8 lanes per channel (0: one lane per channel)
-#endif
 
 template <typename TIN>
 __device__ __forceinline__ double ext_sample(const void* x, long long cbase, long long T, int edge, long long i) {
@@ -1131,7 +1128,7 @@ extern "C" int tl_filtfilt_f64(const void* x, int x_is_f64, const double* b, con
   else
     hipLaunchKernelGGL((filtfilt_build_kernel<float>), dim3((unsigned)g), dim3(256), 0, st, x, work, C, (long long)T, edge);
   dim3 grid((unsigned)((C + 63) / 64));
-  if (ntaps <= 9 && FF_LANES8)                              // state over 8 lanes per channel: 8 channels per wave
+  if (ntaps <= 9)                                           // state over 8 lanes per channel: 8 channels per wave
     hipLaunchKernelGGL(filtfilt_iir8_kernel, dim3((unsigned)((C + 3) / 4)), dim3(64), 0, st, b, a, zi, work, C, next, ntaps);
   else if (ntaps <= 5)
     hipLaunchKernelGGL((filtfilt_iir_kernel<5>), grid, dim3(64), 0, st, b, a, zi, work, C, next, ntaps);

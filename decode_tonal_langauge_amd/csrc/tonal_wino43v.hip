@@ -180,37 +180,15 @@ constexpr int V4_APIECES = 6 * V4_BQ / 16;               // 48
 constexpr int V4_BPIECES = 6 * V4_BN / 16;               // 24
 
 typedef __attribute__((address_space(3))) void lds_void_t;
-#ifndef V4_STAGGER
-#define V4_STAGGER 0      // 1: waves 4-7 issue their LDS-DMA pieces in the second half of a K-step (see kstep)
-#endif
-#ifndef V4_PERSIST
-#define V4_PERSIST 1      // workgroups per CU of the persistent launch (the next tile's first fetch overlaps the epilogue); 0:
-#endif                    // one workgroup per tile, as before
-#ifndef V4_SCHED
-#define V4_SCHED 1        // 1: hand-specified issue order of a K-step (see kstep)
-#endif
-#ifndef V4_LEAN
-#define V4_LEAN 1         // round 4: quads of a wave in the order of tonal_wino43v_epi.h (a lane owns 16 consecutive quads), scalar-side
-#endif                    // epilogues, first K-step of a tile without the empty carried group; 0: the round-3 kernel (A/B partner)
-#ifndef V4_ABL
-#define V4_ABL 0          // timing-only build variants (scripts/build_v_variants.sh): 1 no steady-state DMA, 2 no epilogue,
-#endif                    // 4 no barrier, 8 order pinned at the top of a K-step, 16 no fragment reads
 
 __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, char* lds_dst, unsigned voff, unsigned soff) {
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t*)lds_dst, 16, voff, soff, 0, 0);
 }
-// the same with the non-temporal cache policy (aux = 2): for a stream every CU reads once or eight times within a few
-// microseconds (the V operand of the NT kernels) and that should not push a re-used operand (the taps) out of the L2
-__device__ __forceinline__ void dma16_nt(__amdgpu_buffer_rsrc_t rs, char* lds_dst, unsigned voff, unsigned soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t*)lds_dst, 16, voff, soff, 0, 2);
-}
-#ifndef V4_NT
-#define V4_NT 0           // cache policy experiment of the NT kernel: 1 = V (streaming operand) non-temporal, 2 = taps non-temporal
-#endif
+// (the non-temporal cache policy, aux = 2, on the V pieces of the NT kernel: conv2 forward 40.2 -> 49.25 ms, r04_kernel_notes.md)
 
 template <int EPI>
 __global__ __launch_bounds__(512, 2) void wino43v_nt_kernel(const tl_nt_params p) {
-  __shared__ __attribute__((aligned(1024))) char lds[2 * V4_STAGE + (EPI == W_EPI_POOLV ? 4096 : (EPI == W_EPI_C1W && V4_LEAN) ? 16384 : 0)];
+  __shared__ __attribute__((aligned(1024))) char lds[2 * V4_STAGE + (EPI == W_EPI_POOLV ? 4096 : EPI == W_EPI_C1W ? 16384 : 0)];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -263,14 +241,10 @@ __global__ __launch_bounds__(512, 2) void wino43v_nt_kernel(const tl_nt_params p
     for (int k = 0; k < 6; ++k) {
       const int pa = wave * 6 + k;
       const int i = pa >> 3, j = pa & 7;
-#if V4_LEAN
       // LDS row rho = 8 g + 4 lh + j' of a wave's 32 (the MFMA row whose results lane half lh holds in accumulator
       // elements 4 g + j') takes quad 16 lh + 4 g + j': a lane owns 16 consecutive quads (tonal_wino43v_epi.h)
       const int rho = (j & 1) * 16 + prow;
       long long ql = (j >> 1) * 32 + ((rho & 3) | ((rho >> 3) << 2) | (((rho >> 2) & 1) << 4));
-#else
-      long long ql = j * 16 + prow;
-#endif
       if (ql > q_left - 1) ql = q_left - 1;
       t.avoff[k] = (unsigned)(((ql * 6 + i) * p.lda + src_chunk * 4) * 4);
     }
@@ -285,7 +259,6 @@ __global__ __launch_bounds__(512, 2) void wino43v_nt_kernel(const tl_nt_params p
     return t;
   };
   tile_t cur = setup(blockIdx.x);
-#if V4_LEAN
   // Next tile of this workgroup WITHOUT the divisions of setup(): with a persistent launch of 8 k workgroups the XCD-aware
   // remap sends tile sequence blockIdx.x + j gridDim.x to b' + j gridDim.x / 8, so (tm, tn) advance by a fixed (dq, dr) with
   // a carry; the V quads of a tile always exist (host-checked: V holds whole 128-quad tiles), so the per-lane source
@@ -329,24 +302,13 @@ __global__ __launch_bounds__(512, 2) void wino43v_nt_kernel(const tl_nt_params p
     }
     return t;
   };
-#endif
   auto issue = [&](const tile_t& tl_, int step) {
     char* base = lds + (step & 1) * V4_STAGE;
     const unsigned soff = (unsigned)step * (V4_BK * 4);
-    if (!(V4_ABL & 64) || step < 2) {
 #pragma unroll
-      for (int t = 0; t < 6; ++t) {
-        if (V4_NT & 1) dma16_nt(tl_.rsA, base + adst[t], tl_.avoff[t], soff);
-        else dma16(tl_.rsA, base + adst[t], tl_.avoff[t], soff);
-      }
-    }
-    if (!(V4_ABL & 128) || step < 2) {
+    for (int t = 0; t < 6; ++t) dma16(tl_.rsA, base + adst[t], tl_.avoff[t], soff);
 #pragma unroll
-      for (int t = 0; t < 3; ++t) {
-        if (V4_NT & 2) dma16_nt(rsB, base + bdst[t], tl_.bvoff[t], soff);
-        else dma16(rsB, base + bdst[t], tl_.bvoff[t], soff);
-      }
-    }
+    for (int t = 0; t < 3; ++t) dma16(rsB, base + bdst[t], tl_.bvoff[t], soff);
   };
 
   // ---- fragment reads: row r of a tile, logical chunk c = 2 g + lh -> r * 64 + ((c ^ ((r >> 2) & 3)) << 4)
@@ -370,24 +332,20 @@ __global__ __launch_bounds__(512, 2) void wino43v_nt_kernel(const tl_nt_params p
       for (int i = 0; i < 6; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][q], fb[i][q], acc[i], 0, 0, 0);
   };
   issue(cur, 0);
-  auto kstep = [&](auto LAST, auto LATE, int s) {
+  auto kstep = [&](auto LAST, int s) {
     const int stage = s & 1;
-    if (!(V4_ABL & 16) || s == 0) load_frag(fa0, fb0, stage, c_g0);
-    if constexpr (!decltype(LAST)::value)
-      if (!(V4_ABL & 1) || s == 0) issue(cur, s + 1);       // the other stage was released at the last barrier
+    load_frag(fa0, fb0, stage, c_g0);
+    if constexpr (!decltype(LAST)::value) issue(cur, s + 1);  // the other stage was released at the last barrier
     mfma_group(fa1, fb1);                                   // k-group 1 of the previous step (registers)
-    if (!(V4_ABL & 16) || s == 0) load_frag(fa1, fb1, stage, c_g1);
+    load_frag(fa1, fb1, stage, c_g1);
     mfma_group(fa0, fb0);
-#if V4_SCHED
     // Issue order of the step (sched_group_barrier: 0x008 MFMA, 0x010 vector memory, 0x100 LDS read).  An LDS-DMA
     // piece costs the issuing wave ~60 cycles; issued as a clump after the barrier by both waves of a SIMD at once it
     // idles the matrix pipe (ablation: 6.4 of 45.4 ms), one piece per two MFMAs hides behind the partner's MFMAs.
     // The reads of k-group 1 are spread over the MFMAs of k-group 0 so none of their latency is left at the barrier.
-    // V4_STAGGER: waves 4-7 (the SIMD partners of waves 0-3) issue their pieces in the SECOND half of the step, so the two
-    // waves of a SIMD are never in their DMA-issue phase together (MI355X_MICROARCH.md, two waves per SIMD, item 9)
-    constexpr bool late = decltype(LATE)::value;
+    // (waves 4-7 issuing their pieces in the second half of the step: conv2 forward 43.1 -> 47.3 ms, r03_kernel_notes.md)
     __builtin_amdgcn_sched_group_barrier(0x100, 12, 0);
-    if constexpr (!decltype(LAST)::value && !late) {
+    if constexpr (!decltype(LAST)::value) {
 #pragma unroll
       for (int t = 0; t < 9; ++t) {
         __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
@@ -401,25 +359,15 @@ __global__ __launch_bounds__(512, 2) void wino43v_nt_kernel(const tl_nt_params p
     for (int t = 0; t < 12; ++t) {
       __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
       __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      if constexpr (!decltype(LAST)::value && late)
-        if (t < 9) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
     }
-#endif
     if constexpr (!decltype(LAST)::value) {
       // the builtin (not inline asm) so that the compiler's own wait-count bookkeeping sees the drained counters: after
       // an asm wait it re-waits lgkmcnt(0) behind the first reads of the next step, in front of the carried MFMAs
-#if V4_ABL & 32
-      __builtin_amdgcn_s_waitcnt(0x3f7f & ~0x0f00);         // lgkmcnt(0)
-#else
       __builtin_amdgcn_s_waitcnt(0x0070);                   // vmcnt(0) lgkmcnt(0)
-#endif
-#if !(V4_ABL & 4)
       __builtin_amdgcn_s_barrier();
-#endif
       asm volatile("" ::: "memory");
     }
   };
-#if V4_LEAN
   // First K-step of a tile: the accumulators start from the zero constant of the first MFMA of each (no 96 moves) and there
   // is no carried k-group (round 3 ran 24 MFMAs on zero operands per tile here: 1.5 % of a tile's matrix time).
   auto mfma_group0 = [&](const f32x4 (&fa)[6], const f32x4 (&fb)[6]) {
@@ -436,7 +384,6 @@ __global__ __launch_bounds__(512, 2) void wino43v_nt_kernel(const tl_nt_params p
     if constexpr (!decltype(LAST)::value) issue(cur, 1);
     load_frag(fa1, fb1, 0, c_g1);
     mfma_group0(fa0, fb0);
-#if V4_SCHED
     __builtin_amdgcn_sched_group_barrier(0x100, 12, 0);
 #pragma unroll
     for (int t = 0; t < 12; ++t) {
@@ -445,37 +392,17 @@ __global__ __launch_bounds__(512, 2) void wino43v_nt_kernel(const tl_nt_params p
       if constexpr (!decltype(LAST)::value)
         if (t < 9) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
     }
-#endif
     if constexpr (!decltype(LAST)::value) {
       __builtin_amdgcn_s_waitcnt(0x0070);                   // vmcnt(0) lgkmcnt(0)
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
     }
   };
-#endif
-#if V4_LEAN
   __builtin_amdgcn_s_waitcnt(0x0f70);                       // vmcnt(0): the first tile's first stage
-#endif
   for (long long vb = blockIdx.x; vb < nwg; vb += gridDim.x) {
-#if !V4_LEAN
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) fa1[i] = fb1[i] = f32x4{0.f, 0.f, 0.f, 0.f};   // carried k-group of step -1: adds nothing
-#endif
-#if V4_LEAN
     // stage 0 of this tile has landed (waited for at the end of the tile in front), every wave is past that epilogue
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-#else
-    // stage 0 of this tile has landed (so have the stores of the epilogue in front of it), every wave is past that epilogue
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-#endif
-#if V4_LEAN
     // What the epilogue reads from global memory is requested in front of the LAST K-step: the loads return under its 72
     // MFMAs and - vmcnt counts in issue order - in front of the next tile's LDS-DMA pieces, so their consumer does not
     // wait for those (tonal_wino43v_epi.h)
@@ -487,61 +414,32 @@ __global__ __launch_bounds__(512, 2) void wino43v_nt_kernel(const tl_nt_params p
     decltype(prefetch()) pre;
     if (nsteps > 1) {
       kstep_first(std::false_type{});
-      for (int s = 1; s + 1 < nsteps; ++s) kstep(std::false_type{}, std::false_type{}, s);
+      for (int s = 1; s + 1 < nsteps; ++s) kstep(std::false_type{}, s);
       pre = prefetch();
       __builtin_amdgcn_sched_barrier(0);
-      kstep(std::true_type{}, std::false_type{}, nsteps - 1);
+      kstep(std::true_type{}, nsteps - 1);
     } else {
       pre = prefetch();
       __builtin_amdgcn_sched_barrier(0);
       kstep_first(std::true_type{});
     }
-#else
-#if V4_STAGGER
-    if (wave >= 4) {
-      for (int s = 0; s + 1 < nsteps; ++s) kstep(std::false_type{}, std::true_type{}, s);
-    } else
-#endif
-    {
-      for (int s = 0; s + 1 < nsteps; ++s) kstep(std::false_type{}, std::false_type{}, s);
-    }
-    kstep(std::true_type{}, std::false_type{}, nsteps - 1);
-#endif
     mfma_group(fa1, fb1);
 
-#if V4_ABL & 2
-    {
-      float t = 0.f;
-#pragma unroll
-      for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) t += acc[i][e];
-      if (t == 12345.678f) p.out[tid] = t;
-    }
-#endif
     // the first K-step of the next tile goes into stage 0 - last read in step nsteps - 2 when nsteps is even, and every
     // wave is past that step's closing barrier; the last step's stage is still being read by slower waves
     const tile_t done = cur;
     const long long nb = vb + gridDim.x;
-#if V4_LEAN
     // the prefetched words have landed (they were requested a K-step ago; nothing else is in flight).  Stated here so that the
     // compiler does not place a vmcnt(0) of its own behind the conditional LDS-DMA issue below - in front of the epilogue
     __builtin_amdgcn_s_waitcnt(0x0f70);
-#endif
-    if (V4_PERSIST && nb < nwg) {
+    if (nb < nwg) {
       if (nsteps & 1) __syncthreads();
-#if V4_LEAN
       cur = advance(cur);
-#else
-      cur = setup(nb);
-#endif
       issue(cur, 0);
     }
-#if V4_LEAN
     __builtin_amdgcn_sched_barrier(0);
     // ---- epilogue (tonal_wino43v_epi.h): the four conv rows of a quad from its six products, then pool (-> P and / or V
     // of the next stage) / mask / fused first-stage weight gradient; row logic on the scalar ALU ----
-#if !(V4_ABL & 2)
     float* scratch = reinterpret_cast<float*>(lds + ((nsteps - 1) & 1) * V4_STAGE);
     (void)scratch;
     // (workgroup-uniform) interior tile: every row / column / output quad exists - the in-matrix masks of the stores fold away
@@ -561,31 +459,12 @@ __global__ __launch_bounds__(512, 2) void wino43v_nt_kernel(const tl_nt_params p
       v5_epilogue_c1w(p, acc, pre, reinterpret_cast<float*>(lds + 2 * V4_STAGE) + wave * 512, scratch, done.R0, done.n0, wm, wn,
                       lr, lh, done.tm);
     }
-#endif
     {
       // The next tile's first stage (issued in front of the epilogue) has landed; the epilogue's own stores need not: a
       // wave issues v5_stores<EPI>() of them per tile and vmcnt counts in issue order.  (Round 3 waited for vmcnt(0) here:
       // every tile paid the write latency of its last store with no MFMA in flight.)
-      constexpr int N = V4_PERSIST ? v5_stores<EPI>() : 0;
+      constexpr int N = v5_stores<EPI>();
       __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
-    }
-#else
-    // ---- epilogue (shared with the in-loop-transform kernels, tonal_wino43_epi.h): the four conv rows of a quad from
-    // its six products, then pool / mask / fused first-stage weight gradient.  The reduction of the fused weight gradient
-    // takes the LAST step's stage as its scratch (behind a barrier: other waves may still be reading it) ----
-    if constexpr (EPI == W_EPI_C1W) __syncthreads();
-#if !(V4_ABL & 2)
-    float* scratch = reinterpret_cast<float*>(lds + ((nsteps - 1) & 1) * V4_STAGE);
-    if (done.R0 + 4 * V4_BQ <= p.M && done.n0 + V4_BN <= p.N)     // (workgroup-uniform) interior tile: no per-store bounds tests
-      wino43_epilogue<EPI, true>(p, acc, scratch, done.R0, done.n0, wm, wn, lr, lh, done.tm);
-    else
-      wino43_epilogue<EPI, false>(p, acc, scratch, done.R0, done.n0, wm, wn, lr, lh, done.tm);
-#endif
-#endif
-    if (!V4_PERSIST && nb < nwg) {                         // (no prefetch: plain sequence of tiles)
-      __syncthreads();
-      cur = setup(nb);
-      issue(cur, 0);
     }
   }
 }
@@ -602,15 +481,6 @@ constexpr int T4_BN = 64, T4_Q = 8;                       // C_out tile, quads p
 constexpr int T4_PLANE = T4_Q * 64;                       // floats per transform plane
 constexpr int T4_TILE = 6 * T4_PLANE;                     // floats per operand tile (12 KB)
 constexpr int T4V_NA = 4;                                 // V ring slots
-#ifndef T4V_NT_STORE
-#define T4V_NT_STORE 1     // Vd is written once and read by a later kernel: stream it past the L2
-#endif
-#ifndef T4V_ABL
-#define T4V_ABL 0          // timing-only ablations (results garbage): 1 no steady-state V pieces, 2 no steady-state Y loads,
-#endif                     // 4 no Vd stores, 8 no Y transform / LDS store in the steady state
-#ifndef T4V_SCHED
-#define T4V_SCHED 0        // > 0: hand-specified issue order of a K-step with this many VALU per MFMA slot
-#endif
 
 // WVD: this launch covers the first C_in tile only and also writes Vd (see write_vd below); the other C_in tiles run in
 // a second launch of the plain instantiation (a run-time branch around the Vd code splits the K-step into basic blocks
@@ -822,17 +692,17 @@ __global__ __launch_bounds__(128 * MW, MW == 2 ? 2 : 1) void wino43v_tn_kernel(c
     float* dst = Bs + buf * T4_TILE + qi * 64 + sw;
 #pragma unroll
     for (int i = 0; i < 6; ++i) *reinterpret_cast<yv*>(dst + i * T4_PLANE) = o[i];
-    if constexpr (write_vd && !(T4V_ABL & 4)) {
+    if constexpr (write_vd) {
       // buffer stores relative to the first quad of this split: a lane with nothing to write (column past C_out, quad of
       // the padding) carries an offset past the resource and the hardware drops its store - no branch in the K-step (an
       // exec-mask branch around the stores splits it into basic blocks the scheduler cannot interleave across)
       const unsigned off = (bnok && r.q < (int)quads_all) ? (unsigned)(r.q - (int)v_q0) * vd_qstride + vd_coff : 0xfffffff0u;
 #pragma unroll
-      for (int i = 0; i < 6; ++i) {
+      for (int i = 0; i < 6; ++i) {                        // (last operand 2 = non-temporal: Vd is written once and read by a later kernel)
         if constexpr (CPT == 2)
-          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u32, vd[i]), rsVd, off, (unsigned)(i * p.ld_vd * 4), T4V_NT_STORE ? 2 : 0);
+          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u32, vd[i]), rsVd, off, (unsigned)(i * p.ld_vd * 4), 2);
         else
-          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vd[i]), rsVd, off, (unsigned)(i * p.ld_vd * 4), T4V_NT_STORE ? 2 : 0);
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vd[i]), rsVd, off, (unsigned)(i * p.ld_vd * 4), 2);
       }
     }
   };
@@ -863,15 +733,13 @@ __global__ __launch_bounds__(128 * MW, MW == 2 ? 2 : 1) void wino43v_tn_kernel(c
     const int abuf = s & (T4V_NA - 1), bbuf = s & 1;
     load_frag(fa0, fb0, abuf, bbuf, 0);
     if constexpr (!tail) {
-      if (!(T4V_ABL & 2)) load_regs(std::true_type{}, r_ld);
-      if (!(T4V_ABL & 1)) issue_v(s + 3);
+      load_regs(std::true_type{}, r_ld);
+      issue_v(s + 3);
     } else if (s + 3 < nsteps) {
       load_regs(std::false_type{}, r_ld);
       issue_v(s + 3);
     }
-#if !T4V_SCHED
     __builtin_amdgcn_sched_barrier(0);
-#endif
     mfma6(fa1, fb1);                                        // slice 3 of the previous step
     load_frag(fa1, fb1, abuf, bbuf, 1);
     mfma6(fa0, fb0);
@@ -887,25 +755,10 @@ __global__ __launch_bounds__(128 * MW, MW == 2 ? 2 : 1) void wino43v_tn_kernel(c
       else
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(w.g[0]), "+v"(w.g[1]), "+v"(w.gp), "+v"(w.wa), "+v"(w.wb), "+v"(w.wp));
     }
-    if ((!tail && !(T4V_ABL & 8)) || (tail && s + 1 < nsteps)) store_b(r_st, bbuf ^ 1);
+    if (!tail || s + 1 < nsteps) store_b(r_st, bbuf ^ 1);
     load_frag(fa1, fb1, abuf, bbuf, 3);
     mfma6(fa0, fb0);
-#if T4V_SCHED
-    // issue order of the step: the first fragment reads, then one vector-memory operation (4 Y loads, 3 V pieces),
-    // two transform VALU and one fragment read per MFMA slot, the three Y stores late (0x008 MFMA, 0x002 VALU,
-    // 0x010 vector memory, 0x100 / 0x200 LDS read / write)
-    if constexpr (!tail) {
-      __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
-#pragma unroll
-      for (int t = 0; t < 24; ++t) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        if (t < 7) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, T4V_SCHED, 0);
-        if (t < 18) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        if (t >= 18 && t < 21) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-      }
-    }
-#endif
+    // (a hand-specified sched_group_barrier order of this step: 43.6 -> 46.3 ms, r03_kernel_notes.md)
     // (a workgroup that also writes Vd issues 2 more loads and 6 stores per step - stores count in vmcnt too: the
     // younger operations are then the 6 stores of step s - 2 and 15 + 15 of steps s - 1 and s = 36)
     if constexpr (!tail) {
@@ -998,13 +851,6 @@ __global__ __launch_bounds__(128 * MW, MW == 2 ? 2 : 1) void wino43v_tn_kernel(c
 // zeros), the quads of a step past the end get all-zero masks, so the vmcnt arithmetic of the closing wait never
 // changes: what may stay in flight are the operations of this step and the one before, 2 x (4 or 6).
 // ------------------------------------------------------------------------------------------
-#ifndef T8_SCHED
-#define T8_SCHED 1
-#endif
-#ifndef T8_ABL
-#define T8_ABL 0           // timing-only: 1 no V pieces, 2 no G piece, 4 no Vd stores, 8 no transform, 16 no barrier,
-                           // 512 Vd stores issued with offsets past the resource (no memory traffic)
-#endif
 template <bool WVD>
 __global__ __launch_bounds__(512, 1) void wino43v_tn8_kernel(const tl_tn_params p, int mt0, int mtn) {
   constexpr int NA = T4V_NA, NG = 6;             // V ring slots; raw ring slots (steps s - 1 .. s + 4 are live)
@@ -1202,14 +1048,12 @@ __global__ __launch_bounds__(512, 1) void wino43v_tn8_kernel(const tl_tn_params 
     stage(v[1], v[3], hi, X2{});
     const f32x4 va4 = {v[0], v[1], v[2], v[3]};
     const f32x4 vb4 = {v[4], v[5], xch(v[4], X2{}), xch(v[5], X2{})};   // (rows 4, 5: lanes 0, 1 of a group)
-    const bool ok = q < qs_lim && !(T8_ABL & 512);
+    const bool ok = q < qs_lim;
     const unsigned qoff = (unsigned)(q - q_first) * vd_qstride;
-    if (!(T8_ABL & 4)) {
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u32, va4), rsVd, ok ? qoff + vdA_lane : 0xfffffff0u, 0u,
-                                             T4V_NT_STORE ? 2 : 0);
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u32, vb4), rsVd,
-                                             ok && (lane & 3) < 2 ? qoff + vdB_lane : 0xfffffff0u, 0u, T4V_NT_STORE ? 2 : 0);
-    }
+    // (last operand 2 = non-temporal: Vd is written once and read by a later kernel)
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u32, va4), rsVd, ok ? qoff + vdA_lane : 0xfffffff0u, 0u, 2);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u32, vb4), rsVd,
+                                           ok && (lane & 3) < 2 ? qoff + vdB_lane : 0xfffffff0u, 0u, 2);
   };
 
   // ---- MFMA side (as wino43v_tn_kernel<., 4>) ----
@@ -1271,13 +1115,12 @@ __global__ __launch_bounds__(512, 1) void wino43v_tn8_kernel(const tl_tn_params 
     const int abuf = s & (NA - 1), bbuf = s & 1;
     const int slot0 = slot1 == 0 ? NG - 1 : slot1 - 1;
     __builtin_amdgcn_sched_barrier(0);
-    if (!(T8_ABL & 1)) issue_v(s + 3);
-    if (!(T8_ABL & 2)) issue_g(s + 4, slot4);
+    issue_v(s + 3);
+    issue_g(s + 4, slot4);
     load_frag(fa0, fb0, abuf, bbuf, 0);
     load_frag(fa1, fb1, abuf, bbuf, 1);
     mfma6(fac, fbc);                                        // slice 3 of the previous step
     mfma6(fa0, fb0);
-#if T8_SCHED
     // first half of the step: one vector-memory operation behind each MFMA while there are any, the fragment reads of
     // slices 0 and 1 (the compiler pairs them across the two slices: 12 ds_read2st64_b32) behind the MFMAs of the carried
     // slice (0x008 MFMA, 0x010 vector memory, 0x100 LDS read)
@@ -1287,18 +1130,17 @@ __global__ __launch_bounds__(512, 1) void wino43v_tn8_kernel(const tl_tn_params 
       if (t < 4) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
       if (t < 6) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
     }
-#endif
     __builtin_amdgcn_sched_barrier(0);
     // second half: the transform of step s + 1 beside the MFMAs of slices 1 and 2
     y_in yn;
     y_out un = {};
-    if (!(T8_ABL & 8)) fetch_y(s + 1, slot1, slot0, yn);
+    fetch_y(s + 1, slot1, slot0, yn);
     load_frag(fa2, fb2, abuf, bbuf, 2);
     load_frag(fac, fbc, abuf, bbuf, 3);
     mfma6(fa1, fb1);
-    if (!(T8_ABL & 8)) un = compute_y(s + 1, yn);
+    un = compute_y(s + 1, yn);
     if constexpr (write_vd) {
-      if (turn == mi && s + 1 < nsteps && !(T8_ABL & 8)) vd_part(s + 1, slot1, slot0, yn.tq, un);
+      if (turn == mi && s + 1 < nsteps) vd_part(s + 1, slot1, slot0, yn.tq, un);
       turn = turn + 1 == mtn ? 0 : turn + 1;
     }
     mfma6(fa2, fb2);
@@ -1306,9 +1148,7 @@ __global__ __launch_bounds__(512, 1) void wino43v_tn8_kernel(const tl_tn_params 
     // everything issued up to step s - 2 has landed: V(s + 1), G(s + 2).  In flight: the 4 pieces of this step and of the
     // one before (a Vd store among them only makes the wait reach further back)
     __builtin_amdgcn_s_waitcnt(0x0078);                           // vmcnt(8) lgkmcnt(0)
-#if !(T8_ABL & 16)
     __builtin_amdgcn_s_barrier();
-#endif
     asm volatile("" ::: "memory");
     slot1 = next6(slot1);
     slot4 = next6(slot4);
@@ -1444,24 +1284,17 @@ extern "C" int tl_conv3_wino43v_nt(const tl_nt_params* pp, void* stream) {
   TL_REQUIRE(128LL * 6 * p.lda * 4 + 4LL * p.K < (1LL << 31), "wino43v_nt: tile span too large");
   const long long nwg = ((p.M + 4 * V4_BQ - 1) / (4 * V4_BQ)) * ((p.N + V4_BN - 1) / V4_BN);
   TL_REQUIRE(nwg < (1LL << 31), "wino43v_nt: grid too large");
-#if V4_LEAN
   // (the epilogues of tonal_wino43v_epi.h: a wave's 32 columns are in or out of the matrix together; 32-bit row arithmetic)
   TL_REQUIRE(p.N % 32 == 0 && p.M + 4 * V4_BQ < (1LL << 31), "wino43v_nt: N %% 32 == 0 and M < 2^31 - 512 needed");
   TL_REQUIRE(p.slope >= 0.f && p.slope <= 1.f, "wino43v_nt: LeakyReLU slope must lie in [0, 1]");
   TL_REQUIRE(p.A_rows >= ((p.M + 4 * V4_BQ - 1) / (4 * V4_BQ)) * V4_BQ, "wino43v_nt: V must hold whole 128-quad tiles (pad it with zero quads)");
-#endif
   hipStream_t st = (hipStream_t)stream;
-#if V4_PERSIST
-  const long long ngrid = nwg < 256 * V4_PERSIST ? nwg : 256 * V4_PERSIST;      // one workgroup per CU (144 KB of LDS each)
-#else
-  const long long ngrid = nwg;
-#endif
+  const long long ngrid = nwg < 256 ? nwg : 256;      // one workgroup per CU (144 KB of LDS each)
   if (p.epilogue == W_EPI_POOL) {
     TL_REQUIRE(p.row_shift == 0 && p.out && p.ldo >= p.N, "wino43v_nt: forward needs row_shift 0 and an output");
     TL_REQUIRE(p.obits != nullptr && p.Tvalid % 2 == 0 && p.Tvalid <= p.Tp, "wino43v_nt: POOL needs obits and an even Tvalid");
     TL_REQUIRE(p.N % 32 == 0 && p.ld_obits * 32 >= p.N, "wino43v_nt: POOL needs N %% 32 == 0");
     hipLaunchKernelGGL((wino43v_nt_kernel<W_EPI_POOL>), dim3((unsigned)ngrid), dim3(512), 0, st, p);
-#if V4_LEAN
   } else if (p.epilogue == W_EPI_POOLV) {
     TL_REQUIRE(p.row_shift == 0 && (p.out == nullptr || p.ldo >= p.N), "wino43v_nt: forward needs row_shift 0");
     TL_REQUIRE(p.obits != nullptr && p.Tvalid % 2 == 0 && p.Tvalid <= p.Tp, "wino43v_nt: POOLV needs obits and an even Tvalid");
@@ -1469,14 +1302,9 @@ extern "C" int tl_conv3_wino43v_nt(const tl_nt_params* pp, void* stream) {
     TL_REQUIRE(p.vout && p.vhalo && p.ld_vout >= p.N && p.vout_quads >= p.M / 8, "wino43v_nt: POOLV needs vout (>= M / 8 quads) and vhalo");
     TL_REQUIRE(64LL * 6 * p.ld_vout * 4 < (1LL << 31), "wino43v_nt: ld_vout too large");
     hipLaunchKernelGGL((wino43v_nt_kernel<W_EPI_POOLV>), dim3((unsigned)ngrid), dim3(512), 0, st, p);
-#endif
   } else if (p.epilogue == W_EPI_MASK) {
     TL_REQUIRE(p.row_shift == -2 && p.ldo >= p.N, "wino43v_nt: input gradient needs row_shift -2");
-#if V4_LEAN
     TL_REQUIRE(p.auxbits != nullptr, "wino43v_nt: MASK needs auxbits (the sign bits of the stage input)");
-#else
-    TL_REQUIRE(p.aux != nullptr || p.auxbits != nullptr, "wino43v_nt: MASK needs aux or auxbits");
-#endif
     hipLaunchKernelGGL((wino43v_nt_kernel<W_EPI_MASK>), dim3((unsigned)ngrid), dim3(512), 0, st, p);
   } else if (p.epilogue == W_EPI_C1W) {
     TL_REQUIRE(p.row_shift == -2, "wino43v_nt: input gradient needs row_shift -2");

@@ -238,34 +238,7 @@ constexpr int V6_A_BYTES = 8 * V6_BH * V6_ROWB;          // 32768
 constexpr int V6_B_BYTES = 8 * V6_BN * V6_ROWB;          // 16384
 constexpr int V6_STAGE = V6_A_BYTES + V6_B_BYTES;        // 49152
 constexpr int V6_ROWS = 6 * V6_BH;                       // conv rows per tile (768)
-#ifndef V6_PRIO
-#define V6_PRIO 0         // 1: s_setprio 1 for waves 4-7 (experiment)
-#endif
-#ifndef V6_RDSCHED
-#define V6_RDSCHED -1     // issue order of the second half-set's fragment reads: -1 per instantiation (see kstep), 0 / 1 force one
-#endif
-#ifndef V6_ABL
-#define V6_ABL 0          // timing-only build variants: 1 no steady-state DMA, 2 no epilogue, 4 no barrier
-#endif
-#ifndef V6_STAMP
-#define V6_STAMP 0        // diagnostic build only (scripts/build_w63_variants.sh): wave 0 of every workgroup stamps s_memtime at the
-#endif                    // phase boundaries of its first V6_STAMP_TILES tiles into a buffer of its own (tl_debug_v6_stamps reads it)
-#if V6_STAMP
-constexpr int V6_STAMP_TILES = 96, V6_STAMP_SLOTS = 16;
-__device__ unsigned long long v6_stamp_buf[256 * V6_STAMP_TILES * V6_STAMP_SLOTS];
-#define V6_STAMP_AT(k)                                                                                                         \
-  do {                                                                                                                         \
-    if (tid == 0 && stamp_tile < V6_STAMP_TILES && blockIdx.x < 256)                                                           \
-      v6_stamp_buf[((long long)blockIdx.x * V6_STAMP_TILES + stamp_tile) * V6_STAMP_SLOTS + (k)] =                             \
-          ((k) == 0 || (k) == 7) ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime();                           \
-  } while (0)
-#else
-#define V6_STAMP_AT(k) do { } while (0)
-#endif
 
-#ifndef V6_GY_SIX
-#define V6_GY_SIX 1          // 0: the eight-batch K loop for epilogue 7 as well (A/B partner)
-#endif
 template <int EPI>
 __global__ __launch_bounds__(512, 2) void wino63v_nt_kernel(const tl_nt_params p) {
   __shared__ __attribute__((aligned(1024))) char lds[3 * V6_STAGE + ((EPI == W_EPI_POOLV || EPI == W_EPI_MASKY || EPI == W_EPI_GY) ? 4096 : EPI == W_EPI_C1W ? 16384 : 0)];
@@ -275,11 +248,6 @@ __global__ __launch_bounds__(512, 2) void wino63v_nt_kernel(const tl_nt_params p
   const int wm = wave >> 1, wn = wave & 1;
   const int lr = lane & 31, lh = lane >> 5;
 
-#if V6_PRIO
-  // static priority for the second-dispatched half of the workgroup (MI355X_MICROARCH.md, two waves per SIMD, item 4): waves
-  // 4-7 are the SIMD partners of waves 0-3 and lose the issue arbitration by age on every segment
-  if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
   const int ntn = (p.N + V6_BN - 1) / V6_BN;
   const long long ntm = (p.M + V6_ROWS - 1) / V6_ROWS;
   const long long nwg = ntm * ntn;
@@ -289,7 +257,7 @@ __global__ __launch_bounds__(512, 2) void wino63v_nt_kernel(const tl_nt_params p
   constexpr bool SEG3 = EPI == W_EPI_LRELU;
   // EPI == GY (tl_conv1_wino63v_dgrad_nt): transforms 6, 7 of both operands are zero - the six-batch K loop (V6K6_*: half-set H =
   // transforms 4, 5; 24 MFMAs per K-step), and waves 6, 7 fetch through empty resources (their planes are never read)
-  constexpr bool SIX = EPI == W_EPI_GY && V6_GY_SIX;
+  constexpr bool SIX = EPI == W_EPI_GY;
   const int kseg = p.K / V6_BK;                            // K-steps per segment (host-checked: K % 8 == 0)
   const int nsteps = SEG3 ? 3 * kseg : kseg;               // host-checked: >= 5
   // Accumulators and fragments live in FIXED registers (tonal_wino63_kloop.h: v0 - v127, v128 - v191): every K-step is one asm
@@ -437,8 +405,8 @@ __global__ __launch_bounds__(512, 2) void wino63v_nt_kernel(const tl_nt_params p
   };
   // The reads of H between L's MFMAs: one per MFMA in the first half of L's window, so that the last eight MFMAs cover their
   // latency behind the barrier - for the conv2 launches (POOLV, fused conv1 gradient: -0.5 / -0.4 ms, same-call A/B, twice);
-  // the instantiations of conv3 (POOL, MASKY) measured +0.2 ms with it and keep one read per two MFMAs (V6_RDSCHED forces one)
-  constexpr bool early = V6_RDSCHED == 1 || (V6_RDSCHED < 0 && (EPI == W_EPI_POOLV || EPI == W_EPI_C1W));
+  // the instantiations of conv3 (POOL, MASKY) measured +0.2 ms with it and keep one read per two MFMAs
+  constexpr bool early = EPI == W_EPI_POOLV || EPI == W_EPI_C1W;
   constexpr int NST = v6_stores<EPI>();
   constexpr int first_n = NST + 6 > 63 ? 63 : NST + 6;
   constexpr int first_wait = (first_n & 15) | (7 << 4) | (0 << 8) | ((first_n >> 4) << 14);       // vmcnt(n) lgkmcnt(0)
@@ -447,15 +415,10 @@ __global__ __launch_bounds__(512, 2) void wino63v_nt_kernel(const tl_nt_params p
   issue(cur, 0, 0);
   issue(cur, 1, 1);
   __builtin_amdgcn_s_waitcnt(0x0f70);                       // vmcnt(0)
-#if V6_STAMP
-  int stamp_tile = 0;
-#endif
   for (long long vb = blockIdx.x; vb < nwg; vb += gridDim.x) {
     // stage stg of this tile has landed (waited for at the end of the tile in front), every wave is past that epilogue
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    V6_STAMP_AT(0);
-    V6_STAMP_AT(1);
     // What the epilogue reads from global memory is requested in front of the LAST K-step (tonal_wino43v.hip)
     auto prefetch = [&] {
       if constexpr (EPI == W_EPI_POOL || EPI == W_EPI_POOLV || EPI == W_EPI_LRELU) return v5_prefetch_pool(p, cur.n0, wn, lr);
@@ -483,7 +446,6 @@ __global__ __launch_bounds__(512, 2) void wino63v_nt_kernel(const tl_nt_params p
     // once: across a branch with two successors the allocator moves the pinned values out of their registers and back)
     V6K_RUN(STEP1, _STEP1, cur, 3, stg == 0 ? 2 : stg - 1, 0);
     stg = next3(stg);
-    V6_STAMP_AT(2);
     {
       int s = 2;
       do {
@@ -491,25 +453,13 @@ __global__ __launch_bounds__(512, 2) void wino63v_nt_kernel(const tl_nt_params p
         stg = next3(stg);
       } while (++s + 2 < nsteps);
     }
-    V6_STAMP_AT(3);
     V6K_RUN(PRELAST, , cur, 0, 0, 0);
     stg = next3(stg);
     pre = prefetch();
     V6K_RUN(LAST, , cur, 0, 0, 0);
     stg = next3(stg);
 #undef V6K_RUN
-    V6_STAMP_AT(4);
 
-#if V6_ABL & 2
-    {
-      float t = 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) t += acc[i][e];
-      if (t == 12345.678f) p.out[tid] = t;
-    }
-#endif
     // The first two K-steps of the next tile go into the two stages that are NOT the last step's: stg (read in step
     // nsteps - 3) and stg + 1 (step nsteps - 2) - every wave is past the barrier that closed step nsteps - 2.  The last
     // step's stage (stg + 2) is still being read by slower waves; it is the epilogue's scratch behind a barrier.
@@ -524,23 +474,16 @@ __global__ __launch_bounds__(512, 2) void wino63v_nt_kernel(const tl_nt_params p
       issue(cur, 1, next3(stg));
     }
     __builtin_amdgcn_sched_barrier(0);
-#if V6_STAMP
-    unsigned long long* est = (tid == 0 && stamp_tile < V6_STAMP_TILES && blockIdx.x < 256)
-                                  ? v6_stamp_buf + ((long long)blockIdx.x * V6_STAMP_TILES + stamp_tile) * V6_STAMP_SLOTS : nullptr;
-#else
-    constexpr unsigned long long* est = nullptr;
-#endif
-#if !(V6_ABL & 2)
     float* scratch = reinterpret_cast<float*>(lds + last_stage * V6_STAGE);
     (void)scratch;
     const bool full = done.R0 + V6_ROWS <= p.M && done.n0 + V6_BN <= p.N;
     if constexpr (EPI == W_EPI_POOL) {
-      if (full) v6_epilogue_pool<false, true>(p, acc, pre, nullptr, done.R0, done.n0, wm, wn, lr, lh, done.tm, est);
-      else v6_epilogue_pool<false, false>(p, acc, pre, nullptr, done.R0, done.n0, wm, wn, lr, lh, done.tm, est);
+      if (full) v6_epilogue_pool<false, true>(p, acc, pre, nullptr, done.R0, done.n0, wm, wn, lr, lh, done.tm);
+      else v6_epilogue_pool<false, false>(p, acc, pre, nullptr, done.R0, done.n0, wm, wn, lr, lh, done.tm);
     } else if constexpr (EPI == W_EPI_POOLV) {
       float* xch = reinterpret_cast<float*>(lds + 3 * V6_STAGE);
-      if (full) v6_epilogue_pool<true, true>(p, acc, pre, xch, done.R0, done.n0, wm, wn, lr, lh, done.tm, est);
-      else v6_epilogue_pool<true, false>(p, acc, pre, xch, done.R0, done.n0, wm, wn, lr, lh, done.tm, est);
+      if (full) v6_epilogue_pool<true, true>(p, acc, pre, xch, done.R0, done.n0, wm, wn, lr, lh, done.tm);
+      else v6_epilogue_pool<true, false>(p, acc, pre, xch, done.R0, done.n0, wm, wn, lr, lh, done.tm);
     } else if constexpr (EPI == W_EPI_LRELU) {
       if (full) v6_epilogue_lrelu<true>(p, acc, pre, done.R0, done.n0, wm, wn, lr, lh);
       else v6_epilogue_lrelu<false>(p, acc, pre, done.R0, done.n0, wm, wn, lr, lh);
@@ -549,48 +492,25 @@ __global__ __launch_bounds__(512, 2) void wino63v_nt_kernel(const tl_nt_params p
       else v6_epilogue_mask<false>(p, acc, pre, done.R0, done.n0, wm, wn, lr, lh);
     } else if constexpr (EPI == W_EPI_MASKY) {
       float* xch = reinterpret_cast<float*>(lds + 3 * V6_STAGE);
-      if (full) v6_epilogue_masky<true>(p, acc, pre, xch, done.R0, done.n0, wm, wn, lr, lh, done.tm, est);
-      else v6_epilogue_masky<false>(p, acc, pre, xch, done.R0, done.n0, wm, wn, lr, lh, done.tm, est);
+      if (full) v6_epilogue_masky<true>(p, acc, pre, xch, done.R0, done.n0, wm, wn, lr, lh, done.tm);
+      else v6_epilogue_masky<false>(p, acc, pre, xch, done.R0, done.n0, wm, wn, lr, lh, done.tm);
     } else if constexpr (EPI == W_EPI_GY) {
       float* xch = reinterpret_cast<float*>(lds + 3 * V6_STAGE);
-      if (full) v6_epilogue_masky<true, true>(p, acc, pre, xch, done.R0, done.n0, wm, wn, lr, lh, done.tm, est);
-      else v6_epilogue_masky<false, true>(p, acc, pre, xch, done.R0, done.n0, wm, wn, lr, lh, done.tm, est);
+      if (full) v6_epilogue_masky<true, true>(p, acc, pre, xch, done.R0, done.n0, wm, wn, lr, lh, done.tm);
+      else v6_epilogue_masky<false, true>(p, acc, pre, xch, done.R0, done.n0, wm, wn, lr, lh, done.tm);
     } else {
       v6_epilogue_c1w(p, acc, pre, reinterpret_cast<float*>(lds + 3 * V6_STAGE) + wave * 512, scratch, done.R0, done.n0, wm, wn,
                       lr, lh, done.tm);
     }
-#endif
-    V6_STAMP_AT(5);
     {
       // The next tile's first stage (issued in front of the epilogue) has landed; its second stage and the epilogue's own
       // stores need not: vmcnt counts in issue order (6 bits)
       constexpr int n = NST + 6 > 63 ? 63 : NST + 6;
       __builtin_amdgcn_s_waitcnt((n & 15) | (7 << 4) | (15 << 8) | ((n >> 4) << 14));
     }
-    V6_STAMP_AT(6);
-    V6_STAMP_AT(7);
-#if V6_STAMP
-    ++stamp_tile;
-#endif
   }
 }
 
-#if V6_STAMP
-}  // namespace tl
-// diagnostic build only: the stamps of the last wino63v_nt launch (256 workgroups x 96 tiles x 16 slots; 8.. inside the epilogue: realtime (100 MHz) at the
-// tile's first barrier, s_memtime there / after K-step 1 / after the steady-state loop / at the end of the K loop / at the
-// end of the epilogue's instruction stream / behind its closing wait, realtime there)
-extern "C" int tl_debug_v6_stamps(unsigned long long* dst, int clear) {
-  if (dst && hipMemcpyFromSymbol(dst, HIP_SYMBOL(tl::v6_stamp_buf), sizeof(tl::v6_stamp_buf)) != hipSuccess) return -1;
-  if (clear) {
-    void* p = nullptr;
-    if (hipGetSymbolAddress(&p, HIP_SYMBOL(tl::v6_stamp_buf)) != hipSuccess) return -1;
-    if (hipMemset(p, 0, sizeof(tl::v6_stamp_buf)) != hipSuccess) return -1;
-  }
-  return 0;
-}
-namespace tl {
-#endif
 
 
 // ------------------------------------------------------------------------------------------
@@ -614,9 +534,6 @@ constexpr int T6_TILE = 8 * T6_PLANE;                     // floats per operand 
 constexpr int T6_NA = 4, T6_NG = 6;
 constexpr int T6_GW = T6_H * 4 * 64;                      // floats of gradient rows per raw slot (6 hexes x 4 rows x 64)
 constexpr int T6_GT = T6_GW + 64;                         // + 6 x 4 rows x 2 words (48 of 64 four-byte lanes)
-#ifndef T6_ABL
-#define T6_ABL 0           // timing-only: 1 no V pieces, 2 no G piece, 4 no Vd stores, 8 no transform, 16 no barrier
-#endif
 
 template <bool WVD>
 __global__ __launch_bounds__(512, 1) void wino63v_tn_kernel(const tl_tn_params p, int mtn) {
@@ -827,10 +744,8 @@ __global__ __launch_bounds__(512, 1) void wino63v_tn_kernel(const tl_tn_params p
     const f32x4 vb4 = {v[4], v[5], v[6], v[7]};
     const bool ok = ywave && h < hs_lim;
     const unsigned hoff = (unsigned)((h - h_first) >> 1) * vd_pstride + (unsigned)((h - h_first) & 1) * 32u;
-    if (!(T6_ABL & 4)) {
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u32, va4), rsVd, ok ? hoff + vdA_lane : 0xfffffff0u, 0u, 2);
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u32, vb4), rsVd, ok ? hoff + vdB_lane : 0xfffffff0u, 0u, 2);
-    }
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u32, va4), rsVd, ok ? hoff + vdA_lane : 0xfffffff0u, 0u, 2);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u32, vb4), rsVd, ok ? hoff + vdB_lane : 0xfffffff0u, 0u, 2);
   };
   // the row in front of this wave's hex at step sd: row 2 of the piece in front (hex wave - 1; for wave 0 the last hex
   // of the previous step, still in the ring)
@@ -907,8 +822,8 @@ __global__ __launch_bounds__(512, 1) void wino63v_tn_kernel(const tl_tn_params p
     const int abuf = s & (NA - 1), bbuf = s & 1;
     const int slot0 = slot1 == 0 ? NG - 1 : slot1 - 1;
     __builtin_amdgcn_sched_barrier(0);
-    if (!(T6_ABL & 1)) issue_v(s + 3);
-    if (!(T6_ABL & 2)) issue_g(slot4);
+    issue_v(s + 3);
+    issue_g(slot4);
     load_frag(fa0, fb0, abuf, bbuf, 0);
     mfma8(fac, fbc);                                        // slice 2 of the previous step
     load_frag(fa1, fb1, abuf, bbuf, 1);
@@ -916,7 +831,7 @@ __global__ __launch_bounds__(512, 1) void wino63v_tn_kernel(const tl_tn_params p
     __builtin_amdgcn_sched_barrier(0);
     // second half: the transform of step s + 1 beside the MFMAs of slice 1
     load_frag(fac, fbc, abuf, bbuf, 2);
-    if (ywave && !(T6_ABL & 8)) {                           // (wave-uniform: waves 6, 7 own no hex)
+    if (ywave) {                                            // (wave-uniform: waves 6, 7 own no hex)
       y_in yn;
       fetch_y(s + 1, slot1, yn);
       const y_out un = compute_y(s + 1, yn);
@@ -935,9 +850,7 @@ __global__ __launch_bounds__(512, 1) void wino63v_tn_kernel(const tl_tn_params p
     // everything issued up to step s - 2 has landed: V(s + 1), G(s + 2).  In flight: the 4 pieces of this step and of the
     // one before (a Vd store among them only makes the wait reach further back)
     __builtin_amdgcn_s_waitcnt(0x0078);                           // vmcnt(8) lgkmcnt(0)
-#if !(T6_ABL & 16)
     __builtin_amdgcn_s_barrier();
-#endif
     asm volatile("" ::: "memory");
     slot1 = next6(slot1);
     slot4 = next6(slot4);
@@ -1133,16 +1046,10 @@ __global__ __launch_bounds__(512, 1) void wino63v_tn4_kernel(const tl_tn_params 
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
       y.g[q] = r.g[q];
-#if T6_ABL & 64
-      (void)live;
-      y.mo[q] = 0x5555555555555555ull;                        // timing only: no word broadcast, no row validity
-      y.me[q] = 0xaaaaaaaaaaaaaaaaull;
-#else
       const unsigned long long w = uni(r.w[q]);
       const int v = live & (tq + 2 * q < p.Tvalid);
       y.mo[q] = v ? w : 0ull;
       y.me[q] = v ? ~w : 0ull;
-#endif
     }
     y.tq = tq;
     tq += dstep;
@@ -1217,10 +1124,8 @@ __global__ __launch_bounds__(512, 1) void wino63v_tn4_kernel(const tl_tn_params 
     const f32x4 vb4 = {v[4], v[5], v[6], v[7]};
     const bool ok = ywave && h < hs_lim;
     const unsigned hoff = (unsigned)((h - h_first) >> 1) * vd_pstride + (unsigned)((h - h_first) & 1) * 32u;
-    if (!(T6_ABL & 4)) {
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u32, va4), rsVd, ok ? hoff + vdA_lane : 0xfffffff0u, 0u, 2);
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u32, vb4), rsVd, ok ? hoff + vdB_lane : 0xfffffff0u, 0u, 2);
-    }
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u32, va4), rsVd, ok ? hoff + vdA_lane : 0xfffffff0u, 0u, 2);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u32, vb4), rsVd, ok ? hoff + vdB_lane : 0xfffffff0u, 0u, 2);
   };
   // the row in front of this wave's hex at step sd: row 2 of the piece in front (hex wave - 1; for wave 0 the last hex
   // of the previous step, still in the ring)
@@ -1304,8 +1209,8 @@ __global__ __launch_bounds__(512, 1) void wino63v_tn4_kernel(const tl_tn_params 
     __builtin_amdgcn_sched_barrier(0);
     // first half: the pieces of steps s + 3 / s + 4 go out, the raw gradient rows and words of step s + 1 are read from
     // the ring (they return under the 16 MFMAs), the carried slice and slice 0 run
-    if (!(T6_ABL & 1)) issue_v(s + 3);
-    if (!(T6_ABL & 2)) issue_g(slot4);
+    issue_v(s + 3);
+    issue_g(slot4);
     y_raw yr;
     fetch_raw(slot1, yr);
     load_frag(fa0, fb0, abuf, bbuf, 0);
@@ -1325,10 +1230,8 @@ __global__ __launch_bounds__(512, 1) void wino63v_tn4_kernel(const tl_tn_params 
     load_frag(fac, fbc, abuf, bbuf, 2);
     y_in yn;
     y_out un = {};
-    if (!(T6_ABL & 8)) {
-      masks_y(s + 1, yr, yn);
-      un = compute_y(s + 1, yn);
-    }
+    masks_y(s + 1, yr, yn);
+    un = compute_y(s + 1, yn);
     mfma8(fa1, fb1);
     __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
 #pragma unroll
@@ -1339,7 +1242,7 @@ __global__ __launch_bounds__(512, 1) void wino63v_tn4_kernel(const tl_tn_params 
     }
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (write_vd) {
-      if (ywave && turn == mi && s + 1 < nsteps && !(T6_ABL & (8 | 32))) {     // (wave-uniform; every nslots-th step)
+      if (ywave && turn == mi && s + 1 < nsteps) {                             // (wave-uniform; every nslots-th step)
         float gp;
         unsigned long long wp;
         front_row(slot1, slot0, gp, wp);
@@ -1350,9 +1253,7 @@ __global__ __launch_bounds__(512, 1) void wino63v_tn4_kernel(const tl_tn_params 
     // everything issued up to step s - 2 has landed: V(s + 1), G(s + 2).  In flight: the 4 pieces of this step and of the
     // one before (a Vd store among them only makes the wait reach further back)
     __builtin_amdgcn_s_waitcnt(0x0078);                           // vmcnt(8) lgkmcnt(0)
-#if !(T6_ABL & 16)
     __builtin_amdgcn_s_barrier();
-#endif
     asm volatile("" ::: "memory");
     slot1 = next6(slot1);
     slot4 = next6(slot4);
@@ -1436,9 +1337,7 @@ __global__ __launch_bounds__(512, 1) void wino63v_tn4y_kernel(const tl_tn_params
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1, lr = lane & 31, lh = lane >> 5;
-#if V6_PRIO
-  if (wave >= 4) __builtin_amdgcn_s_setprio(1);             // (static priority for the younger half: see wino63v_nt_kernel)
-#endif
+  // s_setprio 1 for waves 4-7 (the younger half): +0.5 ms here, noise in wino63v_nt_kernel, r04_kernel_notes.md
   const int ntn = p.Ndim / T6_BN;
   const long long tiles = 2LL * mtn * ntn;
   const long long nwg = tiles * p.splitk;
@@ -1531,7 +1430,7 @@ __global__ __launch_bounds__(512, 1) void wino63v_tn4y_kernel(const tl_tn_params
   for (int s = 0; s < nsteps; ++s) {
     const int buf = s & (NA - 1);
     __builtin_amdgcn_sched_barrier(0);
-    if (!(T6_ABL & 1)) issue(s + 3);
+    issue(s + 3);
     load_frag(fa0, fb0, buf, 0);
     mfma8(fac, fbc);                                        // slice 2 of the previous step
     load_frag(fa1, fb1, buf, 1);
@@ -1555,9 +1454,7 @@ __global__ __launch_bounds__(512, 1) void wino63v_tn4y_kernel(const tl_tn_params
     }
     // everything issued up to step s + 1 has landed; the 4 pieces of steps s + 2 and s + 3 may fly
     __builtin_amdgcn_s_waitcnt(0x0078);                           // vmcnt(8) lgkmcnt(0)
-#if !(T6_ABL & 16)
     __builtin_amdgcn_s_barrier();
-#endif
     asm volatile("" ::: "memory");
   }
   mfma8(fac, fbc);
@@ -1709,9 +1606,6 @@ __global__ void wino63_weights1_kernel(const float* __restrict__ w, float* __res
 // runs half a KB apart, non-temporal - ran at 0.65 TB/s: 27.9 ms for the 18 GB of V1.)
 // ------------------------------------------------------------------------------------------
 constexpr int C1_MAXKT = 8;
-#ifndef C1V_TEST
-#define C1V_TEST 0
-#endif
 template <int KT>
 __global__ __launch_bounds__(256) void conv1_fwd_vh_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                            const float* __restrict__ b, float* __restrict__ P,
@@ -1801,42 +1695,9 @@ __global__ __launch_bounds__(256) void conv1_fwd_vh_kernel(const float* __restri
 #pragma unroll
         for (int j = 0; j < 8; ++j) ov[j][k] = vv[j];
       }
-#if C1V_TEST == 1
-      float* dst = V + (h0 + q) * 8LL * C1 + o;               // timing only: channels-last rows
-#pragma unroll
-      for (int j = 0; j < 8; ++j) *reinterpret_cast<f32x4*>(dst + (long long)j * C1) = ov[j];
-#elif C1V_TEST == 2
-      float* dst = V + v6_at(h0 + q, 0, o, C1 >> 3);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) __builtin_nontemporal_store(ov[j], reinterpret_cast<f32x4*>(dst + 16 * j));
-#elif C1V_TEST == 3
-      (void)ov;                                               // timing only: no V stores
-      if (o == 12345) V[0] = ov[0][0] + ov[7][3];
-#elif C1V_TEST == 4
-      // timing experiment: whole 128-byte lines per store instruction.  The eight lanes of two neighbouring chunks trade
-      // transforms through a half-row mirror (lane i <-> 7 - i): the even chunk's lanes keep the even transform of a pair of
-      // transforms and write the odd chunk's even transform at the mirror lane's position, and the other way round
-      const int upper = (tl_ >> 2) & 1;
-      const int om = 8 * (kc ^ 1) + 4 * (half ^ 1);
-      float* dst = V + v6_at(h0 + q, 0, o, C1 >> 3) + 16 * upper;
-      float* mdst = V + v6_at((h0 + q) ^ 1, 0, om, C1 >> 3) + 16 * upper;
-#pragma unroll
-      for (int s2 = 0; s2 < 4; ++s2) {
-        f32x4 own, got;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float send = upper ? ov[2 * s2][k] : ov[2 * s2 + 1][k];
-          own[k] = upper ? ov[2 * s2 + 1][k] : ov[2 * s2][k];
-          got[k] = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, send), 0x141, 0xf, 0xf, false));
-        }
-        *reinterpret_cast<f32x4*>((upper ? mdst : dst) + 32 * s2) = upper ? got : own;      // the even chunk's line
-        *reinterpret_cast<f32x4*>((upper ? dst : mdst) + 32 * s2) = upper ? own : got;      // the odd chunk's line
-      }
-#else
       float* dst = V + v6_at(h0 + q, 0, o, C1 >> 3);          // (pair layout: transform j of these four channels at + 16 j)
 #pragma unroll
       for (int j = 0; j < 8; ++j) *reinterpret_cast<f32x4*>(dst + 16 * j) = ov[j];
-#endif
     }
   }
 }
