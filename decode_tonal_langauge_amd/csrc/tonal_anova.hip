@@ -1,0 +1,259 @@
+// Channel selection: one-way ANOVA at every (channel, timepoint) column, and the longest significant run per channel
+// (reference channel_selection/active.py:58-76, discriminative.py:171-180, utils.py:4-30 - scipy.stats.f_oneway in a Python
+// loop over channels).  An (n_samples, C, T) recording is C*T independent columns, each reduced over the samples: one
+// streaming pass.  All arithmetic is fp64; see include/tonal_hip.h for the contracts.
+#include "tonal_common.h"
+#include <math.h>
+
+namespace tl {
+
+// ------------------------------------------------------------------------------------------
+// per-group column sums.  A lane owns a column (loads coalesce along cols) and walks the group's index list, which is
+// wave-uniform, MOM_UNROLL rows in flight.  One group per launch keeps one accumulator pair in registers (an accumulator
+// array indexed by label would be a dynamic register index, i.e. scratch).  The sums are taken of x - shift[col]: scipy
+// subtracts the overall mean before it squares, and raw sums of a recording with mean 1e4 and unit variance lose 8 digits
+// in ss_within.
+// ------------------------------------------------------------------------------------------
+#define MOM_UNROLL 8
+
+template <typename T>
+__global__ __launch_bounds__(256) void group_moments_kernel(const T* __restrict__ x, const T* __restrict__ shift,
+                                                            const int32_t* __restrict__ idx, int n, long long n_rows,
+                                                            long long cols, int chunk, double* __restrict__ sum,
+                                                            double* __restrict__ sumsq) {
+  const long long col = blockIdx.x * 256LL + threadIdx.x;
+  if (col >= cols) return;
+  const int s = blockIdx.y;
+  const int i0 = s * chunk;
+  const int i1 = i0 + chunk < n ? i0 + chunk : n;
+  const double sh = (double)shift[col];
+  const double bad = __builtin_nan("");
+  double a = 0.0, q = 0.0;
+  int i = i0;
+  for (; i + MOM_UNROLL <= i1; i += MOM_UNROLL) {
+    double v[MOM_UNROLL];
+#pragma unroll
+    for (int u = 0; u < MOM_UNROLL; ++u) {
+      const long long r = idx[i + u];
+      v[u] = (r >= 0 && r < n_rows) ? (double)x[r * cols + col] : bad;       // the test is wave-uniform
+    }
+#pragma unroll
+    for (int u = 0; u < MOM_UNROLL; ++u) {
+      const double d = v[u] - sh;
+      a += d;
+      q = fma(d, d, q);
+    }
+  }
+  for (; i < i1; ++i) {
+    const long long r = idx[i];
+    const double d = ((r >= 0 && r < n_rows) ? (double)x[r * cols + col] : bad) - sh;
+    a += d;
+    q = fma(d, d, q);
+  }
+  sum[(long long)s * cols + col] = a;
+  sumsq[(long long)s * cols + col] = q;
+}
+
+// ------------------------------------------------------------------------------------------
+// F survival function: p = I_x(a, b), a = dfw/2, b = dfb/2, x = dfw/(dfw + dfb F), y = 1 - x formed by the caller as
+// dfb F/(dfw + dfb F) (1.0 - x would lose y below 1e-16 and every digit of a p close to 1).
+// ------------------------------------------------------------------------------------------
+// Stirling's correction lgamma(z) - ((z - 1/2) log z - z + log(2 pi)/2); the truncation is below 1e-16 for z >= 16
+__host__ __device__ inline double stirling_corr(double z) {
+  const double r = 1.0 / z, r2 = r * r;
+  return r * (1.0 / 12 - r2 * (1.0 / 360 - r2 * (1.0 / 1260 - r2 * (1.0 / 1680 - r2 * (1.0 / 1188 - r2 * (691.0 / 360360))))));
+}
+// log B(a, b) = lgamma(a) + lgamma(b) - lgamma(a + b).  With dfw/2 in the hundreds the three terms are near 1e3 and cancel
+// to a few units, which would cost three digits of p; for max(a, b) >= 16 the difference lgamma(hi) - lgamma(hi + lo) is
+// taken analytically from Stirling's series instead.
+__host__ __device__ inline double log_beta(double a, double b) {
+  const double lo = a < b ? a : b, hi = a < b ? b : a;
+  if (hi < 16.0) return lgamma(a) + lgamma(b) - lgamma(a + b);
+  return lgamma(lo) - (hi - 0.5) * log1p(lo / hi) - lo * log(hi + lo) + lo + (stirling_corr(hi) - stirling_corr(hi + lo));
+}
+// continued fraction of the incomplete beta function, modified Lentz; converges fast for x < (a + 1)/(a + b + 2)
+__host__ __device__ inline double beta_cf(double a, double b, double x) {
+  const double tiny = 1e-300, qab = a + b, qap = a + 1.0, qam = a - 1.0;
+  double c = 1.0, d = 1.0 - qab * x / qap;
+  if (fabs(d) < tiny) d = tiny;
+  d = 1.0 / d;
+  double h = d;
+  for (int m = 1; m <= 2000; ++m) {
+    const double m2 = 2.0 * m;
+    double aa = m * (b - m) * x / ((qam + m2) * (a + m2));
+    d = 1.0 + aa * d;
+    if (fabs(d) < tiny) d = tiny;
+    c = 1.0 + aa / c;
+    if (fabs(c) < tiny) c = tiny;
+    d = 1.0 / d;
+    h *= d * c;
+    aa = -(a + m) * (qab + m) * x / ((a + m2) * (qap + m2));
+    d = 1.0 + aa * d;
+    if (fabs(d) < tiny) d = tiny;
+    c = 1.0 + aa / c;
+    if (fabs(c) < tiny) c = tiny;
+    d = 1.0 / d;
+    const double del = d * c;
+    h *= del;
+    if (fabs(del - 1.0) < 2e-16) break;
+  }
+  return h;
+}
+// the prefactor x^a y^b / B(a, b) is built in log space: a p of 1e-80 and below keeps its relative accuracy
+__host__ __device__ inline double f_survival(double F, double dfb, double dfw) {
+  if (F != F || dfb <= 0.0 || dfw <= 0.0 || F < 0.0) return __builtin_nan("");
+  const double den = dfw + dfb * F;
+  if (den > 1.7e308) return 0.0;                  // F = inf (ssw = 0 under ssb > 0), or dfb F overflows
+  if (F == 0.0) return 1.0;
+  const double a = 0.5 * dfw, b = 0.5 * dfb, x = dfw / den, y = dfb * F / den;
+  const double pre = exp(a * log(x) + b * log(y) - log_beta(a, b));
+  if (x < (a + 1.0) / (a + b + 2.0)) return pre * beta_cf(a, b, x) / a;
+  return 1.0 - pre * beta_cf(b, a, y) / b;
+}
+
+struct AnovaCounts { int32_t n[64]; };
+
+// sum / sumsq (k, splits, cols): the split slabs of a group are added here.  With S_g, Q_g the shifted sums of group g,
+// ssb = sum_g n_g (S_g/n_g - S/N)^2 and ssw = sum_g (Q_g - S_g^2/n_g) - both invariant under the shift; the group sums are
+// read twice rather than kept in an array indexed by g (a dynamic register index).
+__global__ __launch_bounds__(256) void anova_finalize_kernel(const double* __restrict__ sum, const double* __restrict__ sumsq,
+                                                             AnovaCounts cnt, int k, int splits, long long cols, long long N,
+                                                             double* __restrict__ F, double* __restrict__ p) {
+  const long long col = blockIdx.x * 256LL + threadIdx.x;
+  if (col >= cols) return;
+  double S = 0.0;
+  for (int g = 0; g < k; ++g)
+    for (int s = 0; s < splits; ++s) S += sum[((long long)g * splits + s) * cols + col];
+  const double mean = S / (double)N;
+  double ssb = 0.0, ssw = 0.0;
+  for (int g = 0; g < k; ++g) {
+    double Sg = 0.0, Qg = 0.0;
+    for (int s = 0; s < splits; ++s) {
+      Sg += sum[((long long)g * splits + s) * cols + col];
+      Qg += sumsq[((long long)g * splits + s) * cols + col];
+    }
+    const double ng = (double)cnt.n[g], mg = Sg / ng, d = mg - mean;
+    ssb = fma(ng * d, d, ssb);
+    ssw += Qg - Sg * mg;
+  }
+  const double dfb = (double)(k - 1), dfw = (double)(N - k);
+  double f = __builtin_nan(""), pv = __builtin_nan("");
+  if (N > k) {
+    f = (ssb / dfb) / (ssw / dfw);
+    pv = f_survival(f, dfb, dfw);
+  }
+  F[col] = f;
+  p[col] = pv;
+}
+
+// ------------------------------------------------------------------------------------------
+// longest run of p < thr per row: one wave per row, lane l owns elements [l chunk, (l + 1) chunk) and reduces them to
+// (pre, suf, best, len) = (run at the start, run at the end, longest run, elements); segments combine associatively and an
+// empty segment (all zero) is the identity, so lanes beyond T need no special case.
+// The lanes of a wave read with a stride of chunk doubles - uncoalesced, and fine for what this serves: p is (C, T) of a few hundred
+// timepoints, about a megabyte, read once.  For rows of many thousands of points walk the row 64 elements at a time (coalesced) with a
+// per-lane carry instead of copying this layout.
+// ------------------------------------------------------------------------------------------
+struct RunSeg { int pre, suf, best, len, cnt; };
+
+__device__ __forceinline__ RunSeg run_combine(const RunSeg& L, const RunSeg& R) {
+  RunSeg o;
+  o.pre = L.pre == L.len ? L.len + R.pre : L.pre;
+  o.suf = R.suf == R.len ? R.len + L.suf : R.suf;
+  const int mid = L.suf + R.pre;
+  o.best = L.best > R.best ? L.best : R.best;
+  o.best = o.best > mid ? o.best : mid;
+  o.len = L.len + R.len;
+  o.cnt = L.cnt + R.cnt;
+  return o;
+}
+
+__global__ __launch_bounds__(256) void max_run_below_kernel(const double* __restrict__ p, int C, long long T, double thr,
+                                                            int32_t* __restrict__ count, int32_t* __restrict__ maxrun) {
+  const int lane = threadIdx.x & 63;
+  const long long row = blockIdx.x * 4LL + (threadIdx.x >> 6);
+  if (row >= C) return;                                        // whole waves leave: the shuffles below see 64 live lanes
+  const long long chunk = (T + 63) / 64;
+  long long t0 = lane * chunk, t1 = t0 + chunk;
+  if (t0 > T) t0 = T;
+  if (t1 > T) t1 = T;
+  const double* pr = p + row * T;
+  RunSeg s = {0, 0, 0, (int)(t1 - t0), 0};
+  int run = 0;
+  bool open = true;                                            // no element at or above thr seen yet
+  for (long long t = t0; t < t1; ++t) {
+    if (pr[t] < thr) {                                         // false for NaN
+      ++run;
+      ++s.cnt;
+      if (run > s.best) s.best = run;
+    } else {
+      if (open) { s.pre = run; open = false; }
+      run = 0;
+    }
+  }
+  if (open) s.pre = run;
+  s.suf = run;
+  for (int d = 1; d < 64; d <<= 1) {
+    RunSeg r;
+    r.pre = __shfl_down(s.pre, d, 64);
+    r.suf = __shfl_down(s.suf, d, 64);
+    r.best = __shfl_down(s.best, d, 64);
+    r.len = __shfl_down(s.len, d, 64);
+    r.cnt = __shfl_down(s.cnt, d, 64);
+    s = run_combine(s, r);                                     // exact in the lanes that are multiples of 2d; lane 0 at the end
+  }
+  if (lane == 0) {
+    count[row] = s.cnt;
+    maxrun[row] = s.best;
+  }
+}
+
+}  // namespace tl
+using namespace tl;
+
+extern "C" int tl_group_moments(const void* x, int is_f64, int64_t n_rows, int64_t cols, const int32_t* idx, int n,
+                                const void* shift, int splits, double* sum, double* sumsq, void* stream) {
+  TL_REQUIRE(x && idx && shift && sum && sumsq, "group_moments: null pointer");
+  TL_REQUIRE(n >= 1 && n_rows >= 1 && cols >= 1, "group_moments: n, n_rows and cols must be at least 1");
+  TL_REQUIRE(splits >= 1 && splits <= 1024, "group_moments: splits must lie in [1, 1024]");
+  const long long blocks = (cols + 255) / 256;
+  TL_REQUIRE(blocks <= 0x7fffffffLL, "group_moments: too many columns");
+  const int chunk = (n + splits - 1) / splits;
+  dim3 grid((unsigned)blocks, (unsigned)splits);
+  hipStream_t st = (hipStream_t)stream;
+  if (is_f64)
+    hipLaunchKernelGGL((group_moments_kernel<double>), grid, dim3(256), 0, st, (const double*)x, (const double*)shift, idx, n,
+                       (long long)n_rows, (long long)cols, chunk, sum, sumsq);
+  else
+    hipLaunchKernelGGL((group_moments_kernel<float>), grid, dim3(256), 0, st, (const float*)x, (const float*)shift, idx, n,
+                       (long long)n_rows, (long long)cols, chunk, sum, sumsq);
+  return check_launch("group_moments");
+}
+
+extern "C" int tl_anova_finalize(const double* sum, const double* sumsq, const int32_t* counts, int k, int splits, int64_t cols,
+                                 double* F, double* p, void* stream) {
+  TL_REQUIRE(sum && sumsq && counts && F && p, "anova_finalize: null pointer");
+  TL_REQUIRE(k >= 2 && k <= 64, "anova_finalize: the number of groups k must lie in [2, 64]");
+  TL_REQUIRE(cols >= 1, "anova_finalize: cols must be at least 1");
+  TL_REQUIRE(splits >= 1 && splits <= 1024, "anova_finalize: splits must lie in [1, 1024]");
+  const long long blocks = (cols + 255) / 256;
+  TL_REQUIRE(blocks <= 0x7fffffffLL, "anova_finalize: too many columns");
+  AnovaCounts cnt = {};
+  long long N = 0;
+  for (int g = 0; g < k; ++g) {
+    TL_REQUIRE(counts[g] >= 1, "anova_finalize: every group needs at least one sample");
+    cnt.n[g] = counts[g];
+    N += counts[g];
+  }
+  hipLaunchKernelGGL(anova_finalize_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, sum, sumsq, cnt, k, splits,
+                     (long long)cols, N, F, p);
+  return check_launch("anova_finalize");
+}
+
+extern "C" int tl_max_run_below(const double* p, int C, int64_t T, double thr, int32_t* count, int32_t* maxrun, void* stream) {
+  TL_REQUIRE(p && count && maxrun, "max_run_below: null pointer");
+  TL_REQUIRE(C >= 1 && T >= 1 && T <= 0x7fffffffLL, "max_run_below: C and T must be at least 1");
+  hipLaunchKernelGGL(max_run_below_kernel, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p, C, (long long)T, thr,
+                     count, maxrun);
+  return check_launch("max_run_below");
+}

@@ -511,6 +511,28 @@ int tl_car(const void* x, int is_f64, const int32_t* include, void* y, int C, in
 /* pandas rolling(window, min_periods=1) z-score, sample std (rolling_zscore.py:36-49); y float64   */
 int tl_rolling_zscore(const void* x, int is_f64, double* y, int C, int64_t T, int window, int zero_nans, void* stream);
 
+/* ---- channel selection: one-way ANOVA at every (channel, timepoint) column (channel_selection/active.py:58-76,
+ * channel_selection/discriminative.py:171-180 run scipy.stats.f_oneway per channel).  x is (n_rows, cols) row-major with
+ * cols = C*T contiguous, float32 or float64 (is_f64); all arithmetic is fp64.
+ *
+ * per-group column sums: for the n samples idx[0..n) (int32, device; each in [0, n_rows), anything else poisons the
+ * column with NaN) of ONE group,  sum[s][col] = sum_i (x[idx[i]][col] - shift[col])  and  sumsq[s][col] = the same of the
+ * squares; shift is a row of cols values of x's dtype close to the data (any row of x), and must be the same row for
+ * every group of one test.  The samples are cut into `splits` contiguous parts (grid.y), part s writes slab s:
+ * sum and sumsq are (splits, cols) float64.  1 <= splits <= 1024                                                          */
+int tl_group_moments(const void* x, int is_f64, int64_t n_rows, int64_t cols, const int32_t* idx, int n, const void* shift,
+                     int splits, double* sum, double* sumsq, void* stream);
+/* F statistic and p-value from the sums of k groups: sum / sumsq are (k, splits, cols) float64 as written above, counts
+ * a HOST array of the k group sizes (each >= 1; it travels in the kernel arguments).  F = (ssb/(k-1)) / (ssw/(N-k)),
+ * p = the F survival function I_x((N-k)/2, (k-1)/2), x = (N-k)/((N-k) + (k-1) F), evaluated on the device (continued
+ * fraction, log-space prefactor).  Degenerate columns as IEEE gives them and scipy returns them: NaN in -> NaN, ssw = 0 with
+ * ssb > 0 -> (inf, 0), both 0 -> NaN, N <= k -> NaN.  2 <= k <= 64                                                       */
+int tl_anova_finalize(const double* sum, const double* sumsq, const int32_t* counts, int k, int splits, int64_t cols,
+                      double* F, double* p, void* stream);
+/* per row of p (C, T) float64: count[c] = number of p < thr, maxrun[c] = longest run of consecutive p < thr (NaN is not
+ * below) - channel_selection/utils.py:4-30 per channel; one wave per row.  count / maxrun are (C) int32                   */
+int tl_max_run_below(const double* p, int C, int64_t T, double thr, int32_t* count, int32_t* maxrun, void* stream);
+
 /* FFT resampling = scipy.signal.resample(x, num, axis=1) (downsample.py:21-27): Bluestein chirp-z on
  * power-of-two FFTs.  Host-prepared coefficient arrays (complex128 interleaved): w1 (nx) / w2 (num)
  * chirps exp(i pi m^2 / n); bf1 (m2a) / bf2 (m2b) spectra of the chirp filters; tw1 (m2a/2) / tw2
