@@ -46,6 +46,12 @@ from ..._lib import check, ptr
 
 _MAX_TAPS_LDS = 7169      # (1024 + ntap - 1) * 8 B <= 64 KiB
 _OLS_N = 1024             # FFT length of the overlap-save path (tl_hilbert_ols)
+_MAX_ROWS = 65535         # channels per call of the time-domain and overlap-save kernels: one grid row each (tl_hilbert_fft chunks)
+
+
+def _check_rows(C: int, what: str) -> None:
+    if C > _MAX_ROWS:
+        raise ValueError(f"{what}: {C} channels; the band kernels take at most {_MAX_ROWS} per call (split the recording by rows)")
 
 
 def _device() -> torch.device:
@@ -261,6 +267,7 @@ def hilbert_filter(data, sampling_rate: int, freq_ranges: Union[List[Tuple[float
             raise ValueError(f"hilbert_filter: the band kernels need {ntap} taps at this sampling rate; the time-domain "
                              f"kernel supports up to {_MAX_TAPS_LDS} (TONAL_KERNELS hilbert={mode} forbids the DFT-domain path)")
         return _ret(_hilbert_dft(x, sampling_rate, cfs, sds, bool(envelope)), was_np)
+    _check_rows(C, "hilbert_filter")
     y = torch.empty(C, T, dtype=torch.float64, device=x.device)
     # hilbert = auto: the first form below that the bank / recording allows; ols, ols_full, sym, taps force one
     if ols is not None and ols[3] is not None and mode in ("auto", "ols"):
@@ -407,6 +414,7 @@ def fir_bandpass_filter(data, fs: float, order: int, center_frequencies: List[fl
         squeeze = True
     x, was_np = _to_device(data)
     C, T = x.shape
+    _check_rows(C, "fir_bandpass_filter")
     use_ols = T >= _OLS_N                      # (shorter recordings: the time-domain kernel, tl_fir_bank)
     coef, nb, ntap, ols = _fir_coefficients(float(fs), int(order), tuple(float(f) for f in center_frequencies), bool(use_ols),
                                             x.device)

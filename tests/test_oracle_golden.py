@@ -463,3 +463,37 @@ def test_flip_checker_rejects_corrupted_planes_and_accepts_a_near_tie():
         for fn in (lambda v: torch.roll(v, 1, dims=1), invert_word, zero_last_row_tile):     # shifted, inverted, zero tile
             with pytest.raises(AssertionError, match=re.escape(k + ":")):
                 check_flips(corrupted(k, fn), own, margins)
+
+
+BAND_REF_CASES = [(400, [70., 150.], 5003), (500, [70., 150.], 1024), (512, [70., 150.], 2449), (1000, [70., 150.], 5003),
+                  (2000, [70., 150.], 1024), (400, [30., 70.], 1025), (1000, [150., 300.], 1000), (400, [70., 199.], 7169),
+                  (400, [1., 4.], 7170)]
+
+
+def test_band_filter_references_are_pinned_to_extended_precision():
+    """The references tests/test_gpu_band_filters.py holds the kernels to: the float64 Hilbert oracle within 1e-12 of the
+    ``np.longdouble`` statement of the same function on zero-mean noise and on a DC level of 1000 standard deviations
+    (observed 7.6e-16 and 6.7e-13; the deviation grows with the level, which is why the GPU test takes the longdouble
+    statement itself at an offset), over nine (rate, range, length) cases that cover every row kind of its decision table;
+    ``scipy.signal.lfilter`` per band and the oracle's FIR bank within 1e-14 of a longdouble ``np.convolve``."""
+    from tests.signal_refs import band_cases, fir_bank_longdouble, hilbert_filter_longdouble, scipy_fir_bank
+    assert np.finfo(np.longdouble).eps < 1e-18, "np.longdouble is not an extended format on this platform"
+
+    def relq(a, b):
+        return float(np.max(np.abs(a.astype(np.longdouble) - b)) / np.max(np.abs(b)))
+
+    for off in (0.0, 1e3):
+        worst = 0.0
+        for fs, fr, T in BAND_REF_CASES:
+            x = band_cases(np.random.default_rng(T), 4, T, offset=off)
+            for env in (True, False):
+                d = relq(sg.hilbert_filter(x, fs, fr, envelope=env), hilbert_filter_longdouble(x, fs, fr, envelope=env))
+                assert d < 1e-12, (off, fs, fr, T, env, d)
+                worst = max(worst, d)
+        print(f"float64 Hilbert oracle vs longdouble, offset {off:g} sd: {worst:.2e}")
+    x = band_cases(np.random.default_rng(1), 3, 700, offset=1e3)
+    for order, cfs in ((64, [60., 120.]), (390, [100.])):
+        taps = sg.fir_taps(400, order, cfs)
+        ref = fir_bank_longdouble(x, taps)
+        assert relq(scipy_fir_bank(x, taps), ref) < 1e-14
+        assert relq(sg.fir_bandpass_filter(x, 400, order, cfs), ref) < 1e-14
