@@ -82,10 +82,14 @@ def _build_classifier(name: str, n_channels: int, seq_length: int, n_classes: in
 
 def _mels_from_dataset(dataset, params, mel_kwargs) -> np.ndarray:
     """Mel targets: a pre-computed 'mel' array of the sample file, else the audio of every sample through
-    ``utils.audio.audio_to_mel`` (reference train_synthesizer.py:189-201)."""
+    ``utils.audio.audio_to_mel`` (reference train_synthesizer.py:189-201) - on a CUDA device the whole ``audio`` array in one
+    ``audio_to_mel_batch`` call, on 'cpu' trial by trial on the host."""
     if 'mel' in dataset:
         return np.asarray(dataset['mel'], dtype=np.float32)
-    from .utils.audio import audio_to_mel
+    from .utils.audio import audio_to_mel, audio_to_mel_batch
+    if 'cuda' in str(params.device):
+        return audio_to_mel_batch(np.asarray(dataset['audio']), params.audio_sampling_rate, mel_kwargs=mel_kwargs,
+                                  device=params.device)
     return np.array([audio_to_mel(audio, params.audio_sampling_rate, mel_kwargs=mel_kwargs) for audio in dataset['audio']])
 
 

@@ -20,6 +20,7 @@ synthesis trainer consumes its output (mel targets), nothing here runs per train
 """
 from __future__ import annotations
 
+import functools
 from typing import Optional
 
 import numpy as np
@@ -143,6 +144,110 @@ def audio_to_mel(audio: np.ndarray, audio_sampling_rate: int, mel_in_db: bool = 
     if mel_in_db:
         mel = power_to_db(mel, ref=np.max)
     return mel.astype(np.float32).reshape(-1)
+
+
+# ------------------------------------------------------------------------------------------ the same, a batch on the GPU
+MEL_BATCH_N_FFT = (256, 512, 1024, 2048)
+
+
+def pack_mel_filterbank(fb: np.ndarray):
+    """A dense (n_mels, n_bins) bank as per-band runs: ``bands`` (n_mels, 3) int32 = first bin, one past the last non-zero
+    bin, offset of the run in ``weights`` (float64, the float32 values widened).  A triangle touches a short run of bins."""
+    bands = np.zeros((fb.shape[0], 3), dtype=np.int32)
+    runs, off = [], 0
+    for m, row in enumerate(fb):
+        nz = np.flatnonzero(row)
+        first, last = (int(nz[0]), int(nz[-1]) + 1) if nz.size else (0, 0)
+        bands[m] = (first, last, off)
+        runs.append(row[first:last].astype(np.float64))
+        off += last - first
+    return bands, (np.concatenate(runs) if off else np.zeros(0))
+
+
+@functools.lru_cache(maxsize=8)
+def _mel_batch_tables(device: str, sr: float, n_fft: int, win_length: int, n_mels: int, fmin: float, fmax: Optional[float]):
+    """Device copies of the per-call tables of ``tl_mel_power``: window (as ``stft`` builds it), twiddles, packed bank."""
+    import torch
+    win = np.zeros(n_fft)
+    off = (n_fft - win_length) // 2
+    win[off:off + win_length] = _hann(win_length)
+    ang = 2.0 * np.pi * np.arange(n_fft) / n_fft
+    tw = np.stack([np.cos(ang), -np.sin(ang)], axis=1)
+    bands, weights = pack_mel_filterbank(mel_filterbank(sr, n_fft, n_mels=n_mels, fmin=fmin, fmax=fmax))
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    # an empty tensor has no device pointer: keep one weight so the entry point always gets an address
+    return up(win), up(tw), up(bands), up(weights if weights.size else np.zeros(1)), int(weights.size)
+
+
+def audio_to_mel_batch(audio, audio_sampling_rate: int, mel_in_db: bool = True, mel_kwargs: Optional[dict] = None,
+                       device=None):
+    """``audio_to_mel`` of every row of an (N, S) batch in two kernel launches (``tl_mel_power``, ``tl_mel_finish``): row n of
+    the (N, n_mels * n_frames) float32 result is ``audio_to_mel(audio[n], ...)`` up to float32 rounding, the dB reference
+    being each trial's own maximum.  NumPy in (float32 / float64 kept, anything else becomes float64) -> NumPy out; CUDA
+    tensor in -> CUDA tensor out on its device.  ``n_fft`` must be one of ``MEL_BATCH_N_FFT``.  No CPU fallback."""
+    import torch
+    from .. import _lib
+    is_tensor = isinstance(audio, torch.Tensor)
+    if not is_tensor:
+        audio = np.asarray(audio)
+    if audio.ndim != 2:
+        raise ValueError("Audio input must be a 2D array (trials, samples).")
+    stft_kw, power, mel_kw = _split_kwargs(mel_kwargs)
+    n_fft = stft_kw.get("n_fft", 2048)
+    if n_fft not in MEL_BATCH_N_FFT:
+        raise ValueError(f"n_fft = {n_fft} is not supported on the GPU (supported: {', '.join(map(str, MEL_BATCH_N_FFT))})")
+    n_fft = int(n_fft)
+    hop = n_fft // 4 if stft_kw.get("hop_length") is None else int(stft_kw["hop_length"])
+    wl = n_fft if stft_kw.get("win_length") is None else int(stft_kw["win_length"])
+    center = bool(stft_kw.get("center", True))
+    n_mels = int(mel_kw.get("n_mels", 128))
+    if not 1 <= wl <= n_fft:
+        raise ValueError(f"win_length = {wl} must lie in [1, n_fft = {n_fft}]")
+    if hop < 1:
+        raise ValueError(f"hop_length = {hop} must be at least 1")
+    if power not in (1, 2):
+        raise ValueError(f"power = {power} is not supported on the GPU (supported: 1, 2)")
+    if n_mels < 1:
+        raise ValueError(f"n_mels = {n_mels} must be at least 1")
+    N, S = int(audio.shape[0]), int(audio.shape[1])
+    if N < 1:
+        raise ValueError("Audio input holds no trial.")
+    padded = S + n_fft if center else S
+    if padded < n_fft or S < 1:
+        raise ValueError(f"audio of {padded} samples is shorter than n_fft = {n_fft}")
+    n_frames = 1 + (padded - n_fft) // hop
+
+    if is_tensor:
+        _lib.require_gpu(audio, "audio_to_mel_batch")
+        x = audio if audio.dtype in (torch.float32, torch.float64) else audio.double()
+        if x.stride(1) != 1 or (N > 1 and x.stride(0) < S):
+            x = x.contiguous()
+    else:
+        if not torch.cuda.is_available():
+            raise RuntimeError("audio_to_mel_batch (MI355X build): no GPU visible; this package has no CPU fallback")
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError(f"audio_to_mel_batch: device '{dev}' is not a CUDA device; this package has no CPU fallback")
+        if audio.dtype not in (np.float32, np.float64):
+            audio = audio.astype(np.float64)
+        x = torch.from_numpy(np.array(audio, order="C")).to(dev)          # a copy: read-only arrays upload without a warning
+    dev = x.device
+    fmax = mel_kw.get("fmax")
+    win, tw, bands, weights, n_weights = _mel_batch_tables(
+        str(dev), float(audio_sampling_rate), n_fft, wl, n_mels, float(mel_kw.get("fmin", 0.0)),
+        None if fmax is None else float(fmax))
+    work = torch.empty(N, n_mels, n_frames, dtype=torch.float64, device=dev)
+    rowmax = torch.empty(N, dtype=torch.float64, device=dev)
+    out = torch.empty(N, n_mels * n_frames, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        _lib.check(lib.tl_mel_power(x.data_ptr(), int(x.dtype == torch.float64), x.stride(0) if N > 1 else S, win.data_ptr(),
+                                    tw.data_ptr(), bands.data_ptr(), weights.data_ptr(), n_weights, work.data_ptr(),
+                                    rowmax.data_ptr(), N, S, n_fft, wl, hop, int(center), int(power), n_mels, n_frames,
+                                    _lib.stream_ptr()), "tl_mel_power")
+        _lib.check(lib.tl_mel_finish(work.data_ptr(), rowmax.data_ptr(), out.data_ptr(), N, n_mels, n_frames,
+                                     int(bool(mel_in_db)), _lib.stream_ptr()), "tl_mel_finish")
+    return out if is_tensor else out.cpu().numpy()
 
 
 def griffinlim(mag: np.ndarray, n_iter: int = 32, hop_length: Optional[int] = None, win_length: Optional[int] = None,

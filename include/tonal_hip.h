@@ -533,6 +533,26 @@ int tl_anova_finalize(const double* sum, const double* sumsq, const int32_t* cou
  * below) - channel_selection/utils.py:4-30 per channel; one wave per row.  count / maxrun are (C) int32                   */
 int tl_max_run_below(const double* p, int C, int64_t T, double thr, int32_t* count, int32_t* maxrun, void* stream);
 
+/* ---- mel-spectrogram targets of a batch of trials (utils/audio.py audio_to_mel, one trial at a time on the host):
+ * STFT -> |X|^power -> mel bank -> dB, two launches, fp64 throughout, float32 at the final store.
+ *
+ * audio is (N, S) float32 or float64 (audio_is_f64) with row_stride elements between trials.  Frame f of a trial covers the
+ * samples f*hop - (center ? n_fft/2 : 0) + [0, n_fft); samples outside [0, S) read as zero (no padded copy).  window
+ * (n_fft) float64 = periodic Hann of win_length, zero-padded and centred to n_fft; tw (n_fft, 2) float64 = (cos, -sin)
+ * (2 pi i / n_fft); the mel bank as per-band runs: bands (n_mels, 3) int32 = {first bin, one past the last bin, offset of
+ * the run's first weight in weights}, weights (n_weights) float64 (a run outside [0, n_fft/2 + 1) or outside weights makes
+ * its band NaN).  Writes mel (N, n_mels, n_frames) float64 and rowmax (N) float64 = each trial's maximum (cleared here).
+ * n_fft in {256, 512, 1024, 2048}, 1 <= win_length <= n_fft, hop >= 1, power 1 or 2, n_mels >= 1, and
+ * n_frames == 1 + (S + (center ? n_fft : 0) - n_fft) / hop                                                              */
+int tl_mel_power(const void* audio, int audio_is_f64, int64_t row_stride, const double* window, const double* tw,
+                 const int32_t* bands, const double* weights, int n_weights, double* mel, double* rowmax, int N, int64_t S,
+                 int n_fft, int win_length, int hop, int center, int power, int n_mels, int64_t n_frames, void* stream);
+/* mel / rowmax as written above -> out (N, n_mels * n_frames) float32, band-major per trial.  in_db = 0: a cast; 1:
+ * 10 log10(max(1e-10, v)) - 10 log10(max(1e-10, rowmax[n])), clipped from below at the trial's largest dB value - 80
+ * (power_to_db(ref=np.max, top_db=80) per trial)                                                                      */
+int tl_mel_finish(const double* mel, const double* rowmax, float* out, int N, int n_mels, int64_t n_frames, int in_db,
+                  void* stream);
+
 /* FFT resampling = scipy.signal.resample(x, num, axis=1) (downsample.py:21-27): Bluestein chirp-z on
  * power-of-two FFTs.  Host-prepared coefficient arrays (complex128 interleaved): w1 (nx) / w2 (num)
  * chirps exp(i pi m^2 / n); bf1 (m2a) / bf2 (m2b) spectra of the chirp filters; tw1 (m2a/2) / tw2
