@@ -57,6 +57,7 @@ _P = C.c_void_p
 _I = C.c_int
 _L = C.c_int64
 _F = C.c_float
+_D = C.c_double
 
 #: every symbol include/tonal_hip.h declares -> (restype, argtypes)
 SIGNATURES = {
@@ -153,6 +154,10 @@ SIGNATURES = {
     "tl_max_run_below": (_I, [_P, _I, _L, C.c_double, _P, _P, _P]),
     "tl_mel_power": (_I, [_P, _I, _L, _P, _P, _P, _P, _I, _P, _P, _I, _L, _I, _I, _I, _I, _I, _I, _L, _P]),
     "tl_mel_finish": (_I, [_P, _P, _P, _I, _I, _L, _I, _P]),
+    "tl_mel_invert": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _L, _I, _D, _I, _P]),
+    "tl_gl_synth": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _L, _P]),
+    "tl_gl_analyse": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _L, _D, _I, _P]),
+    "tl_gl_overlap_add": (_I, [_P, _P, _P, _I, _I, _I, _I, _L, _L, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -17,6 +17,10 @@
 //            are non-negative doubles, whose order is the order of their bit patterns; max is order-independent).
 // LDS: 4 images of 1024 + 64 doubles = 34 KB -> four workgroups per CU.  The index padding d + (d >> 4) takes the stride-4
 // stores of the first pass off each other's banks (a 16-lane store group then covers 16 different bank pairs).
+//
+// The way back (utils/audio.py mel_to_audio_batch) is further down: tl_mel_invert (mel -> linear spectrum by FISTA, the whole
+// solve in LDS and registers) and Griffin-Lim as tl_gl_synth / tl_gl_analyse / tl_gl_overlap_add, whose inverse and forward
+// transforms are the mel_fft below (the inverse runs it on the conjugate).
 #include "tonal_common.h"
 #include <math.h>
 
@@ -40,47 +44,36 @@ __device__ __forceinline__ void mel_bfly(const double (&xr)[4], const double (&x
   yr[3] = t1r - t3r; yi[3] = t1i - t3i;
 }
 
-// bands (n_mels, 3) int32: first bin, one past the last bin, offset of the band's first weight in `weights`
-template <typename TIN, int LOG2M>
-__global__ __launch_bounds__(MEL_Q) void mel_power_kernel(const void* __restrict__ audio, long long row_stride, long long S,
-                                                          const mel_d2* __restrict__ window, const mel_d2* __restrict__ tw,
-                                                          const int32_t* __restrict__ bands, const double* __restrict__ weights,
-                                                          int n_weights, double* __restrict__ mel, double* __restrict__ rowmax,
-                                                          int blocks_per_trial, long long n_frames, int hop, int center,
-                                                          int power, int n_mels) {
-  constexpr int M = 1 << LOG2M, NFFT = 2 * M, F = MEL_PTS / M, Q = M / 4, NS4 = LOG2M / 2, HAS2 = LOG2M & 1;
-  constexpr int FIN = HAS2 ? (NS4 & 1) : ((NS4 - 1) & 1);    // the image that holds the transform
-  __shared__ __attribute__((aligned(16))) double lds[4 * MEL_PAD];
-  __shared__ double wmax[MEL_Q / 64];
-  double* re[2] = {lds, lds + 2 * MEL_PAD};
-  double* im[2] = {lds + MEL_PAD, lds + 3 * MEL_PAD};
-  const int tid = threadIdx.x, fl = tid >> (LOG2M - 2), j = tid & (Q - 1), fbase = fl * M;
-  const long long n = blockIdx.x / blocks_per_trial;
-  const long long frame0 = (long long)(blockIdx.x % blocks_per_trial) * F;
-  const long long frame = frame0 + fl;
-  const long long start = frame * hop - (center ? M : 0);
-  const long long row = n * row_stride;
+// ---- the M-point transform every kernel of this file shares (the inverse runs it on the conjugate)
+// the LDS image that holds the transform after the last pass
+constexpr int mel_fin(int log2m) { return (log2m & 1) ? ((log2m / 2) & 1) : ((log2m / 2 - 1) & 1); }
 
-  // the thread's twiddles of every pass, requested before the first barrier: one memory latency instead of one per pass
-  mel_d2 twr[NS4][3], tw2[2];
+// the thread's twiddles of every pass, requested before the first barrier: one memory latency instead of one per pass
+template <int LOG2M>
+struct MelTwiddles {
+  mel_d2 r4[LOG2M / 2][3], r2[2];
+};
+
+template <int LOG2M>
+__device__ __forceinline__ void mel_load_twiddles(const mel_d2* __restrict__ tw, int j, MelTwiddles<LOG2M>& t) {
+  constexpr int M = 1 << LOG2M, NFFT = 2 * M, Q = M / 4, NS4 = LOG2M / 2, HAS2 = LOG2M & 1;
 #pragma unroll
   for (int st = 1; st < NS4; ++st)
 #pragma unroll
-    for (int r = 1; r < 4; ++r) twr[st][r - 1] = tw[r * (j & ((1 << (2 * st)) - 1)) * (NFFT >> (2 * st + 2))];
+    for (int r = 1; r < 4; ++r) t.r4[st][r - 1] = tw[r * (j & ((1 << (2 * st)) - 1)) * (NFFT >> (2 * st + 2))];
   if (HAS2) {
-    tw2[0] = tw[2 * j];
-    tw2[1] = tw[2 * (j + Q)];
+    t.r2[0] = tw[2 * j];
+    t.r2[1] = tw[2 * (j + Q)];
   }
-  // ---- gather + window + first pass (Ns = 1, no twiddles) straight from registers
-  double xr[4], xi[4], yr[4], yi[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int m = j + r * Q;
-    const long long s0 = start + 2 * m, s1 = s0 + 1;
-    const mel_d2 w = window[m];
-    xr[r] = (frame < n_frames && s0 >= 0 && s0 < S) ? mel_ld<TIN>(audio, row + s0) * w[0] : 0.0;
-    xi[r] = (frame < n_frames && s1 >= 0 && s1 < S) ? mel_ld<TIN>(audio, row + s1) * w[1] : 0.0;
-  }
+}
+
+// FFT_M of the frame at fbase: the thread brings the points j + r M/4 in registers (the first pass, Ns = 1, has no twiddles and
+// never goes through LDS); the transform lands in natural order in image FIN of re / im; ends on a barrier
+template <int LOG2M>
+__device__ __forceinline__ void mel_fft(double (&xr)[4], double (&xi)[4], const MelTwiddles<LOG2M>& t, double* const (&re)[2],
+                                        double* const (&im)[2], int j, int fbase) {
+  constexpr int M = 1 << LOG2M, Q = M / 4, NS4 = LOG2M / 2, HAS2 = LOG2M & 1;
+  double yr[4], yi[4];
   mel_bfly(xr, xi, yr, yi);
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -99,7 +92,7 @@ __global__ __launch_bounds__(MEL_Q) void mel_power_kernel(const void* __restrict
     }
 #pragma unroll
     for (int r = 1; r < 4; ++r) {
-      const mel_d2 w = twr[st][r - 1];                       // W_{4 Ns}^{rk} = W_nfft^{rk nfft / 4 Ns} as (cos, -sin)
+      const mel_d2 w = t.r4[st][r - 1];                      // W_{4 Ns}^{rk} = W_nfft^{rk nfft / 4 Ns} as (cos, -sin)
       const double tr = fma(-xi[r], w[1], xr[r] * w[0]), ti = fma(xr[r], w[1], xi[r] * w[0]);
       xr[r] = tr;
       xi[r] = ti;
@@ -121,7 +114,7 @@ __global__ __launch_bounds__(MEL_Q) void mel_power_kernel(const void* __restrict
       const int jj = j + u * Q;
       const double ar = re[src][mel_idx(fbase + jj)], ai = im[src][mel_idx(fbase + jj)];
       const double br = re[src][mel_idx(fbase + jj + H)], bi = im[src][mel_idx(fbase + jj + H)];
-      const mel_d2 w = tw2[u];                               // W_M^jj
+      const mel_d2 w = t.r2[u];                              // W_M^jj
       const double tr = fma(-bi, w[1], br * w[0]), ti = fma(br, w[1], bi * w[0]);
       re[dst][mel_idx(fbase + jj)] = ar + tr;
       im[dst][mel_idx(fbase + jj)] = ai + ti;
@@ -130,16 +123,62 @@ __global__ __launch_bounds__(MEL_Q) void mel_power_kernel(const void* __restrict
     }
     __syncthreads();
   }
+}
+
+// bin k = 0..M of the real transform from the packed one Z: X[k] = E[k] + W_nfft^k O[k], E = (Z[k] + conj Z[M-k]) / 2,
+// O = (Z[k] - conj Z[M-k]) / 2i
+template <int LOG2M>
+__device__ __forceinline__ void mel_unpack_bin(const double* zr, const double* zi, const mel_d2* __restrict__ tw, int fbase, int k,
+                                               double& Xr, double& Xi) {
+  constexpr int M = 1 << LOG2M;
+  const int ka = k & (M - 1), kb = (M - k) & (M - 1);
+  const double ar = zr[mel_idx(fbase + ka)], ai = zi[mel_idx(fbase + ka)];
+  const double cr = zr[mel_idx(fbase + kb)], ci = zi[mel_idx(fbase + kb)];
+  const double er = 0.5 * (ar + cr), ei = 0.5 * (ai - ci);
+  const double orr = 0.5 * (ai + ci), oi = -0.5 * (ar - cr);
+  const mel_d2 w = tw[k];
+  Xr = er + fma(-oi, w[1], orr * w[0]);
+  Xi = ei + fma(orr, w[1], oi * w[0]);
+}
+
+// bands (n_mels, 3) int32: first bin, one past the last bin, offset of the band's first weight in `weights`
+template <typename TIN, int LOG2M>
+__global__ __launch_bounds__(MEL_Q) void mel_power_kernel(const void* __restrict__ audio, long long row_stride, long long S,
+                                                          const mel_d2* __restrict__ window, const mel_d2* __restrict__ tw,
+                                                          const int32_t* __restrict__ bands, const double* __restrict__ weights,
+                                                          int n_weights, double* __restrict__ mel, double* __restrict__ rowmax,
+                                                          int blocks_per_trial, long long n_frames, int hop, int center,
+                                                          int power, int n_mels) {
+  constexpr int M = 1 << LOG2M, F = MEL_PTS / M, Q = M / 4, FIN = mel_fin(LOG2M);
+  __shared__ __attribute__((aligned(16))) double lds[4 * MEL_PAD];
+  __shared__ double wmax[MEL_Q / 64];
+  double* re[2] = {lds, lds + 2 * MEL_PAD};
+  double* im[2] = {lds + MEL_PAD, lds + 3 * MEL_PAD};
+  const int tid = threadIdx.x, fl = tid >> (LOG2M - 2), j = tid & (Q - 1), fbase = fl * M;
+  const long long n = blockIdx.x / blocks_per_trial;
+  const long long frame0 = (long long)(blockIdx.x % blocks_per_trial) * F;
+  const long long frame = frame0 + fl;
+  const long long start = frame * hop - (center ? M : 0);
+  const long long row = n * row_stride;
+
+  MelTwiddles<LOG2M> twd;
+  mel_load_twiddles<LOG2M>(tw, j, twd);
+  // ---- gather + window + first pass (Ns = 1, no twiddles) straight from registers
+  double xr[4], xi[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int m = j + r * Q;
+    const long long s0 = start + 2 * m, s1 = s0 + 1;
+    const mel_d2 w = window[m];
+    xr[r] = (frame < n_frames && s0 >= 0 && s0 < S) ? mel_ld<TIN>(audio, row + s0) * w[0] : 0.0;
+    xi[r] = (frame < n_frames && s1 >= 0 && s1 < S) ? mel_ld<TIN>(audio, row + s1) * w[1] : 0.0;
+  }
+  mel_fft<LOG2M>(xr, xi, twd, re, im, j, fbase);
   // ---- unpack to the M + 1 bins of the real transform, |X|^power into the image nobody reads any more
   double* pw = re[FIN ^ 1];                                  // [F][M + 1], F (M + 1) <= 1032 doubles
   for (int k = j; k <= M; k += Q) {
-    const int ka = k & (M - 1), kb = (M - k) & (M - 1);
-    const double ar = re[FIN][mel_idx(fbase + ka)], ai = im[FIN][mel_idx(fbase + ka)];
-    const double cr = re[FIN][mel_idx(fbase + kb)], ci = im[FIN][mel_idx(fbase + kb)];
-    const double er = 0.5 * (ar + cr), ei = 0.5 * (ai - ci);
-    const double orr = 0.5 * (ai + ci), oi = -0.5 * (ar - cr);
-    const mel_d2 w = tw[k];
-    const double Xr = er + fma(-oi, w[1], orr * w[0]), Xi = ei + fma(orr, w[1], oi * w[0]);
+    double Xr, Xi;
+    mel_unpack_bin<LOG2M>(re[FIN], im[FIN], tw, fbase, k, Xr, Xi);
     const double p2 = fma(Xr, Xr, Xi * Xi);
     pw[fl * (M + 1) + k] = power == 2 ? p2 : sqrt(p2);
   }
@@ -204,6 +243,244 @@ __global__ __launch_bounds__(256) void mel_finish_kernel(const double* __restric
     v = db < floor_db ? floor_db : db;                       // np.maximum: NaN stays NaN
   }
   out[i] = (float)v;
+}
+
+
+// ---------------------------------------------------------------------------------------------- mel -> linear spectrum
+// min_{x >= 0} ||fb x - p||^2 per frame by FISTA (utils/audio.py mel_to_linear states it): 1024 / M frames per workgroup as
+// above.  Per iteration r = fb z - p is a reduction per (frame, band) over the band's run, four lanes each, and the gradient
+// fb^T r of a bin needs the at most two bands that cover it (bin_bands / bin_weights), so it is two multiplies per bin:
+// no search, no atomics.  z, r, p, the band table and the weights stay in LDS and x in registers for the whole solve; global
+// memory is read before the first iteration and written after the last, but for the iteration's momentum factor.
+constexpr int INV_MAX_MELS = 256, INV_MAX_WEIGHTS = 2 * (MEL_PTS + 1), INV_BINS = 5;   // 5 * 256 threads >= 1032 bins
+
+template <int LOG2M>
+__global__ __launch_bounds__(MEL_Q) void mel_invert_kernel(const double* __restrict__ p, const int32_t* __restrict__ bands,
+                                                           const double* __restrict__ weights, int n_weights,
+                                                           const int32_t* __restrict__ bin_bands,
+                                                           const double* __restrict__ bin_weights,
+                                                           const double* __restrict__ momentum, double* __restrict__ out,
+                                                           int blocks_per_trial, long long n_frames, int n_mels, int iters,
+                                                           double step, int power) {
+  // utils/audio.py bank_operators writes out the order of every sum and rounds every product and sum on its own; with no
+  // fused multiply-add here the kernel returns the bits of mel_to_linear
+#pragma clang fp contract(off)
+  constexpr int M = 1 << LOG2M, F = MEL_PTS / M, NB = M + 1;
+  __shared__ double zs[F * NB], rs[F * INV_MAX_MELS], ps[F * INV_MAX_MELS], ws[INV_MAX_WEIGHTS];
+  __shared__ int32_t bs[3 * INV_MAX_MELS];
+  const int tid = threadIdx.x, sub = tid & 3, total = F * n_mels;
+  const long long n = blockIdx.x / blocks_per_trial;
+  const long long frame0 = (long long)(blockIdx.x % blocks_per_trial) * F;
+
+  for (int i = tid; i < total; i += MEL_Q) {
+    const int f = i / n_mels, m = i - f * n_mels;
+    ps[i] = frame0 + f < n_frames ? p[(n * n_mels + m) * n_frames + frame0 + f] : 0.0;
+  }
+  for (int i = tid; i < n_weights; i += MEL_Q) ws[i] = weights[i];
+  // a run that leaves the spectrum or the weights is emptied here and its band comes out NaN: nothing reads out of bounds
+  bool bad = false;
+  for (int m = tid; m < n_mels; m += MEL_Q) {
+    const int first = bands[3 * m], last = bands[3 * m + 1], off = bands[3 * m + 2];
+    const bool sane = first >= 0 && first <= last && last <= NB && off >= 0 && (long long)off + (last - first) <= n_weights;
+    bs[3 * m] = sane ? first : 0;
+    bs[3 * m + 1] = sane ? last : 0;
+    bs[3 * m + 2] = sane ? off : 0;
+    bad |= !sane;
+  }
+  // the thread's bins: flat index tid + i * 256 over (frame, bin)
+  double x[INV_BINS], z[INV_BINS], gw[INV_BINS][2];
+  int gb[INV_BINS][2];
+#pragma unroll
+  for (int i = 0; i < INV_BINS; ++i) {
+    const int idx = tid + i * MEL_Q, f = idx / NB, k = idx - f * NB;
+    x[i] = z[i] = 0.0;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int b = idx < F * NB ? bin_bands[2 * k + u] : -1;
+      gw[i][u] = b >= 0 && b < n_mels ? bin_weights[2 * k + u] : 0.0;
+      gb[i][u] = b >= 0 && b < n_mels ? f * n_mels + b : 0;
+      bad |= b >= n_mels;
+    }
+    if (idx < F * NB) zs[idx] = 0.0;
+  }
+  __syncthreads();
+
+  double beta = momentum[0];
+  for (int it = 0; it < iters; ++it) {
+    const double beta_next = momentum[min(it + 1, iters - 1)];   // one uniform 8-byte load, a whole iteration ahead of its use
+    // ---- r = fb z - p: every lane runs every trip so the shuffles see whole groups
+    for (int trip = 0; trip * (MEL_Q / 4) < total; ++trip) {
+      const int item = trip * (MEL_Q / 4) + (tid >> 2);
+      const bool live = item < total;
+      const int f = live ? item / n_mels : 0, m = live ? item - f * n_mels : 0;
+      const int first = bs[3 * m], last = bs[3 * m + 1], off = bs[3 * m + 2];
+      double acc = 0.0;
+      if (live)
+        for (int k = first + sub; k < last; k += 4) acc = acc + ws[off + k - first] * zs[f * NB + k];
+      acc += __shfl_xor(acc, 1);                             // (s0 + s1) + (s2 + s3)
+      acc += __shfl_xor(acc, 2);
+      if (live && sub == 0) rs[item] = acc - ps[item];
+    }
+    __syncthreads();
+    // ---- x+ = max(z - step fb^T r, 0),  z+ = x+ + beta (x+ - x)
+#pragma unroll
+    for (int i = 0; i < INV_BINS; ++i) {
+      const int idx = tid + i * MEL_Q;
+      const double g = gw[i][0] * rs[gb[i][0]] + gw[i][1] * rs[gb[i][1]];
+      const double x_new = fmax(z[i] - step * g, 0.0);
+      z[i] = x_new + beta * (x_new - x[i]);
+      x[i] = x_new;
+      if (idx < F * NB) zs[idx] = z[i];
+    }
+    beta = beta_next;
+    __syncthreads();
+  }
+  bad = __syncthreads_or(bad);
+#pragma unroll
+  for (int i = 0; i < INV_BINS; ++i) {
+    const int idx = tid + i * MEL_Q, f = idx / NB, k = idx - f * NB;
+    if (idx < F * NB && frame0 + f < n_frames)
+      out[(n * NB + k) * n_frames + frame0 + f] = bad ? __builtin_nan("") : (power == 2 ? sqrt(x[i]) : x[i]);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- Griffin-Lim
+// One iteration = gl_synth_kernel (spectrum -> windowed frames) + gl_analyse_kernel (frames -> overlap-added signal ->
+// spectrum -> new phases); utils/audio.py griffinlim / istft / stft state it.  Both hold 1024 / M frames per workgroup as
+// mel_power_kernel does.  The overlap-add is a gather: sample q of the signal is the sum, frame by frame in rising order as
+// the host adds them, of the at most ceil(n_fft / hop) frames that cover it, over the window-square sum - no atomics, and the
+// same bits on every run.
+
+// sample q of the overlap-added signal of one trial, q counted from the start of frame 0 (the centre trim not yet applied)
+template <int NFFT>
+__device__ __forceinline__ double gl_sample(const double* __restrict__ fr, const double* __restrict__ wsum, long long q,
+                                            long long n_frames, int hop) {
+  const long long t0 = q >= NFFT ? (q - NFFT) / hop + 1 : 0, t1 = min(n_frames - 1, q / hop);
+  double acc = 0.0;
+  for (long long t = t0; t <= t1; ++t) acc += fr[t * NFFT + (q - t * hop)];
+  const double w = wsum[q];
+  return w > 1.1754943508222875e-38 ? acc / w : acc;        // istft: wsum > np.finfo(np.float32).tiny
+}
+
+// frames (N, T, n_fft) = irfft(mag * angles) * window.  The inverse real transform is the packed one run backwards:
+// Z[k] = E[k] + i O[k], E = (X[k] + conj X[M-k]) / 2, O = (X[k] - conj X[M-k]) / 2 * conj W_nfft^k, z = IFFT_M(Z) =
+// conj(FFT_M(conj Z)) / M, x[2m] = Re z[m], x[2m+1] = Im z[m].  mag is (N, T, M + 1), angles (T, M + 1) complex shared by all
+// trials (angle_stride 0) or (N, T, M + 1)
+template <int LOG2M>
+__global__ __launch_bounds__(MEL_Q) void gl_synth_kernel(const double* __restrict__ mag, const mel_d2* __restrict__ angles,
+                                                         long long angle_stride, const mel_d2* __restrict__ window,
+                                                         const mel_d2* __restrict__ tw, mel_d2* __restrict__ frames,
+                                                         int blocks_per_trial, long long n_frames) {
+  constexpr int M = 1 << LOG2M, F = MEL_PTS / M, Q = M / 4, FIN = mel_fin(LOG2M);
+  __shared__ __attribute__((aligned(16))) double lds[4 * MEL_PAD];
+  double* re[2] = {lds, lds + 2 * MEL_PAD};
+  double* im[2] = {lds + MEL_PAD, lds + 3 * MEL_PAD};
+  const int tid = threadIdx.x, fl = tid >> (LOG2M - 2), j = tid & (Q - 1), fbase = fl * M;
+  const long long n = blockIdx.x / blocks_per_trial;
+  const long long frame = (long long)(blockIdx.x % blocks_per_trial) * F + fl;
+  const bool live = frame < n_frames;
+  const double* mg = mag + (n * n_frames + frame) * (M + 1);
+  const mel_d2* an = angles + n * angle_stride + frame * (M + 1);
+
+  MelTwiddles<LOG2M> twd;
+  mel_load_twiddles<LOG2M>(tw, j, twd);
+  double xr[4], xi[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int m = j + r * Q, mc = M - m;
+    double ar = 0.0, ai = 0.0, cr = 0.0, ci = 0.0;
+    if (live) {
+      const double ma = mg[m], mb = mg[mc];
+      const mel_d2 pa = an[m], pb = an[mc];
+      ar = ma * pa[0];
+      ai = m == 0 ? 0.0 : ma * pa[1];                        // irfft reads the real parts of X[0] and X[M] only
+      cr = mb * pb[0];
+      ci = m == 0 ? 0.0 : mb * pb[1];
+    }
+    const double er = 0.5 * (ar + cr), ei = 0.5 * (ai - ci), dr = 0.5 * (ar - cr), di = 0.5 * (ai + ci);
+    const mel_d2 w = tw[m];                                  // (cos, -sin): conj W^m = (w0, -w1)
+    const double orr = fma(di, w[1], dr * w[0]), oi = fma(-dr, w[1], di * w[0]);
+    xr[r] = er - oi;                                         // conj Z, Z = E + i O
+    xi[r] = -(ei + orr);
+  }
+  mel_fft<LOG2M>(xr, xi, twd, re, im, j, fbase);
+  if (live) {
+    constexpr double inv_m = 1.0 / M;
+    mel_d2* dst = frames + (n * n_frames + frame) * M;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int m = j + r * Q;
+      const mel_d2 w = window[m];
+      mel_d2 v;
+      v[0] = re[FIN][mel_idx(fbase + m)] * inv_m * w[0];
+      v[1] = -im[FIN][mel_idx(fbase + m)] * inv_m * w[1];
+      dst[m] = v;
+    }
+  }
+}
+
+// frames -> signal (samples [M, M + length) of the overlap-add) -> stft with n_fft / 2 zeros on both sides -> rebuilt;
+// angles = rebuilt - coef * tprev (rebuilt alone on the first iteration), angles /= |angles| + 1e-16, tprev = rebuilt.
+// Frames from re_frames = 1 + length / hop on are past the rebuilt signal: zero
+template <int LOG2M>
+__global__ __launch_bounds__(MEL_Q) void gl_analyse_kernel(const double* __restrict__ frames, const double* __restrict__ wsum,
+                                                           const mel_d2* __restrict__ window, const mel_d2* __restrict__ tw,
+                                                           mel_d2* __restrict__ angles, mel_d2* __restrict__ tprev,
+                                                           int blocks_per_trial, long long n_frames, long long length,
+                                                           long long re_frames, int hop, double coef, int first) {
+  constexpr int M = 1 << LOG2M, NFFT = 2 * M, F = MEL_PTS / M, Q = M / 4, FIN = mel_fin(LOG2M);
+  __shared__ __attribute__((aligned(16))) double lds[4 * MEL_PAD];
+  double* re[2] = {lds, lds + 2 * MEL_PAD};
+  double* im[2] = {lds + MEL_PAD, lds + 3 * MEL_PAD};
+  const int tid = threadIdx.x, fl = tid >> (LOG2M - 2), j = tid & (Q - 1), fbase = fl * M;
+  const long long n = blockIdx.x / blocks_per_trial;
+  const long long frame = (long long)(blockIdx.x % blocks_per_trial) * F + fl;
+  const bool live = frame < n_frames && frame < re_frames;
+  const long long start = frame * hop - M;
+  const double* fr = frames + n * n_frames * NFFT;
+
+  MelTwiddles<LOG2M> twd;
+  mel_load_twiddles<LOG2M>(tw, j, twd);
+  double xr[4], xi[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int m = j + r * Q;
+    const long long s0 = start + 2 * m, s1 = s0 + 1;
+    const mel_d2 w = window[m];
+    xr[r] = (live && s0 >= 0 && s0 < length) ? gl_sample<NFFT>(fr, wsum, s0 + M, n_frames, hop) * w[0] : 0.0;
+    xi[r] = (live && s1 >= 0 && s1 < length) ? gl_sample<NFFT>(fr, wsum, s1 + M, n_frames, hop) * w[1] : 0.0;
+  }
+  mel_fft<LOG2M>(xr, xi, twd, re, im, j, fbase);
+  if (frame < n_frames)
+    for (int k = j; k <= M; k += Q) {
+      double Xr, Xi;
+      mel_unpack_bin<LOG2M>(re[FIN], im[FIN], tw, fbase, k, Xr, Xi);
+      if (k == 0 || k == M) Xi = 0.0;                        // exactly real, as rfft returns them
+      const long long idx = (n * n_frames + frame) * (M + 1) + k;
+      double ar = Xr, ai = Xi;
+      if (!first) {
+        const mel_d2 pv = tprev[idx];
+        ar = Xr - coef * pv[0];
+        ai = Xi - coef * pv[1];
+      }
+      const double d = sqrt(ar * ar + ai * ai) + 1e-16;
+      mel_d2 a, x;
+      a[0] = ar / d;
+      a[1] = ai / d;
+      x[0] = Xr;
+      x[1] = Xi;
+      angles[idx] = a;
+      tprev[idx] = x;
+    }
+}
+
+// out (N, length) = samples [M, M + length) of the overlap-add of frames (N, T, n_fft)
+template <int NFFT>
+__global__ __launch_bounds__(256) void gl_overlap_add_kernel(const double* __restrict__ frames, const double* __restrict__ wsum,
+                                                             double* __restrict__ out, long long n_frames, long long length,
+                                                             int hop) {
+  const long long s = blockIdx.x * 256LL + threadIdx.x, n = blockIdx.y;
+  if (s < length) out[n * length + s] = gl_sample<NFFT>(frames + n * n_frames * NFFT, wsum, s + NFFT / 2, n_frames, hop);
 }
 
 }  // namespace tl
@@ -283,4 +560,137 @@ extern "C" int tl_mel_finish(const double* mel, const double* rowmax, float* out
   hipLaunchKernelGGL(mel_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, mel, rowmax, out, per, total,
                      in_db);
   return check_launch("mel_finish");
+}
+
+// the checks the four entries of the inverse share; 0 = refused
+static int mel_inverse_args(const char* who, int N, int n_fft, int64_t n_frames, long long* bpt) {
+  const int log2m = mel_log2m(n_fft);
+  if (!log2m) {
+    tl::set_error("%s: n_fft must be one of 256, 512, 1024, 2048 (got %d)", who, n_fft);
+    return 0;
+  }
+  if (N < 1 || n_frames < 1) {
+    tl::set_error("%s: N and n_frames must be at least 1 (got %d, %lld)", who, N, (long long)n_frames);
+    return 0;
+  }
+  const int fpb = tl::MEL_PTS / (n_fft / 2);
+  *bpt = ((long long)n_frames + fpb - 1) / fpb;
+  if (n_frames > (1LL << 40) || *bpt * N > 0x7fffffffLL) {
+    tl::set_error("%s: too many frames for one launch", who);
+    return 0;
+  }
+  return log2m;
+}
+
+#define MEL_BY_SIZE(LAUNCH)   \
+  switch (log2m) {            \
+    case 7: LAUNCH(7); break; \
+    case 8: LAUNCH(8); break; \
+    case 9: LAUNCH(9); break; \
+    default: LAUNCH(10); break; \
+  }
+
+extern "C" int tl_mel_invert(const double* mel_power, const int32_t* bands, const double* weights, int n_weights,
+                             const int32_t* bin_bands, const double* bin_weights, const double* momentum, double* out, int N,
+                             int n_fft, int n_mels, int64_t n_frames, int nnls_iter, double step, int power, void* stream) {
+  TL_REQUIRE(mel_power && bands && weights && bin_bands && bin_weights && momentum && out, "mel_invert: null pointer");
+  long long bpt = 0;
+  const int log2m = mel_inverse_args("mel_invert", N, n_fft, n_frames, &bpt);
+  if (!log2m) return TL_EINVAL;
+  TL_REQUIRE(n_mels >= 1 && n_mels <= tl::INV_MAX_MELS, "mel_invert: n_mels must lie in [1, %d] (got %d)", tl::INV_MAX_MELS, n_mels);
+  TL_REQUIRE(n_weights >= 0 && n_weights <= n_fft + 2,
+             "mel_invert: n_weights must lie in [0, n_fft + 2]: at most two bands cover a bin (got %d)", n_weights);
+  TL_REQUIRE(nnls_iter >= 1, "mel_invert: nnls_iter must be at least 1 (got %d)", nnls_iter);
+  TL_REQUIRE(step > 0.0 && step < INFINITY, "mel_invert: step must be positive and finite");
+  TL_REQUIRE(power == 1 || power == 2, "mel_invert: power must be 1 or 2 (got %d)", power);
+  dim3 grid((unsigned)(bpt * N));
+#define INV_LAUNCH(L2M)                                                                                                   \
+  hipLaunchKernelGGL((mel_invert_kernel<L2M>), grid, dim3(MEL_Q), 0, (hipStream_t)stream, mel_power, bands, weights, n_weights,  \
+                     bin_bands, bin_weights, momentum, out, (int)bpt, (long long)n_frames, n_mels, nnls_iter, step, power)
+  MEL_BY_SIZE(INV_LAUNCH)
+#undef INV_LAUNCH
+  return check_launch("mel_invert");
+}
+
+extern "C" int tl_gl_synth(const double* mag, const double* angles, int angles_shared, const double* window, const double* tw,
+                           double* frames, int N, int n_fft, int64_t n_frames, void* stream) {
+  TL_REQUIRE(mag && angles && window && tw && frames, "gl_synth: null pointer");
+  long long bpt = 0;
+  const int log2m = mel_inverse_args("gl_synth", N, n_fft, n_frames, &bpt);
+  if (!log2m) return TL_EINVAL;
+  TL_REQUIRE(angles_shared == 0 || angles_shared == 1, "gl_synth: angles_shared must be 0 or 1");
+  const long long stride = angles_shared ? 0 : (long long)n_frames * (n_fft / 2 + 1);
+  dim3 grid((unsigned)(bpt * N));
+#define SYNTH_LAUNCH(L2M)                                                                                              \
+  hipLaunchKernelGGL((gl_synth_kernel<L2M>), grid, dim3(MEL_Q), 0, (hipStream_t)stream, mag,                              \
+                     reinterpret_cast<const mel_d2*>(angles), stride, reinterpret_cast<const mel_d2*>(window),            \
+                     reinterpret_cast<const mel_d2*>(tw), reinterpret_cast<mel_d2*>(frames), (int)bpt, (long long)n_frames)
+  MEL_BY_SIZE(SYNTH_LAUNCH)
+#undef SYNTH_LAUNCH
+  return check_launch("gl_synth");
+}
+
+// what istft keeps of n_frames frames after the centre trim: at most n_fft / 2 + hop (n_frames - 1) samples
+static int gl_signal_args(const char* who, int n_fft, int win_length, int hop, int64_t n_frames, int64_t length) {
+  if (win_length < 1 || win_length > n_fft) {
+    tl::set_error("%s: win_length must lie in [1, n_fft] (got %d)", who, win_length);
+    return 0;
+  }
+  if (hop < 1) {
+    tl::set_error("%s: hop must be at least 1 (got %d)", who, hop);
+    return 0;
+  }
+  if (hop > win_length) {
+    tl::set_error("%s: hop = %d > win_length = %d leaves gaps in the window-square sum", who, hop, win_length);
+    return 0;
+  }
+  const long long most = n_fft / 2 + (long long)hop * (n_frames - 1);
+  if (length < 1 || length > most) {
+    tl::set_error("%s: length = %lld disagrees with n_frames = %lld, n_fft and hop (1 .. %lld)", who, (long long)length,
+                  (long long)n_frames, most);
+    return 0;
+  }
+  return 1;
+}
+
+extern "C" int tl_gl_analyse(const double* frames, const double* wsum, const double* window, const double* tw, double* angles,
+                             double* tprev, int N, int n_fft, int win_length, int hop, int64_t n_frames, int64_t length,
+                             double momentum, int first, void* stream) {
+  TL_REQUIRE(frames && wsum && window && tw && angles && tprev, "gl_analyse: null pointer");
+  long long bpt = 0;
+  const int log2m = mel_inverse_args("gl_analyse", N, n_fft, n_frames, &bpt);
+  if (!log2m) return TL_EINVAL;
+  if (!gl_signal_args("gl_analyse", n_fft, win_length, hop, n_frames, length)) return TL_EINVAL;
+  TL_REQUIRE(momentum >= 0.0 && momentum < INFINITY, "gl_analyse: momentum must be finite and not negative");
+  TL_REQUIRE(first == 0 || first == 1, "gl_analyse: first must be 0 or 1");
+  const double coef = momentum / (1.0 + momentum);
+  const long long re_frames = 1 + length / hop;
+  dim3 grid((unsigned)(bpt * N));
+#define ANA_LAUNCH(L2M)                                                                                                \
+  hipLaunchKernelGGL((gl_analyse_kernel<L2M>), grid, dim3(MEL_Q), 0, (hipStream_t)stream, frames, wsum,                   \
+                     reinterpret_cast<const mel_d2*>(window), reinterpret_cast<const mel_d2*>(tw),                        \
+                     reinterpret_cast<mel_d2*>(angles), reinterpret_cast<mel_d2*>(tprev), (int)bpt, (long long)n_frames,  \
+                     (long long)length, re_frames, hop, coef, first)
+  MEL_BY_SIZE(ANA_LAUNCH)
+#undef ANA_LAUNCH
+  return check_launch("gl_analyse");
+}
+
+extern "C" int tl_gl_overlap_add(const double* frames, const double* wsum, double* out, int N, int n_fft, int win_length, int hop,
+                                 int64_t n_frames, int64_t length, void* stream) {
+  TL_REQUIRE(frames && wsum && out, "gl_overlap_add: null pointer");
+  long long bpt = 0;
+  const int log2m = mel_inverse_args("gl_overlap_add", N, n_fft, n_frames, &bpt);
+  if (!log2m) return TL_EINVAL;
+  if (!gl_signal_args("gl_overlap_add", n_fft, win_length, hop, n_frames, length)) return TL_EINVAL;
+  TL_REQUIRE(N <= 65535, "gl_overlap_add: at most 65535 trials per launch (got %d)", N);
+  const long long blocks = ((long long)length + 255) / 256;
+  TL_REQUIRE(blocks <= 0x7fffffffLL, "gl_overlap_add: length too large for one launch");
+  dim3 grid((unsigned)blocks, (unsigned)N);
+#define OLA_LAUNCH(L2M)                                                                                                 \
+  hipLaunchKernelGGL((gl_overlap_add_kernel<(2 << L2M)>), grid, dim3(256), 0, (hipStream_t)stream, frames, wsum, out,       \
+                     (long long)n_frames, (long long)length, hop)
+  MEL_BY_SIZE(OLA_LAUNCH)
+#undef OLA_LAUNCH
+  return check_launch("gl_overlap_add");
 }

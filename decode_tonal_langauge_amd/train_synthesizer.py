@@ -203,14 +203,23 @@ def train(params: Namespace) -> dict:
         print("Saved training losses figure to ", path)
     if params.audio_dir:
         np.savez(os.path.join(params.audio_dir, 'mels.npz'), origin=origin_mels[:10], recon=recon_mels[:10])
-        # the first samples as audio (reference :408-428): Griffin-Lim inversion of the original / synthesised dB mels
+        # the first samples as audio (reference :408-428): Griffin-Lim inversion of the original / synthesised dB mels - on a
+        # CUDA device all of them in one mel_to_audio_batch call, on 'cpu' trial by trial on the host
         from scipy.io.wavfile import write as write_wave
-        from .utils.audio import mel_to_audio
+        from .utils.audio import mel_to_audio, mel_to_audio_batch
         stft_kw = {k: mel_kwargs[k] for k in ("n_fft", "hop_length", "win_length", "fmin", "fmax") if k in mel_kwargs}
-        for i in range(min(int(getattr(params, "n_audio_samples", 10)), len(origin_mels))):
-            for tag, mel in (("origin", origin_mels[i]), ("recon", recon_mels[i])):
-                wave = mel_to_audio(np.asarray(mel), mel_kwargs['n_mels'], audio_sampling_rate=params.audio_sampling_rate,
-                                    **stft_kw)
+        n_audio = min(int(getattr(params, "n_audio_samples", 10)), len(origin_mels))
+        waves = None
+        if 'cuda' in str(params.device) and n_audio > 0:
+            # one call for all selected originals and reconstructions: rows [0, n_audio) origin, [n_audio, 2 n_audio) recon
+            both = np.concatenate([np.asarray(origin_mels[:n_audio]).reshape(n_audio, -1),
+                                   np.asarray(recon_mels[:n_audio]).reshape(n_audio, -1)])
+            waves = mel_to_audio_batch(both, mel_kwargs['n_mels'], audio_sampling_rate=params.audio_sampling_rate,
+                                       device=params.device, **stft_kw)
+        for i in range(n_audio):
+            for k, (tag, mel) in enumerate((("origin", origin_mels[i]), ("recon", recon_mels[i]))):
+                wave = waves[k * n_audio + i] if waves is not None else \
+                    mel_to_audio(np.asarray(mel), mel_kwargs['n_mels'], audio_sampling_rate=params.audio_sampling_rate, **stft_kw)
                 if wave.size == 0:          # a single mel frame inverts to zero samples (centred STFT)
                     continue
                 path = os.path.join(params.audio_dir, f'{tag}_audio_{i}.wav')

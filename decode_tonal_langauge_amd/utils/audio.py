@@ -164,19 +164,29 @@ def pack_mel_filterbank(fb: np.ndarray):
     return bands, (np.concatenate(runs) if off else np.zeros(0))
 
 
-@functools.lru_cache(maxsize=8)
-def _mel_batch_tables(device: str, sr: float, n_fft: int, win_length: int, n_mels: int, fmin: float, fmax: Optional[float]):
-    """Device copies of the per-call tables of ``tl_mel_power``: window (as ``stft`` builds it), twiddles, packed bank."""
+def _upload(a: np.ndarray, device):
     import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to(device)
+
+
+@functools.lru_cache(maxsize=8)
+def _stft_batch_tables(device: str, n_fft: int, win_length: int):
+    """Device copies of the window (as ``stft`` builds it) and the full-circle twiddles (cos, -sin)."""
     win = np.zeros(n_fft)
     off = (n_fft - win_length) // 2
     win[off:off + win_length] = _hann(win_length)
     ang = 2.0 * np.pi * np.arange(n_fft) / n_fft
-    tw = np.stack([np.cos(ang), -np.sin(ang)], axis=1)
+    return _upload(win, device), _upload(np.stack([np.cos(ang), -np.sin(ang)], axis=1), device)
+
+
+@functools.lru_cache(maxsize=8)
+def _mel_batch_tables(device: str, sr: float, n_fft: int, win_length: int, n_mels: int, fmin: float, fmax: Optional[float]):
+    """Device copies of the per-call tables of ``tl_mel_power``: window (as ``stft`` builds it), twiddles, packed bank."""
+    win, tw = _stft_batch_tables(device, n_fft, win_length)
     bands, weights = pack_mel_filterbank(mel_filterbank(sr, n_fft, n_mels=n_mels, fmin=fmin, fmax=fmax))
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    up = lambda a: _upload(a, device)
     # an empty tensor has no device pointer: keep one weight so the entry point always gets an address
-    return up(win), up(tw), up(bands), up(weights if weights.size else np.zeros(1)), int(weights.size)
+    return win, tw, up(bands), up(weights if weights.size else np.zeros(1)), int(weights.size)
 
 
 def audio_to_mel_batch(audio, audio_sampling_rate: int, mel_in_db: bool = True, mel_kwargs: Optional[dict] = None,
@@ -250,6 +260,85 @@ def audio_to_mel_batch(audio, audio_sampling_rate: int, mel_in_db: bool = True, 
     return out if is_tensor else out.cpu().numpy()
 
 
+# ------------------------------------------------------------------------------------------ mel -> linear spectrum
+#: FISTA iterations of ``mel_to_linear`` / ``tl_mel_invert``: the smallest count of the CPU sweep in profiles/mel_inverse.md
+#: whose per-frame relative residual exceeds ``scipy.optimize.nnls``'s by at most 1e-5 on every input of that sweep
+NNLS_ITER_DEFAULT = 1000
+
+
+def _bank_lipschitz(fb: np.ndarray) -> float:
+    """Largest eigenvalue of ``fb^T fb``: the Lipschitz constant of the gradient of ``||fb x - p||^2 / 2``."""
+    return float(np.linalg.svd(np.asarray(fb, dtype=np.float64), compute_uv=False)[0]) ** 2
+
+
+def fista_momentum(nnls_iter: int) -> np.ndarray:
+    """``beta_k = (t_k - 1) / t_{k+1}`` of the standard sequence ``t_1 = 1``, ``t_{k+1} = (1 + sqrt(1 + 4 t_k^2)) / 2``."""
+    beta, t = np.empty(int(nnls_iter)), 1.0
+    for k in range(int(nnls_iter)):
+        t_new = 0.5 * (1.0 + np.sqrt(1.0 + 4.0 * t * t))
+        beta[k] = (t - 1.0) / t_new
+        t = t_new
+    return beta
+
+
+def bank_operators(fb: np.ndarray):
+    """``apply(z)`` = ``fb @ z`` and ``transposed(r)`` = ``fb.T @ r`` of a triangular bank with the order of operations written
+    out, every product and every sum rounded on its own: a band's sum runs over its bins ``[first, last)`` as four interleaved
+    partial sums (bins ``first + s, first + s + 4, ...``, each in rising order) combined as ``(s0 + s1) + (s2 + s3)``; a bin's
+    gradient is ``w0 r[b0] + w1 r[b1]`` over the at most two bands that cover it.  ``tl_mel_invert`` computes exactly this."""
+    fb = np.asarray(fb, dtype=np.float64)
+    bands, weights = pack_mel_filterbank(fb)
+    bin_bands, bin_weights = bin_pair_table(fb)
+    first, last, off = bands[:, 0], bands[:, 1], bands[:, 2]
+    steps = int(-(-max(int((last - first).max()), 1) // 4))
+    k = first[None, None, :] + np.arange(4)[None, :, None] + 4 * np.arange(steps)[:, None, None]       # (steps, 4, n_mels)
+    live = k < last[None, None, :]
+    idx = np.where(live, k, 0)
+    wt = np.where(live, np.append(weights, 0.0)[np.where(live, off[None, None, :] + k - first[None, None, :], weights.size)], 0.0)
+    b = np.maximum(bin_bands, 0)
+    w0, w1 = bin_weights[:, 0, None], bin_weights[:, 1, None]
+
+    def apply(z):
+        acc = np.zeros((4, fb.shape[0], z.shape[1]))
+        for j in range(steps):
+            acc = acc + wt[j][:, :, None] * z[idx[j]]
+        return (acc[0] + acc[1]) + (acc[2] + acc[3])
+
+    def transposed(r):
+        return w0 * r[b[:, 0]] + w1 * r[b[:, 1]]
+
+    return apply, transposed
+
+
+def mel_to_linear(mel_power: np.ndarray, fb: np.ndarray, nnls_iter: int = NNLS_ITER_DEFAULT, _perturb=None) -> np.ndarray:
+    """``min_{x >= 0} ||fb x - p_t||^2`` for every column ``p_t`` of ``mel_power`` (n_mels, T) by accelerated projected
+    gradient (FISTA) from ``x = 0``: step ``1 / L`` with ``L`` the squared largest singular value of ``fb``, the standard
+    ``t_k`` momentum sequence, ``nnls_iter`` iterations, float64.  Returns (n_bins, T).  ``fb`` must be a triangular bank (at
+    most two bands per bin).  This NumPy form states the method of ``tl_mel_invert`` down to the order of its sums
+    (``bank_operators``), so the kernel reproduces it bit for bit: the projection and, downstream, the square root make the
+    solve sensitive to rounding at the 1e-7 level of the final waveform, and an oracle that rounds differently could not be
+    compared there.  It is the oracle of the tests; ``mel_to_audio_batch`` never calls it.  ``_perturb(grad)`` is for the
+    sensitivity measurements of scripts/mel_inverse_sweep.py."""
+    fb = np.asarray(fb, dtype=np.float64)
+    p = np.asarray(mel_power, dtype=np.float64)
+    if p.ndim != 2 or p.shape[0] != fb.shape[0]:
+        raise ValueError(f"mel_power must be (n_mels = {fb.shape[0]}, T), got {p.shape}")
+    if nnls_iter < 1:
+        raise ValueError(f"nnls_iter = {nnls_iter} must be at least 1")
+    step = 1.0 / _bank_lipschitz(fb)
+    apply, transposed = bank_operators(fb)
+    x = np.zeros((fb.shape[1], p.shape[1]))
+    z = x
+    for beta in fista_momentum(nnls_iter):
+        grad = transposed(apply(z) - p)
+        if _perturb is not None:
+            grad = _perturb(grad)
+        x_new = np.maximum(z - step * grad, 0.0)
+        z = x_new + beta * (x_new - x)
+        x = x_new
+    return x
+
+
 def griffinlim(mag: np.ndarray, n_iter: int = 32, hop_length: Optional[int] = None, win_length: Optional[int] = None,
                momentum: float = 0.99, seed: int = 0, length: Optional[int] = None) -> np.ndarray:
     """Fast Griffin-Lim (Perraudin et al. 2013) from random initial phases."""
@@ -284,3 +373,207 @@ def mel_to_audio(mel: np.ndarray, n_mels: int, audio_sampling_rate: int = 24414,
     lin = np.stack([nnls(fb, mel[:, t])[0] for t in range(mel.shape[1])], axis=1)      # power (or magnitude^power) spectrum
     mag = np.power(np.maximum(lin, 0.0), 1.0 / power)
     return griffinlim(mag, n_iter=n_iter, hop_length=hop_length, win_length=win_length, seed=seed, length=length).astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------ the way back, a batch on the GPU
+#: Griffin-Lim workspace (frames, angles, tprev, the frame-major magnitudes) of one chunk of trials stays under this
+GL_WORKSPACE_BYTES = 1 << 30
+MEL_INVERT_MAX_MELS = 256
+
+
+def bin_pair_table(fb: np.ndarray):
+    """A dense (n_mels, n_bins) bank by bin: ``bin_bands`` (n_bins, 2) int32 = the at most two bands whose triangles cover
+    the bin (-1 = none), ``bin_weights`` (n_bins, 2) float64 their weights - what ``fb.T @ r`` needs per bin."""
+    fb = np.asarray(fb)
+    bin_bands = np.full((fb.shape[1], 2), -1, dtype=np.int32)
+    bin_weights = np.zeros((fb.shape[1], 2))
+    for k in range(fb.shape[1]):
+        nz = np.flatnonzero(fb[:, k])
+        if nz.size > 2:
+            raise ValueError(f"bin {k} lies in {nz.size} bands; a triangular mel bank covers a bin with at most two")
+        bin_bands[k, :nz.size] = nz
+        bin_weights[k, :nz.size] = fb[nz, k]
+    return bin_bands, bin_weights
+
+
+@functools.lru_cache(maxsize=8)
+def _mel_inverse_tables(device: str, sr: float, n_fft: int, n_mels: int, fmin: float, fmax: Optional[float]):
+    """What ``tl_mel_invert`` needs beside the packed bank of ``_mel_batch_tables``: the bank by bin and the step 1 / L."""
+    fb = mel_filterbank(sr, n_fft, n_mels=n_mels, fmin=fmin, fmax=fmax)
+    bin_bands, bin_weights = bin_pair_table(fb)
+    return _upload(bin_bands, device), _upload(bin_weights, device), 1.0 / _bank_lipschitz(fb)
+
+
+@functools.lru_cache(maxsize=4)
+def _fista_momentum_table(device: str, nnls_iter: int):
+    return _upload(fista_momentum(nnls_iter), device)
+
+
+def _batch_on_gpu(a, device, what: str):
+    """``a`` (NumPy array or tensor) as a contiguous float64 CUDA tensor, by the container rules of ``audio_to_mel_batch``."""
+    import torch
+    from .. import _lib
+    if isinstance(a, torch.Tensor):
+        _lib.require_gpu(a, what)
+        return a.double().contiguous()
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"{what} (MI355X build): no GPU visible; this package has no CPU fallback")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"{what}: device '{dev}' is not a CUDA device; this package has no CPU fallback")
+    return torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev)
+
+
+def _check_stft_args(n_fft, hop_length, win_length):
+    """(n_fft, hop, win_length) as ints, refused with the messages of ``audio_to_mel_batch``."""
+    if n_fft not in MEL_BATCH_N_FFT:
+        raise ValueError(f"n_fft = {n_fft} is not supported on the GPU (supported: {', '.join(map(str, MEL_BATCH_N_FFT))})")
+    n_fft = int(n_fft)
+    hop = n_fft // 4 if hop_length is None else int(hop_length)
+    wl = n_fft if win_length is None else int(win_length)
+    if not 1 <= wl <= n_fft:
+        raise ValueError(f"win_length = {wl} must lie in [1, n_fft = {n_fft}]")
+    if hop < 1:
+        raise ValueError(f"hop_length = {hop} must be at least 1")
+    if hop > wl:
+        raise ValueError(f"hop_length = {hop} > win_length = {wl} leaves gaps in the window-square sum of the inverse STFT")
+    return n_fft, hop, wl
+
+
+def griffinlim_batch(mag, n_iter: int = 32, hop_length: Optional[int] = None, win_length: Optional[int] = None,
+                     momentum: float = 0.99, seed: int = 0, length: Optional[int] = None, device=None):
+    """``griffinlim`` of every trial of an (N, n_bins, T) batch on the GPU: row n of the (N, samples) float64 result is
+    ``griffinlim(mag[n], ..., seed=seed)`` up to fp64 rounding.  All trials start from the one (n_bins, T) phase table the
+    host function draws from ``default_rng(seed)``.  Per iteration one ``tl_gl_synth`` and one ``tl_gl_analyse`` launch, then
+    ``tl_gl_synth`` + ``tl_gl_overlap_add``; trials go in chunks whose workspace stays under 1 GiB.  NumPy in -> NumPy out,
+    CUDA tensor in -> CUDA tensor out.  ``n_fft = 2 (n_bins - 1)`` must be one of ``MEL_BATCH_N_FFT`` and
+    ``hop_length <= win_length``.  No CPU fallback."""
+    import torch
+    from .. import _lib
+    is_tensor = isinstance(mag, torch.Tensor)
+    if not is_tensor:
+        mag = np.asarray(mag)
+    if mag.ndim != 3:
+        raise ValueError("Magnitude input must be a 3D array (trials, bins, frames).")
+    N, n_bins, T = (int(v) for v in mag.shape)
+    n_fft, hop, wl = _check_stft_args(2 * (n_bins - 1), hop_length, win_length)
+    if N < 1 or T < 1:
+        raise ValueError("Magnitude input holds no trial or no frame.")
+    if n_iter < 0:
+        raise ValueError(f"n_iter = {n_iter} must not be negative")
+    if length is not None and length < 0:
+        raise ValueError(f"length = {length} must not be negative")
+    # what istft keeps after the centre trim: hop (T - 1) samples, or the first `length` of the n_fft / 2 + hop (T - 1) it has
+    L = hop * (T - 1) if length is None else min(int(length), n_fft // 2 + hop * (T - 1))
+    x = _batch_on_gpu(mag, device, "griffinlim_batch")
+    dev = x.device
+    out = torch.empty(N, L, dtype=torch.float64, device=dev)
+    if L > 0:
+        win, tw = _stft_batch_tables(str(dev), n_fft, wl)
+        phases = np.exp(2j * np.pi * np.random.default_rng(seed).random((n_bins, T)))      # as griffinlim draws them
+        phase0 = _upload(np.ascontiguousarray(phases.T).view(np.float64).reshape(T, n_bins, 2), dev)
+        w2 = np.zeros(n_fft)
+        off = (n_fft - wl) // 2
+        w2[off:off + wl] = _hann(wl)
+        w2 = w2 ** 2
+        wsum_host = np.zeros(n_fft + hop * (T - 1))
+        for t in range(T):                                                                 # the additions of istft, in its order
+            wsum_host[t * hop:t * hop + n_fft] += w2
+        wsum = _upload(wsum_host, dev)
+        per_trial = T * (8 * n_fft + 8 * n_bins + 2 * 16 * n_bins)
+        chunk = max(1, min(N, 65535, GL_WORKSPACE_BYTES // per_trial))
+        frames = torch.empty(chunk, T, n_fft, dtype=torch.float64, device=dev)
+        angles = torch.empty(chunk, T, n_bins, 2, dtype=torch.float64, device=dev)
+        tprev = torch.empty_like(angles)
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            for c0 in range(0, N, chunk):
+                c = min(chunk, N - c0)
+                mag_t = x[c0:c0 + c].transpose(1, 2).contiguous()                          # frame-major, as the kernels read it
+                src, shared = phase0, 1
+                for it in range(int(n_iter) + 1):
+                    _lib.check(lib.tl_gl_synth(mag_t.data_ptr(), src.data_ptr(), shared, win.data_ptr(), tw.data_ptr(),
+                                               frames.data_ptr(), c, n_fft, T, _lib.stream_ptr()), "tl_gl_synth")
+                    if it == n_iter:
+                        break
+                    _lib.check(lib.tl_gl_analyse(frames.data_ptr(), wsum.data_ptr(), win.data_ptr(), tw.data_ptr(),
+                                                 angles.data_ptr(), tprev.data_ptr(), c, n_fft, wl, hop, T, L, float(momentum),
+                                                 int(it == 0), _lib.stream_ptr()), "tl_gl_analyse")
+                    src, shared = angles, 0
+                _lib.check(lib.tl_gl_overlap_add(frames.data_ptr(), wsum.data_ptr(), out[c0:c0 + c].data_ptr(), c, n_fft, wl,
+                                                 hop, T, L, _lib.stream_ptr()), "tl_gl_overlap_add")
+    return out if is_tensor else out.cpu().numpy()
+
+
+def mel_invert_batch(mel_power, audio_sampling_rate: float, n_fft: int, n_mels: int, fmin: float = 0.0,
+                     fmax: Optional[float] = None, nnls_iter: int = NNLS_ITER_DEFAULT, power: int = 2):
+    """``tl_mel_invert`` on a contiguous float64 CUDA tensor (N, n_mels, T) of mel power: (N, n_bins, T) =
+    ``mel_to_linear(mel_power[n], fb, nnls_iter) ** (1 / power)`` for the bank of these arguments."""
+    import torch
+    from .. import _lib
+    _lib.require_gpu(mel_power, "mel_invert_batch")
+    N, _, T = mel_power.shape
+    dev = mel_power.device
+    fmax = None if fmax is None else float(fmax)
+    sr = float(audio_sampling_rate)
+    _, _, bands, weights, n_weights = _mel_batch_tables(str(dev), sr, n_fft, n_fft, n_mels, float(fmin), fmax)
+    bin_bands, bin_weights, step = _mel_inverse_tables(str(dev), sr, n_fft, n_mels, float(fmin), fmax)
+    momentum = _fista_momentum_table(str(dev), int(nnls_iter))
+    p = mel_power.double().contiguous()
+    mag = torch.empty(N, n_fft // 2 + 1, T, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().tl_mel_invert(p.data_ptr(), bands.data_ptr(), weights.data_ptr(), n_weights, bin_bands.data_ptr(),
+                                             bin_weights.data_ptr(), momentum.data_ptr(), mag.data_ptr(), N, n_fft, n_mels, T, int(nnls_iter),
+                                             step,
+                                             int(power), _lib.stream_ptr()), "tl_mel_invert")
+    return mag
+
+
+def mel_to_audio_batch(mels, n_mels: int, audio_sampling_rate: int = 24414, mel_in_db: bool = True, device=None, **kwargs):
+    """Waveforms of an (N, n_mels * T) batch of flattened mel spectrograms on the GPU: ``db_to_power(., ref=1e-4)`` ->
+    ``tl_mel_invert`` (the FISTA solve ``mel_to_linear`` states, ``nnls_iter`` iterations) -> ``griffinlim_batch``; returns
+    (N, samples) float32.  Keywords are those of ``mel_to_audio`` (n_fft, hop_length, win_length, power, n_iter, length, seed,
+    fmin, fmax) plus ``nnls_iter``.  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out.  No CPU fallback.
+
+    Row n is NOT ``mel_to_audio(mels[n], ...)`` sample for sample: the mel bank is under-determined, so the active-set solver
+    of the host function and the projected-gradient solver here pick different minimisers of the same objective.  The
+    contract is: row n equals ``griffinlim(mel_to_linear(p_n, fb, nnls_iter) ** (1 / power), ...)`` cast to float32 within
+    2e-7 of the row's peak, and the per-frame residual of the inversion exceeds ``scipy.optimize.nnls``'s by at most 1e-4
+    relative (tests/test_gpu_mel_inverse.py, profiles/mel_inverse.md)."""
+    import torch
+    is_tensor = isinstance(mels, torch.Tensor)
+    if not is_tensor:
+        mels = np.asarray(mels)
+    if mels.ndim != 2:
+        raise ValueError("Mel input must be a 2D array (trials, n_mels * frames).")
+    n_fft = kwargs.pop("n_fft", 2048)
+    hop_length, win_length = kwargs.pop("hop_length", None), kwargs.pop("win_length", None)
+    power, n_iter = kwargs.pop("power", 2.0), kwargs.pop("n_iter", 32)
+    length, seed = kwargs.pop("length", None), kwargs.pop("seed", 0)
+    nnls_iter = kwargs.pop("nnls_iter", NNLS_ITER_DEFAULT)
+    fmin, fmax = kwargs.pop("fmin", 0.0), kwargs.pop("fmax", None)
+    if kwargs:
+        raise TypeError(f"unsupported keyword(s) {sorted(kwargs)}")
+    n_fft, hop, wl = _check_stft_args(n_fft, hop_length, win_length)
+    if power not in (1, 2):
+        raise ValueError(f"power = {power} is not supported on the GPU (supported: 1, 2)")
+    n_mels = int(n_mels)
+    if n_mels < 1:
+        raise ValueError(f"n_mels = {n_mels} must be at least 1")
+    if n_mels > MEL_INVERT_MAX_MELS:
+        raise ValueError(f"n_mels = {n_mels} is not supported by the GPU mel inversion (at most {MEL_INVERT_MAX_MELS})")
+    if nnls_iter < 1:
+        raise ValueError(f"nnls_iter = {nnls_iter} must be at least 1")
+    N, width = int(mels.shape[0]), int(mels.shape[1])
+    if N < 1:
+        raise ValueError("Mel input holds no trial.")
+    if width < n_mels or width % n_mels:
+        raise ValueError(f"mel rows of {width} values are not n_mels = {n_mels} bands times a whole number of frames")
+    T = width // n_mels
+    x = _batch_on_gpu(mels, device, "mel_to_audio_batch")
+    p = x.reshape(N, n_mels, T)
+    if mel_in_db:
+        p = 0.0001 * torch.pow(10.0, 0.1 * p)                                              # db_to_power(., ref=1e-4)
+    mag = mel_invert_batch(p, audio_sampling_rate, n_fft, n_mels, fmin=fmin, fmax=fmax, nnls_iter=nnls_iter, power=int(power))
+    wave = griffinlim_batch(mag, n_iter=n_iter, hop_length=hop, win_length=wl, seed=seed, length=length).float()
+    return wave if is_tensor else wave.cpu().numpy()

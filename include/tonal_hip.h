@@ -553,6 +553,37 @@ int tl_mel_power(const void* audio, int audio_is_f64, int64_t row_stride, const 
 int tl_mel_finish(const double* mel, const double* rowmax, float* out, int N, int n_mels, int64_t n_frames, int in_db,
                   void* stream);
 
+/* ---- the way back (utils/audio.py mel_to_audio, one trial at a time on the host): mel -> linear spectrum -> Griffin-Lim.
+ * window, tw, bands, weights are the tables of tl_mel_power; n_fft in {256, 512, 1024, 2048}; every array float64.
+ *
+ * min_{x >= 0} ||fb x - p||^2 per frame by nnls_iter iterations of accelerated projected gradient (FISTA) from x = 0 with
+ * step = 1 / (largest singular value of fb)^2 (utils/audio.py mel_to_linear).  mel_power is (N, n_mels, n_frames); the bank
+ * a second time by bin: bin_bands (n_fft/2 + 1, 2) int32 = the at most two bands that cover the bin (-1 = none),
+ * bin_weights (n_fft/2 + 1, 2) their weights; momentum (nnls_iter) = the factors (t_k - 1) / t_{k+1} of the t_k sequence.
+ * Every product and sum is rounded on its own, in the order utils/audio.py bank_operators writes out, so x has the bits of
+ * the host statement.  out (N, n_fft/2 + 1, n_frames) = x^(1/power), power 1 or 2.
+ * 1 <= n_mels <= 256, n_weights <= n_fft + 2, nnls_iter >= 1, step > 0                                                   */
+int tl_mel_invert(const double* mel_power, const int32_t* bands, const double* weights, int n_weights, const int32_t* bin_bands,
+                  const double* bin_weights, const double* momentum, double* out, int N, int n_fft, int n_mels,
+                  int64_t n_frames, int nnls_iter, double step, int power, void* stream);
+/* Griffin-Lim, one iteration = tl_gl_synth + tl_gl_analyse (utils/audio.py griffinlim).  Spectra are frame-major here:
+ * mag (N, n_frames, n_fft/2 + 1), angles and tprev (N, n_frames, n_fft/2 + 1, 2) = (re, im).
+ * synth: frames (N, n_frames, n_fft) = irfft(mag * angles) * window, per frame; angles_shared = 1: angles is one
+ * (n_frames, n_fft/2 + 1, 2) table used for every trial (the initial phases)                                             */
+int tl_gl_synth(const double* mag, const double* angles, int angles_shared, const double* window, const double* tw,
+                double* frames, int N, int n_fft, int64_t n_frames, void* stream);
+/* analyse: signal = samples [n_fft/2, n_fft/2 + length) of the overlap-add of frames over wsum (n_fft + hop (n_frames - 1)) =
+ * the window-square sum where it exceeds float32 tiny, else undivided (istft); rebuilt = its centred STFT, frames from
+ * 1 + length / hop on zero; angles = rebuilt - momentum / (1 + momentum) * tprev (first = 1: rebuilt alone, tprev not
+ * read), angles /= |angles| + 1e-16, tprev = rebuilt.  1 <= win_length <= n_fft, 1 <= hop <= win_length,
+ * 1 <= length <= n_fft/2 + hop (n_frames - 1)                                                                            */
+int tl_gl_analyse(const double* frames, const double* wsum, const double* window, const double* tw, double* angles,
+                  double* tprev, int N, int n_fft, int win_length, int hop, int64_t n_frames, int64_t length, double momentum,
+                  int first, void* stream);
+/* out (N, length) = the signal as tl_gl_analyse forms it, as a gather per sample: no atomics, the same bits every run     */
+int tl_gl_overlap_add(const double* frames, const double* wsum, double* out, int N, int n_fft, int win_length, int hop,
+                      int64_t n_frames, int64_t length, void* stream);
+
 /* FFT resampling = scipy.signal.resample(x, num, axis=1) (downsample.py:21-27): Bluestein chirp-z on
  * power-of-two FFTs.  Host-prepared coefficient arrays (complex128 interleaved): w1 (nx) / w2 (num)
  * chirps exp(i pi m^2 / n); bf1 (m2a) / bf2 (m2b) spectra of the chirp filters; tw1 (m2a/2) / tw2
