@@ -8,24 +8,33 @@ which is how the synthesis trainer uses it (reference models/synthesis_trainer.p
 outputs are arg-maxed and the classifiers are never updated)."""
 from __future__ import annotations
 
-import os
+import ctypes as C
 from typing import Dict, List, Tuple
 
 import torch
 
-from . import _kernels
-from ._cnn_engine import CnnEngine, _r4
-from ._lib import EPI_LRELU, EPI_STORE, LOAD_DIRECT, check, ptr
+from . import _kernels, _lib
+from ._conv_stack import ConvStack
+from ._launch import launch_nt, r4
+from ._lib import EPI_LRELU, EPI_POOL, EPI_POOLV, EPI_STORE, LOAD_DIRECT, LOAD_V, check, ptr
 
 
-class CnnClassifierEngine(CnnEngine):
+def _cached(packed: dict, key: str, param: torch.Tensor, build):
+    """Packed copies of the (usually frozen) classifier weights in ``packed``, rebuilt when the parameter changes."""
+    ver = (param._version, param.data_ptr())
+    hit = packed.get(key)
+    if hit is None or hit[0] != ver:
+        hit = packed[key] = (ver, build())
+    return hit[1]
+
+
+class CnnClassifierEngine(ConvStack):
     F63_CAPABLE = False        # this engine enqueues its stages itself (F(6,3) prefix, then F(4,3) V form / direct kernels)
 
     def __init__(self, n_electrodes: int, n_timepoints: int, stage_defs, hidden: int, n_classes: int,
                  negative_slope: float):
-        # reuse the conv-stack geometry / buffers of the synthesis engine (no LSTM / concat part)
-        super().__init__(n_classes, n_electrodes, n_timepoints, 0, stage_defs[-1][0], 0.0, negative_slope,
-                         stage_defs, [4])
+        super().__init__(n_electrodes, n_timepoints, stage_defs, negative_slope, stage_defs[-1][0])
+        self.fuse_c1 = False       # forward only: no first-stage weight gradient, conv1 writes raw rows (tl_conv1_fwd)
         self.hidden = hidden
         self.n_classes = n_classes
         last = self.stages[-1]
@@ -41,7 +50,6 @@ class CnnClassifierEngine(CnnEngine):
         self.n63, self.tp63 = self._plan63(stage_defs, n_timepoints)
 
     def _plan63(self, stage_defs, T):
-        from . import _kernels
         if _kernels.get("wino") != "6":
             return 0, []
         c1, k1, p1 = stage_defs[0]
@@ -66,21 +74,16 @@ class CnnClassifierEngine(CnnEngine):
     def _forward63(self, convs, x, S, T):
         """Stages 1 .. 1 + n63 on the F(6,3) kernels; leaves the pooled rows of stage 1 + n63 in self.P (row geometry of this
         engine) and returns the number of conv layers consumed."""
-        from ._lib import EPI_POOL, EPI_POOLV, LOAD_V
         lib, st_ = self.lib, self._stream()
-        dev = x.device
-        z = lambda *sh: torch.zeros(*sh, dtype=torch.float32, device=dev)
-        zi = lambda *sh: torch.zeros(*sh, dtype=torch.int32, device=dev)
-        buf = self._buf63
+        zi = lambda *sh: torch.zeros(*sh, dtype=torch.int32, device=x.device)
+        buf = self._bits63
         w1, b1 = convs[0]
         tp1 = self.tp63[0]
-        if "V1" not in buf:
-            nh = S * tp1 // 6
-            buf["V1"] = z((nh + 24 + 127) // 128 * 128, 8, self.c1)
-            buf["b1"] = zi(S * tp1, self.c1 // 32)
-        check(lib.tl_conv1_fwd_v6(ptr(x), ptr(w1.reshape(self.c1, self.k1).contiguous()), ptr(b1), None, ptr(buf["V1"]),
-                                  ptr(buf["b1"]), None, S, T, self.k1, self.c1, tp1, self.tout1, self.slope, st_), "tl_conv1_fwd_v6")
-        V = buf["V1"]
+        V = self._v_hex_buffer(self.V, 1, S * tp1, self.c1)
+        if 1 not in buf:
+            buf[1] = zi(S * tp1, self.c1 // 32)
+        check(lib.tl_conv1_fwd_v6(ptr(x), ptr(w1.reshape(self.c1, self.k1).contiguous()), ptr(b1), None, ptr(V),
+                                  ptr(buf[1]), None, S, T, self.k1, self.c1, tp1, self.tout1, self.slope, st_), "tl_conv1_fwd_v6")
         tile_rows = self._nt63_rows()
         for i in range(self.n63):
             st, (w, b) = self.stages[i], convs[1 + i]
@@ -88,24 +91,19 @@ class CnnClassifierEngine(CnnEngine):
             last = i == self.n63 - 1
             wp = self._cached(f"conv{st.idx}w63", w, lambda w=w: self._pack_wino63(w, True))
             rows_in = S * tp_in
-            kb = f"bits{st.idx}"
-            if kb not in buf:
-                buf[kb] = zi(S * (st.tp_out if last else tp_in // 2), st.cout // 32)
+            if st.idx not in buf:
+                buf[st.idx] = zi(S * (st.tp_out if last else tp_in // 2), st.cout // 32)
             kw = dict(A=ptr(V), A_rows=V.shape[0], lda=V.shape[2], loader=LOAD_V, Bw=ptr(wp), bias=ptr(b), M=rows_in, N=st.cout,
-                      K=st.cin, ldb=st.cin, J=3, row_shift=0, Tp=tp_in, slope=self.slope, obits=ptr(buf[kb]),
+                      K=st.cin, ldb=st.cin, J=3, row_shift=0, Tp=tp_in, slope=self.slope, obits=ptr(buf[st.idx]),
                       ld_obits=st.cout // 32, Tvalid=2 * st.tout)
             if last:
                 dst = self.P[st.idx]
                 self._nt(fn="tl_conv3_wino63v_nt", out=ptr(dst), ldo=dst.shape[1], epilogue=EPI_POOL, out_tp=st.tp_out, **kw)
             else:
                 rows_out = S * (tp_in // 2)
-                kv, kh = f"V{st.idx}", f"halo{st.idx}"
                 ntm = -(-rows_in // tile_rows)
-                if kv not in buf:
-                    nh = rows_out // 6
-                    buf[kv] = z((nh + 24 + 127) // 128 * 128, 8, st.cout)
-                    buf[kh] = z(ntm, 2, st.cout)
-                Vn, halo = buf[kv], buf[kh]
+                Vn = self._v_hex_buffer(self.V, st.idx, rows_out, st.cout)
+                halo = self._halo_buffer(st.idx, ntm, st.cout)
                 self._nt(fn="tl_conv3_wino63v_nt", out=None, ldo=st.cout, epilogue=EPI_POOLV, vout=ptr(Vn), vhalo=ptr(halo),
                          vout_quads=Vn.shape[0], ld_vout=Vn.shape[2], **kw)
                 check(lib.tl_wino63_v_fixup(ptr(Vn), ptr(halo), rows_out // 6, ntm, tp_in // 2, st.cout, Vn.shape[2], st_),
@@ -113,33 +111,23 @@ class CnnClassifierEngine(CnnEngine):
                 V = Vn
         return 1 + self.n63
 
-    def _alloc(self, B: int, dev):
-        if self._B == B and getattr(self, "_dev", None) == dev:
-            return
-        self._B, self._dev = B, dev
-        S = B * self.C
-        self.S = S
-        self._buf63 = {}
-        self.V = {}
-        self._gy_A = None
-        self._vhalo = {}
+    def _alloc_rows(self):
+        # forward only: every stage keeps its raw rows (each transforms its own input), no sign bits
+        S, dev = self.S, self._dev
         z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
         zi = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
         self.P = {1: z(S * self.tp1, self.c1)}
         self.bits = {1: zi(S * self.tp1, self.c1 // 32)}
+        self.sbits = {}
+        self._bits63 = {}          # arg-max bits of the F(6,3) prefix (its own row geometry, tp63)
         for st in self.stages:
             rows = S * st.tp_out
-            self.P[st.idx] = z(rows, st.cout if st.pool else _r4(st.cout))
+            self.P[st.idx] = z(rows, st.cout if st.pool else r4(st.cout))
             if st.pool:
                 self.bits[st.idx] = zi(rows, st.cout // 32)
 
-    def _cached(self, key: str, param: torch.Tensor, build):
-        """Packed copies of the (usually frozen) classifier weights, rebuilt when the parameter changes."""
-        ver = (param._version, param.data_ptr())
-        hit = self._packed.get(key)
-        if hit is None or hit[0] != ver:
-            hit = self._packed[key] = (ver, build())
-        return hit[1]
+    def _cached(self, key, param, build):
+        return _cached(self._packed, key, param, build)
 
     def forward_scores(self, convs: List[Tuple[torch.Tensor, torch.Tensor]], fc1, fc2, x: torch.Tensor,
                        p_drop: float = 0.0, seed: int = 0) -> torch.Tensor:
@@ -153,14 +141,11 @@ class CnnClassifierEngine(CnnEngine):
         self._alloc(B, dev)
         lib, st_ = self.lib, self._stream()
         S = self.S
-        w1, b1 = convs[0]
         done = 1
         if self.n63:
             done = self._forward63(convs, x, S, T)
         else:
-            check(lib.tl_conv1_fwd(ptr(x), ptr(w1.reshape(self.c1, self.k1).contiguous()), ptr(b1), ptr(self.P[1]),
-                                   ptr(self.bits[1]), None, S, T, self.k1, self.c1, self.tp1, self.tout1, self.slope, st_),
-                  "tl_conv1_fwd")
+            self.conv1_forward(x, *convs[0])
         for st, (w, b) in list(zip(self.stages, convs[1:]))[done - 1:]:
             # pooled 3-tap stages the F(4,3) V form covers: one transform pass over the stage's input, then the transform-free
             # kernel of the synthesis engine (half the direct form's MFMA work); everything else on the direct MFMA kernel
@@ -174,12 +159,10 @@ class CnnClassifierEngine(CnnEngine):
                       N=st.cout, K=st.cin, lda=src.shape[1], ldb=st.cin, ldo=dst.shape[1], J=st.k, row_shift=0,
                       Tp=st.tp_in, slope=self.slope, loader=LOAD_DIRECT)
             if st.pool:
-                from ._lib import EPI_POOL
                 kw.update(epilogue=EPI_POOL, obits=ptr(self.bits[st.idx]), ld_obits=st.cout // 32, Tvalid=2 * st.tout)
             else:
                 kw.update(epilogue=EPI_LRELU, Tvalid=st.tout)
             if v43:
-                from ._lib import LOAD_V
                 V = self._input_transform(st)
                 kw.update(A=ptr(V), A_rows=V.shape[0], lda=V.shape[2], loader=LOAD_V)
             self._nt(fn="tl_conv3_wino43v_nt" if v43 else "tl_gemm_nt_window", **kw)
@@ -225,17 +208,6 @@ class CnnClassifierEngine(CnnEngine):
         return torch.sigmoid(out)
 
 
-def _launch_nt(lib, fn: str = "tl_gemm_nt_window", **kw) -> None:
-    """One NT windowed-GEMM launch on torch's current stream (fields of ``NtParams`` by keyword)."""
-    import ctypes as C
-    from ._lib import NtParams
-    p = NtParams()
-    p.splitk, p.bm, p.J, p.Tp, p.Tvalid, p.slope = 1, 128, 1, 1, 1, 0.0
-    for k, v in kw.items():
-        setattr(p, k, v)
-    check(getattr(lib, fn)(C.byref(p), torch.cuda.current_stream().cuda_stream), fn)
-
-
 class LstmInferEngine:
     """Last hidden state of a one-layer ``nn.LSTM(batch_first=True)`` with zero initial state, forward only -
     the two LSTMs of ``CNNRNNClassifier`` (reference models/deep_classifiers.py:230-233, 263-264, 294-296,
@@ -250,10 +222,9 @@ class LstmInferEngine:
     g = 0, so its c and h stay exactly 0 and feed nothing)."""
 
     def __init__(self, in_dim: int, hidden: int):
-        from . import _lib
         self.lib = _lib.load()
         self.in_dim, self.H = in_dim, hidden
-        self.Kp, self.Hp = _r4(in_dim), (hidden + 7) // 8 * 8
+        self.Kp, self.Hp = r4(in_dim), (hidden + 7) // 8 * 8
         self._packed = None
 
     def _weights(self, w_ih, w_hh, b_ih, b_hh):
@@ -289,11 +260,10 @@ class LstmInferEngine:
         rows = B * T
         xp = torch.empty(rows, 4 * Hp, **f32)
         # phase 1: every step's input projection + both biases
-        _launch_nt(self.lib, A=ptr(x), Bw=ptr(wi), bias=ptr(bs), out=ptr(xp), M=rows, A_rows=rows, N=4 * Hp, K=Kp,
-                   lda=Kp, ldb=Kp, ldo=4 * Hp, loader=LOAD_DIRECT, epilogue=EPI_STORE)
+        launch_nt(self.lib, A=ptr(x), Bw=ptr(wi), bias=ptr(bs), out=ptr(xp), M=rows, A_rows=rows, N=4 * Hp, K=Kp,
+                  lda=Kp, ldb=Kp, ldo=4 * Hp, Tvalid=1, loader=LOAD_DIRECT, epilogue=EPI_STORE)
         h = torch.empty(B, Hp, **f32)
         c = torch.empty(B, Hp, **f32)
-        import ctypes as C
         h2 = torch.empty(B, Hp, **f32)
         in_b = C.c_int(0)
         check(self.lib.tl_lstm_infer_seq_fused(ptr(xp), T * 4 * Hp, ptr(whp), ptr(h), ptr(h2), ptr(c), B, Hp, T,
@@ -316,7 +286,6 @@ class CnnRnnConvEngine:
     K = 7
 
     def __init__(self, input_channels: int, input_length: int, lstm_dim: int, negative_slope: float):
-        from . import _lib
         self.lib = _lib.load()
         self.C, self.T = input_channels, input_length
         self.w1 = lstm_dim // input_length
@@ -339,12 +308,8 @@ class CnnRnnConvEngine:
         self._packed: Dict[str, Tuple[tuple, torch.Tensor]] = {}
         self._B = None
 
-    def _cached(self, key: str, param: torch.Tensor, build):
-        ver = (param._version, param.data_ptr())
-        hit = self._packed.get(key)
-        if hit is None or hit[0] != ver:
-            hit = self._packed[key] = (ver, build())
-        return hit[1]
+    def _cached(self, key, param, build):
+        return _cached(self._packed, key, param, build)
 
     def _alloc(self, B: int, dev):
         if self._B == B and self._dev == dev:
@@ -371,8 +336,6 @@ class CnnRnnConvEngine:
 
     def _conv7(self, src, w, b, dst, cin, cout, key, rows):
         """dst[r] = lrelu(sum_j w[:, :, j] src[r + j] + b) for r < rows; src holds rows + 8 rows."""
-        from ._lib import NtParams
-        import ctypes as C
         st_ = torch.cuda.current_stream().cuda_stream
         if self.conv7_form == "wino63" and cin % 8 == 0 and cout % 32 == 0:
             nhex = rows // 6
@@ -396,22 +359,17 @@ class CnnRnnConvEngine:
                                                   self.K, st_), "tl_wino63_weights7")
                 return wp
             wp = self._cached(key + "wino63", w, pack63)
-            from ._lib import LOAD_V
-            _launch_nt(self.lib, fn="tl_conv7_wino63v_nt", A=ptr(V0), aux=ptr(V1), A_rows=V0.shape[0], lda=cin, Bw=ptr(wp),
-                       bias=ptr(b.detach()), out=ptr(dst), M=rows, N=cout, K=cin, ldb=3 * cin, ldo=dst.shape[1], J=self.K,
-                       row_shift=0, Tp=self.Tp, Tvalid=self.Tp, slope=self.slope, loader=LOAD_V, epilogue=EPI_LRELU)
+            launch_nt(self.lib, fn="tl_conv7_wino63v_nt", A=ptr(V0), aux=ptr(V1), A_rows=V0.shape[0], lda=cin, Bw=ptr(wp),
+                      bias=ptr(b.detach()), out=ptr(dst), M=rows, N=cout, K=cin, ldb=3 * cin, ldo=dst.shape[1], J=self.K,
+                      row_shift=0, Tp=self.Tp, Tvalid=self.Tp, slope=self.slope, loader=LOAD_V, epilogue=EPI_LRELU)
             return
         # "direct" (or a width the F(6,3) form does not take): the 7-tap window GEMM, which reads rows + 8 input rows
         if src.shape[0] < rows + 8:
             raise RuntimeError("conv7: the input buffer is shorter than the rows the 7-tap window reads")
         wp = self._cached(key + "direct", w, lambda: w.detach().reshape(cout, cin, self.K).permute(2, 0, 1).contiguous())   # [J][O][I]
-        p = NtParams()
-        p.A, p.Bw, p.bias, p.out = ptr(src), ptr(wp), ptr(b.detach()), ptr(dst)
-        p.M, p.A_rows = rows, rows + 8
-        p.N, p.K, p.lda, p.ldb, p.ldo = cout, cin, cin, cin, cout
-        p.J, p.row_shift, p.Tp, p.Tvalid, p.slope = self.K, 0, self.Tp, self.Tp, self.slope
-        p.loader, p.epilogue, p.splitk, p.bm = LOAD_DIRECT, EPI_LRELU, 1, 128
-        check(self.lib.tl_gemm_nt_window(C.byref(p), st_), "tl_gemm_nt_window")
+        launch_nt(self.lib, A=ptr(src), Bw=ptr(wp), bias=ptr(b.detach()), out=ptr(dst), M=rows, A_rows=rows + 8, N=cout, K=cin,
+                  lda=cin, ldb=cin, ldo=cout, J=self.K, row_shift=0, Tp=self.Tp, Tvalid=self.Tp, slope=self.slope,
+                  loader=LOAD_DIRECT, epilogue=EPI_LRELU)
 
     @torch.no_grad()
     def linear(self, a: torch.Tensor, w: torch.Tensor, b: torch.Tensor, sigmoid: bool = False) -> torch.Tensor:
@@ -426,8 +384,8 @@ class CnnRnnConvEngine:
             check(self.lib.tl_linear_rows(ptr(a), ptr(w.contiguous()), ptr(b), ptr(out), B, K, N, K, int(sigmoid),
                                           torch.cuda.current_stream().cuda_stream), "tl_linear_rows")
             return out
-        _launch_nt(self.lib, A=ptr(a), Bw=ptr(w.contiguous()), bias=ptr(b), out=ptr(out), M=B, A_rows=B, N=N, K=K, lda=K,
-                   ldb=K, ldo=N, loader=LOAD_DIRECT, epilogue=EPI_STORE)
+        launch_nt(self.lib, A=ptr(a), Bw=ptr(w.contiguous()), bias=ptr(b), out=ptr(out), M=B, A_rows=B, N=N, K=K, lda=K,
+                  ldb=K, ldo=N, Tvalid=1, loader=LOAD_DIRECT, epilogue=EPI_STORE)
         return torch.sigmoid(out) if sigmoid else out
 
     @torch.no_grad()

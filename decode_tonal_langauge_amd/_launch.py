@@ -1,0 +1,76 @@
+"""Launch plumbing shared by the host engines: the only place that fills ``NtParams`` / ``TnParams`` and calls
+``tl_permute_reduce``, plus the HIP-event timers.  Everything launches on torch's current stream."""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from ._lib import NtParams, TnParams, check, ptr
+
+# bm = 256 (8-wave workgroups) exists but measured slower than two independent 4-wave workgroups per CU (conv2 fwd 127 vs
+# 129, dgrad 114 vs 124 TFLOP/s): not selected.
+_NT_DEFAULTS = dict(splitk=1, bm=128, J=1, Tp=1, slope=0.0)
+_TN_DEFAULTS = dict(splitk=1, J=1, Tp=1, Tvalid=1)
+_NT_FIELDS = frozenset(name for name, _ in NtParams._fields_)
+_TN_FIELDS = frozenset(name for name, _ in TnParams._fields_)
+
+
+def r4(n: int) -> int:
+    return (n + 3) // 4 * 4
+
+
+def _stream() -> int:
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _launch(lib, fn, struct, names, defaults, fields) -> None:
+    if not names.issuperset(fields):       # (a ctypes.Structure takes any attribute: a misspelt field would reach the kernel as 0)
+        raise TypeError(f"{struct.__name__} has no field {', '.join(sorted(set(fields) - names))}")
+    p = struct(**{**defaults, **fields})
+    check(getattr(lib, fn)(C.byref(p), _stream()), fn)
+
+
+def launch_nt(lib, fn: str = "tl_gemm_nt_window", **fields) -> None:
+    """One NT windowed-GEMM launch (fields of ``NtParams`` by keyword; the rest: splitk = J = Tp = 1, bm = 128, else 0)."""
+    _launch(lib, fn, NtParams, _NT_FIELDS, _NT_DEFAULTS, fields)
+
+
+def launch_tn(lib, fn: str = "tl_gemm_tn_window", **fields) -> None:
+    """One TN windowed-GEMM launch (fields of ``TnParams`` by keyword; the rest: splitk = J = Tp = Tvalid = 1, else 0)."""
+    _launch(lib, fn, TnParams, _TN_FIELDS, _TN_DEFAULTS, fields)
+
+
+def permute_reduce(lib, src, dst, dims, strides, lims=None, nz=1, zs=0, src_off=0, bias=None) -> None:
+    """dst = (sum over ``nz`` slabs ``zs`` floats apart of) a 4-d strided view of ``src`` from float ``src_off`` on (+ bias)."""
+    d = (C.c_int64 * 4)(*dims)
+    s = (C.c_int64 * 4)(*strides)
+    l = (C.c_int64 * 4)(*(lims if lims is not None else dims))
+    check(lib.tl_permute_reduce(src.data_ptr() + 4 * src_off, dst.data_ptr(), d, s, l, nz, zs, ptr(bias), _stream()),
+          "tl_permute_reduce")
+
+
+class LaunchTimers:
+    """Per-launch HIP-event timing (bench.py roofline leg).  Events are recorded on the stream the kernels are launched on
+    (torch's current stream)."""
+    timers = None
+
+    def enable_timers(self, on: bool = True):
+        self.timers = {} if on else None
+
+    def _tick(self, name):
+        if self.timers is None or name is None:
+            return None
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        self.timers.setdefault(name, []).append(ev)
+        ev[0].record()
+        return ev
+
+    def timer_summary(self):
+        """{name: (launches, mean ms)} - synchronises."""
+        torch.cuda.synchronize()
+        out = {}
+        for k, evs in (self.timers or {}).items():
+            ms = [a.elapsed_time(b) for a, b in evs]
+            out[k] = (len(ms), sum(ms) / max(len(ms), 1))
+        return out

@@ -4,17 +4,13 @@ models/synthesis_models.py:201-296): two Conv1d+BatchNorm1d+LeakyReLU+MaxPool1d 
 two Linear layers on the fp32-MFMA GEMM kernels.  Layout is the reference's own (B, C, T)."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict
 
 import torch
 
 from . import _lib
-from ._lib import EPI_LRELU, EPI_MASK, EPI_STORE, LOAD_DIRECT, NtParams, TnParams, check, ptr
-
-
-def _r4(n: int) -> int:
-    return (n + 3) // 4 * 4
+from ._launch import launch_nt, launch_tn, permute_reduce, r4
+from ._lib import EPI_MASK, EPI_STORE, LOAD_DIRECT, check, ptr
 
 
 class LiteEngine:
@@ -37,39 +33,26 @@ class LiteEngine:
         self.p_drop, self.slope = float(dropout), float(negative_slope)
         self.T1, self.T2 = n_timepoints // 2, n_timepoints // 2 // 2
         self.F = conv_channels * self.T2
-        self.ldf = _r4(self.F + lstm_hidden)
-        self.ldd = _r4(output_dim)
+        self.ldf = r4(self.F + lstm_hidden)
+        self.ldd = r4(output_dim)
         self.hid = 512
         self.generation = 0
         self._saved_generation = -1
-        self.timers = None
 
     def _stream(self):
         return torch.cuda.current_stream().cuda_stream
 
-    def _permute(self, src, dst, dims, strides, lims=None, nz=1, zs=0, bias=None):
-        d = (C.c_int64 * 4)(*dims)
-        s = (C.c_int64 * 4)(*strides)
-        l = (C.c_int64 * 4)(*(lims if lims is not None else dims))
-        check(self.lib.tl_permute_reduce(ptr(src), ptr(dst), d, s, l, nz, zs, ptr(bias), self._stream()),
-              "tl_permute_reduce")
+    def _permute(self, src, dst, dims, strides, *args, **kw):
+        permute_reduce(self.lib, src, dst, dims, strides, *args, **kw)
 
     def _nt(self, **kw):
-        p = NtParams()
-        p.splitk, p.bm, p.J, p.Tp, p.slope = 1, 128, 1, 1, 0.0
-        for k, v in kw.items():
-            setattr(p, k, v)
-        check(self.lib.tl_gemm_nt_window(C.byref(p), self._stream()), "tl_gemm_nt_window")
+        launch_nt(self.lib, **kw)
 
     def _tn(self, **kw):
-        p = TnParams()
-        p.splitk, p.J, p.Tp, p.Tvalid = 1, 1, 1, 1
-        for k, v in kw.items():
-            setattr(p, k, v)
-        check(self.lib.tl_gemm_tn_window(C.byref(p), self._stream()), "tl_gemm_tn_window")
+        launch_tn(self.lib, **kw)
 
     def _colsum(self, G, rows, ncols, ld, dst):
-        nc4 = _r4(ncols)
+        nc4 = r4(ncols)
         rpb = max(1, 256 // (nc4 // 4))
         nblk = int(min(256, max(1, rows // (rpb * 4))))
         part = torch.empty(nblk, nc4, dtype=torch.float32, device=G.device)
@@ -241,7 +224,7 @@ class LiteEngine:
         gwhh = grads["label_lstm.weight_hh_l0"]
         if L > 1:
             kr = B * L - 1          # pairs (dg[b,t], h[b,t-1]): A row R+1, B row R, rows with R%L == L-1 masked
-            h4 = _r4(H)
+            h4 = r4(H)
             if h4 == H:
                 # a few hundred rows: the reduction is split over 64-row chunks (tn_short_kernel), the slabs summed in order
                 sk = max(1, min(8, (kr + 63) // 64))

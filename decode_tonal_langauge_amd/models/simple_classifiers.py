@@ -50,16 +50,16 @@ def _hidden_layer(layer: nn.Linear, act: nn.Module, x: torch.Tensor) -> torch.Te
             and not (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad))
             and layer.bias is not None and x.shape[1] % 4 == 0 and x.shape[0] > 0):
         from .. import _lib
-        from .._classifier_engine import _launch_nt
+        from .._launch import launch_nt
         from .._lib import EPI_LRELU, EPI_STORE, LOAD_DIRECT, ptr
         x = x.contiguous()
         B, K = x.shape
         N = w.shape[0]
         out = torch.empty(B, N, dtype=torch.float32, device=x.device)
         slope = 0.0 if isinstance(act, nn.ReLU) else (float(act.negative_slope) if isinstance(act, nn.LeakyReLU) else None)
-        _launch_nt(_lib.load(), A=ptr(x), Bw=ptr(w.detach().contiguous()), bias=ptr(layer.bias.detach()), out=ptr(out), M=B,
-                   A_rows=B, N=N, K=K, lda=K, ldb=K, ldo=N, loader=LOAD_DIRECT,
-                   epilogue=EPI_STORE if slope is None else EPI_LRELU, slope=slope or 0.0)
+        launch_nt(_lib.load(), A=ptr(x), Bw=ptr(w.detach().contiguous()), bias=ptr(layer.bias.detach()), out=ptr(out), M=B,
+                  A_rows=B, N=N, K=K, lda=K, ldb=K, ldo=N, Tvalid=1, loader=LOAD_DIRECT,
+                  epilogue=EPI_STORE if slope is None else EPI_LRELU, slope=slope or 0.0)
         return out if slope is not None else act(out)
     return act(layer(x))
 

@@ -547,7 +547,7 @@ def test_one_tap_nt_gemm_forms_match_matmul(dev, shape, monkeypatch):
     direct-to-LDS kernel (default): STORE (+ split-K slabs), bias + LeakyReLU, and the input-gradient MASK from the stage input
     (whose values a tile requests before its first store), against float64 matmul."""
     from decode_tonal_langauge_amd import _lib
-    from decode_tonal_langauge_amd._classifier_engine import _launch_nt
+    from decode_tonal_langauge_amd._launch import launch_nt
     from decode_tonal_langauge_amd._lib import LOAD_DIRECT, EPI_STORE, EPI_LRELU, EPI_MASK, ptr
     lib = _lib.load()
     M, N, K = shape
@@ -560,22 +560,22 @@ def test_one_tap_nt_gemm_forms_match_matmul(dev, shape, monkeypatch):
     scale = float(ref.abs().max())
     for glds in ("0", "1"):
         monkeypatch.setenv("TONAL_GLDS", glds)
-        kw = dict(A=ptr(A), Bw=ptr(W), M=M, A_rows=M + 3, N=N, K=K, lda=K + 4, ldb=K + 8, loader=LOAD_DIRECT)
+        kw = dict(A=ptr(A), Bw=ptr(W), M=M, A_rows=M + 3, N=N, K=K, lda=K + 4, ldb=K + 8, Tvalid=1, loader=LOAD_DIRECT)
         out = torch.full((M, N + 4), float("nan"), device=dev)
-        _launch_nt(lib, out=ptr(out), ldo=N + 4, epilogue=EPI_STORE, **kw)
+        launch_nt(lib, out=ptr(out), ldo=N + 4, epilogue=EPI_STORE, **kw)
         assert float((out[:, :N].double() - ref).abs().max()) < 2e-6 * scale and bool(torch.isnan(out[:, N:]).all())
         out.fill_(float("nan"))
-        _launch_nt(lib, out=ptr(out), ldo=N + 4, epilogue=EPI_LRELU, bias=ptr(bias), slope=0.1, **kw)
+        launch_nt(lib, out=ptr(out), ldo=N + 4, epilogue=EPI_LRELU, bias=ptr(bias), slope=0.1, **kw)
         y = ref + bias.double()
         assert float((out[:, :N].double() - torch.where(y > 0, y, 0.1 * y)).abs().max()) < 2e-6 * scale
         out.fill_(float("nan"))
-        _launch_nt(lib, out=ptr(out), ldo=N + 4, epilogue=EPI_MASK, aux=ptr(aux), ldaux=N + 4, slope=0.1, **kw)
+        launch_nt(lib, out=ptr(out), ldo=N + 4, epilogue=EPI_MASK, aux=ptr(aux), ldaux=N + 4, slope=0.1, **kw)
         assert float((out[:, :N].double() - torch.where(aux[:, :N] > 0, ref, 0.1 * ref)).abs().max()) < 2e-6 * scale
         assert bool(torch.isnan(out[:, N:]).all())
         nk = K // 16
         for sk in sorted({1, min(2, nk), min(3, nk), nk}):
             slab = torch.full((sk, M, N), float("nan"), device=dev)
-            _launch_nt(lib, out=ptr(slab), ldo=N, epilogue=EPI_STORE, splitk=sk, slab_stride=M * N, **kw)
+            launch_nt(lib, out=ptr(slab), ldo=N, epilogue=EPI_STORE, splitk=sk, slab_stride=M * N, **kw)
             assert float((slab.double().sum(0) - ref).abs().max()) < 2e-6 * scale, (glds, sk)
 
 
