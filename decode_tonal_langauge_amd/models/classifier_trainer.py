@@ -12,6 +12,9 @@ out as a plain loop:
   * test: macro accuracy and macro F1 over the classes that occur (torchmetrics' macro average
     ignores classes with no true and no predicted sample), confusion matrix rows = true class;
   * ``metrics.csv`` per run with Lightning's column names, ``confusion_matrix_test.csv`` after test.
+
+``fused=True`` runs the same loop on the HIP path (``_simple_classifier_engine``: fused cross-entropy step, ``FusedNAdam``);
+loss and confusion matrix then stay on the device and are read once per epoch.
 """
 from __future__ import annotations
 
@@ -48,14 +51,21 @@ def macro_scores(cm: torch.Tensor) -> Dict[str, float]:
 
 class ClassifierTrainer:
     def __init__(self, model: ClassifierModel, learning_rate: float = 0.0005, weight_decay: float = 0.0,
-                 log_dir: Optional[str] = None, verbose: bool = False) -> None:
+                 log_dir: Optional[str] = None, verbose: bool = False, fused: bool = False) -> None:
         self.model = model
         self.learning_rate = float(learning_rate)
         self.weight_decay = float(weight_decay)
         self.criterion = nn.CrossEntropyLoss()
         self.log_dir = log_dir
         self.verbose = verbose
-        self.optimizer = self.configure_optimizers()
+        self.fused = bool(fused)
+        self.engine = None
+        if self.fused:         # an explicit request: a model / device pair the engine does not take raises (ValueError)
+            from .._simple_classifier_engine import SimpleClassifierEngine
+            self.engine = SimpleClassifierEngine(model, self.learning_rate, self.weight_decay)
+            self.optimizer = self.engine.optimizer
+        else:
+            self.optimizer = self.configure_optimizers()
         self.history: List[Dict[str, float]] = []
         self.confusion_matrix: Optional[torch.Tensor] = None
         self.test_accuracy: Optional[float] = None
@@ -70,6 +80,8 @@ class ClassifierTrainer:
 
     # ------------------------------------------------------------------ epochs
     def _run_epoch(self, loader, train: bool) -> Dict[str, float]:
+        if self.engine is not None:
+            return self._run_epoch_fused(loader, train)
         n_cls = self.model.n_classes
         loss_sum, n_seen = 0.0, 0
         cm = torch.zeros(n_cls, n_cls, dtype=torch.long)
@@ -86,6 +98,15 @@ class ClassifierTrainer:
             loss_sum += float(loss.detach()) * len(y)
             n_seen += len(y)
             cm += _confusion(y.cpu(), logits.detach().argmax(1).cpu(), n_cls)
+        return {"loss": loss_sum / max(n_seen, 1), "accuracy": macro_scores(cm)["accuracy"]}
+
+    def _run_epoch_fused(self, loader, train: bool) -> Dict[str, float]:
+        """The same epoch on the engine: the per-sample losses and the confusion matrix accumulate on the device, one read."""
+        self.model.train(train)
+        step = self.engine.train_batch if train else self.engine.eval_batch
+        for x, y in loader:
+            step(x, y)
+        loss_sum, n_seen, cm = self.engine.epoch_stats()
         return {"loss": loss_sum / max(n_seen, 1), "accuracy": macro_scores(cm)["accuracy"]}
 
     def fit(self, train_loader, val_loader, max_epochs: int, patience: int) -> List[Dict[str, float]]:
@@ -116,8 +137,13 @@ class ClassifierTrainer:
         n_cls = self.model.n_classes
         cm = torch.zeros(n_cls, n_cls, dtype=torch.long)
         self.model.eval()
-        for x, y in loader:
-            cm += _confusion(y.long().cpu(), self.model(x).argmax(1).cpu(), n_cls)
+        if self.engine is not None:
+            for x, y in loader:
+                self.engine.eval_batch(x, y)
+            cm = self.engine.epoch_stats()[2]
+        else:
+            for x, y in loader:
+                cm += _confusion(y.long().cpu(), self.model(x).argmax(1).cpu(), n_cls)
         scores = macro_scores(cm)
         self.test_accuracy, self.test_f1, self.confusion_matrix = scores["accuracy"], scores["f1"], cm
         if self.log_dir is not None:
@@ -128,6 +154,8 @@ class ClassifierTrainer:
     @torch.no_grad()
     def predict(self, loader) -> torch.Tensor:
         self.model.eval()
+        if self.engine is not None:
+            return torch.cat([self.engine.predict_batch(x) for x, _ in loader])
         return torch.cat([self.model(x).argmax(dim=1) for x, _ in loader])
 
     # ------------------------------------------------------------------ helpers

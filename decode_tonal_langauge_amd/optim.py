@@ -7,6 +7,7 @@ Same update rule and defaults as ``torch.optim.NAdam`` built by the reference tr
 from __future__ import annotations
 
 import os
+import struct
 from typing import Dict, Iterable, Optional
 
 import torch
@@ -28,7 +29,7 @@ def nadam_scalars(step: int, mu_product: float, lr: float, beta1: float, beta2: 
 
 class FusedNAdam(torch.optim.Optimizer):
     def __init__(self, params: Iterable[torch.nn.Parameter], lr: float = 2e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0, momentum_decay: float = 4e-3):
+                 weight_decay: float = 0.0, momentum_decay: float = 4e-3, stored_beta2: bool = False):
         if lr < 0 or eps < 0 or weight_decay < 0 or momentum_decay < 0:
             raise ValueError("FusedNAdam: negative hyper-parameter")
         if not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
@@ -37,7 +38,20 @@ class FusedNAdam(torch.optim.Optimizer):
                                       momentum_decay=momentum_decay))
         self._lib = _lib.load()
         self._tables = {}
+        # The kernels take beta2 as a float and form 1 - beta2 from it: 1 - float32(0.999) is 1.29e-5 (relative) below 0.001, so
+        # with bias_corr2 = 1 - 0.999^t from the host's double the early updates come out 6.4e-6 (relative) too large - the
+        # whole distance of the classifier trajectories from their float64 reference, which hold 4e-6.  ``stored_beta2``: the
+        # correction is formed from the float32 value the kernels use, i.e. the step is NAdam with beta2 moved by 1.3e-8.
+        # Off by default: the synthesis trainer's numbers would move (by that 6e-6 of its first updates).
+        self.stored_beta2 = bool(stored_beta2)
         self.multi_tensor = True       # one launch for all dense tensors at the same point of the schedule (tests may clear it)
+
+    def _scalars(self, step: int, mu_product: float, group) -> tuple:
+        b1, b2 = group["betas"]
+        cg, cm, bc2, mu_product = nadam_scalars(step, mu_product, group["lr"], b1, b2, group["momentum_decay"])
+        if self.stored_beta2:
+            bc2 = 1.0 - struct.unpack("f", struct.pack("f", b2))[0] ** step
+        return cg, cm, bc2, mu_product
 
     def _state_for(self, p, shard_rows=None):
         """``shard_rows`` = (row0, rows): this rank owns (and keeps moments for) only those rows of ``p``."""
@@ -95,8 +109,7 @@ class FusedNAdam(torch.optim.Optimizer):
         _lib.require_gpu(p, "FusedNAdam.step")
         st = self._state_for(p, shard)
         st["step"] += 1
-        cg, cm, bc2, st["mu_product"] = nadam_scalars(st["step"], st["mu_product"], group["lr"], b1, b2,
-                                                      group["momentum_decay"])
+        cg, cm, bc2, st["mu_product"] = self._scalars(st["step"], st["mu_product"], group)
         if dh is not None:
             slab, U, row_tiles = dh
             nslab = -(-(-(-rows // 32)) // row_tiles)
@@ -147,7 +160,7 @@ class FusedNAdam(torch.optim.Optimizer):
                 dense.setdefault((st["step"], st["mu_product"]), []).append((p, g, st))
             # tensors at the same point of the schedule (normally all of them) share one launch
             for (step_no, mu_prod), items in dense.items():
-                cg, cm, bc2, mu_prod = nadam_scalars(step_no, mu_prod, group["lr"], b1, b2, group["momentum_decay"])
+                cg, cm, bc2, mu_prod = self._scalars(step_no, mu_prod, group)
                 for _, _, st in items:
                     st["mu_product"] = mu_prod
                 if len(items) == 1 or not self.multi_tensor:
@@ -198,8 +211,7 @@ class FusedNAdam(torch.optim.Optimizer):
                     continue
                 st = self._state_for(p)
                 st["step"] += 1
-                cg, cm, bc2, st["mu_product"] = nadam_scalars(st["step"], st["mu_product"], group["lr"], b1, b2,
-                                                              group["momentum_decay"])
+                cg, cm, bc2, st["mu_product"] = self._scalars(st["step"], st["mu_product"], group)
                 if out is not None and out != (cg, cm, bc2):
                     raise RuntimeError("FusedNAdam.advance_scalars: parameters at different points of the schedule")
                 out = (cg, cm, bc2)

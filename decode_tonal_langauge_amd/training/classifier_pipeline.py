@@ -38,7 +38,7 @@ def _fit_one(params: Namespace, dataset, seed: int, n_classes: int, n_channels: 
         print(f"Number of trainable parameters: {model.get_layer_nparams()}")
     run_dir = os.path.join(params.log_dir, f"{tag}_csv", f"subject_{params.subject_id}", "seed_" + str(seed))
     trainer = ClassifierTrainer(model, learning_rate=params.lr, weight_decay=float(getattr(params, "weight_decay", 0.0)),
-                                log_dir=run_dir, verbose=verbose > 1)
+                                log_dir=run_dir, verbose=verbose > 1, fused=bool(getattr(params, "fused", False)))
     trainer.fit(loaders[0], loaders[1], max_epochs=params.epochs, patience=params.patience)
     trainer.test(loaders[2])
     preds = trainer.predict(loaders[2]).cpu().numpy()

@@ -405,6 +405,35 @@ int tl_labels_from_scores(const float* tone_scores, const float* syl_scores, con
                           int64_t* syl, int32_t* pair, int32_t* err, int B, int n_tone_cls, int n_syl_cls, int n_rows, int n_syl,
                           int L, void* stream);
 
+/* ---- classifier training (models/classifier_trainer.py:72-89: nn.CrossEntropyLoss, loss.backward(), the confusion matrix) ---- */
+/* softmax cross-entropy of logits (B, N; row stride ldl >= N), 1 <= N <= 64, against labels (B) int64, and its statistics.
+ * Optional outputs (null to skip):
+ *   dlogits[b][n] = (softmax(logits[b])[n] - [n == labels[b]]) * grad_scale at row stride ldd, N <= ldd <= 64; columns
+ *                   N .. ldd - 1 are written as zeros (pad to a multiple of 4 and the rows are GEMM operands); pass
+ *                   grad_scale = 1 / B for the mean loss
+ *   dbias[n]      = sum over b of dlogits[b][n]
+ *   pred[b]       = arg-max of the row by torch's rule (first maximum, a NaN counts as the maximum), int64
+ * Accumulating outputs - ADDED to, so a caller zeroes them once per epoch and reads them once per epoch:
+ *   loss_sum      += sum over b of logsumexp(logits[b]) - logits[b][labels[b]]  (fp64; the row maximum is subtracted first)
+ *   count         += rows counted (int64);  confusion[t][p] += 1, (N, N) int64, row = true class
+ * A label outside [0, N) sets *err = 1 and contributes nothing (its dlogits row is zero).  The same inputs give the same
+ * bits of every output on every run (one workgroup walks the rows; the sums have a fixed order).
+ * labels = null: only pred is written (loss_sum, count, confusion and err are not touched and may be null).               */
+int tl_ce_loss(const float* logits, const int64_t* labels, float* dlogits, float* dbias, int64_t* pred, double* loss_sum,
+               int64_t* count, int64_t* confusion, int32_t* err, int B, int N, int ldl, int ldd, float grad_scale, void* stream);
+/* backward of a head layer z = h W^T + b with N <= 64 outputs over K inputs (K % 4 == 0), in one pass over its input:
+ * dlogits (B, N; row stride ldd), h (B, K) the layer's input, W (N, K).  Optional outputs (null to skip; each has the same
+ * bits whichever of the others are asked for):
+ *   dh[b][k]   = (sum_n dlogits[b][n] W[n][k]) * act'(h[b][k])   (B, K), act' of the layer BELOW read off its stored output
+ *                h: act 0 none (1), 1 ReLU (h > 0), 2 LeakyReLU (h > 0 ? 1 : slope) - the sign of the output is the sign of
+ *                the pre-activation
+ *   dbias_h[k] = sum_b dh[b][k]   (K)
+ *   dw[n][k]   = sum_b dlogits[b][n] h[b][k]   (N, K)
+ * All sums over b are taken in row order by the thread that owns the column: deterministic.  h, W and the outputs 16-byte
+ * aligned.  With dh null and h = x this is the weight gradient of LogisticRegressionClassifier's layer.                    */
+int tl_head_bwd(const float* dlogits, const float* h, const float* W, float* dh, float* dbias_h, float* dw, int B, int K, int N,
+                int ldd, int act, float slope, void* stream);
+
 /* ---- SynthesisLite blocks (models/synthesis_models.py:236-263,265-296) ----------------------
  * x (B,Cin,T) channels-first like the reference's Conv1d; 'same' padding (2*pad == k-1).       */
 /* z = conv1d(x,w)+bias; part[(b*ntile+tile)][Cout][2] = per-tile (sum z, sum (z - tile mean)^2),
