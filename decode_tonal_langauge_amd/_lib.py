@@ -124,6 +124,7 @@ SIGNATURES = {
     "tl_splitk_bias_lrelu": (_I, [_P, _P, _P, _I, _L, _I, _F, _P]),
     "tl_labels_from_scores": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "tl_ce_loss": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
+    "tl_ce_scores_loss": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "tl_head_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
     "tl_lite_conv_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "tl_lite_bn_finalize": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _I, _F, _F, _I, _P, _P]),

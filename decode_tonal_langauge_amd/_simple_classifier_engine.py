@@ -28,7 +28,9 @@ from .models.utils import split_decay_groups
 from .optim import FusedNAdam
 
 SUPPORTED = ("the fused classifier step supports LogisticRegressionClassifier and ShallowNNClassifier with fp32 parameters on "
-             "a CUDA device, input_dim % 4 == 0, hidden_dim % 4 == 0, n_classes <= 64 and a ReLU or LeakyReLU activation")
+             "a CUDA device, input_dim % 4 == 0, hidden_dim % 4 == 0, n_classes <= 64 and a ReLU or LeakyReLU activation; "
+             "CNNClassifier (_cnn_classifier_train_engine) with fp32 parameters on a CUDA device, negative_slope >= 0, "
+             "n_classes <= 64 and dropout < 1")
 
 
 def check_supported(model) -> None:

@@ -12,6 +12,10 @@ namespace tl {
 // fixed order - a wave adds its rows in row order, the 16 partial sums meet in wave order - and the same inputs give the same
 // bits.  The row arithmetic is fp64: B N exponentials are nothing next to the launch, and dlogits comes out as the rounding
 // of the exact value instead of carrying an fp32 log-sum-exp.  The integer counts use vector atomics.
+//   SCORES: the rows are the sigmoid outputs s = sigmoid(z) of the deep classifiers, which the reference trainer hands to
+// nn.CrossEntropyLoss as they are (models/deep_classifiers.py:97-99): loss = CE(s), and the gradient written is the one with
+// respect to the pre-sigmoid z, (softmax(s) - onehot) s (1 - s), with s (1 - s) formed from the stored fp32 score (a score
+// saturated at 0 or 1 gives exactly 0).
 // ------------------------------------------------------------------------------------------
 constexpr int CE_WAVES = 16;
 
@@ -22,6 +26,7 @@ __device__ __forceinline__ bool ce_better(float va, int ia, float vb, int ib) {
   return va > vb || (va == vb && ia < ib);
 }
 
+template <bool SCORES>
 __global__ __launch_bounds__(CE_WAVES * 64) void ce_loss_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
                                                                 float* __restrict__ dlogits, float* __restrict__ dbias,
                                                                 long long* __restrict__ pred, double* loss_sum, long long* count,
@@ -56,7 +61,9 @@ __global__ __launch_bounds__(CE_WAVES * 64) void ce_loss_kernel(const float* __r
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
     float g = 0.f;
     if (ok) {
-      g = (float)((e / s - (lane == (int)y ? 1.0 : 0.0)) * (double)grad_scale);
+      double gd = (e / s - (lane == (int)y ? 1.0 : 0.0)) * (double)grad_scale;
+      if constexpr (SCORES) gd *= (double)x * (1.0 - (double)x);       // d sigmoid / dz off the stored score
+      g = (float)gd;
       const double xy = (double)__shfl(x, (int)y, 64);
       loss += log(s) + m - xy;
       cnt += 1;
@@ -186,9 +193,10 @@ __global__ __launch_bounds__(64) void head_bwd_kernel(const float* __restrict__ 
 }  // namespace tl
 using namespace tl;
 
-extern "C" int tl_ce_loss(const float* logits, const int64_t* labels, float* dlogits, float* dbias, int64_t* pred,
-                          double* loss_sum, int64_t* count, int64_t* confusion, int32_t* err, int B, int N, int ldl, int ldd,
-                          float grad_scale, void* stream) {
+template <bool SCORES>
+static int ce_launch(const float* logits, const int64_t* labels, float* dlogits, float* dbias, int64_t* pred, double* loss_sum,
+                     int64_t* count, int64_t* confusion, int32_t* err, int B, int N, int ldl, int ldd, float grad_scale,
+                     void* stream) {
   TL_REQUIRE(logits != nullptr, "ce_loss: null logits");
   TL_REQUIRE(labels != nullptr || pred != nullptr, "ce_loss: null labels (allowed only to get pred alone)");
   TL_REQUIRE(labels == nullptr || (loss_sum && count && confusion && err),
@@ -198,10 +206,24 @@ extern "C" int tl_ce_loss(const float* logits, const int64_t* labels, float* dlo
   TL_REQUIRE(B >= 1, "ce_loss: the batch B must be at least 1");
   TL_REQUIRE(ldl >= N, "ce_loss: row stride ldl of logits below N");
   TL_REQUIRE(dlogits == nullptr || (ldd >= N && ldd <= 64), "ce_loss: row stride ldd of dlogits must lie in [N, 64]");
-  hipLaunchKernelGGL(ce_loss_kernel, dim3(1), dim3(CE_WAVES * 64), 0, (hipStream_t)stream, logits, (const long long*)labels,
-                     dlogits, dbias, (long long*)pred, loss_sum, (long long*)count, (unsigned long long*)confusion, err, B, N,
-                     ldl, ldd, grad_scale);
-  return check_launch("ce_loss");
+  hipLaunchKernelGGL(ce_loss_kernel<SCORES>, dim3(1), dim3(CE_WAVES * 64), 0, (hipStream_t)stream, logits,
+                     (const long long*)labels, dlogits, dbias, (long long*)pred, loss_sum, (long long*)count,
+                     (unsigned long long*)confusion, err, B, N, ldl, ldd, grad_scale);
+  return check_launch(SCORES ? "ce_scores_loss" : "ce_loss");
+}
+
+extern "C" int tl_ce_loss(const float* logits, const int64_t* labels, float* dlogits, float* dbias, int64_t* pred,
+                          double* loss_sum, int64_t* count, int64_t* confusion, int32_t* err, int B, int N, int ldl, int ldd,
+                          float grad_scale, void* stream) {
+  return ce_launch<false>(logits, labels, dlogits, dbias, pred, loss_sum, count, confusion, err, B, N, ldl, ldd, grad_scale,
+                          stream);
+}
+
+extern "C" int tl_ce_scores_loss(const float* scores, const int64_t* labels, float* dlogits, float* dbias, int64_t* pred,
+                                 double* loss_sum, int64_t* count, int64_t* confusion, int32_t* err, int B, int N, int ldl,
+                                 int ldd, float grad_scale, void* stream) {
+  return ce_launch<true>(scores, labels, dlogits, dbias, pred, loss_sum, count, confusion, err, B, N, ldl, ldd, grad_scale,
+                         stream);
 }
 
 extern "C" int tl_head_bwd(const float* dlogits, const float* h, const float* W, float* dh, float* dbias_h, float* dw, int B,

@@ -13,7 +13,8 @@ out as a plain loop:
     ignores classes with no true and no predicted sample), confusion matrix rows = true class;
   * ``metrics.csv`` per run with Lightning's column names, ``confusion_matrix_test.csv`` after test.
 
-``fused=True`` runs the same loop on the HIP path (``_simple_classifier_engine``: fused cross-entropy step, ``FusedNAdam``);
+``fused=True`` runs the same loop on the HIP path (``_simple_classifier_engine`` for the linear and shallow classifiers,
+``_cnn_classifier_train_engine`` for ``CNNClassifier``: fused cross-entropy step, ``FusedNAdam``);
 loss and confusion matrix then stay on the device and are read once per epoch.
 """
 from __future__ import annotations
@@ -61,8 +62,12 @@ class ClassifierTrainer:
         self.fused = bool(fused)
         self.engine = None
         if self.fused:         # an explicit request: a model / device pair the engine does not take raises (ValueError)
-            from .._simple_classifier_engine import SimpleClassifierEngine
-            self.engine = SimpleClassifierEngine(model, self.learning_rate, self.weight_decay)
+            from .deep_classifiers import CNNClassifier
+            if isinstance(model, CNNClassifier):
+                from .._cnn_classifier_train_engine import CnnClassifierTrainEngine as Engine
+            else:
+                from .._simple_classifier_engine import SimpleClassifierEngine as Engine
+            self.engine = Engine(model, self.learning_rate, self.weight_decay)
             self.optimizer = self.engine.optimizer
         else:
             self.optimizer = self.configure_optimizers()

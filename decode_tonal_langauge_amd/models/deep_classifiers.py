@@ -8,6 +8,9 @@ reference's constructor arguments, sub-module names (hence ``state_dict`` keys, 
 (how the trainer calls them) they run on the HIP kernels (``_classifier_engine``) - in eval mode and, with their
 ``nn.Dropout`` drawn from the package's counter-hash stream, in train mode (the reference CLI's default,
 train_synthesizer.py:275-284); only a call that needs autograd THROUGH the classifier uses the module graph.
+``CNNClassifier``'s own training runs on the HIP path too when asked for: ``ClassifierTrainer(model, fused=True)`` drives
+``_cnn_classifier_train_engine`` (conv-stack backward, cross-entropy on the sigmoid scores, ``FusedNAdam``) and never calls
+``forward``; ``CNNRNNClassifier`` trains through autograd only.
 """
 from __future__ import annotations
 
@@ -81,8 +84,8 @@ class CNNClassifier(ClassifierModel):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         # Inference on the GPU (how the synthesis trainer calls it): hand-written HIP path.  Anything
-        # that needs autograd through the classifier (its own training is outside the hot-path
-        # scope) uses the module graph on stock PyTorch-ROCm.
+        # that needs autograd through the classifier uses the module graph on stock PyTorch-ROCm (its
+        # fused training, ClassifierTrainer(fused=True), has an engine of its own and does not come here).
         needs_graph = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         p_drop = float(self.feature_extractor[-1].p) if self.training else 0.0
         if x.is_cuda and not needs_graph and p_drop < 1.0 and self._hip_cfg[2] >= 0:

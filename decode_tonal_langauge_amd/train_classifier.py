@@ -26,7 +26,7 @@ def run(config: dict) -> str:
     flat = {}
     for section in ("io", "experiment", "training"):
         flat.update(train_cfg.get(section, {}))
-    if "fused" in train_cfg:               # training.params.fused: the HIP train step of the simple classifiers
+    if "fused" in train_cfg:               # training.params.fused: the HIP train step of the classifiers that have one
         flat["fused"] = bool(train_cfg["fused"])
     model_cfg = config.get("model", {})
     dataset_cfg = config.get("dataset", {})

@@ -421,6 +421,16 @@ int tl_labels_from_scores(const float* tone_scores, const float* syl_scores, con
  * labels = null: only pred is written (loss_sum, count, confusion and err are not touched and may be null).               */
 int tl_ce_loss(const float* logits, const int64_t* labels, float* dlogits, float* dbias, int64_t* pred, double* loss_sum,
                int64_t* count, int64_t* confusion, int32_t* err, int B, int N, int ldl, int ldd, float grad_scale, void* stream);
+/* the same step for the deep classifiers, whose forward ends in a sigmoid and whose trainer applies nn.CrossEntropyLoss to those
+ * sigmoid outputs (models/deep_classifiers.py:97-99 under models/classifier_trainer.py:72-89): `scores` (B, N) are the fp32
+ * s = sigmoid(z) exactly as tl_linear_rows(act = 1) writes them, the loss is CE(s), and
+ *   dlogits[b][n] = (softmax(s[b])[n] - [n == labels[b]]) * s (1 - s) * grad_scale
+ * is the gradient with respect to the PRE-sigmoid z - what tl_head_bwd takes; s (1 - s) is formed from the stored score, so a
+ * score saturated at 0.0f or 1.0f gives exactly 0.  dbias, pred (arg-max of the scores), the accumulating statistics, the
+ * label check, the fixed summation order and the argument checks are tl_ce_loss's.                                        */
+int tl_ce_scores_loss(const float* scores, const int64_t* labels, float* dlogits, float* dbias, int64_t* pred, double* loss_sum,
+                      int64_t* count, int64_t* confusion, int32_t* err, int B, int N, int ldl, int ldd, float grad_scale,
+                      void* stream);
 /* backward of a head layer z = h W^T + b with N <= 64 outputs over K inputs (K % 4 == 0), in one pass over its input:
  * dlogits (B, N; row stride ldd), h (B, K) the layer's input, W (N, K).  Optional outputs (null to skip; each has the same
  * bits whichever of the others are asked for):
