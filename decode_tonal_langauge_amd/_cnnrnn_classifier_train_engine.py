@@ -1,0 +1,482 @@
+"""Training of ``CNNRNNClassifier`` on the HIP path (the loop of reference models/classifier_trainer.py:22-177 around the model
+of models/deep_classifiers.py:158-343: ``nn.CrossEntropyLoss`` on the model's SIGMOID outputs, ``loss.backward()``, ``NAdam``
+with two decay groups, a confusion matrix per epoch).
+
+One train step of a batch (B, C, T); t1 = (T - 6) // 2, ta = t1 - 6, tb = ta - 6, t' = tb // 3, w1 = lstm_dim / T, W = w1 + C:
+  lstm1     input projection of all T steps by one NT GEMM, then ``tl_lstm_train_seq`` (one fused launch per step) keeping
+            hs / cs / the activated gates of every step, rows time-major (t * B + b); h1 = hs[T - 1];
+  trunk     two ``tl_conv1_fwd`` launches (7 taps) write one branch-major row matrix - the B * w1 sequences cut from h1, then
+            the B * C electrode sequences - the two 7-tap stages run in the form ``TONAL_KERNELS conv7=`` selects (``wino63``:
+            ``tl_conv7_wino63v_nt``, or ``direct``), ``tl_pool3_fwd`` pools (3,1), applies the dropout mask and writes lstm2's
+            input matrix in the reference's raw-view order, rows time-major;
+  lstm2     as lstm1 over the t' steps; ``tl_linear_rows(act=1)`` on its last hidden state gives the sigmoid scores;
+  loss      ``tl_ce_scores_loss``: dz with respect to the pre-sigmoid output, the output bias gradient, loss sum / count /
+            confusion matrix ADDED to device words read once per epoch;
+  backward  ``tl_head_bwd`` -> dh2; ``tl_lstm_bptt_seq`` (one fused launch per step) -> dgates and their transposed copy;
+            dW_hh, dW_ih, db and dX2 = dgates . W_ih (ONE read of the weight, A = dgates^T) on the TN GEMM; ``tl_pool3_bwd``;
+            ``ConvStack.stage_wgrad`` / ``stage_dgrad`` for the two 7-tap stages (direct kernels, J = 7); ``tl_conv1_wgrad`` per
+            branch; ``tl_conv1_dgrad`` on the LSTM branch -> dh1; lstm1's BPTT and GEMMs;
+  update    one ``FusedNAdam`` over dense gradients (an LSTM weight gradient has rank T * B: no low-rank form).
+
+No host read happens in ``train_batch`` / ``eval_batch``.  There is no CPU fallback and no fallback to autograd."""
+from __future__ import annotations
+
+from typing import Dict, Optional
+
+import torch
+import torch.nn as nn
+
+from . import _kernels, _lib
+from ._conv_stack import ConvStack
+from ._launch import r4
+from ._lib import EPI_LRELU, EPI_STORE, LOAD_DIRECT, LOAD_V, check, ptr
+from ._simple_classifier_engine import SUPPORTED, SimpleClassifierEngine
+from .models.utils import split_decay_groups
+from .optim import FusedNAdam
+
+K7 = 7            # taps of every convolution of the model
+C_FIRST, C_A, C_B = 1024, 512, 256
+
+
+def geometry(n_channels: int, n_timepoints: int, lstm_dim: int) -> Dict[str, int]:
+    """Row counts of the trunk: after block 1 / 2 (t1), the two 7-tap stages (ta, tb), the (3,1) pool (tq)."""
+    t1 = (n_timepoints - K7 + 1) // 2
+    ta = t1 - K7 + 1
+    tb = ta - K7 + 1
+    w1 = lstm_dim // n_timepoints
+    return dict(t1=t1, ta=ta, tb=tb, tq=tb // 3, w1=w1, W=w1 + n_channels)
+
+
+def lstm2_input_index(b: int, ch: int, s: int, w: int, B: int, tq: int, W: int, channels: int = C_B):
+    """(row, column) of element (b, ch, s, w) of the contiguous (B, channels, tq, W) activation in lstm2's input matrix as this
+    engine keeps it: the reference's raw ``view(B, tq, -1)`` (:315) with rows time-major, row = step * B + b."""
+    f = (ch * tq + s) * W + w
+    return (f // (channels * W)) * B + b, f % (channels * W)
+
+
+def check_supported(model) -> None:
+    """Raise ``ValueError`` (stating the supported set) unless ``model`` can be trained by ``CnnRnnClassifierTrainEngine``."""
+    from .models.deep_classifiers import CNNRNNClassifier
+
+    def refuse(why: str):
+        raise ValueError(f"{why}: {SUPPORTED}")
+    if not isinstance(model, CNNRNNClassifier):
+        refuse(f"model {type(model).__name__}")
+    for m in model.modules():
+        if isinstance(m, nn.LeakyReLU) and m.negative_slope < 0:
+            refuse(f"negative_slope {m.negative_slope}")
+    if model.n_classes > 64:
+        refuse(f"n_classes {model.n_classes}")
+    p_drop = float(model.conv_block3[5].p)
+    if not p_drop < 1.0:
+        refuse(f"dropout {p_drop}")
+    if geometry(model.input_channels, model.input_length, model.lstm1.hidden_size)["tq"] < 1:
+        refuse(f"input_length {model.input_length} (no row is left behind the (3,1) pool)")
+    for p in model.parameters():
+        if not p.is_cuda or p.dtype != torch.float32:
+            refuse(f"parameters on '{p.device}' in {p.dtype}")
+
+
+class _Lstm:
+    """Packed weights and the kept state of one ``nn.LSTM`` for one batch size; rows are time-major (t * B + b)."""
+
+    def __init__(self, name: str, mod: nn.LSTM, T: int, B: int, dev, want_dx: bool):
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.name, self.T, self.B = name, T, B
+        self.in_dim, self.H = mod.input_size, mod.hidden_size
+        self.Kp, self.Hp = r4(self.in_dim), (self.H + 7) // 8 * 8
+        self.padded = self.Kp != self.in_dim or self.Hp != self.H
+        H4, rows = 4 * self.Hp, T * B
+        self.wi = torch.zeros(H4, self.Kp, **f32) if self.padded else None      # (lstm2: weight_ih_l0 is used where it lies)
+        self.bs = torch.zeros(H4, **f32)
+        self.whp = torch.zeros(H4, self.Hp, **f32)                               # unit-major: row 4 u + g
+        self.whT = torch.zeros(self.Hp, H4, **f32)                               # W_hh^T: row u', column g Hp + u
+        self.xp = torch.empty(rows, H4, **f32)
+        self.hs = torch.empty(rows, self.Hp, **f32)
+        self.cs = torch.empty(rows, self.Hp, **f32)
+        self.act = torch.empty(rows, H4, **f32)
+        self.dgates = torch.empty(rows, H4, **f32)
+        self.dc = torch.empty(B, self.Hp, **f32)
+        self.dh_last = torch.zeros(B, self.Hp, **f32)                            # pad columns stay zero
+        self.ldt = (rows + 31) // 32 * 32
+        self.dgT = torch.zeros(H4, self.ldt, **f32) if want_dx else None         # pad columns stay zero
+        self.colsum = torch.empty(H4, **f32)
+        self.packed = None                                                       # weight version the packs were made from
+
+    def h_last(self) -> torch.Tensor:
+        return self.hs[(self.T - 1) * self.B:]
+
+
+class _Ws:
+    """Buffers outside the conv stack for one batch size."""
+
+    def __init__(self, eng, B: int, dev):
+        f32 = dict(dtype=torch.float32, device=dev)
+        m = eng.model
+        self.l1 = _Lstm("lstm1", m.lstm1, eng.T, B, dev, False)
+        self.l2 = _Lstm("lstm2", m.lstm2, eng.tq, B, dev, True)
+        self.x1 = torch.zeros(eng.T * B, self.l1.Kp, **f32)                      # lstm1's input rows (t * B + b, electrode)
+        self.xb = torch.empty(B * eng.w1, eng.T, **f32)                          # block 2's sequences cut from h1
+        self.X2 = torch.empty(eng.tq * B, C_B * eng.W, **f32)                    # lstm2's input rows
+        self.dX2 = torch.empty(eng.tq * B, C_B * eng.W, **f32)
+        self.scores = torch.empty(B, eng.N, **f32)
+        self.dz = torch.zeros(B, r4(eng.N), **f32)
+        self.pred = torch.empty(B, dtype=torch.int64, device=dev)
+
+
+class CnnRnnClassifierTrainEngine(ConvStack):
+    F63_CAPABLE = False        # (the 3-tap F(6,3) stack does not apply: every stage here has 7 taps)
+
+    def __init__(self, model, learning_rate: float = 0.0005, weight_decay: float = 0.0):
+        check_supported(model)
+        Cn, T = int(model.input_channels), int(model.input_length)
+        slope = float(model.conv_pool_block1[1].negative_slope)
+        geo = geometry(Cn, T, model.lstm1.hidden_size)
+        self.w1, self.W, self.Cn = geo["w1"], geo["W"], Cn
+        # the conv stack sees W sequences per batch element (branch-major: see _forward); three 7-tap stages, the first pooled
+        super().__init__(self.W, T, [(C_FIRST, K7, True), (C_A, K7, False), (C_B, K7, False)], slope, C_B)
+        self.t1, self.ta, self.tb, self.tq = geo["t1"], geo["ta"], geo["tb"], geo["tq"]
+        assert self.t1 == self.tout1 and self.stages[1].tout == self.tb
+        # rows per sequence: whole hexes for the F(6,3) form of the 7-tap forward, whole quads otherwise (CnnRnnConvEngine's)
+        self.conv7_form = _kernels.get("conv7")
+        self.Tp = (self.t1 + 5) // 6 * 6 if self.conv7_form == "wino63" else (self.t1 + 3) // 4 * 4
+        self.tp1 = self.Tp
+        for st in self.stages:
+            st.tp_in = st.tp_out = self.Tp
+        self.fuse_c1 = False
+        self.model = model
+        self.STAGE_NAMES = {2: "conv_block3.0", 3: "conv_block3.2"}
+        self.N = int(model.n_classes)
+        self.p_drop = float(model.conv_block3[5].p)
+        self.device = model.output.weight.device
+        if model.lstm2.hidden_size % 8 != 0 or model.lstm2.input_size != C_B * self.W:
+            raise ValueError(f"lstm2 ({model.lstm2.input_size} -> {model.lstm2.hidden_size}): {SUPPORTED}")
+        self.params: Dict[str, nn.Parameter] = dict(model.named_parameters())
+        decay, no_decay = split_decay_groups(model.named_parameters())
+        self.optimizer = FusedNAdam([{"params": decay, "weight_decay": float(weight_decay)},
+                                     {"params": no_decay, "weight_decay": 0.0}], lr=float(learning_rate), stored_beta2=True)
+        # loss sum (the bits of a double), sample count, label-range flag, confusion matrix: one buffer, one read per epoch
+        self.stats = torch.zeros(3 + self.N * self.N, dtype=torch.int64, device=self.device)
+        self.grads: Dict[str, torch.Tensor] = {k: torch.zeros_like(p) for k, p in self.params.items()}
+        self._ws: Dict[int, _Ws] = {}
+        self._updates = 0                  # optimiser steps taken: part of the key of every weight pack
+        self._packs: Dict[str, tuple] = {}
+        self.last_seed = 0                 # dropout seed of the last forward pass (0: no dropout applied)
+
+    # ------------------------------------------------------------------ buffers
+    def _alloc_rows(self):
+        S, dev, Tp = self.S, self._dev, self.Tp
+        z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+        zi = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
+        rows = S * Tp
+        # + 8 rows: a 7-tap window reads up to 6 rows past the last row it is asked about
+        self.P = {1: z(rows + 8, C_FIRST), 2: z(rows + 8, C_A), 3: z(rows, C_B)}
+        self.bits = {1: zi(rows, C_FIRST // 32)}
+        self.sbits = {1: zi(rows, C_FIRST // 32)}
+        self.V7 = None
+        if self.conv7_form == "wino63":
+            nh_pad = (rows // 6 + 2 + 127) // 128 * 128
+            self.V7 = (z(nh_pad, 8, C_FIRST), z(nh_pad, 8, C_FIRST))
+
+    def _alloc_bwd(self) -> bool:
+        if self.G is not None:
+            return False
+        z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=self._dev)
+        rows = self.S * self.Tp
+        self.G = {1: z(rows, C_FIRST), 2: z(rows, C_A), 3: z(rows, C_B)}
+        return True
+
+    def _work(self, B: int) -> _Ws:
+        ws = self._ws.get(B)
+        if ws is None or ws.scores.device != self._dev:
+            if len(self._ws) > 2:
+                self._ws.clear()
+            ws = self._ws[B] = _Ws(self, B, self._dev)
+        return ws
+
+    def _input(self, x: torch.Tensor) -> torch.Tensor:
+        _lib.require_gpu(x, "CnnRnnClassifierTrainEngine")
+        if x.ndim != 3 or x.shape[1] != self.Cn or x.shape[2] != self.T:
+            raise ValueError(f"expected input (B, {self.Cn}, {self.T}), got {tuple(x.shape)}")
+        if x.shape[0] < 1:
+            raise ValueError("empty batch")
+        return x.float().contiguous()
+
+    def _labels(self, y: torch.Tensor, B: int) -> torch.Tensor:
+        _lib.require_gpu(y, "CnnRnnClassifierTrainEngine")
+        if y.shape != (B,):
+            raise ValueError(f"expected {B} labels, got {tuple(y.shape)}")
+        return y.long().contiguous()
+
+    def _call(self, tag: str, name: str, *args) -> None:
+        ev = self._tick(tag)
+        check(getattr(self.lib, name)(*args, self._stream()), name)
+        if ev:
+            ev[1].record()
+
+    # ------------------------------------------------------------------ LSTM
+    def _version(self, *names) -> tuple:
+        """What a pack of these parameters is keyed on: the engine's own update count (FusedNAdam writes through ``data_ptr``
+        and leaves ``_version`` alone) and torch's version / storage of every tensor (``load_state_dict``, ``.to``)."""
+        return (self._updates,) + tuple((self.params[n]._version, self.params[n].data_ptr()) for n in names)
+
+    def _lstm_pack(self, l: _Lstm) -> None:
+        """The packs of the CURRENT weights: once per weight version (a train step moves it, ``eval_batch`` does not)."""
+        prm = self.params
+        ver = self._version(*(f"{l.name}.{n}" for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")))
+        if l.packed == ver:
+            return
+        l.packed = ver
+        w_ih, w_hh = prm[f"{l.name}.weight_ih_l0"].data, prm[f"{l.name}.weight_hh_l0"].data
+        H, Hp, D, Kp = l.H, l.Hp, l.in_dim, l.Kp
+        if l.padded:
+            self._permute(w_ih, l.wi, (1, 4, Hp, Kp), (0, H * D, D, 1), (1, 4, H, D))
+        self._permute(w_hh, l.whp, (1, Hp, 4, Hp), (0, H, H * H, 1), (1, H, 4, H))
+        self._permute(w_hh, l.whT, (1, Hp, 4, Hp), (0, 1, H * H, H), (1, H, 4, H))
+        l.bs.view(4, Hp)[:, :H] = (prm[f"{l.name}.bias_ih_l0"].data + prm[f"{l.name}.bias_hh_l0"].data).view(4, H)
+
+    def _w_ih(self, l: _Lstm) -> torch.Tensor:
+        return l.wi if l.padded else self.params[f"{l.name}.weight_ih_l0"].data
+
+    def _lstm_forward(self, l: _Lstm, x_rows: torch.Tensor) -> None:
+        self._lstm_pack(l)
+        rows, H4 = l.T * l.B, 4 * l.Hp
+        self._nt(tag=f"{l.name}_xproj", A=ptr(x_rows), Bw=ptr(self._w_ih(l)), bias=ptr(l.bs), out=ptr(l.xp), M=rows, A_rows=rows,
+                 N=H4, K=l.Kp, lda=l.Kp, ldb=l.Kp, ldo=H4, Tvalid=1, loader=LOAD_DIRECT, epilogue=EPI_STORE)
+        self._call(f"{l.name}_fwd_seq", "tl_lstm_train_seq", ptr(l.xp), H4, l.B * H4, ptr(l.whp), ptr(l.hs), ptr(l.cs),
+                   ptr(l.act), l.B, l.Hp, l.T)
+
+    def _colsum_wide(self, M: torch.Tensor, rows: int, ncols: int, dst: torch.Tensor) -> None:
+        flat = M.view(-1)
+        for c0 in range(0, ncols, 1024):
+            nc = min(1024, ncols - c0)
+            self._colsum(flat[c0:], rows, nc, ncols, 1, 1, dst[c0:c0 + nc])
+
+    def _tn_reduced(self, tag, A, a_off, Bm, Krows, Mdim, Ndim, lda, ldb, dst, dst_dims, dst_strides) -> None:
+        """dst (a 4-d contiguous view given by ``dst_dims``) = the (Mdim, Ndim) product A^T . B read through ``dst_strides``,
+        split-K slabs summed on the way; written in place when no split and no re-indexing is needed."""
+        f32 = dict(dtype=torch.float32, device=self._dev)
+        tiles = ((Mdim + 127) // 128) * ((Ndim + 127) // 128)
+        sk = self._splitk(tiles, (Krows + 31) // 32, 1024)
+        direct = sk == 1 and dst.numel() == Mdim * Ndim
+        slab = dst if direct else torch.empty(sk, Mdim, Ndim, **f32)
+        self._tn(tag=tag, A=A.data_ptr() + 4 * a_off, B=ptr(Bm), slab=ptr(slab), Krows=Krows, A_rows=Krows, B_rows=Krows,
+                 Mdim=Mdim, Ndim=Ndim, lda=lda, ldb=ldb, ldc=Ndim, loader=LOAD_DIRECT, splitk=sk, slab_stride=Mdim * Ndim)
+        if not direct:
+            self._permute(slab, dst, dst_dims, dst_strides, nz=sk, zs=Mdim * Ndim)
+
+    def _lstm_backward(self, l: _Lstm, x_rows: torch.Tensor, dx: Optional[torch.Tensor]) -> None:
+        """BPTT from ``l.dh_last``; dW_ih, dW_hh, both bias gradients into ``self.grads``; ``dx`` (rows, in_dim) on request."""
+        rows, B, T, H, Hp, H4 = l.T * l.B, l.B, l.T, l.H, l.Hp, 4 * l.Hp
+        g = self.grads
+        self._call(f"{l.name}_bptt_seq", "tl_lstm_bptt_seq", ptr(l.whT), ptr(l.dh_last), ptr(l.act), ptr(l.cs), ptr(l.dc),
+                   ptr(l.dgates), ptr(l.dgT), l.ldt, B, Hp, T)
+        ghh = g[f"{l.name}.weight_hh_l0"]
+        if T > 1:          # dW_hh = dgates[1:]^T . hs[:-1]: a row offset of B between the operands
+            self._tn_reduced(f"{l.name}_whh_grad", l.dgates, B * H4, l.hs, (T - 1) * B, H4, Hp, H4, Hp, ghh, (1, 4, H, H),
+                             (0, Hp * Hp, Hp, 1))
+        else:
+            ghh.zero_()
+        self._tn_reduced(f"{l.name}_wih_grad", l.dgates, 0, x_rows, rows, H4, l.Kp, H4, l.Kp, g[f"{l.name}.weight_ih_l0"],
+                         (1, 4, H, l.in_dim), (0, Hp * l.Kp, l.Kp, 1))
+        self._colsum_wide(l.dgates, rows, H4, l.colsum)
+        for which in ("bias_ih_l0", "bias_hh_l0"):
+            self._permute(l.colsum, g[f"{l.name}.{which}"], (1, 1, 4, H), (0, 0, Hp, 1))
+        if dx is None:
+            return
+        # dx (rows, in) = dgates . W_ih: the TN GEMM reduces over the 4 H rows of the weight as stored, A = dgates^T (pad
+        # columns zero) - one read of the weight, no transposed copy
+        w, ldt, K = self._w_ih(l), l.ldt, l.Kp
+        if ldt <= 32:                # skinny streaming kernel: 512-column tiles, 16-deep K stages
+            sk = self._splitk((K + 511) // 512, (H4 + 15) // 16, 1024)
+        else:
+            sk = self._splitk(((ldt + 127) // 128) * ((K + 127) // 128), (H4 + 31) // 32, 1024)
+        slab = torch.empty(sk, ldt, K, dtype=torch.float32, device=self._dev)
+        self._tn(tag=f"{l.name}_dx", A=ptr(l.dgT), B=ptr(w), slab=ptr(slab), Krows=H4, A_rows=H4, B_rows=H4, Mdim=ldt, Ndim=K,
+                 lda=ldt, ldb=K, ldc=K, loader=LOAD_DIRECT, splitk=sk, slab_stride=ldt * K)
+        self._permute(slab, dx, (1, 1, rows, l.in_dim), (0, 0, K, 1), nz=sk, zs=ldt * K)
+
+    # ------------------------------------------------------------------ the 7-tap stages, forward
+    def _conv7(self, tag, src, name, dst, cin, cout, tvalid) -> None:
+        """dst[r] = lrelu(sum_j w[:, :, j] src[r + j] + b) for every row r of the stack; src holds 8 rows more."""
+        rows = self.S * self.Tp
+        st_ = self._stream()
+        w, b = self.params[name + ".weight"].data, self.params[name + ".bias"].data
+        name = name + ".weight"
+        if self.conv7_form == "wino63":
+            nhex = rows // 6
+            V0 = self.V7[0].view(-1)[: self.V7[0].shape[0] * 8 * cin].view(-1, 8, cin)
+            V1 = self.V7[1].view(-1)[: self.V7[1].shape[0] * 8 * cin].view(-1, 8, cin)
+            if cin != self.V7[0].shape[2]:
+                # a narrower layer re-views the storage: its pad hexes overlay the wider layer's transform data - zero them
+                # ("zero hexes appended", tl_conv7_wino63v_nt's contract)
+                h0 = (nhex + 1) // 2 * 2
+                V0[h0:].zero_()
+                V1[h0:].zero_()
+            ev = self._tick(tag + "_xform")
+            check(self.lib.tl_wino63_xform2(ptr(src), ptr(V0), ptr(V1), rows, self.Tp, tvalid, cin, src.shape[1], cin, st_),
+                  "tl_wino63_xform2")
+            hit = self._packs.get(tag)
+            if hit is None or hit[0] != self._version(name):
+                wp = hit[1] if hit is not None else torch.empty(3 * cin // 8, 8, cout, 8, dtype=torch.float32, device=w.device)
+                check(self.lib.tl_wino63_weights7(ptr(w.reshape(cout, cin, K7)), ptr(wp), cout, cin, K7, st_), "tl_wino63_weights7")
+                self._packs[tag] = (self._version(name), wp)
+            wp = self._packs[tag][1]
+            if ev:
+                ev[1].record()
+            self._nt(tag=tag, fn="tl_conv7_wino63v_nt", A=ptr(V0), aux=ptr(V1), A_rows=V0.shape[0], lda=cin, Bw=ptr(wp),
+                     bias=ptr(b), out=ptr(dst), M=rows, N=cout, K=cin, ldb=3 * cin, ldo=dst.shape[1], J=K7, row_shift=0,
+                     Tp=self.Tp, Tvalid=self.Tp, slope=self.slope, loader=LOAD_V, epilogue=EPI_LRELU)
+            return
+        hit = self._packs.get(tag)
+        if hit is None or hit[0] != self._version(name):
+            self._packs[tag] = (self._version(name), self._pack_conv(w, cin, False))     # [J][O][I]
+        wp = self._packs[tag][1]
+        self._nt(tag=tag, A=ptr(src), Bw=ptr(wp), bias=ptr(b), out=ptr(dst), M=rows, A_rows=rows + 8, N=cout, K=cin, lda=cin,
+                 ldb=cin, ldo=cout, J=K7, row_shift=0, Tp=self.Tp, Tvalid=self.Tp, slope=self.slope, loader=LOAD_DIRECT,
+                 epilogue=EPI_LRELU)
+
+    # ------------------------------------------------------------------ forward
+    def _branches(self, ws: _Ws, B: int):
+        """(sequences, count, first row of the stack, parameter prefix) of the two first-stage branches, in storage order:
+        the LSTM branch (block 2), then the electrodes (block 1) - the width order of ``torch.cat((x1, x), dim=3)``."""
+        nb = B * self.w1
+        return ((ws.xb, nb, 0, "conv_pool_block2.0"), (self._x, B * self.Cn, nb * self.Tp, "conv_pool_block1.0"))
+
+    def _forward(self, x: torch.Tensor, dropout: bool) -> _Ws:
+        B = x.shape[0]
+        self._alloc(B, x.device)
+        ws = self._work(B)
+        prm = self.params
+        self.generation += 1
+        self._x = x
+        Cn, T, w1, Tp = self.Cn, self.T, self.w1, self.Tp
+        # lstm1 over the electrodes: rows (t * B + b), columns the electrodes (pad columns stay zero)
+        l1, l2 = ws.l1, ws.l2
+        self._permute(x, ws.x1, (1, T, B, l1.Kp), (0, 1, Cn * T, T), (1, T, B, Cn))
+        self._lstm_forward(l1, ws.x1)
+        # block 2 reads h1 as (B, 1, T, w1): sequence (b, j) holds h1[b][t * w1 + j]
+        self._permute(l1.hs, ws.xb, (1, B, w1, T), (0, l1.Hp, 1, w1), src_off=(T - 1) * B * l1.Hp)
+        ev = self._tick("conv1_fwd")
+        for seqs, n, row0, name in self._branches(ws, B):
+            w = prm[name + ".weight"].data.reshape(C_FIRST, K7)
+            check(self.lib.tl_conv1_fwd(ptr(seqs), ptr(w), ptr(prm[name + ".bias"].data), ptr(self.P[1][row0:]),
+                                        ptr(self.bits[1][row0:]), ptr(self.sbits[1][row0:]), n, T, K7, C_FIRST, Tp, self.t1,
+                                        self.slope, self._stream()), "tl_conv1_fwd")
+        if ev:
+            ev[1].record()
+        self._conv7("conv3a_fwd", self.P[1], "conv_block3.0", self.P[2], C_FIRST, C_A, self.t1)
+        self._conv7("conv3b_fwd", self.P[2], "conv_block3.2", self.P[3], C_A, C_B, self.ta)
+        self.last_seed = 0
+        if dropout and self.p_drop > 0.0:
+            self.last_seed = int(self.model._next_seed())
+        self._call("pool3_fwd", "tl_pool3_fwd", ptr(self.P[3]), ptr(ws.X2), B, w1, Cn, C_B, Tp, self.tq, C_B, 1, B,
+                   self.p_drop if self.last_seed else 0.0, self.last_seed)
+        self._lstm_forward(l2, ws.X2)
+        out = self.model.output
+        check(self.lib.tl_linear_rows(ptr(l2.h_last()), ptr(out.weight.data), ptr(out.bias.data), ptr(ws.scores), B, l2.Hp,
+                                      self.N, l2.Hp, 1, self._stream()), "tl_linear_rows")
+        return ws
+
+    def _ce(self, ws: _Ws, y: Optional[torch.Tensor], B: int, grad: bool, pred: bool) -> None:
+        base = self.stats.data_ptr()
+        check(self.lib.tl_ce_scores_loss(ptr(ws.scores), ptr(y), ptr(ws.dz) if grad else None,
+                                         ptr(self.grads["output.bias"]) if grad else None, ptr(ws.pred) if pred else None,
+                                         base, base + 8, base + 24, base + 16, B, self.N, self.N, ws.dz.shape[1], 1.0 / B,
+                                         self._stream()), "tl_ce_scores_loss")
+
+    # ------------------------------------------------------------------ backward
+    def _backward(self, ws: _Ws, B: int) -> None:
+        """Every gradient of the step from ``ws.dz`` into ``self.grads``."""
+        self._alloc_bwd()
+        prm, g = self.params, self.grads
+        l1, l2 = ws.l1, ws.l2
+        Cn, T, w1, Tp = self.Cn, self.T, self.w1, self.Tp
+        check(self.lib.tl_head_bwd(ptr(ws.dz), ptr(l2.h_last()), ptr(self.model.output.weight.data), ptr(l2.dh_last), None,
+                                   ptr(g["output.weight"]), B, l2.Hp, self.N, ws.dz.shape[1], 0, self.slope, self._stream()),
+              "tl_head_bwd")
+        self._lstm_backward(l2, ws.X2, ws.dX2)
+        self._call("pool3_bwd", "tl_pool3_bwd", ptr(self.P[3]), ptr(ws.dX2), ptr(self.G[3]), B, w1, Cn, C_B, Tp, self.tq, C_B,
+                   C_B, 1, B, self.p_drop if self.last_seed else 0.0, self.last_seed, self.slope)
+        for st in reversed(self.stages):
+            name = self.STAGE_NAMES[st.idx]
+            self.stage_wgrad(st, g[name + ".weight"], g[name + ".bias"])
+            self.stage_dgrad(st, prm[name + ".weight"].data)
+        f32 = dict(dtype=torch.float32, device=self._dev)
+        ev = self._tick("conv1_wgrad")
+        for seqs, n, row0, name in self._branches(ws, B):
+            nblk = int(min(2048, n))
+            part = torch.empty(nblk, (K7 + 1) * C_FIRST, **f32)
+            check(self.lib.tl_conv1_wgrad(ptr(seqs), ptr(self.G[1][row0:]), ptr(self.bits[1][row0:]), ptr(part), nblk, n, T, K7,
+                                          C_FIRST, Tp, self.t1, self._stream()), "tl_conv1_wgrad")
+            self._reduce_c1_partials(part, g[name + ".weight"], g[name + ".bias"])
+        if ev:
+            ev[1].record()
+        # dh1[b][t * w1 + j] = dx of sequence (b, j) at sample t: straight into lstm1's dh_last (pad columns stay zero)
+        w2 = prm["conv_pool_block2.0.weight"].data.reshape(C_FIRST, K7)
+        self._call("conv1_dgrad", "tl_conv1_dgrad", ptr(self.G[1]), ptr(self.bits[1]), ptr(w2), ptr(l1.dh_last), B * w1, T, K7,
+                   C_FIRST, Tp, self.t1, w1, l1.Hp, w1, 1)
+        self._lstm_backward(l1, ws.x1, None)
+
+    def _refresh_inference_packs(self) -> None:
+        # FusedNAdam writes through data_ptr: the module's inference engines key their packed weights on ``_version``, which
+        # did not move
+        m = self.model
+        if getattr(m, "_hip", None) is not None:
+            m._hip._packed.clear()
+            m._hip_lstm1._packed = None
+            m._hip_lstm2._packed = None
+
+    def _step(self, x: torch.Tensor, y: torch.Tensor, update: bool) -> _Ws:
+        x = self._input(x)
+        B = x.shape[0]
+        y = self._labels(y, B)
+        ws = self._forward(x, dropout=self.model.training)
+        self._ce(ws, y, B, grad=True, pred=False)
+        self._backward(ws, B)
+        if update:
+            ev = self._tick("update")
+            self.optimizer.step(grads={self.params[k]: g for k, g in self.grads.items()})
+            if ev:
+                ev[1].record()
+            self._updates += 1
+            self._refresh_inference_packs()
+        return ws
+
+    # ------------------------------------------------------------------ the public steps
+    @torch.no_grad()
+    def train_batch(self, x: torch.Tensor, y: torch.Tensor) -> None:
+        """Forward, loss, backward and update for one batch; everything stays on the stream (no host read)."""
+        self._step(x, y, update=True)
+
+    @torch.no_grad()
+    def backward_only(self, x: torch.Tensor, y: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """Debug hook: forward, loss and backward of one batch WITHOUT the update.  {parameter name: gradient}; the tensors are
+        the engine's buffers: valid until the next step.  The batch is counted in the epoch statistics like any other."""
+        self._step(x, y, update=False)
+        return self.step_gradients()
+
+    def step_gradients(self) -> Dict[str, torch.Tensor]:
+        """The gradients of the last ``train_batch`` / ``backward_only`` (all dense)."""
+        return dict(self.grads)
+
+    @torch.no_grad()
+    def eval_batch(self, x: torch.Tensor, y: torch.Tensor) -> None:
+        """Forward (no dropout) and loss statistics of one batch (no gradients, no update)."""
+        x = self._input(x)
+        ws = self._forward(x, dropout=False)
+        self._ce(ws, self._labels(y, x.shape[0]), x.shape[0], grad=False, pred=False)
+
+    @torch.no_grad()
+    def predict_batch(self, x: torch.Tensor) -> torch.Tensor:
+        """Arg-max class of every row (int64, on the device)."""
+        x = self._input(x)
+        ws = self._forward(x, dropout=False)
+        self._ce(ws, None, x.shape[0], grad=False, pred=True)
+        return ws.pred.clone()
+
+    def scores(self, B: int) -> torch.Tensor:
+        """The float32 sigmoid scores (B, n_classes) of the last forward pass at batch ``B``."""
+        return self._ws[B].scores
+
+    epoch_stats = SimpleClassifierEngine.epoch_stats      # (the same statistics buffer: one read per epoch, zeroed afterwards)

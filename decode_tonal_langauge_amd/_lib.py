@@ -126,6 +126,11 @@ SIGNATURES = {
     "tl_ce_loss": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "tl_ce_scores_loss": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "tl_head_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
+    "tl_lstm_train_seq": (_I, [_P, _L, _L, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "tl_lstm_bptt_seq": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _P]),
+    "tl_pool3_fwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _L, _F, C.c_uint64, _P]),
+    "tl_pool3_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _L, _L, _F, C.c_uint64, _F, _P]),
+    "tl_conv1_dgrad": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _L, _L, _L, _P]),
     "tl_lite_conv_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "tl_lite_bn_finalize": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _I, _F, _F, _I, _P, _P]),
     "tl_lite_bn_act_pool_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P]),

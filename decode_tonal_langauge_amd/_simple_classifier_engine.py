@@ -30,7 +30,8 @@ from .optim import FusedNAdam
 SUPPORTED = ("the fused classifier step supports LogisticRegressionClassifier and ShallowNNClassifier with fp32 parameters on "
              "a CUDA device, input_dim % 4 == 0, hidden_dim % 4 == 0, n_classes <= 64 and a ReLU or LeakyReLU activation; "
              "CNNClassifier (_cnn_classifier_train_engine) with fp32 parameters on a CUDA device, negative_slope >= 0, "
-             "n_classes <= 64 and dropout < 1")
+             "n_classes <= 64 and dropout < 1; CNNRNNClassifier (_cnnrnn_classifier_train_engine) under the same conditions with "
+             "at least one row left behind its (3,1) pool")
 
 
 def check_supported(model) -> None:

@@ -31,5 +31,15 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ float lrelu(float z, float slope) { return z > 0.f ? z : z * slope; }
+__device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
+
+// counter-based uniform in [0,1): splitmix64 finaliser over (seed, index)
+__device__ __forceinline__ float u01(uint64_t seed, uint64_t idx) {
+  uint64_t zz = seed + 0x9E3779B97F4A7C15ull * (idx + 1);
+  zz = (zz ^ (zz >> 30)) * 0xBF58476D1CE4E5B9ull;
+  zz = (zz ^ (zz >> 27)) * 0x94D049BB133111EBull;
+  zz ^= zz >> 31;
+  return (float)(zz >> 40) * (1.0f / 16777216.0f);
+}
 
 }  // namespace tl

@@ -1348,7 +1348,7 @@ extern "C" int tl_gemm_tn_window(const tl_tn_params* pp, void* stream) {
   TL_REQUIRE(p.Krows > 0 && p.Mdim > 0 && p.Ndim > 0, "tn_window: bad sizes");
   TL_REQUIRE(p.Krows + 64 < (1LL << 31), "tn_window: more than 2^31 reduction rows");
   TL_REQUIRE(p.Mdim % 4 == 0 && p.Ndim % 4 == 0 && p.lda % 4 == 0 && p.ldb % 4 == 0, "tn_window: dims/ld must be multiples of 4");
-  TL_REQUIRE(p.J >= 1 && p.J <= 3, "tn_window: J must be 1..3");
+  TL_REQUIRE(p.J >= 1 && p.J <= 7, "tn_window: J must be 1..7");
   TL_REQUIRE(p.Tp > 0, "tn_window: Tp must be positive");
   TL_REQUIRE(p.splitk <= 65535, "tn_window: splitk too large");
   if (p.loader == LOAD_UNPOOL) {

@@ -16,15 +16,6 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-// counter-based uniform in [0,1): splitmix64 finaliser over (seed, index)
-__device__ __forceinline__ float u01(uint64_t seed, uint64_t idx) {
-  uint64_t zz = seed + 0x9E3779B97F4A7C15ull * (idx + 1);
-  zz = (zz ^ (zz >> 30)) * 0xBF58476D1CE4E5B9ull;
-  zz = (zz ^ (zz >> 27)) * 0x94D049BB133111EBull;
-  zz ^= zz >> 31;
-  return (float)(zz >> 40) * (1.0f / 16777216.0f);
-}
-
 // ------------------------------------------------------------------------------------------
 // conv1 forward: one workgroup per sequence, thread = output channel(s)
 // ------------------------------------------------------------------------------------------
@@ -306,7 +297,8 @@ __global__ __launch_bounds__(256) void stage_step_kernel(stage_args a, float* __
 }
 
 // conv1 weight/bias gradient partials: block handles a contiguous range of sequences;
-// thread owns channels tid and tid + 256 (C1 <= 512), barriers are outside every guard.
+// thread owns channels tid and tid + 256 of its 512-channel slice (blockIdx.y; one slice for C1 <= 512), barriers are outside
+// every guard.
 __global__ __launch_bounds__(256) void conv1_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ G,
                                                           const uint32_t* __restrict__ bits, float* __restrict__ partial,
                                                           long long S, int T, int kt, int C1, int Tp, int Tout) {
@@ -325,7 +317,7 @@ __global__ __launch_bounds__(256) void conv1_wgrad_kernel(const float* __restric
     __syncthreads();
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      const int o = threadIdx.x + h * 256;
+      const int o = blockIdx.y * 512 + threadIdx.x + h * 256;
       if (o < C1) {
         int p = 0;
         for (; p + 4 <= Tout; p += 4) {          // 4 independent loads in flight per thread
@@ -362,7 +354,7 @@ __global__ __launch_bounds__(256) void conv1_wgrad_kernel(const float* __restric
   float* dst = partial + (long long)blockIdx.x * (kt + 1) * C1;
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
-    const int o = threadIdx.x + h * 256;
+    const int o = blockIdx.y * 512 + threadIdx.x + h * 256;
     if (o < C1) {
 #pragma unroll
       for (int j = 0; j < MAXKT; ++j)
@@ -492,8 +484,6 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ G
 // ------------------------------------------------------------------------------------------
 // LSTM cell (torch gate order i, f, g, o)
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
-
 __global__ __launch_bounds__(256) void lstm_cell_fwd_kernel(const float* __restrict__ hh, const float* __restrict__ x_t,
                                                             const float* __restrict__ w_ih, const float* __restrict__ b_ih,
                                                             const float* __restrict__ b_hh, const float* __restrict__ c_prev,
@@ -1294,10 +1284,10 @@ extern "C" int tl_conv1_wgrad(const float* x, const float* G, const uint32_t* bi
   TL_REQUIRE(x && G && bits && partial, "conv1_wgrad: null pointer");
   TL_REQUIRE(nblk > 0 && S > 0, "conv1_wgrad: bad sizes");
   TL_REQUIRE(ktaps >= 1 && ktaps <= MAXKT, "conv1_wgrad: ktaps must be 1..%d", MAXKT);
-  TL_REQUIRE(C1 % 32 == 0 && C1 <= 512, "conv1_wgrad: C1 must be a multiple of 32 and <= 512");
+  TL_REQUIRE(C1 % 32 == 0 && C1 <= 2048, "conv1_wgrad: C1 must be a multiple of 32 and <= 2048");
   TL_REQUIRE(Tout >= 0 && Tout <= Tp && 2 * Tout + ktaps - 1 <= T, "conv1_wgrad: Tout/Tp/T inconsistent");
   TL_REQUIRE((size_t)T * 4 <= 64 * 1024, "conv1_wgrad: T too large for the LDS window");
-  hipLaunchKernelGGL(conv1_wgrad_kernel, dim3((unsigned)nblk), dim3(256), (size_t)T * 4, (hipStream_t)stream, x, G,
+  hipLaunchKernelGGL(conv1_wgrad_kernel, dim3((unsigned)nblk, (unsigned)((C1 + 511) / 512)), dim3(256), (size_t)T * 4, (hipStream_t)stream, x, G,
                      bits, partial, (long long)S, T, ktaps, C1, Tp, Tout);
   return check_launch("conv1_wgrad");
 }

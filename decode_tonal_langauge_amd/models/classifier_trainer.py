@@ -14,7 +14,8 @@ out as a plain loop:
   * ``metrics.csv`` per run with Lightning's column names, ``confusion_matrix_test.csv`` after test.
 
 ``fused=True`` runs the same loop on the HIP path (``_simple_classifier_engine`` for the linear and shallow classifiers,
-``_cnn_classifier_train_engine`` for ``CNNClassifier``: fused cross-entropy step, ``FusedNAdam``);
+``_cnn_classifier_train_engine`` for ``CNNClassifier``, ``_cnnrnn_classifier_train_engine`` for ``CNNRNNClassifier``: fused
+cross-entropy step, ``FusedNAdam``);
 loss and confusion matrix then stay on the device and are read once per epoch.
 """
 from __future__ import annotations
@@ -62,9 +63,11 @@ class ClassifierTrainer:
         self.fused = bool(fused)
         self.engine = None
         if self.fused:         # an explicit request: a model / device pair the engine does not take raises (ValueError)
-            from .deep_classifiers import CNNClassifier
+            from .deep_classifiers import CNNClassifier, CNNRNNClassifier
             if isinstance(model, CNNClassifier):
                 from .._cnn_classifier_train_engine import CnnClassifierTrainEngine as Engine
+            elif isinstance(model, CNNRNNClassifier):
+                from .._cnnrnn_classifier_train_engine import CnnRnnClassifierTrainEngine as Engine
             else:
                 from .._simple_classifier_engine import SimpleClassifierEngine as Engine
             self.engine = Engine(model, self.learning_rate, self.weight_decay)

@@ -8,9 +8,10 @@ reference's constructor arguments, sub-module names (hence ``state_dict`` keys, 
 (how the trainer calls them) they run on the HIP kernels (``_classifier_engine``) - in eval mode and, with their
 ``nn.Dropout`` drawn from the package's counter-hash stream, in train mode (the reference CLI's default,
 train_synthesizer.py:275-284); only a call that needs autograd THROUGH the classifier uses the module graph.
-``CNNClassifier``'s own training runs on the HIP path too when asked for: ``ClassifierTrainer(model, fused=True)`` drives
-``_cnn_classifier_train_engine`` (conv-stack backward, cross-entropy on the sigmoid scores, ``FusedNAdam``) and never calls
-``forward``; ``CNNRNNClassifier`` trains through autograd only.
+Their own training runs on the HIP path too when asked for: ``ClassifierTrainer(model, fused=True)`` drives
+``_cnn_classifier_train_engine`` (conv-stack backward, cross-entropy on the sigmoid scores, ``FusedNAdam``) for
+``CNNClassifier`` and ``_cnnrnn_classifier_train_engine`` (the same plus LSTM BPTT, the (3,1) pool and the first stage's input
+gradient) for ``CNNRNNClassifier``; neither calls ``forward``.
 """
 from __future__ import annotations
 

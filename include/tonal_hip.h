@@ -110,7 +110,7 @@ typedef struct {
   int64_t A_rows, B_rows;
   int Mdim, Ndim;     /* A columns used (per tap), B columns                       */
   int lda, ldb, ldc, ld_bbits;
-  int J;
+  int J;              /* taps (1..7; 3: the all-taps kernel)                        */
   int Tp, Tvalid;
   int loader;
   int splitk; int64_t slab_stride;
@@ -443,6 +443,48 @@ int tl_ce_scores_loss(const float* scores, const int64_t* labels, float* dlogits
  * aligned.  With dh null and h = x this is the weight gradient of LogisticRegressionClassifier's layer.                    */
 int tl_head_bwd(const float* dlogits, const float* h, const float* W, float* dh, float* dbias_h, float* dw, int B, int K, int N,
                 int ldd, int act, float slope, void* stream);
+
+/* ---- training of CNNRNNClassifier (models/deep_classifiers.py:158-343 under models/classifier_trainer.py:72-89) ----------
+ * The LSTM pair keeps ROWS TIME-MAJOR (row = t * B + b), so the kept arrays are directly the (T B)-row operands of the
+ * weight-gradient GEMMs (tl_gemm_tn_window): dW_hh = dgates[1:]^T . hs[:-1] (a row offset of B between the operands),
+ * dW_ih = dgates^T . x, db = column sums of dgates, dX = dgates . W_ih as the TN GEMM with A = dgates_t.  H is the hidden
+ * width padded to a multiple of 8; a padded unit (zero weight rows / columns and bias) keeps c = h = 0.
+ *   tl_lstm_train_seq   all T steps, one fused launch per step (the tiling of tl_lstm_infer_seq_fused: 32 batch rows x 8 units
+ *                       per workgroup, 8 K slices).  xp[b * xp_row_stride + t * xp_step_stride + gate * H + u] = input projection
+ *                       + both biases; wp = W_hh packed unit-major (row 4 u + g = W_hh row g H + u), (4 H, H).  Step t reads
+ *                       hs[t-1], cs[t-1] (zero state at t = 0) and writes hs[t], cs[t] (T, B, H) and the activated gates
+ *                       act[t] (T, B, 4 H; columns gate * H + u, gates i, f, g, o).  Rows beyond B are clamped for loads and never
+ *                       stored.
+ *   tl_lstm_bptt_seq    steps t = T-1 .. 0, one fused launch per step: dh_t = [t == T-1] dh_last (B, H) + dgates_{t+1} . W_hh on
+ *                       the matrix cores (whT = W_hh^T (H, 4 H), row u contiguous over the gate rows g H + u'), then the cell
+ *                       backward of tl_lstm_cell_bwd per (row, unit); dc (B, H) is scratch carried in place (need not be
+ *                       initialised); dgates (T, B, 4 H) row-major; dgates_t optional: (4 H, ldt) with column t * B + b,
+ *                       ldt >= T * B.  No atomics: the same inputs give the same bits.  Pad units come out exactly zero when
+ *                       dh_last's pad columns are zero.                                                                       */
+int tl_lstm_train_seq(const float* xp, int64_t xp_row_stride, int64_t xp_step_stride, const float* wp, float* hs, float* cs,
+                      float* act, int B, int H, int T, void* stream);
+int tl_lstm_bptt_seq(const float* whT, const float* dh_last, const float* act, const float* cs, float* dc, float* dgates,
+                     float* dgates_t, int64_t ldt, int B, int H, int T, void* stream);
+/* MaxPool2d((3,1)) + Dropout behind the un-pooled last conv stage (:256-258) and the reference's raw view of the result as the
+ * second LSTM's input (:309-315).  Y rows [seq * Tp + t][ldy] (post-activation), sequences branch-major: B * w1 LSTM-branch
+ * columns (seq = b * w1 + j), then B * Cn electrode columns.  Element (b, ch, s, w) of the contiguous (B, C, tq, W = w1 + Cn)
+ * activation, w in torch.cat((x1, x), dim=3) order, has offset f = (ch * tq + s) * W + w in its batch element and lands in
+ * X[(b * rs_b + (f / (C W)) * rs_t) * C W + f % (C W)]: rs_b = tq, rs_t = 1 is the reference's (B tq, C W) matrix, rs_b = 1,
+ * rs_t = B its time-major form.  keep = tl_dropout_scale's decision at position (seq * tq + s) * C + ch (p = 0: none).
+ *   tl_pool3_fwd   X = first maximum of rows 3 s .. 3 s + 2, times keep / (1 - p)
+ *   tl_pool3_bwd   dZ[seq * Tp + 3 s + arg][ch] = dX * keep / (1 - p) * (Y[arg] > 0 ? 1 : slope) with the arg-max recomputed
+ *                  from Y (torch's rule: the first maximum); the other two rows of the triple, rows t >= 3 tq and the pad rows of
+ *                  every sequence are written as zeros (all Tp rows, C columns of dZ, row stride lddz)                        */
+int tl_pool3_fwd(const float* Y, float* X, int B, int w1, int Cn, int C, int Tp, int tq, int ldy, int64_t rs_b, int64_t rs_t, float p,
+                 uint64_t seed, void* stream);
+int tl_pool3_bwd(const float* Y, const float* dX, float* dZ, int B, int w1, int Cn, int C, int Tp, int tq, int ldy, int lddz,
+                 int64_t rs_b, int64_t rs_t, float p, uint64_t seed, float slope, void* stream);
+/* input gradient of the first conv stage (C_in = 1) from G1 = dL/dZ at the arg-max (rows [seq * Tp + t][C1], C1 = 1024),
+ * its arg-max bits and w (C1, ktaps = 7: the one shape built): dx[seq][u] = sum over the (t, j) with 2 t + a + j = u of sum_c G1[t][c] w[c][j];
+ * every sample u < T is written (zero where nothing reaches it) to dx[(seq / n_inner) * stride_outer + u * stride_t +
+ * (seq % n_inner) * stride_inner].  One workgroup per sequence, no atomics.                                                  */
+int tl_conv1_dgrad(const float* G, const uint32_t* bits, const float* w, float* dx, int64_t S, int T, int ktaps, int C1, int Tp,
+                   int Tout, int n_inner, int64_t stride_outer, int64_t stride_t, int64_t stride_inner, void* stream);
 
 /* ---- SynthesisLite blocks (models/synthesis_models.py:236-263,265-296) ----------------------
  * x (B,Cin,T) channels-first like the reference's Conv1d; 'same' padding (2*pad == k-1).       */
