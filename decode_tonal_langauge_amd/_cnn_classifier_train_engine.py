@@ -18,6 +18,12 @@ One train step of a batch (B, C, T):
   update    one ``FusedNAdam``; at B <= ``FusedNAdam.LOWRANK_MAX`` the two Linear weights go as rank-B factors (fc1's 1.2 GB
             gradient is never written), above that dW1 comes from the TN GEMM and dW2 from ``tl_head_bwd``.
 
+Under a process group (``parallel.active()``) every public step takes the GLOBAL batch and works on this rank's rows
+(``_classifier_dp``): the dropout mask is indexed by the element's position in the global batch (``tl_dropout_scale_at``, same
+masks for 1 or N ranks), ``grad_scale`` is 1 / B_global, the conv and bias gradients are views of one arena summed by one bucketed
+all-reduce, and at B_global <= ``LOWRANK_MAX`` the two Linear weights travel as the gathered factor rows (da1, flat) and
+(dz, a1) - fc1's gradient is never reduced and never written.  Without one nothing changes.
+
 No host read happens in ``train_batch`` / ``eval_batch``.  There is no CPU fallback and no fallback to autograd."""
 from __future__ import annotations
 
@@ -27,6 +33,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._classifier_dp import ClassifierDP
 from ._conv_stack import ConvStack
 from ._launch import r4
 from ._lib import EPI_LRELU, EPI_MASK, EPI_STORE, LOAD_DIRECT, check, ptr
@@ -85,7 +92,7 @@ class _Head:
         self.pred = torch.empty(B, dtype=torch.int64, device=dev)
 
 
-class CnnClassifierTrainEngine(ConvStack):
+class CnnClassifierTrainEngine(ClassifierDP, ConvStack):
     def __init__(self, model, learning_rate: float = 0.0005, weight_decay: float = 0.0):
         check_supported(model)
         stage_defs, conv_at = _stage_defs(model)
@@ -118,8 +125,12 @@ class CnnClassifierTrainEngine(ConvStack):
         self.stats = torch.zeros(3 + self.N * self.N, dtype=torch.int64, device=self.device)
         # dense gradient buffers (kept: the optimiser caches its pointer table); the two Linear weights get one on demand
         lin_w = (self.fc1.weight, self.fc2.weight)
-        self.grads: Dict[str, torch.Tensor] = {k: torch.zeros_like(p) for k, p in self.params.items()
-                                               if all(p is not w for w in lin_w)}
+        self._dp_setup()
+        shapes = {k: p.shape for k, p in self.params.items() if all(p is not w for w in lin_w)}
+        if self.dp:            # ... as views of one arena, in the order the backward finishes them: one all-reduce
+            self.grads: Dict[str, torch.Tensor] = dict(self._make_arena(shapes, list(shapes)[::-1]))
+        else:
+            self.grads = {k: torch.zeros_like(self.params[k]) for k in shapes}
         self._heads: Dict[int, _Head] = {}
         self._eye = None
         self.last_seed = 0                 # dropout seed of the last forward pass (0: no dropout applied)
@@ -175,8 +186,8 @@ class CnnClassifierTrainEngine(ConvStack):
         feat = self.P[self.stages[-1].idx]                       # [S * tp_last][ld_last]
         self.last_seed = 0
         if dropout and self.p_drop > 0.0:
-            self.last_seed = int(self.model._next_seed())
-            check(lib.tl_dropout_scale(ptr(feat), feat.numel(), self.p_drop, self.last_seed, st_), "tl_dropout_scale")
+            self.last_seed = self._step_seed() if self.dp else int(self.model._next_seed())
+            self._drop(feat)
         # torch's flatten of (B, ch, t, c): column ch * lat * C + t * C + c  <-  row (b * C + c) * tp + t, column ch
         lat, Cn, tp, ld = self.lat, self.C, self.tp_last, self.ld_last
         self._permute(feat, ws.flat, (B, self.c_last, lat, Cn), (Cn * tp * ld, 1, ld, tp * ld))
@@ -196,12 +207,23 @@ class CnnClassifierTrainEngine(ConvStack):
                                  H, 1, st_), "tl_linear_rows")
         return ws
 
+    def _drop(self, rows: torch.Tensor) -> None:
+        """Dropout (forward and backward alike) on the last stage's rows [(b * C + c) * tp + t][ld] with ``last_seed``; a shard
+        that starts at global row b0 draws its rows of the single-process mask."""
+        if self.dp:
+            index0 = self._plan.row0 * self.C * self.tp_last * self.ld_last
+            check(self.lib.tl_dropout_scale_at(ptr(rows), rows.numel(), self.p_drop, self.last_seed, index0, self._stream()),
+                  "tl_dropout_scale_at")
+        else:
+            check(self.lib.tl_dropout_scale(ptr(rows), rows.numel(), self.p_drop, self.last_seed, self._stream()),
+                  "tl_dropout_scale")
+
     def _ce(self, ws: _Head, y: Optional[torch.Tensor], B: int, grad: bool, pred: bool) -> None:
-        base = self.stats.data_ptr()
+        base = self._stats_base()
         check(self.lib.tl_ce_scores_loss(ptr(ws.scores), ptr(y), ptr(ws.dz) if grad else None,
                                          ptr(self.grads["classifier.3.bias"]) if grad else None, ptr(ws.pred) if pred else None,
-                                         base, base + 8, base + 24, base + 16, B, self.N, self.N, ws.dz.shape[1], 1.0 / B,
-                                         self._stream()), "tl_ce_scores_loss")
+                                         base, base + 8, base + 24, base + 16, B, self.N, self.N, ws.dz.shape[1],
+                                         self._grad_scale(), self._stream()), "tl_ce_scores_loss")
 
     # ------------------------------------------------------------------ backward
     def _backward(self, ws: _Head, B: int, dense: bool) -> None:
@@ -249,7 +271,7 @@ class CnnClassifierTrainEngine(ConvStack):
         self._nt(tag="feat_mask", A=ptr(dfeat), Bw=ptr(self._eye), aux=ptr(feat), out=ptr(G), M=G.shape[0], A_rows=G.shape[0],
                  N=ld, K=ld, lda=ld, ldb=ld, ldo=ld, ldaux=ld, loader=LOAD_DIRECT, epilogue=EPI_MASK, slope=self.slope)
         if self.last_seed:           # dropout's backward: same index, same keep decision, same 1 / (1 - p)
-            check(lib.tl_dropout_scale(ptr(G), G.numel(), self.p_drop, self.last_seed, st_), "tl_dropout_scale")
+            self._drop(G)
         part = None
         for st in reversed(self.stages):
             name = self.STAGE_NAMES[st.idx]
@@ -265,12 +287,19 @@ class CnnClassifierTrainEngine(ConvStack):
 
     def _step(self, x: torch.Tensor, y: torch.Tensor, update: bool) -> _Head:
         x = self._input(x)
+        y = self._labels(y, x.shape[0])
+        dense = self.force_dense or x.shape[0] > FusedNAdam.LOWRANK_MAX      # (from the GLOBAL batch: the same on every rank)
+        x, y = self._take(x, y)
         B = x.shape[0]
-        y = self._labels(y, B)
         ws = self._forward(x, dropout=self.model.training)
         self._ce(ws, y, B, grad=True, pred=False)
-        dense = self.force_dense or B > FusedNAdam.LOWRANK_MAX
         self._backward(ws, B, dense)
+        if self.dp:
+            N = self.N
+            sent = {k: (ws.dz if k == "classifier.3.weight" else fa, fb) for k, (fa, fb) in self.last_lowrank.items()}
+            got = self._exchange(extra=[self.grads[k] for k in ("classifier.1.weight", "classifier.3.weight")] if dense else (),
+                                 lowrank=sent)
+            self.last_lowrank = {k: (fa[:, :N] if k == "classifier.3.weight" else fa, fb) for k, (fa, fb) in got.items()}
         if update:
             lin = ("classifier.1.weight", "classifier.3.weight")
             grads = {self.params[k]: g for k, g in self.grads.items() if dense or k not in lin}
@@ -306,19 +335,20 @@ class CnnClassifierTrainEngine(ConvStack):
     def eval_batch(self, x: torch.Tensor, y: torch.Tensor) -> None:
         """Forward (no dropout) and loss statistics of one batch (no gradients, no update)."""
         x = self._input(x)
+        x, y = self._take(x, self._labels(y, x.shape[0]))
         ws = self._forward(x, dropout=False)
-        self._ce(ws, self._labels(y, x.shape[0]), x.shape[0], grad=False, pred=False)
+        self._ce(ws, y, x.shape[0], grad=False, pred=False)
 
     @torch.no_grad()
     def predict_batch(self, x: torch.Tensor) -> torch.Tensor:
         """Arg-max class of every row (int64, on the device)."""
-        x = self._input(x)
+        x, _ = self._take(self._input(x))
         ws = self._forward(x, dropout=False)
         self._ce(ws, None, x.shape[0], grad=False, pred=True)
-        return ws.pred.clone()
+        return self._gather_pred(ws.pred) if self.dp else ws.pred.clone()
 
     def scores(self, B: int) -> torch.Tensor:
         """The float32 sigmoid scores (B, n_classes) of the last forward pass at batch ``B``."""
         return self._heads[B].scores
 
-    epoch_stats = SimpleClassifierEngine.epoch_stats      # (the same statistics buffer: one read per epoch, zeroed afterwards)
+    epoch_stats = ClassifierDP.epoch_stats      # (the same statistics buffer: one read per epoch, zeroed afterwards)

@@ -18,6 +18,12 @@ One train step of a batch (B, C, T); t1 = (T - 6) // 2, ta = t1 - 6, tb = ta - 6
             branch; ``tl_conv1_dgrad`` on the LSTM branch -> dh1; lstm1's BPTT and GEMMs;
   update    one ``FusedNAdam`` over dense gradients (an LSTM weight gradient has rank T * B: no low-rank form).
 
+Under a process group (``parallel.active()``) every public step takes the GLOBAL batch and works on this rank's rows
+(``_classifier_dp``): the dropout mask of the (3,1) pool is indexed by the sequence's number in the global batch's branch-major
+order (``tl_pool3_fwd_shard`` / ``tl_pool3_bwd_shard``, same masks for 1 or N ranks), ``grad_scale`` is 1 / B_global, and all
+gradients - views of one arena - are summed by one bucketed all-reduce (an LSTM weight gradient has no low-rank form, and
+``output.weight`` is 4 KB).  Without one nothing changes.
+
 No host read happens in ``train_batch`` / ``eval_batch``.  There is no CPU fallback and no fallback to autograd."""
 from __future__ import annotations
 
@@ -27,6 +33,7 @@ import torch
 import torch.nn as nn
 
 from . import _kernels, _lib
+from ._classifier_dp import ClassifierDP
 from ._conv_stack import ConvStack
 from ._launch import r4
 from ._lib import EPI_LRELU, EPI_STORE, LOAD_DIRECT, LOAD_V, check, ptr
@@ -124,7 +131,7 @@ class _Ws:
         self.pred = torch.empty(B, dtype=torch.int64, device=dev)
 
 
-class CnnRnnClassifierTrainEngine(ConvStack):
+class CnnRnnClassifierTrainEngine(ClassifierDP, ConvStack):
     F63_CAPABLE = False        # (the 3-tap F(6,3) stack does not apply: every stage here has 7 taps)
 
     def __init__(self, model, learning_rate: float = 0.0005, weight_decay: float = 0.0):
@@ -157,7 +164,15 @@ class CnnRnnClassifierTrainEngine(ConvStack):
                                      {"params": no_decay, "weight_decay": 0.0}], lr=float(learning_rate), stored_beta2=True)
         # loss sum (the bits of a double), sample count, label-range flag, confusion matrix: one buffer, one read per epoch
         self.stats = torch.zeros(3 + self.N * self.N, dtype=torch.int64, device=self.device)
-        self.grads: Dict[str, torch.Tensor] = {k: torch.zeros_like(p) for k, p in self.params.items()}
+        self._dp_setup()
+        if self.dp:            # views of one arena, in the order the backward finishes them: one all-reduce, no staging copy
+            self.grads: Dict[str, torch.Tensor] = dict(self._make_arena(
+                {k: p.shape for k, p in self.params.items()},
+                ["output.bias", "output.weight"] + [k for k in self.params if k.startswith("lstm2.")]
+                + [k for k in self.params if k.startswith("conv_block3.")][::-1]
+                + [k for k in self.params if k.startswith("conv_pool_block")] + [k for k in self.params if k.startswith("lstm1.")]))
+        else:
+            self.grads = {k: torch.zeros_like(p) for k, p in self.params.items()}
         self._ws: Dict[int, _Ws] = {}
         self._updates = 0                  # optimiser steps taken: part of the key of every weight pack
         self._packs: Dict[str, tuple] = {}
@@ -369,9 +384,13 @@ class CnnRnnClassifierTrainEngine(ConvStack):
         self._conv7("conv3b_fwd", self.P[2], "conv_block3.2", self.P[3], C_A, C_B, self.ta)
         self.last_seed = 0
         if dropout and self.p_drop > 0.0:
-            self.last_seed = int(self.model._next_seed())
-        self._call("pool3_fwd", "tl_pool3_fwd", ptr(self.P[3]), ptr(ws.X2), B, w1, Cn, C_B, Tp, self.tq, C_B, 1, B,
-                   self.p_drop if self.last_seed else 0.0, self.last_seed)
+            self.last_seed = self._step_seed() if self.dp else int(self.model._next_seed())
+        if self.dp:
+            self._call("pool3_fwd", "tl_pool3_fwd_shard", ptr(self.P[3]), ptr(ws.X2), B, w1, Cn, C_B, Tp, self.tq, C_B, 1, B,
+                       self.p_drop if self.last_seed else 0.0, self.last_seed, self._plan.row0, self._plan.B)
+        else:
+            self._call("pool3_fwd", "tl_pool3_fwd", ptr(self.P[3]), ptr(ws.X2), B, w1, Cn, C_B, Tp, self.tq, C_B, 1, B,
+                       self.p_drop if self.last_seed else 0.0, self.last_seed)
         self._lstm_forward(l2, ws.X2)
         out = self.model.output
         check(self.lib.tl_linear_rows(ptr(l2.h_last()), ptr(out.weight.data), ptr(out.bias.data), ptr(ws.scores), B, l2.Hp,
@@ -379,11 +398,11 @@ class CnnRnnClassifierTrainEngine(ConvStack):
         return ws
 
     def _ce(self, ws: _Ws, y: Optional[torch.Tensor], B: int, grad: bool, pred: bool) -> None:
-        base = self.stats.data_ptr()
+        base = self._stats_base()
         check(self.lib.tl_ce_scores_loss(ptr(ws.scores), ptr(y), ptr(ws.dz) if grad else None,
                                          ptr(self.grads["output.bias"]) if grad else None, ptr(ws.pred) if pred else None,
-                                         base, base + 8, base + 24, base + 16, B, self.N, self.N, ws.dz.shape[1], 1.0 / B,
-                                         self._stream()), "tl_ce_scores_loss")
+                                         base, base + 8, base + 24, base + 16, B, self.N, self.N, ws.dz.shape[1],
+                                         self._grad_scale(), self._stream()), "tl_ce_scores_loss")
 
     # ------------------------------------------------------------------ backward
     def _backward(self, ws: _Ws, B: int) -> None:
@@ -396,8 +415,13 @@ class CnnRnnClassifierTrainEngine(ConvStack):
                                    ptr(g["output.weight"]), B, l2.Hp, self.N, ws.dz.shape[1], 0, self.slope, self._stream()),
               "tl_head_bwd")
         self._lstm_backward(l2, ws.X2, ws.dX2)
-        self._call("pool3_bwd", "tl_pool3_bwd", ptr(self.P[3]), ptr(ws.dX2), ptr(self.G[3]), B, w1, Cn, C_B, Tp, self.tq, C_B,
-                   C_B, 1, B, self.p_drop if self.last_seed else 0.0, self.last_seed, self.slope)
+        if self.dp:
+            self._call("pool3_bwd", "tl_pool3_bwd_shard", ptr(self.P[3]), ptr(ws.dX2), ptr(self.G[3]), B, w1, Cn, C_B, Tp, self.tq,
+                       C_B, C_B, 1, B, self.p_drop if self.last_seed else 0.0, self.last_seed, self.slope, self._plan.row0,
+                       self._plan.B)
+        else:
+            self._call("pool3_bwd", "tl_pool3_bwd", ptr(self.P[3]), ptr(ws.dX2), ptr(self.G[3]), B, w1, Cn, C_B, Tp, self.tq, C_B,
+                       C_B, 1, B, self.p_drop if self.last_seed else 0.0, self.last_seed, self.slope)
         for st in reversed(self.stages):
             name = self.STAGE_NAMES[st.idx]
             self.stage_wgrad(st, g[name + ".weight"], g[name + ".bias"])
@@ -429,11 +453,13 @@ class CnnRnnClassifierTrainEngine(ConvStack):
 
     def _step(self, x: torch.Tensor, y: torch.Tensor, update: bool) -> _Ws:
         x = self._input(x)
+        x, y = self._take(x, self._labels(y, x.shape[0]))
         B = x.shape[0]
-        y = self._labels(y, B)
         ws = self._forward(x, dropout=self.model.training)
         self._ce(ws, y, B, grad=True, pred=False)
         self._backward(ws, B)
+        if self.dp:
+            self._exchange()
         if update:
             ev = self._tick("update")
             self.optimizer.step(grads={self.params[k]: g for k, g in self.grads.items()})
@@ -464,19 +490,20 @@ class CnnRnnClassifierTrainEngine(ConvStack):
     def eval_batch(self, x: torch.Tensor, y: torch.Tensor) -> None:
         """Forward (no dropout) and loss statistics of one batch (no gradients, no update)."""
         x = self._input(x)
+        x, y = self._take(x, self._labels(y, x.shape[0]))
         ws = self._forward(x, dropout=False)
-        self._ce(ws, self._labels(y, x.shape[0]), x.shape[0], grad=False, pred=False)
+        self._ce(ws, y, x.shape[0], grad=False, pred=False)
 
     @torch.no_grad()
     def predict_batch(self, x: torch.Tensor) -> torch.Tensor:
         """Arg-max class of every row (int64, on the device)."""
-        x = self._input(x)
+        x, _ = self._take(self._input(x))
         ws = self._forward(x, dropout=False)
         self._ce(ws, None, x.shape[0], grad=False, pred=True)
-        return ws.pred.clone()
+        return self._gather_pred(ws.pred) if self.dp else ws.pred.clone()
 
     def scores(self, B: int) -> torch.Tensor:
         """The float32 sigmoid scores (B, n_classes) of the last forward pass at batch ``B``."""
         return self._ws[B].scores
 
-    epoch_stats = SimpleClassifierEngine.epoch_stats      # (the same statistics buffer: one read per epoch, zeroed afterwards)
+    epoch_stats = ClassifierDP.epoch_stats      # (the same statistics buffer: one read per epoch, zeroed afterwards)

@@ -99,6 +99,7 @@ SIGNATURES = {
     "tl_conv1_fwd": (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _F, _P]),
     "tl_conv1_fwd_v": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _F, _P]),
     "tl_dropout_scale": (_I, [_P, _L, _F, C.c_uint64, _P]),
+    "tl_dropout_scale_at": (_I, [_P, _L, _F, C.c_uint64, _L, _P]),
     "tl_conv1_wgrad": (_I, [_P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _I, _P]),
     "tl_permute_reduce": (_I, [_P, _P, C.POINTER(_L), C.POINTER(_L), C.POINTER(_L), _I, _L, _P, _P]),
     "tl_colsum": (_I, [_P, _P, _I, _L, _I, _I, _I, _I, _P]),
@@ -130,6 +131,8 @@ SIGNATURES = {
     "tl_lstm_bptt_seq": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _P]),
     "tl_pool3_fwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _L, _F, C.c_uint64, _P]),
     "tl_pool3_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _L, _L, _F, C.c_uint64, _F, _P]),
+    "tl_pool3_fwd_shard": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _L, _F, C.c_uint64, _I, _I, _P]),
+    "tl_pool3_bwd_shard": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _L, _L, _F, C.c_uint64, _F, _I, _I, _P]),
     "tl_conv1_dgrad": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _L, _L, _L, _P]),
     "tl_lite_conv_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "tl_lite_bn_finalize": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _I, _F, _F, _I, _P, _P]),

@@ -13,6 +13,11 @@ One train step of a batch (B, K):
             ``dout^T . input`` and is applied by ``tl_nadam_lowrank`` without ever being stored; above that it is written by
             ``tl_head_bwd`` (head) or the TN GEMM (hidden layer) and applied by ``tl_nadam``.
 
+Under a process group (``parallel.active()``) every public step takes the GLOBAL batch and works on this rank's rows
+(``_classifier_dp``): ``grad_scale`` is 1 / B_global, the bias gradients (and dense weight gradients) are summed by one bucketed
+all-reduce, and at B_global <= ``LOWRANK_MAX`` the weights travel as the gathered factor rows - every rank applies the same
+rank-B_global update.  Without one nothing changes.
+
 There is no CPU fallback and no fallback to autograd: a model outside the supported set is refused."""
 from __future__ import annotations
 
@@ -22,6 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._classifier_dp import ClassifierDP
 from ._launch import launch_nt, launch_tn, r4
 from ._lib import EPI_LRELU, LOAD_DIRECT, check, ptr
 from .models.utils import split_decay_groups
@@ -74,7 +80,7 @@ class _Workspace:
         self.dh = torch.empty(B, H, **f32) if H else None
 
 
-class SimpleClassifierEngine:
+class SimpleClassifierEngine(ClassifierDP):
     def __init__(self, model, learning_rate: float = 0.0005, weight_decay: float = 0.0):
         check_supported(model)
         self.lib = _lib.load()
@@ -97,8 +103,15 @@ class SimpleClassifierEngine:
         self.force_dense = False           # tests / the benchmark: materialise dW at a batch the low-rank update would take
         # loss sum (the bits of a double), sample count, label-range flag, confusion matrix: one buffer, one read per epoch
         self.stats = torch.zeros(3 + self.N * self.N, dtype=torch.int64, device=self.device)
-        self.grads: Dict[nn.Parameter, torch.Tensor] = {p: torch.zeros_like(p) for p in no_decay}
+        self._dp_setup()
+        if self.dp:            # the always-dense gradients (the biases) as views of one arena: one all-reduce, no staging copy
+            named = {k: p for k, p in model.named_parameters() if any(p is q for q in no_decay)}
+            views = self._make_arena({k: p.shape for k, p in named.items()})
+            self.grads: Dict[nn.Parameter, torch.Tensor] = {named[k]: v for k, v in views.items()}
+        else:
+            self.grads = {p: torch.zeros_like(p) for p in no_decay}
         self._ws: Dict[int, _Workspace] = {}
+        self.last_lowrank: Dict[nn.Parameter, Tuple[torch.Tensor, torch.Tensor]] = {}   # the factors of the last train step
 
     # ------------------------------------------------------------------ plumbing
     def _workspace(self, B: int) -> _Workspace:
@@ -142,11 +155,11 @@ class SimpleClassifierEngine:
                                       0, st), "tl_linear_rows")
 
     def _ce(self, ws: _Workspace, y: Optional[torch.Tensor], B: int, grad: bool, pred: bool) -> None:
-        base = self.stats.data_ptr()
+        base = self._stats_base()
         check(self.lib.tl_ce_loss(ptr(ws.logits), ptr(y), ptr(ws.dlogits) if grad else None,
                                   ptr(self.grads[self.head.bias]) if grad else None, ptr(ws.pred) if pred else None,
-                                  base, base + 8, base + 24, base + 16, B, self.N, self.N, ws.dlogits.shape[1], 1.0 / B,
-                                  self._stream()), "tl_ce_loss")
+                                  base, base + 8, base + 24, base + 16, B, self.N, self.N, ws.dlogits.shape[1],
+                                  self._grad_scale(), self._stream()), "tl_ce_loss")
 
     def _dense(self, p: nn.Parameter) -> torch.Tensor:
         g = self.grads.get(p)
@@ -159,14 +172,15 @@ class SimpleClassifierEngine:
     def train_batch(self, x: torch.Tensor, y: torch.Tensor) -> None:
         """Forward, loss, backward and update for one batch; everything stays on the stream (no host read)."""
         x = self._input(x)
+        y = self._labels(y, x.shape[0])
+        dense = self.force_dense or x.shape[0] > FusedNAdam.LOWRANK_MAX      # (from the GLOBAL batch: the same on every rank)
+        x, y = self._take(x, y)
         B = x.shape[0]
-        y = self._labels(y, B)
         ws = self._workspace(B)
         st = self._stream()
         self._forward(x, ws)
         self._ce(ws, y, B, grad=True, pred=False)
         ldd = ws.dlogits.shape[1]
-        dense = self.force_dense or B > FusedNAdam.LOWRANK_MAX
         hw = self.head.weight
         grads = {p: g for p, g in self.grads.items() if p.ndim < 2}
         lowrank: Dict[nn.Parameter, Tuple[torch.Tensor, torch.Tensor]] = {}
@@ -188,30 +202,30 @@ class SimpleClassifierEngine:
             grads[hw] = self.grads[hw]
         else:
             lowrank[hw] = (dout, x)
+        if self.dp:
+            # dlogits travels at its stored width (the factor is its first N columns)
+            sent = {p: (ws.dlogits if fa is dout else fa, fb) for p, (fa, fb) in lowrank.items()}
+            got = self._exchange(extra=[g for p, g in grads.items() if p.ndim >= 2], lowrank=sent)
+            lowrank = {p: (fa[:, :self.N] if sent[p][0] is ws.dlogits else fa, fb) for p, (fa, fb) in got.items()}
+        self.last_lowrank = lowrank
         self.optimizer.step(grads=grads, lowrank=lowrank or None)
 
     @torch.no_grad()
     def eval_batch(self, x: torch.Tensor, y: torch.Tensor) -> None:
         """Forward and loss statistics of one batch (no gradients, no update)."""
         x = self._input(x)
+        x, y = self._take(x, self._labels(y, x.shape[0]))
         ws = self._workspace(x.shape[0])
         self._forward(x, ws)
-        self._ce(ws, self._labels(y, x.shape[0]), x.shape[0], grad=False, pred=False)
+        self._ce(ws, y, x.shape[0], grad=False, pred=False)
 
     @torch.no_grad()
     def predict_batch(self, x: torch.Tensor) -> torch.Tensor:
         """Arg-max class of every row (int64, on the device)."""
-        x = self._input(x)
+        x, _ = self._take(self._input(x))
         ws = self._workspace(x.shape[0])
         self._forward(x, ws)
         self._ce(ws, None, x.shape[0], grad=False, pred=True)
-        return ws.pred.clone()
+        return self._gather_pred(ws.pred) if self.dp else ws.pred.clone()
 
-    def epoch_stats(self) -> Tuple[float, int, torch.Tensor]:
-        """(loss sum, samples counted, confusion matrix (N, N) int64 on the host) since the last call - ONE device-to-host
-        read - and zero them.  Raises ``ValueError`` if a label was outside [0, n_classes)."""
-        host = self.stats.cpu()
-        self.stats.zero_()
-        if int(host[2]) != 0:
-            raise ValueError(f"labels must lie in [0, {self.N}) for a model with {self.N} classes")
-        return float(host[0:1].view(torch.float64)[0]), int(host[1]), host[3:].reshape(self.N, self.N).clone()
+    epoch_stats = ClassifierDP.epoch_stats

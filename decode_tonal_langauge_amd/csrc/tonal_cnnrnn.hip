@@ -171,7 +171,16 @@ struct pool3_geom {
   long long rs_b, rs_t;
   float p, inv_keep;
   uint64_t seed;
+  // data-parallel shard: what a local sequence number is short of the sequence's number in the GLOBAL batch's branch-major
+  // order, per branch ((b0 + b) * w1 + j, and B_global * w1 + (b0 + b) * Cn + e); both 0 for a whole batch
+  long long kseq_lstm, kseq_el;
 };
+
+// position of element (seq, s, ch) in the (seq, s, ch) buffer of the global batch: the index of the keep decision
+__device__ __forceinline__ uint64_t pool3_keep_index(const pool3_geom& g, long long seq, int s, int ch) {
+  const long long gseq = seq + (seq < (long long)g.B * g.w1 ? g.kseq_lstm : g.kseq_el);
+  return (uint64_t)((gseq * g.tq + s) * g.C + ch);
+}
 
 __device__ __forceinline__ long long pool3_x_index(const pool3_geom& g, long long seq, int s, int ch) {
   const long long nb = (long long)g.B * g.w1;
@@ -211,7 +220,7 @@ __global__ __launch_bounds__(256) void pool3_fwd_kernel(const float* __restrict_
     const float v0 = y[0], v1 = y[g.ldy], v2 = y[2LL * g.ldy];
     const int arg = first_max3(v0, v1, v2);
     float m = arg == 0 ? v0 : (arg == 1 ? v1 : v2);
-    if (g.p > 0.f) m = u01(g.seed, (uint64_t)i) >= g.p ? m * g.inv_keep : 0.f;
+    if (g.p > 0.f) m = u01(g.seed, pool3_keep_index(g, seq, s, ch)) >= g.p ? m * g.inv_keep : 0.f;
     X[pool3_x_index(g, seq, s, ch)] = m;
   }
 }
@@ -234,7 +243,7 @@ __global__ __launch_bounds__(256) void pool3_bwd_kernel(const float* __restrict_
       const int arg = first_max3(v0, v1, v2);
       const float m = arg == 0 ? v0 : (arg == 1 ? v1 : v2);
       float d = dX[pool3_x_index(g, seq, s, ch)];
-      if (g.p > 0.f) d = u01(g.seed, (uint64_t)((seq * g.tq + s) * g.C + ch)) >= g.p ? d * g.inv_keep : 0.f;
+      if (g.p > 0.f) d = u01(g.seed, pool3_keep_index(g, seq, s, ch)) >= g.p ? d * g.inv_keep : 0.f;
       d *= m > 0.f ? 1.f : slope;
 #pragma unroll
       for (int a = 0; a < 3; ++a) out[a] = a == arg ? d : 0.f;
@@ -371,7 +380,9 @@ extern "C" int tl_lstm_bptt_seq(const float* whT, const float* dh_last, const fl
 }
 
 static int pool3_geom_check(tl::pool3_geom& g, const char* what, int B, int w1, int Cn, int C, int Tp, int tq, int ldy, int64_t rs_b,
-                            int64_t rs_t, float p, uint64_t seed) {
+                            int64_t rs_t, float p, uint64_t seed, int b0, int B_global) {
+  TL_REQUIRE(b0 >= 0 && B_global >= 1 && (long long)b0 + B <= B_global, "%s: rows [%d, %d + %d) outside the global batch of %d", what,
+             b0, b0, B, B_global);
   TL_REQUIRE(B > 0 && w1 >= 0 && Cn >= 0 && w1 + Cn > 0 && C > 0, "%s: bad sizes", what);
   TL_REQUIRE(tq >= 1 && 3LL * tq <= Tp, "%s: 1 <= tq and 3 tq <= Tp needed (%d, %d)", what, tq, Tp);
   TL_REQUIRE(ldy >= C, "%s: row stride %d shorter than the %d channels", what, ldy, C);
@@ -382,6 +393,9 @@ static int pool3_geom_check(tl::pool3_geom& g, const char* what, int B, int w1, 
   g.B = B; g.w1 = w1; g.Cn = Cn; g.C = C; g.Tp = Tp; g.tq = tq; g.ldy = ldy;
   g.rs_b = rs_b; g.rs_t = rs_t;
   g.p = p; g.inv_keep = 1.0f / (1.0f - p); g.seed = seed;
+  g.kseq_lstm = (long long)b0 * w1;
+  g.kseq_el = (long long)(B_global - B) * w1 + (long long)b0 * Cn;
+  TL_REQUIRE((long long)B_global * (w1 + Cn) * tq * (long long)C < (1LL << 62), "%s: global batch too large", what);
   return TL_OK;
 }
 
@@ -390,26 +404,51 @@ static unsigned pool3_blocks(long long total) {
   return (unsigned)(nb > 65536 ? 65536 : nb);
 }
 
+static int pool3_fwd_launch(const char* what, const float* Y, float* X, int B, int w1, int Cn, int C, int Tp, int tq, int ldy,
+                            int64_t rs_b, int64_t rs_t, float p, uint64_t seed, int b0, int B_global, void* stream) {
+  using namespace tl;
+  TL_REQUIRE(Y && X, "%s: null pointer", what);
+  pool3_geom g;
+  if (int rc = pool3_geom_check(g, what, B, w1, Cn, C, Tp, tq, ldy, rs_b, rs_t, p, seed, b0, B_global)) return rc;
+  hipLaunchKernelGGL(pool3_fwd_kernel, dim3(pool3_blocks(g.nseq * tq * C)), dim3(256), 0, (hipStream_t)stream, Y, X, g);
+  return check_launch(what);
+}
+
+static int pool3_bwd_launch(const char* what, const float* Y, const float* dX, float* dZ, int B, int w1, int Cn, int C, int Tp, int tq,
+                            int ldy, int lddz, int64_t rs_b, int64_t rs_t, float p, uint64_t seed, float slope, int b0,
+                            int B_global, void* stream) {
+  using namespace tl;
+  TL_REQUIRE(Y && dX && dZ, "%s: null pointer", what);
+  TL_REQUIRE(lddz >= C, "%s: row stride %d of dZ shorter than the %d channels", what, lddz, C);
+  pool3_geom g;
+  if (int rc = pool3_geom_check(g, what, B, w1, Cn, C, Tp, tq, ldy, rs_b, rs_t, p, seed, b0, B_global)) return rc;
+  hipLaunchKernelGGL(pool3_bwd_kernel, dim3(pool3_blocks(g.nseq * ((Tp + 2) / 3) * C)), dim3(256), 0, (hipStream_t)stream, Y, dX, dZ,
+                     lddz, slope, g);
+  return check_launch(what);
+}
+
 extern "C" int tl_pool3_fwd(const float* Y, float* X, int B, int w1, int Cn, int C, int Tp, int tq, int ldy, int64_t rs_b,
                             int64_t rs_t, float p, uint64_t seed, void* stream) {
-  using namespace tl;
-  TL_REQUIRE(Y && X, "pool3_fwd: null pointer");
-  pool3_geom g;
-  if (int rc = pool3_geom_check(g, "pool3_fwd", B, w1, Cn, C, Tp, tq, ldy, rs_b, rs_t, p, seed)) return rc;
-  hipLaunchKernelGGL(pool3_fwd_kernel, dim3(pool3_blocks(g.nseq * tq * C)), dim3(256), 0, (hipStream_t)stream, Y, X, g);
-  return check_launch("pool3_fwd");
+  return pool3_fwd_launch("pool3_fwd", Y, X, B, w1, Cn, C, Tp, tq, ldy, rs_b, rs_t, p, seed, 0, B, stream);
 }
 
 extern "C" int tl_pool3_bwd(const float* Y, const float* dX, float* dZ, int B, int w1, int Cn, int C, int Tp, int tq, int ldy,
                             int lddz, int64_t rs_b, int64_t rs_t, float p, uint64_t seed, float slope, void* stream) {
-  using namespace tl;
-  TL_REQUIRE(Y && dX && dZ, "pool3_bwd: null pointer");
-  TL_REQUIRE(lddz >= C, "pool3_bwd: row stride %d of dZ shorter than the %d channels", lddz, C);
-  pool3_geom g;
-  if (int rc = pool3_geom_check(g, "pool3_bwd", B, w1, Cn, C, Tp, tq, ldy, rs_b, rs_t, p, seed)) return rc;
-  hipLaunchKernelGGL(pool3_bwd_kernel, dim3(pool3_blocks(g.nseq * ((Tp + 2) / 3) * C)), dim3(256), 0, (hipStream_t)stream, Y, dX, dZ,
-                     lddz, slope, g);
-  return check_launch("pool3_bwd");
+  return pool3_bwd_launch("pool3_bwd", Y, dX, dZ, B, w1, Cn, C, Tp, tq, ldy, lddz, rs_b, rs_t, p, seed, slope, 0, B, stream);
+}
+
+// The same two kernels on rows [b0, b0 + B) of a global batch of B_global: X / dZ addressing stays local, the keep decision is the
+// global batch's (a shard draws its rows of the single-process mask).
+extern "C" int tl_pool3_fwd_shard(const float* Y, float* X, int B, int w1, int Cn, int C, int Tp, int tq, int ldy, int64_t rs_b,
+                                  int64_t rs_t, float p, uint64_t seed, int b0, int B_global, void* stream) {
+  return pool3_fwd_launch("pool3_fwd_shard", Y, X, B, w1, Cn, C, Tp, tq, ldy, rs_b, rs_t, p, seed, b0, B_global, stream);
+}
+
+extern "C" int tl_pool3_bwd_shard(const float* Y, const float* dX, float* dZ, int B, int w1, int Cn, int C, int Tp, int tq, int ldy,
+                                  int lddz, int64_t rs_b, int64_t rs_t, float p, uint64_t seed, float slope, int b0, int B_global,
+                                  void* stream) {
+  return pool3_bwd_launch("pool3_bwd_shard", Y, dX, dZ, B, w1, Cn, C, Tp, tq, ldy, lddz, rs_b, rs_t, p, seed, slope, b0, B_global,
+                          stream);
 }
 
 extern "C" int tl_conv1_dgrad(const float* G, const uint32_t* bits, const float* w, float* dx, int64_t S, int T, int ktaps, int C1,

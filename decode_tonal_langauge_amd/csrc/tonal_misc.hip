@@ -242,10 +242,11 @@ __global__ __launch_bounds__(256) void conv1_fwd_vq_kernel(const float* __restri
 // models/deep_classifiers.py:81,258, active when the synthesis trainer runs them in train mode): keep with
 // probability 1 - p, scale by 1 / (1 - p); the counter-hash stream of the synthesis model's dropout (u01 above),
 // indexed by the element's position in the buffer.
+// index0: position of x[0] in the buffer the mask is defined on (a data-parallel shard of it starts mid-buffer; 0 otherwise).
 __global__ __launch_bounds__(256) void dropout_scale_kernel(float* __restrict__ x, long long n, float p, float inv_keep,
-                                                            uint64_t seed) {
+                                                            uint64_t seed, long long index0) {
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-    x[i] = u01(seed, (uint64_t)i) >= p ? x[i] * inv_keep : 0.f;
+    x[i] = u01(seed, (uint64_t)(index0 + i)) >= p ? x[i] * inv_keep : 0.f;
 }
 
 // The per-step scalars of a HIP-graph-replayed train step (tl_nadam_multi_dev, tl_lite_cat_dev / tl_lite_uncat_dev) are
@@ -1238,15 +1239,24 @@ extern "C" int tl_conv1_fwd_v(const float* x, const float* w, const float* b, fl
   return check_launch("conv1_fwd_v");
 }
 
-extern "C" int tl_dropout_scale(float* x, int64_t n, float p, uint64_t seed, void* stream) {
-  TL_REQUIRE(x && n > 0, "dropout_scale: bad arguments");
-  TL_REQUIRE(p >= 0.f && p < 1.f, "dropout_scale: p must be in [0, 1)");
+static int dropout_scale_launch(const char* what, float* x, int64_t n, float p, uint64_t seed, int64_t index0, void* stream) {
+  TL_REQUIRE(x && n > 0, "%s: bad arguments", what);
+  TL_REQUIRE(p >= 0.f && p < 1.f, "%s: p must be in [0, 1)", what);
+  TL_REQUIRE(index0 >= 0 && index0 <= INT64_MAX - n, "%s: index0 must be >= 0 and index0 + n must fit 63 bits", what);
   if (p == 0.f) return TL_OK;
   long long g = (n + 255) / 256;
   if (g > 16384) g = 16384;
   hipLaunchKernelGGL(dropout_scale_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, x, (long long)n, p,
-                     1.0f / (1.0f - p), seed);
-  return check_launch("dropout_scale");
+                     1.0f / (1.0f - p), seed, (long long)index0);
+  return check_launch(what);
+}
+
+extern "C" int tl_dropout_scale(float* x, int64_t n, float p, uint64_t seed, void* stream) {
+  return dropout_scale_launch("dropout_scale", x, n, p, seed, 0, stream);
+}
+
+extern "C" int tl_dropout_scale_at(float* x, int64_t n, float p, uint64_t seed, int64_t index0, void* stream) {
+  return dropout_scale_launch("dropout_scale_at", x, n, p, seed, index0, stream);
 }
 
 extern "C" int tl_set_step_scalars(float* scalars_dev, uint64_t* seed_dev, float coef_grad, float coef_mom, float bias_corr2,

@@ -17,6 +17,10 @@ out as a plain loop:
 ``_cnn_classifier_train_engine`` for ``CNNClassifier``, ``_cnnrnn_classifier_train_engine`` for ``CNNRNNClassifier``: fused
 cross-entropy step, ``FusedNAdam``);
 loss and confusion matrix then stay on the device and are read once per epoch.
+
+Under a multi-rank process group (``parallel.init_from_env``; ``fused=True`` only) every rank iterates the same global batches,
+the engine works on its rows and exchanges gradients, ``epoch_stats`` returns the global statistics on every rank - so early
+stopping decides alike everywhere - and rank 0 alone writes ``metrics.csv`` / ``confusion_matrix_test.csv``.
 """
 from __future__ import annotations
 
@@ -29,6 +33,7 @@ import torch
 import torch.nn as nn
 from torch.optim import NAdam
 
+from .. import parallel
 from .classifier import ClassifierModel
 from .utils import split_decay_groups
 
@@ -62,6 +67,9 @@ class ClassifierTrainer:
         self.verbose = verbose
         self.fused = bool(fused)
         self.engine = None
+        if not self.fused and parallel.world()[1] > 1:
+            raise ValueError(f"ClassifierTrainer(fused=False) under a process group of {parallel.world()[1]} ranks: data-parallel "
+                             "classifier training runs on the HIP engines only (fused=True); the autograd loop is single-process")
         if self.fused:         # an explicit request: a model / device pair the engine does not take raises (ValueError)
             from .deep_classifiers import CNNClassifier, CNNRNNClassifier
             if isinstance(model, CNNClassifier):
@@ -154,7 +162,7 @@ class ClassifierTrainer:
                 cm += _confusion(y.long().cpu(), self.model(x).argmax(1).cpu(), n_cls)
         scores = macro_scores(cm)
         self.test_accuracy, self.test_f1, self.confusion_matrix = scores["accuracy"], scores["f1"], cm
-        if self.log_dir is not None:
+        if self.log_dir is not None and parallel.is_writer():
             os.makedirs(self.log_dir, exist_ok=True)
             np.savetxt(os.path.join(self.log_dir, "confusion_matrix_test.csv"), cm.numpy(), fmt="%d", delimiter=",")
         return {"accuracy": self.test_accuracy, "f1": self.test_f1, "confusion_matrix": cm}
@@ -177,7 +185,7 @@ class ClassifierTrainer:
         return float(sum(float(p.detach().norm(2)) ** 2 for p in self.model.parameters() if p.requires_grad) ** 0.5)
 
     def _write_metrics(self) -> None:
-        if self.log_dir is None or not self.history:
+        if self.log_dir is None or not self.history or not parallel.is_writer():
             return
         os.makedirs(self.log_dir, exist_ok=True)
         with open(os.path.join(self.log_dir, "metrics.csv"), "w", newline="") as f:

@@ -104,6 +104,11 @@ def world() -> Tuple[int, int]:
     return 0, 1
 
 
+def is_writer() -> bool:
+    """True on the one rank that writes files (rank 0; always true without a process group)."""
+    return world()[0] == 0
+
+
 def active() -> bool:
     """True when the gradient exchange must run: a process group with more than one rank, or a
     single-rank group under ``TONAL_DP_FORCE=1`` (drives the real RCCL calls on a one-GPU box)."""

@@ -5,7 +5,10 @@ train_classifier.py:19-155; BASELINE config C1 runs this on CPU).
 ``evaluation`` into one namespace (reference :23-34), derives the log directory from a hash of that
 configuration (:58-65), writes the merged configuration next to the results (:67-90), draws the
 per-repeat seeds from ``np.random.seed(seed); randint(0, 10000, repeat)`` (:92-93) and trains every
-selected ``subject_<id>.npz`` jointly or per target (:97-113).  Returns the log directory."""
+selected ``subject_<id>.npz`` jointly or per target (:97-113).  Returns the log directory.
+
+Under ``torch.distributed.run`` (``parallel.init_from_env``) every rank runs the same seeded loop on ``cuda:LOCAL_RANK`` - the
+splits and batches are deterministic per seed, the fused engines shard each batch by rows - and rank 0 alone writes files."""
 from __future__ import annotations
 
 import os
@@ -15,12 +18,16 @@ from argparse import Namespace
 import numpy as np
 import yaml
 
+from . import parallel
 from .training.classifier_pipeline import save_and_plot_results, train_joint_targets, train_separate_targets
 from .utils.config import dict_to_namespace, generate_hash_name_from_config, load_config
 
 
 def run(config: dict) -> str:
-    print("Running train_classifier ...")
+    _rank, _world, local_rank = parallel.init_from_env()
+    writer = parallel.is_writer()
+    if writer:
+        print("Running train_classifier ...")
     training_section = config.get("training", {})
     train_cfg = training_section.get("params", {})
     flat = {}
@@ -43,6 +50,11 @@ def run(config: dict) -> str:
         raise FileNotFoundError(f"Sample directory {sample_dir} does not exist."
                                 "Please specify a valid sample_dir in the config.")
     params.sample_dir = sample_dir
+    if parallel.active():
+        params.device = f"cuda:{local_rank}"
+        if parallel.world()[1] > 1 and not getattr(params, "fused", False):
+            raise ValueError("train_classifier under a multi-rank process group needs training.params.fused: true "
+                             "(data-parallel classifier training runs on the HIP engines only)")
     subject_files = sorted(f for f in os.listdir(sample_dir) if f.endswith(".npz") and f.startswith("subject_"))
     if not subject_files:
         raise FileNotFoundError(f"No subject files found in {sample_dir}. "
@@ -60,8 +72,9 @@ def run(config: dict) -> str:
         if path and os.path.exists(path):
             merged.update(load_config(path))
     merged.update(model=model_cfg, training=training_section, dataset=dataset_cfg, evaluation=evaluation_cfg)
-    with open(os.path.join(params.log_dir, "config.yaml"), "w") as f:
-        yaml.dump(merged, f)
+    if writer:
+        with open(os.path.join(params.log_dir, "config.yaml"), "w") as f:
+            yaml.dump(merged, f)
 
     np.random.seed(getattr(params, "seed", 42))
     seeds = np.random.randint(0, 10000, getattr(params, "repeat", 1))
@@ -70,7 +83,8 @@ def run(config: dict) -> str:
         subject_id = subject_file.split("_")[1].split(".")[0]
         if subject_id not in wanted:
             continue
-        print("--------- Processing file:", subject_file, "---------")
+        if writer:
+            print("--------- Processing file:", subject_file, "---------")
         sp = _prepare_subject_params(params, subject_id)
         train = train_separate_targets if getattr(params, "separate_models", False) else train_joint_targets
         results, confusion, labels = train(sp, seeds)

@@ -16,6 +16,7 @@ import numpy as np
 import pandas as pd
 import torch
 
+from .. import parallel
 from ..data_loading.dataloaders import split_dataset
 from ..data_loading.sample_loading import ClassificationSampleHandler
 from ..models.classifier_factory import get_classifier_by_name
@@ -42,7 +43,7 @@ def _fit_one(params: Namespace, dataset, seed: int, n_classes: int, n_channels: 
     trainer.fit(loaders[0], loaders[1], max_epochs=params.epochs, patience=params.patience)
     trainer.test(loaders[2])
     preds = trainer.predict(loaders[2]).cpu().numpy()
-    if getattr(params, "save_checkpoints", False):
+    if getattr(params, "save_checkpoints", False) and parallel.is_writer():
         model_dir = os.path.join(params.log_dir, "model_checkpoints")
         os.makedirs(model_dir, exist_ok=True)
         path = os.path.join(model_dir, f"{tag}_{params.model_name}_seed_{seed}.pt")
@@ -136,6 +137,8 @@ def train_separate_targets(params: Namespace, seeds: np.ndarray) -> Tuple[Dict, 
 
 def save_and_plot_results(params: Namespace, result_info: Dict, confusion_matrix: np.ndarray,
                           class_labels: List[str]) -> None:
+    if not parallel.is_writer():       # data-parallel run: every rank holds the same results, rank 0 writes them
+        return
     metrics = getattr(params, "metrics", ["accuracy"])
     aggregates = getattr(params, "aggregates", ["mean", "std"])
     if isinstance(aggregates, str):

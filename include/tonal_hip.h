@@ -276,6 +276,10 @@ int tl_conv1_wgrad(const float* x, const float* G, const uint32_t* bits, float* 
 /* nn.Dropout of the deep classifiers (models/deep_classifiers.py:81,258) in train mode, in place on a flat buffer:
  * x[i] = keep(seed, i) ? x[i] / (1 - p) : 0 with the counter-hash stream of tl_concat_pack (index = position i)   */
 int tl_dropout_scale(float* x, int64_t n, float p, uint64_t seed, void* stream);
+/* the same kernel on a slice of the buffer the mask is defined on: x[i] = keep(seed, index0 + i) ? x[i] / (1 - p) : 0.  A
+ * data-parallel rank whose shard starts at row b0 of the global batch passes index0 = b0 * (elements per batch row) and draws
+ * its rows of the single-process mask; index0 = 0 is tl_dropout_scale bit for bit.  index0 >= 0.                          */
+int tl_dropout_scale_at(float* x, int64_t n, float p, uint64_t seed, int64_t index0, void* stream);
 
 /* ---- small strided helpers --------------------------------------------------------------- */
 /* dst[i0][i1][i2][i3] (contiguous) = sum_{z<nz} src[z*zs + i0*s0 + i1*s1 + i2*s2 + i3*s3];
@@ -479,6 +483,14 @@ int tl_pool3_fwd(const float* Y, float* X, int B, int w1, int Cn, int C, int Tp,
                  uint64_t seed, void* stream);
 int tl_pool3_bwd(const float* Y, const float* dX, float* dZ, int B, int w1, int Cn, int C, int Tp, int tq, int ldy, int lddz,
                  int64_t rs_b, int64_t rs_t, float p, uint64_t seed, float slope, void* stream);
+/* the same two kernels on rows [b0, b0 + B) of a global batch of B_global (data-parallel shard): Y / X / dX / dZ are this rank's
+ * (local addressing, B local rows); only the keep position changes - seq becomes the sequence's number in the GLOBAL batch's
+ * branch-major order, (b0 + b) * w1 + j for an LSTM-branch column and B_global * w1 + (b0 + b) * Cn + e for an electrode column.
+ * b0 = 0, B_global = B are tl_pool3_fwd / tl_pool3_bwd bit for bit.  0 <= b0, b0 + B <= B_global.                           */
+int tl_pool3_fwd_shard(const float* Y, float* X, int B, int w1, int Cn, int C, int Tp, int tq, int ldy, int64_t rs_b, int64_t rs_t,
+                       float p, uint64_t seed, int b0, int B_global, void* stream);
+int tl_pool3_bwd_shard(const float* Y, const float* dX, float* dZ, int B, int w1, int Cn, int C, int Tp, int tq, int ldy, int lddz,
+                       int64_t rs_b, int64_t rs_t, float p, uint64_t seed, float slope, int b0, int B_global, void* stream);
 /* input gradient of the first conv stage (C_in = 1) from G1 = dL/dZ at the arg-max (rows [seq * Tp + t][C1], C1 = 1024),
  * its arg-max bits and w (C1, ktaps = 7: the one shape built): dx[seq][u] = sum over the (t, j) with 2 t + a + j = u of sum_c G1[t][c] w[c][j];
  * every sample u < T is written (zero where nothing reaches it) to dx[(seq / n_inner) * stride_outer + u * stride_t +
