@@ -64,10 +64,12 @@ class ConvStack(LaunchTimers):
         tp1_default = self.tp1
         if self.wino63:
             self.tp1 = (self.tout1 + 11) // 12 * 12
-        # the input gradient of stage 3 writes the operands of stage 2's backward - Y2 = A dz and Vd2 - instead of the gradient
-        # rows G2 (epilogue 6 of tl_conv3_wino63v_nt): the weight gradient of stage 2 then runs without a transform
-        # (tl_conv3_wino63v_tn, loader 3; needs C_in of stage 2 % 256 == 0).  TONAL_F63_YPROD=0: off (G2 is stored, the
-        # weight-gradient kernel un-pools and transforms it itself, as stage 3's does)
+        # the input gradient of stage 3 writes the operand of stage 2's backward - Y2 = A dz - instead of the gradient rows G2
+        # (epilogue 6 of tl_conv3_wino63v_nt): the weight gradient of stage 2 then runs without a transform
+        # (tl_conv3_wino63v_tn, loader 3; needs C_in of stage 2 % 256 == 0) and its input gradient on the same Y2 (epilogue 4
+        # with row_shift 0, taps of tl_wino63_weights_y); Vd2 is written only under store_p1 (nothing reads it).
+        # TONAL_F63_YPROD=0: off (G2 is stored, the weight-gradient kernel un-pools and transforms it itself and writes
+        # Vd2, the operand of the input gradient, as stage 3's does)
         self.f63_yprod = (self.wino63 and _kernels.get("f63_yprod") != "0" and stage_defs[0][0] % 256 == 0
                           and self.tp1 >= 12)
         # ... and stage 3's (whose gradient rows no Winograd epilogue produces) from a kernel of its own, tl_wino63_unpool_yvd
@@ -96,7 +98,8 @@ class ConvStack(LaunchTimers):
         mode = _kernels.get("wino")
         self.wino43 = mode != "0"
         # with V written by the first stage the raw pooled rows P1 (13.4 GB at the north-star shape) have no reader
-        # left (the LeakyReLU' mask of the backward pass comes from the 1-bit sign array); store_p1 keeps them anyway
+        # left (the LeakyReLU' mask of the backward pass comes from the 1-bit sign array); store_p1 keeps them anyway - and
+        # with them the other operands the default path no longer writes (P2; Vd2 of the f63_yprod form)
         self.store_p1 = _kernels.get("store_p1") == "1"
         # fold the first stage's weight gradient into the stage-2 input-gradient epilogue (Winograd kernels)
         self.fuse_c1 = True                    # (tests clear it to reach the stand-alone tl_conv1_wgrad)
@@ -306,7 +309,8 @@ class ConvStack(LaunchTimers):
             self._y_ready[3] = self.generation
             self._vd_ready[3] = self.generation
         if self._y_ready.get(st.idx) == self.generation:
-            # both operands pre-transformed: Y (and Vd) of this stage were written by the input gradient of the stage above
+            # both operands pre-transformed: Y of this stage was written by the input gradient of the stage above.  (_y_ready
+            # is this pass's flag alone: stage 2's input gradient reads the same Y2 after it, under _vd_ready)
             Y = self.Yt[st.idx]
             self._y_ready[st.idx] = -1
             self._tn(tag=f"conv{st.idx}_wgrad", fn="tl_conv3_wino63v_tn", A=ptr(V), B=ptr(Y), slab=ptr(slab), Krows=rows_in,
@@ -388,26 +392,35 @@ class ConvStack(LaunchTimers):
     def _stage_dgrad63(self, st, w):
         S = self.S
         rows_in = S * st.tp_in
+        # _vd_ready[idx]: the operand of this pass is there - Vd of the stage, or (stage 2 with f63_yprod) Y2
         if self._vd_ready.get(st.idx) != self.generation:
-            raise RuntimeError("F(6,3) input gradient: the stage's weight-gradient pass (which writes Vd) must run first")
+            raise RuntimeError("F(6,3) input gradient: its operand (Vd from the stage's weight-gradient pass, or Y2 from the "
+                               "input gradient of stage 3) must be written first")
         self._vd_ready[st.idx] = -1
-        Vd = self.Vd[st.idx]
-        wd = self._pack_wino63(w, False)                   # [8][cin][cout]
+        on_y = st.idx == 2 and self.f63_yprod              # hex H of Y2 yields rows 6 H .. 6 H + 7 (tonal_wino63_epi.h)
+        Vd = self.Yt[2] if on_y else self.Vd[st.idx]
+        if on_y:
+            wd = torch.empty(8, st.cin, st.cout, dtype=torch.float32, device=w.device)
+            check(self.lib.tl_wino63_weights_y(ptr(w), ptr(wd), st.cout, st.cin, st.cout, self._stream()), "tl_wino63_weights_y")
+        else:
+            wd = self._pack_wino63(w, False)               # [8][cin][cout]
         kw = dict(A=ptr(Vd), A_rows=Vd.shape[0], lda=Vd.shape[2], loader=LOAD_V, Bw=ptr(wd), M=rows_in, N=st.cin,
-                  K=st.cout, ldb=st.cout, ldo=st.cin, J=3, row_shift=-2, Tp=st.tp_in, slope=self.slope,
+                  K=st.cout, ldb=st.cout, ldo=st.cin, J=3, row_shift=0 if on_y else -2, Tp=st.tp_in, slope=self.slope,
                   auxbits=ptr(self.sbits[st.idx - 1]), ld_auxbits=self.sbits[st.idx - 1].shape[1])
         if st.idx == 3 and self.f63_yprod:
             below = self.stages[0]
             rows2 = S * below.tp_in                              # conv rows of stage 2: six per hex = three of this GEMM's rows
             Y2 = self._v_hex_buffer(self.Yt, 2, rows2, below.cout)
-            Vd2 = self._v_hex_buffer(self.Vd, 2, rows2, below.cout)
+            # Vd2 has no reader (stage 2's input gradient runs on Y2): written, with its fix-up pass, only under store_p1
+            Vd2 = self._v_hex_buffer(self.Vd, 2, rows2, below.cout) if self.store_p1 else None
             ntm = -(-rows_in // self._nt63_rows())
-            halo = self._halo_buffer("d2", ntm, below.cout)
+            halo = self._halo_buffer("d2", ntm, below.cout) if self.store_p1 else None
             self._nt(tag="conv3_dgrad", fn="tl_conv3_wino63v_nt", epilogue=EPI_MASKY, out=None, vout=ptr(Y2), vout2=ptr(Vd2),
                      vhalo=ptr(halo), vout_quads=Y2.shape[0], ld_vout=Y2.shape[2], abits=ptr(self.bits[2]),
                      ld_abits=below.cout // 32, Tvalid_in=2 * below.tout, **kw)
-            check(self.lib.tl_wino63_vd_fixup(ptr(Vd2), ptr(halo), rows_in // 3, ntm, below.tp_in // 6, below.cout, Vd2.shape[2],
-                                              self._stream()), "tl_wino63_vd_fixup")
+            if Vd2 is not None:
+                check(self.lib.tl_wino63_vd_fixup(ptr(Vd2), ptr(halo), rows_in // 3, ntm, below.tp_in // 6, below.cout,
+                                                  Vd2.shape[2], self._stream()), "tl_wino63_vd_fixup")
             self._y_ready[2] = self.generation
             self._vd_ready[2] = self.generation
             return None
@@ -508,7 +521,8 @@ class ConvStack(LaunchTimers):
             else:
                 fams[f"{tn} (conv3 weight gradient, {f6}; also writes Vd)"] = ["conv3_wgrad"]
             if self.f63_yprod:
-                fams[f"wino63v_nt_kernel<MASKY> (conv3 input gradient, {f6}; writes Y and Vd of conv2 instead of the gradient rows)"] = ["conv3_dgrad"]
+                both = "Y and Vd" if self.store_p1 else "Y"
+                fams[f"wino63v_nt_kernel<MASKY> (conv3 input gradient, {f6}; writes {both} of conv2 instead of the gradient rows)"] = ["conv3_dgrad"]
                 fams[f"wino63v_tn4y_kernel (conv2 weight gradient, {f6}: both operands by LDS-DMA, no transform in the kernel)"] = ["conv2_wgrad"]
             else:
                 fams[f"wino63v_nt_kernel<MASK> (conv3 input gradient, {f6})"] = ["conv3_dgrad"]

@@ -18,6 +18,7 @@
 // are stored chunk-major for the same reason: U[K / 8][8 transforms][rows][8] - a piece is 1 KB contiguous.
 //
 //   tl_wino63_weights       w (O, I, 3, 1) -> forward taps [8][O][ld_f], input-gradient taps [8][I][ld_d] (flipped)
+//   tl_wino63_weights_y     ... -> the taps of an input gradient that runs on Y = A dz (un-flipped, contracted over C_out)
 //   tl_conv3_wino63v_nt     M_i[hex][n] = sum_k V_i[hex][k] U_i[n][k], i < 8: batched NT GEMM, both operands by LDS-DMA
 //                           into three 8-deep stages, epilogues of tonal_wino63_epi.h
 //   tl_wino63_v_fixup       second half of the V-writing forward epilogue
@@ -57,7 +58,7 @@ __device__ __forceinline__ long long v6_at(long long hex, int i, int c, int kc8)
 // 1/45 (32 -16 8); 0 0 1]
 // ------------------------------------------------------------------------------------------
 __global__ void wino63_weights_kernel(const float* __restrict__ w, float* __restrict__ fwd, float* __restrict__ dgr, int O,
-                                      int I, int ld_f, int ld_d) {
+                                      int I, int ld_f, int ld_d, int flip) {
   const long long n_f = (long long)O * ld_f, n_d = (long long)I * ld_d;
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   // element (transform t, row r of R, reduction index k) of a chunk-major tap set: ((k / 8 * 8 + t) * R + r) * 8 + k % 8
@@ -90,7 +91,8 @@ __global__ void wino63_weights_kernel(const float* __restrict__ w, float* __rest
     float g0 = 0.f, g1 = 0.f, g2 = 0.f;
     if (o < O) {
       const float* s = w + ((long long)o * I + i) * 3;
-      g0 = s[2], g1 = s[1], g2 = s[0];          // flipped taps
+      if (flip) g0 = s[2], g1 = s[1], g2 = s[0];          // flipped taps (the Vd form of the input gradient)
+      else g0 = s[0], g1 = s[1], g2 = s[2];               // as they are (its Y form: tl_wino63_weights_y)
     }
     emit(dgr, I, i, o, g0, g1, g2);
   }
@@ -241,7 +243,7 @@ constexpr int V6_ROWS = 6 * V6_BH;                       // conv rows per tile (
 
 template <int EPI>
 __global__ __launch_bounds__(512, 2) void wino63v_nt_kernel(const tl_nt_params p) {
-  __shared__ __attribute__((aligned(1024))) char lds[3 * V6_STAGE + ((EPI == W_EPI_POOLV || EPI == W_EPI_MASKY || EPI == W_EPI_GY) ? 4096 : EPI == W_EPI_C1W ? 16384 : 0)];
+  __shared__ __attribute__((aligned(1024))) char lds[3 * V6_STAGE + ((EPI == W_EPI_POOLV || EPI == W_EPI_MASKY || EPI == W_EPI_GY) ? 4096 : (EPI == W_EPI_C1W || EPI == W6_EPI_C1W_Y) ? 16384 : 0)];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -406,7 +408,7 @@ __global__ __launch_bounds__(512, 2) void wino63v_nt_kernel(const tl_nt_params p
   // The reads of H between L's MFMAs: one per MFMA in the first half of L's window, so that the last eight MFMAs cover their
   // latency behind the barrier - for the conv2 launches (POOLV, fused conv1 gradient: -0.5 / -0.4 ms, same-call A/B, twice);
   // the instantiations of conv3 (POOL, MASKY) measured +0.2 ms with it and keep one read per two MFMAs
-  constexpr bool early = EPI == W_EPI_POOLV || EPI == W_EPI_C1W;
+  constexpr bool early = EPI == W_EPI_POOLV || EPI == W_EPI_C1W || EPI == W6_EPI_C1W_Y;
   constexpr int NST = v6_stores<EPI>();
   constexpr int first_n = NST + 6 > 63 ? 63 : NST + 6;
   constexpr int first_wait = (first_n & 15) | (7 << 4) | (0 << 8) | ((first_n >> 4) << 14);       // vmcnt(n) lgkmcnt(0)
@@ -423,7 +425,7 @@ __global__ __launch_bounds__(512, 2) void wino63v_nt_kernel(const tl_nt_params p
     auto prefetch = [&] {
       if constexpr (EPI == W_EPI_POOL || EPI == W_EPI_POOLV || EPI == W_EPI_LRELU) return v5_prefetch_pool(p, cur.n0, wn, lr);
       else if constexpr (EPI == W_EPI_MASK) return v6_prefetch_mask(p, cur.R0, cur.n0, wm, wn, lr, lh);
-      else if constexpr (EPI == W_EPI_MASKY) return v6_prefetch_masky(p, cur.R0, cur.n0, wm, wn, lr, lh);
+      else if constexpr (EPI == W_EPI_MASKY || EPI == W6_EPI_MASKY_Y) return v6_prefetch_masky(p, cur.R0, cur.n0, wm, wn, lr, lh);
       else if constexpr (EPI == W_EPI_GY) return v6_prefetch_masky<true>(p, cur.R0, cur.n0, wm, wn, lr, lh);
       else return v6_prefetch_c1w(p, cur.R0, cur.n0, wm, wn, lr, lh);
     };
@@ -494,13 +496,16 @@ __global__ __launch_bounds__(512, 2) void wino63v_nt_kernel(const tl_nt_params p
       float* xch = reinterpret_cast<float*>(lds + 3 * V6_STAGE);
       if (full) v6_epilogue_masky<true>(p, acc, pre, xch, done.R0, done.n0, wm, wn, lr, lh, done.tm);
       else v6_epilogue_masky<false>(p, acc, pre, xch, done.R0, done.n0, wm, wn, lr, lh, done.tm);
+    } else if constexpr (EPI == W6_EPI_MASKY_Y) {
+      if (full) v6_epilogue_masky<true, false, false>(p, acc, pre, nullptr, done.R0, done.n0, wm, wn, lr, lh, done.tm);
+      else v6_epilogue_masky<false, false, false>(p, acc, pre, nullptr, done.R0, done.n0, wm, wn, lr, lh, done.tm);
     } else if constexpr (EPI == W_EPI_GY) {
       float* xch = reinterpret_cast<float*>(lds + 3 * V6_STAGE);
       if (full) v6_epilogue_masky<true, true>(p, acc, pre, xch, done.R0, done.n0, wm, wn, lr, lh, done.tm);
       else v6_epilogue_masky<false, true>(p, acc, pre, xch, done.R0, done.n0, wm, wn, lr, lh, done.tm);
     } else {
-      v6_epilogue_c1w(p, acc, pre, reinterpret_cast<float*>(lds + 3 * V6_STAGE) + wave * 512, scratch, done.R0, done.n0, wm, wn,
-                      lr, lh, done.tm);
+      v6_epilogue_c1w<EPI == W6_EPI_C1W_Y>(p, acc, pre, reinterpret_cast<float*>(lds + 3 * V6_STAGE) + wave * 512, scratch, done.R0,
+                                           done.n0, wm, wn, lr, lh, done.tm);
     }
     {
       // The next tile's first stage (issued in front of the epilogue) has landed; its second stage and the epilogue's own
@@ -1714,8 +1719,21 @@ extern "C" int tl_wino63_weights(const float* w, float* fwd, float* dgr, int O, 
   const long long n = nf > nd ? nf : nd;
   TL_REQUIRE((n + 255) / 256 < (1LL << 31), "wino63_weights: too large");
   hipLaunchKernelGGL(wino63_weights_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, fwd, dgr, O,
-                     I, ld_f, ld_d);
+                     I, ld_f, ld_d, 1);
   return check_launch("wino63_weights");
+}
+
+// Taps of the input gradient that runs on Y = A dz (epilogue 4 with row_shift 0): U = G g of the taps as they are, chunk-major over
+// the reduction index C_out like the flipped set of tl_wino63_weights: [ld_d / 8][8 transforms][I rows][8]
+extern "C" int tl_wino63_weights_y(const float* w, float* dgy, int O, int I, int ld_d, void* stream) {
+  using namespace tl;
+  TL_REQUIRE(w != nullptr && dgy != nullptr, "wino63_weights_y: null pointer");
+  TL_REQUIRE(O > 0 && I > 0 && ld_d >= O && ld_d % 8 == 0, "wino63_weights_y: O, I > 0 and ld_d %% 8 == 0, ld_d >= O needed");
+  const long long n = (long long)I * ld_d;
+  TL_REQUIRE((n + 255) / 256 < (1LL << 31), "wino63_weights_y: too large");
+  hipLaunchKernelGGL(wino63_weights_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w,
+                     (float*)nullptr, dgy, O, I, 0, ld_d, 0);
+  return check_launch("wino63_weights_y");
 }
 
 extern "C" int tl_wino63_wgrad_finalize(const float* red, float* gw, int O, int I, int ld, void* stream) {
@@ -1820,7 +1838,9 @@ extern "C" int tl_conv7_wino63v_nt(const tl_nt_params* pp, void* stream) {
 
 // NT passes on a pre-transformed operand: A = V[hex][8][lda], A_rows = hexes in V (whole 128-hex tiles), M = output rows
 // (6 per hex).  Forward: V of the stage input, POOL / POOLV epilogue.  Input gradient: Vd (written by tl_conv3_wino63v_tn),
-// taps = the flipped / transposed set, MASK or fused-conv1-weight-gradient epilogue.
+// taps = the flipped / transposed set, MASK or fused-conv1-weight-gradient epilogue.  Epilogue 6 (MASKY) writes Y (and, with
+// vout2 / vhalo, Vd) of the stage below instead of rows; epilogue 4 with row_shift 0 takes that Y as its operand:
+//   dd[rows 6 H .. 6 H + 7] = B [sum_cout (G g)_i . (A dz)_i], the transposition of the forward form (tonal_wino63_epi.h).
 extern "C" int tl_wino63_nt_tile_rows(void) { return tl::V6_ROWS; }
 
 extern "C" int tl_conv3_wino63v_nt(const tl_nt_params* pp, void* stream) {
@@ -1867,15 +1887,22 @@ extern "C" int tl_conv3_wino63v_nt(const tl_nt_params* pp, void* stream) {
   } else if (p.epilogue == W_EPI_MASKY) {
     TL_REQUIRE(p.row_shift == -2 && p.auxbits != nullptr && p.abits != nullptr, "wino63v_nt: epilogue 6 needs row_shift -2, auxbits and abits");
     TL_REQUIRE(p.ld_abits * 32 >= p.N && p.Tvalid_in % 2 == 0 && p.Tvalid_in <= 2 * p.Tp, "wino63v_nt: epilogue 6: bad abits / Tvalid_in");
-    TL_REQUIRE(p.vout && p.vout2 && p.vhalo && p.ld_vout >= p.N && p.ld_vout % 8 == 0 && p.vout_quads >= p.M / 3 && p.vout_quads % 2 == 0,
-               "wino63v_nt: epilogue 6 needs vout / vout2 (>= M / 3 hexes, whole pairs, ld_vout %% 8 == 0) and vhalo");
+    TL_REQUIRE(p.vout && p.ld_vout >= p.N && p.ld_vout % 8 == 0 && p.vout_quads >= p.M / 3 && p.vout_quads % 2 == 0,
+               "wino63v_nt: epilogue 6 needs vout (>= M / 3 hexes, whole pairs, ld_vout %% 8 == 0)");
+    TL_REQUIRE((p.vout2 == nullptr) == (p.vhalo == nullptr), "wino63v_nt: epilogue 6 takes vout2 and vhalo together (Y and Vd) or neither (Y only)");
     TL_REQUIRE(128LL * 8 * p.ld_vout * 4 < (1LL << 31), "wino63v_nt: ld_vout too large");
-    hipLaunchKernelGGL((wino63v_nt_kernel<W_EPI_MASKY>), dim3((unsigned)ngrid), dim3(512), 0, st, p);
+    // without vout2 / vhalo: Y only (the stage below runs its input gradient on Y); its fix-up pass has nothing to do then
+    if (p.vout2 != nullptr) hipLaunchKernelGGL((wino63v_nt_kernel<W_EPI_MASKY>), dim3((unsigned)ngrid), dim3(512), 0, st, p);
+    else hipLaunchKernelGGL((wino63v_nt_kernel<W6_EPI_MASKY_Y>), dim3((unsigned)ngrid), dim3(512), 0, st, p);
   } else if (p.epilogue == W_EPI_C1W) {
-    TL_REQUIRE(p.row_shift == -2, "wino63v_nt: input gradient needs row_shift -2");
+    // row_shift -2: A = Vd (B^T of the un-pooled gradient rows 6 H - 2 .. 6 H + 5), flipped taps; row_shift 0: A = Y (A dz of
+    // rows 6 H .. 6 H + 5), taps of tl_wino63_weights_y - hex H yields rows 6 H .. 6 H + 7
+    TL_REQUIRE(p.row_shift == -2 || p.row_shift == 0, "wino63v_nt: epilogue 4 needs row_shift -2 (operand Vd) or 0 (operand Y)");
     TL_REQUIRE(p.auxbits && p.c1x && p.c1bits && p.c1partial, "wino63v_nt: epilogue 4 needs auxbits, c1x, c1bits, c1partial");
     TL_REQUIRE(p.c1kt >= 1 && p.c1kt <= 3 && p.c1T >= 2 * p.Tvalid + 2, "wino63v_nt: epilogue 4: 1..3 taps, c1T >= 2*Tvalid + 2");
-    hipLaunchKernelGGL((wino63v_nt_kernel<W_EPI_C1W>), dim3((unsigned)ngrid), dim3(512), 0, st, p);
+    TL_REQUIRE(p.Tvalid >= 0 && p.Tvalid <= p.Tp, "wino63v_nt: epilogue 4: Tvalid must lie in [0, Tp]");
+    if (p.row_shift == -2) hipLaunchKernelGGL((wino63v_nt_kernel<W_EPI_C1W>), dim3((unsigned)ngrid), dim3(512), 0, st, p);
+    else hipLaunchKernelGGL((wino63v_nt_kernel<W6_EPI_C1W_Y>), dim3((unsigned)ngrid), dim3(512), 0, st, p);
   } else {
     set_error("wino63v_nt: unsupported epilogue %d", p.epilogue);
     return TL_EINVAL;

@@ -13,6 +13,10 @@
 
 namespace tl {
 
+// Instantiations of wino63v_nt_kernel beyond the numbering of tl_nt_params.epilogue; tl_conv3_wino63v_nt picks them from fields
+// the parameters have: epilogue 6 without vout2 / vhalo (Y only, no Vd), epilogue 4 with row_shift 0 (the operand is Y, not Vd)
+enum { W6_EPI_MASKY_Y = 8, W6_EPI_C1W_Y = 9 };
+
 constexpr unsigned V6_DROP = 0x80000000u;     // added to any in-range byte offset (< 2^31) it stays past every resource
 constexpr unsigned long long V6_HI = 0xffffffff00000000ull;
 
@@ -100,6 +104,20 @@ __device__ __forceinline__ void wino63_bt(const float (&d)[8], float (&v)[8]) {
   v[5] = e3 + o3;
   v[6] = e3 - o3;
   v[7] = fmaf(5.25f, d[3] - d[5], d[7] - d[1]);
+}
+// d = B m, B the transpose of the matrix above (same even / odd factoring): the eight input-gradient rows 6 H .. 6 H + 7 a hex
+// contributes, from m_i = sum over C_out of (G g)_i . (A dy)_i - the transposition of y = A^T [(G g) . (B^T d)].  Rows 6, 7 are
+// rows 0, 1 of the next hex as well: the contributions add.
+__device__ __forceinline__ void wino63_b(const float (&m)[8], float (&d)[8]) {
+  const float a12 = m[1] + m[2], s12 = m[1] - m[2], a34 = m[3] + m[4], s34 = m[3] - m[4], a56 = m[5] + m[6], s56 = m[5] - m[6];
+  d[0] = -m[0];
+  d[1] = fmaf(2.f, s56, fmaf(0.5f, s34, s12)) - m[7];
+  d[2] = fmaf(5.25f, m[0], fmaf(4.f, a56, fmaf(0.25f, a34, a12)));
+  d[3] = fmaf(5.25f, m[7], fmaf(-2.5f, s34 + s56, -4.25f * s12));
+  d[4] = fmaf(-5.25f, m[0], fmaf(-5.f, a56, fmaf(-1.25f, a34, -4.25f * a12)));
+  d[5] = fmaf(-5.25f, m[7], fmaf(0.5f, s56, fmaf(2.f, s34, s12)));
+  d[6] = ((m[0] + a12) + a34) + a56;
+  d[7] = m[7];
 }
 
 // lane's bit j of w set ? a : b without a lane mask in scalar registers: sign-extended bit field + bit-field insert.  (The
@@ -346,9 +364,11 @@ __device__ __forceinline__ void v6_epilogue_pool(const tl_nt_params& p, const f3
 }
 
 // Vector-memory stores every wave issues per tile (lower bound where a branch adds some), see v5_stores
+// (MASKY without Vd still issues 256 Y stores per wave and tile: the wait counter holds 63 at the most)
 template <int EPI>
 constexpr int v6_stores() {
-  return EPI == W_EPI_POOL ? 52 : EPI == W_EPI_POOLV ? 70 : (EPI == W_EPI_MASK || EPI == W_EPI_LRELU) ? 96 : (EPI == W_EPI_MASKY || EPI == W_EPI_GY) ? 63 : 0;
+  return EPI == W_EPI_POOL ? 52 : EPI == W_EPI_POOLV ? 70 : (EPI == W_EPI_MASK || EPI == W_EPI_LRELU) ? 96
+         : (EPI == W_EPI_MASKY || EPI == W6_EPI_MASKY_Y || EPI == W_EPI_GY) ? 63 : 0;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -480,7 +500,9 @@ __device__ __forceinline__ v6_pre_masky v6_prefetch_masky(const tl_nt_params& p,
 }
 // DIRECT (epilogue 7): the accumulators ARE the rows - batch i < 6 of the kernel's eight GEMMs is row 6 H + i of hex H (a
 // one-tap stage: tl_conv1_wino63v_dgrad_nt) - where the 3-tap form takes them from the inverse transform.
-template <bool FULL, bool DIRECT = false>
+// VD false (vout2 == vhalo == NULL: the stage below runs its input gradient on Y, v6_epilogue_c1w<true>): Y only - no B^T
+// transform, no Vd stores, no exchange with its barrier, no halo rows; the Y arithmetic and stores are the same instructions.
+template <bool FULL, bool DIRECT = false, bool VD = true>
 __device__ __forceinline__ void v6_epilogue_masky(const tl_nt_params& p, const f32x16 (&acc)[8], const v6_pre_masky& pre, float* xch,
                                                   long long R0, int n0, int wm, int wn, int lr_in, int lh, long long tm) {
   int lr = lr_in;                                           // (opaque copy: see v6_epilogue_c1w)
@@ -497,20 +519,23 @@ __device__ __forceinline__ void v6_epilogue_masky(const tl_nt_params& p, const f
   //   we / wo: ok and the arg-max bit clear / set - the masks of the un-pool select
   //   firstw: hexes that start their sequence (the row in front belongs to the sequence before: zero)
   uint32_t we[3], wo[3], sT[3], firstw = 0;
+  (void)hps;
   {
     const bits96 okA = v6_valid_bits96(rw.tA, Tp, p.Tvalid_in >> 1, Rw, p.M);
     const bits96 okB = v6_valid_bits96(rw.tB, Tp, p.Tvalid_in >> 1, Rw + 96, p.M);
     const uint32_t okw[3] = {lh ? (uint32_t)okB.lo : (uint32_t)okA.lo, lh ? (uint32_t)(okB.lo >> 32) : (uint32_t)(okA.lo >> 32),
                              lh ? okB.hi : okA.hi};
-    uint32_t fA = 0, fB = 0;
-    int ha = rw.tA / 3, hb = rw.tB / 3;
-    for (int k = 0; k < 32; ++k) {
-      fA |= (uint32_t)(ha == 0) << k;
-      fB |= (uint32_t)(hb == 0) << k;
-      ha = ha + 1 == hps ? 0 : ha + 1;
-      hb = hb + 1 == hps ? 0 : hb + 1;
+    if constexpr (VD) {
+      uint32_t fA = 0, fB = 0;
+      int ha = rw.tA / 3, hb = rw.tB / 3;
+      for (int k = 0; k < 32; ++k) {
+        fA |= (uint32_t)(ha == 0) << k;
+        fB |= (uint32_t)(hb == 0) << k;
+        ha = ha + 1 == hps ? 0 : ha + 1;
+        hb = hb + 1 == hps ? 0 : hb + 1;
+      }
+      firstw = lh ? fB : fA;
     }
-    firstw = lh ? fB : fA;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       sT[k] = bit_transpose32(pre.s[k], lr);
@@ -522,7 +547,8 @@ __device__ __forceinline__ void v6_epilogue_masky(const tl_nt_params& p, const f
   const long long Hb = Rw / 3;                              // first hex (of the stage below) of the wave: 64 per wave
   const unsigned pair4 = (unsigned)p.ld_vout * 64u;        // bytes per hex pair (pair layout, tonal_wino63.hip)
   const __amdgpu_buffer_rsrc_t rsY = rsrc_of(p.vout + Hb * 8 * (long long)p.ld_vout, (p.vout_quads - Hb) * 8 * (long long)p.ld_vout * 4);
-  const __amdgpu_buffer_rsrc_t rsD = rsrc_of(p.vout2 + Hb * 8 * (long long)p.ld_vout, (p.vout_quads - Hb) * 8 * (long long)p.ld_vout * 4);
+  const __amdgpu_buffer_rsrc_t rsD = rsrc_of(VD ? p.vout2 + Hb * 8 * (long long)p.ld_vout : nullptr,
+                                            VD ? (p.vout_quads - Hb) * 8 * (long long)p.ld_vout * 4 : 0);
   // (a dropped store carries V6_DROP: the immediates added below must not wrap it back into the resource)
   // after v6_pair_swap: lanes 0-31 / 32-63 = hex j / j + 1 of a pair; first the pairs of lane-half 0's 32 hexes, then half 1's
   const unsigned offP = v6_pair_offset(colbase, lr, lh);
@@ -569,7 +595,8 @@ __device__ __forceinline__ void v6_epilogue_masky(const tl_nt_params& p, const f
       Yp[hh][5] = ev3 + od3;
       Yp[hh][6] = ev3 - od3;
       Yp[hh][7] = d6[5];
-      if (j == 0) {
+      if constexpr (!VD) {
+      } else if (j == 0) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) first_d[k] = d6[k];
       } else {
@@ -590,7 +617,8 @@ __device__ __forceinline__ void v6_epilogue_masky(const tl_nt_params& p, const f
       const unsigned so = (unsigned)e * pair4;
       const unsigned voA = FULL ? vvA : (j < nexA ? vvA : V6_DROP), voB = FULL ? vvB : (j < nexB ? vvB : V6_DROP);
       v6_store_hex_pair<FULL>(Yp[0], Yp[1], rsY, voA, voA + 1024u, voB, voB + 1024u, so);
-      if (e == 0) {
+      if constexpr (!VD) {
+      } else if (e == 0) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) v1keep[i] = Vp[1][i];
       } else {
@@ -599,6 +627,7 @@ __device__ __forceinline__ void v6_epilogue_masky(const tl_nt_params& p, const f
     }
     __builtin_amdgcn_sched_barrier(0);
   }
+  if constexpr (VD) {
   // ---- hex 0 of every lane: its front row is the last row of the half-wave below ----
   const int slot = wm * 2 + lh;
   {
@@ -637,6 +666,7 @@ __device__ __forceinline__ void v6_epilogue_masky(const tl_nt_params& p, const f
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, pe), rsH, ho, 0u, 0);
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, po), rsH, ho, (unsigned)p.N * 4u, 0);
   }
+  }  // VD
 }
 
 // ------------------------------------------------------------------------------------------
@@ -676,6 +706,13 @@ __device__ __forceinline__ v6_pre_c1w v6_prefetch_c1w(const tl_nt_params& p, lon
   r.x[1] = __builtin_bit_cast(f32x4, (v4u)__builtin_amdgcn_raw_buffer_load_b128(rsX, xo + 16u, 0u, 0));
   return r;
 }
+// YFORM (row_shift 0): the operand is Y = A dz of the stage (written by the MASKY epilogue of the stage above) and the taps are
+// the un-flipped set contracted over C_out (tl_wino63_weights_y): a hex yields the EIGHT rows 6 H .. 6 H + 7 = B m (wino63_b).  Rows
+// 6, 7 are rows 0, 1 of the next hex: what follows a row here is linear in it (a per-row factor, then the contraction with the raw
+// signal), so they are carried into the next accumulator element of the same lane; the two rows left over behind the 16th element
+// (rows 96, 97 of the half: another lane's, wave's or tile's rows 0, 1) are contracted on their own with their own sign / arg-max
+// words and sample window, requested at the top of the epilogue.  A carry is dropped where the next hex starts its sequence.
+template <bool YFORM = false>
 __device__ __forceinline__ void v6_epilogue_c1w(const tl_nt_params& p, const f32x16 (&acc)[8], const v6_pre_c1w& pre, float* xw,
                                                 float* red, long long R0, int n0, int wm, int wn, int lr_in, int lh, long long tm) {
   // (an opaque copy of the lane index: what the bit transposes derive from it is then computed here, per tile, instead of
@@ -695,6 +732,49 @@ __device__ __forceinline__ void v6_epilogue_c1w(const tl_nt_params& p, const f32
   float* xh = xw + lh * 256;                                 // this half's sample table: rows 3 l .. 3 l + 2 at xh + 8 l
   *reinterpret_cast<f32x4*>(xh + 8 * lr) = pre.x[0];
   *reinterpret_cast<f32x4*>(xh + 8 * lr + 4) = pre.x[1];
+  // ---- YFORM: the hexes that start a sequence, and everything about rows 96, 97 of the half ----
+  uint32_t keepw = ~0u;                                     // bit e CLEAR: hex e of the lane starts its sequence; bit 16: the hex behind its 16th
+  uint32_t okx0 = 0, okx1 = 0, sx0 = 0, sx1 = 0, cx0 = 0, cx1 = 0;      // rows 96 / 97: the row counts, its sign / arg-max word
+  f32x4 xx = {0.f, 0.f, 0.f, 0.f};                           // samples x[seq][2 t .. 2 t + 5] of row 96 (t its time index)
+  float2 xy = {0.f, 0.f};
+  if constexpr (YFORM) {
+    // hex e of a half whose first row has time t0 (a multiple of 6) starts a sequence where (t0 / 6 + e) % (Tp / 6) == 0
+    const int hps = Tp / 6;
+    auto starts = [hps](int t0) {
+      uint32_t w = 0;
+      for (int e = t0 == 0 ? 0 : hps - t0 / 6; e < 17; e += hps) w |= 1u << e;
+      return w;
+    };
+    keepw = ~(lh ? starts(rw.tB) : starts(rw.tA));
+    // row 96 of half 0 is row 0 of half 1 (time rw.tB, sequence rw.seqB); row 96 of half 1 has time tC in sequence seqC
+    long long seqC = rw.seqB;
+    int tC = rw.tB + 96;
+    while (tC >= Tp) {
+      tC -= Tp;
+      ++seqC;
+    }
+    const int tx = lh ? tC : rw.tB;
+    const long long sqx = lh ? seqC : rw.seqB;
+    const long long Rx = Rw + 96 + 96 * lh;                  // the row itself (Rx % 6 == 0, M % 6 == 0: row 97 is inside with it)
+    const bool inx = colok && Rx < p.M && tx != 0;
+    okx0 = (inx && tx < p.Tvalid) ? ~0u : 0u;
+    okx1 = (inx && tx + 1 < p.Tvalid) ? ~0u : 0u;
+    if (okx0) {                                             // (row 97 counts only where row 96 does)
+      const long long w0 = Rx * (long long)p.ld_auxbits + (colbase >> 5);
+      sx0 = p.auxbits[w0];
+      sx1 = p.auxbits[w0 + p.ld_auxbits];
+      cx0 = p.c1bits[w0];
+      cx1 = p.c1bits[w0 + p.ld_auxbits];
+      const unsigned s0 = (unsigned)(R0 / Tp);               // (the resource of v6_prefetch_c1w)
+      const long long nseq = p.M / Tp;
+      const __amdgpu_buffer_rsrc_t rsX = rsrc_of(p.c1x + (long long)s0 * p.c1T, (nseq - s0) * (long long)p.c1T * 4);
+      typedef unsigned v4u __attribute__((ext_vector_type(4)));
+      typedef unsigned v2u __attribute__((ext_vector_type(2)));
+      const unsigned xo = ((unsigned)(sqx - s0) * (unsigned)p.c1T + 2u * (unsigned)tx) * 4u;
+      xx = __builtin_bit_cast(f32x4, (v4u)__builtin_amdgcn_raw_buffer_load_b128(rsX, xo, 0u, 0));
+      xy = __builtin_bit_cast(float2, (v2u)__builtin_amdgcn_raw_buffer_load_b64(rsX, xo + 16u, 0u, 0));
+    }
+  }
   c1w_acc ca;
   ca.clear();
   uint32_t sT[3], cT[3];                                    // bit j: sign / conv1 arg-max of (row 32 k + j, this lane's column)
@@ -704,10 +784,38 @@ __device__ __forceinline__ void v6_epilogue_c1w(const tl_nt_params& p, const f32
     cT[k] = bit_transpose32(pre.c[k], lr);
   }
   asm volatile("" ::: "memory");
+  auto andf = [](float x, uint32_t m) { return __uint_as_float(__float_as_uint(x) & m); };
+  // one row: dz (already times LeakyReLU' and zero where the row does not count), its arg-max mask, its window x[2 t .. 2 t + 3]
+  auto contract = [&ca](float dz, uint32_t am, float x0, float x1, float x2, float x3) {
+    auto pick = [am](float a, float b) { return __uint_as_float((__float_as_uint(a) & am) | (__float_as_uint(b) & ~am)); };
+    ca.s[0] = fmaf(dz, pick(x1, x0), ca.s[0]);
+    ca.s[1] = fmaf(dz, pick(x2, x1), ca.s[1]);
+    ca.s[2] = fmaf(dz, pick(x3, x2), ca.s[2]);
+    ca.b += dz;
+  };
+  float c6 = 0.f, c7 = 0.f;                                 // YFORM: rows 6, 7 of the hex in front
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
-    float y[6];
-    wino63_rows(acc, e, y);
+    float y[8];
+    if constexpr (YFORM) {
+      float m[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) m[i] = acc[i][e];
+      wino63_b(m, y);
+      if (e > 0) {
+        // (1.0f, or 0.0f where the hex starts its sequence: the carry belongs to no row then)
+        const float kf = __uint_as_float(0x3f800000u & (uint32_t)__builtin_amdgcn_sbfe((int)keepw, e, 1));
+        y[0] = fmaf(c6, kf, y[0]);
+        y[1] = fmaf(c7, kf, y[1]);
+      }
+      c6 = y[6];
+      c7 = y[7];
+    } else {
+      float y6[6];
+      wino63_rows(acc, e, y6);
+#pragma unroll
+      for (int h = 0; h < 6; ++h) y[h] = y6[h];
+    }
 #pragma unroll
     for (int h = 0; h < 6; ++h) {
       const int r = 6 * e + h;
@@ -716,13 +824,15 @@ __device__ __forceinline__ void v6_epilogue_c1w(const tl_nt_params& p, const f32
       const float2 xb = *reinterpret_cast<const float2*>(xh + 8 * (r / 3) + 2 * (r % 3) + 2);
       const float dz = selm0(mask96(okA, okB, r), y[h] * selbit(sT[r >> 5], r & 31, 1.f, p.slope));
       const uint32_t am = (uint32_t)__builtin_amdgcn_sbfe((int)cT[r >> 5], r & 31, 1);
-      auto pick = [am](float a, float b) { return __uint_as_float((__float_as_uint(a) & am) | (__float_as_uint(b) & ~am)); };
-      ca.s[0] = fmaf(dz, pick(xa.y, xa.x), ca.s[0]);
-      ca.s[1] = fmaf(dz, pick(xb.x, xa.y), ca.s[1]);
-      ca.s[2] = fmaf(dz, pick(xb.y, xb.x), ca.s[2]);
-      ca.b += dz;
+      contract(dz, am, xa.x, xa.y, xb.x, xb.y);
     }
     __builtin_amdgcn_sched_barrier(0);                       // (keeps the loads of later hexes from being hoisted: they spill)
+  }
+  if constexpr (YFORM) {
+    // rows 96, 97 of the half; bit lr of a word = this lane's column
+    const float d0 = andf(c6 * selbit(sx0, lr, 1.f, p.slope), okx0), d1 = andf(c7 * selbit(sx1, lr, 1.f, p.slope), okx1);
+    contract(d0, (uint32_t)__builtin_amdgcn_sbfe((int)cx0, lr, 1), xx[0], xx[1], xx[2], xx[3]);
+    contract(d1, (uint32_t)__builtin_amdgcn_sbfe((int)cx1, lr, 1), xx[2], xx[3], xy.x, xy.y);
   }
   __syncthreads();                                          // `red` is a K-loop stage: every wave past its last fragment read
   c1w_reduce_store<4, 64>(p, red, ca, wm, wn * 32 + lr, lh, tm, col, colok);

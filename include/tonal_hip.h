@@ -181,7 +181,9 @@ int tl_conv3_wino43v_tn(const tl_tn_params* p, void* stream);
  *   tl_wino63_weights        w (O, I, 3, 1) -> forward taps [8][O][ld_f], input-gradient taps [8][I][ld_d] (flipped)
  *   tl_conv3_wino63v_nt      tl_conv3_wino43v_nt with A = V in hex form (loader 2, A_rows = hexes, whole tiles;
  *                            M % 6 == 0, K % 8 == 0, K >= 40, N % 32 == 0); epilogues POOL (+ out_tp), POOLV (vout in
- *                            hex form, vout_quads = hexes, Tp % 12 == 0), MASK, conv1-weight-gradient (4)
+ *                            hex form, vout_quads = hexes, Tp % 12 == 0), MASK, conv1-weight-gradient (4: row_shift -2 with
+ *                            A = Vd and the flipped taps, row_shift 0 with A = Y and the taps of tl_wino63_weights_y), MASKY
+ *                            (6: vout = Y of the stage below; vout2 = its Vd and vhalo together, or both NULL: Y only)
  *   tl_wino63_nt_tile_rows   conv rows of a row tile of tl_conv3_wino63v_nt (768: 128 hexes): vhalo holds 2 x C floats per row tile, c1partial one row per row tile, the fix-up passes
  *                            take tiles = ceil(M / that)
  *   tl_wino63_v_fixup        second half of POOLV: the last output hex of every row tile (rows 6, 7 from vhalo)
@@ -193,6 +195,9 @@ int tl_conv3_wino43v_tn(const tl_tn_params* p, void* stream);
  *   tl_conv1_fwd_v6          tl_conv1_fwd_v writing V[S * Tp / 6][8][C1] (Tp % 6 == 0)
  * ------------------------------------------------------------------------------------------ */
 int tl_wino63_weights(const float* w, float* fwd, float* dgr, int O, int I, int ld_f, int ld_d, void* stream);
+/* taps of an input gradient that runs on Y = A dz (tl_conv3_wino63v_nt, epilogue 4 with row_shift 0): the un-flipped transform,
+ * contracted over C_out, [ld_d / 8][8][I][8] - the layout of the flipped set of tl_wino63_weights                              */
+int tl_wino63_weights_y(const float* w, float* dgy, int O, int I, int ld_d, void* stream);
 int tl_conv3_wino63v_nt(const tl_nt_params* p, void* stream);
 int tl_wino63_nt_tile_rows(void);
 int tl_wino63_v_fixup(float* V, const float* vhalo, int64_t hexes, int64_t tiles, int Tq, int C, int ldv, void* stream);

@@ -33,9 +33,8 @@ V1.normal_(generator=g)
 eng._v_ready = {1: V1}
 for k in eng.G:
     eng.G[k].normal_(generator=g)
-if eng.f63_yprod:         # stage 2's backward operands come out of stage 3's input gradient: give the isolated passes something to read
-    for store in (eng.Yt, eng.Vd):
-        eng._v_hex_buffer(store, 2, S * eng.tp1, 512).normal_(generator=g)
+if eng.f63_yprod:         # stage 2's backward operand (Y2: both passes read it) comes out of stage 3's input gradient: give the isolated passes something to read
+    eng._v_hex_buffer(eng.Yt, 2, S * eng.tp1, 512).normal_(generator=g)
 if eng.gy4:               # ... and stage 3's out of stage 4's
     for store in (eng.Yt, eng.Vd):
         eng._v_hex_buffer(store, 3, S * eng.stages[1].tp_in, 512).normal_(generator=g)
@@ -69,7 +68,7 @@ for si in [int(s) for s in args.stages.split(",")]:
     iss = eng.f63_issue_factor(st)
 
     def dgrad():
-        eng._vd_ready[st.idx] = eng.generation       # (Vd left by the last weight-gradient launch / by stage 3's input gradient)
+        eng._vd_ready[st.idx] = eng.generation       # (Vd left by the last weight-gradient launch / Y2 by stage 3's input gradient)
         eng.stage_dgrad(st, w)
 
     def wgrad():
@@ -79,7 +78,7 @@ for si in [int(s) for s in args.stages.split(",")]:
     for name, fn in (("fwd", lambda: eng.stage_forward(st, w, b)), ("wgrad", wgrad), ("dgrad", dgrad)):
         if name not in args.passes.split(","):
             continue
-        if name == "dgrad" and st.idx not in eng.Vd:
+        if name == "dgrad" and st.idx not in eng.Vd and not (eng.f63_yprod and st.idx == 2):
             eng.stage_wgrad(st, gw, gb)
         fn(); torch.cuda.synchronize()
         eng.enable_timers(True)

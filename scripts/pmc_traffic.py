@@ -20,6 +20,9 @@ FAMILIES = {
     "wino63v_nt_kernel<2>": f"wino63v_nt_kernel<POOL> (conv3 forward, {F6})",
     "wino63v_nt_kernel<4>": f"wino63v_nt_kernel<C1WGRAD> (conv2 input gradient + conv1 weight gradient, {F6})",
     "wino63v_nt_kernel<6>": f"wino63v_nt_kernel<MASKY> (conv3 input gradient, {F6}; writes Y and Vd of conv2 instead of the gradient rows)",
+    # instantiations 8 / 9: epilogue 6 without Vd, epilogue 4 on Y (the default path; tonal_wino63_epi.h)
+    "wino63v_nt_kernel<8>": f"wino63v_nt_kernel<MASKY> (conv3 input gradient, {F6}; writes Y of conv2 instead of the gradient rows)",
+    "wino63v_nt_kernel<9>": f"wino63v_nt_kernel<C1WGRAD> (conv2 input gradient + conv1 weight gradient, {F6})",
     "wino63v_nt_kernel<3>": f"wino63v_nt_kernel<MASK> (conv3 input gradient, {F6})",
     "wino63v_nt_kernel<7>": "wino63v_nt_kernel<GY> (conv4 input gradient as six batched GEMMs of the NT63 kernel; writes Y and Vd of conv3 instead of the gradient rows)",
     "wino63_unpool_rows6_kernel": "wino63_unpool_rows6_kernel (conv4's pooled output gradient un-pooled into the hex-slot operand of its input gradient)",
