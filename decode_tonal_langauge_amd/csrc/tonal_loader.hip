@@ -1,0 +1,143 @@
+// Device-resident batch loader: a batch of up to four tensors gathered by one index vector in ONE launch
+// (data_loading/resident.py; the stock DataLoader indexes sample by sample in Python and stacks B views).
+// See include/tonal_hip.h for the contract.
+#include "tonal_common.h"
+
+namespace tl {
+
+// One segment = one output tensor of the batch.  A *unit* is one contiguous copy: a whole sample (C * inner_bytes) without a
+// channel list, one innermost row (inner_bytes) with one.  Units are cut into vectors of `width` bytes (16, 4 or 1: the widest
+// that divides the unit and both base addresses, so that every unit of the segment starts aligned) and a thread moves
+// GATHER_UNROLL vectors, all loads issued before the first store.  Consecutive lanes take consecutive vectors of the flat
+// (batch row, unit, vector) index, so a row shorter than a wave's 1 KiB shares the wave with its neighbours and a segment of
+// tiny rows (labels: 4 or 8 bytes each) is a handful of threads of one workgroup, not a workgroup per row.
+struct gather_seg {
+  const char* src;
+  char* dst;
+  const int32_t* chan;
+  long long src_rows;      // samples in the source
+  long long sample_bytes;  // C * inner_bytes
+  long long unit_bytes;
+  int C;
+  unsigned n_unit;         // units per batch row: n_chan with a channel list, 1 without
+  unsigned vec_per_unit;   // unit_bytes / width
+  unsigned n_vec;          // n_idx * n_unit * vec_per_unit   (< 2^31)
+  unsigned block0;         // first workgroup of the segment
+  int width;
+};
+struct gather_args {
+  gather_seg seg[4];
+  int n;
+};
+
+#define GATHER_UNROLL 4
+#define GATHER_PER_BLOCK (256 * GATHER_UNROLL)
+
+// Three phases without a branch between the loads of one phase, so that each phase has GATHER_UNROLL loads in flight: the
+// indices, the rows, the stores.  A thread past the end, or one whose index is out of range, reads the segment's first
+// vector instead (always there: src_rows, C and inner_bytes are positive) and stores nothing.  Named variables, not arrays:
+// the compiler merges the four guarded stores of an array into one block that indexes it dynamically, which puts the rows
+// in scratch memory and a full wait between the loads.
+#define GATHER_INDEX(u)                                                              \
+  const unsigned v##u = first + u * 256;                                               \
+  bool ok##u = v##u < g.n_vec;                                                       \
+  const unsigned unit##u = ok##u ? v##u / g.vec_per_unit : 0u;                       \
+  const unsigned off##u = ok##u ? v##u - unit##u * g.vec_per_unit : 0u;              \
+  const unsigned b##u = unit##u / g.n_unit, j##u = unit##u - b##u * g.n_unit;        \
+  const long long r##u = idx[b##u];                                                  \
+  const int c##u = CHAN ? g.chan[j##u] : (int)j##u; /* a template argument: no branch between the loads */
+#define GATHER_LOAD(u)                                                                                        \
+  {                                                                                                           \
+    const bool r_ok = r##u >= 0 && r##u < g.src_rows, c_ok = c##u >= 0 && c##u < g.C;                         \
+    if (ok##u) bad |= (r_ok ? 0 : 1) | (c_ok ? 0 : 2);                                                        \
+    ok##u = ok##u && r_ok && c_ok;                                                                            \
+  }                                                                                                           \
+  const long long so##u =                                                                                     \
+      ok##u ? r##u * g.sample_bytes + (long long)c##u * g.unit_bytes + (long long)off##u * (long long)sizeof(V) : 0; \
+  const V val##u = *reinterpret_cast<const V*>(g.src + so##u);
+#define GATHER_STORE(u) \
+  if (ok##u) *reinterpret_cast<V*>(g.dst + (long long)v##u * (long long)sizeof(V)) = val##u;
+
+template <typename V, bool CHAN>
+__device__ __forceinline__ void gather_copy(const gather_seg& g, const long long* __restrict__ idx, int* __restrict__ err,
+                                            unsigned blk) {
+  static_assert(GATHER_UNROLL == 4, "the phases below are written out four times");
+  const unsigned first = blk * GATHER_PER_BLOCK + threadIdx.x;
+  int bad = 0;
+  GATHER_INDEX(0) GATHER_INDEX(1) GATHER_INDEX(2) GATHER_INDEX(3)
+  GATHER_LOAD(0) GATHER_LOAD(1) GATHER_LOAD(2) GATHER_LOAD(3)
+  GATHER_STORE(0) GATHER_STORE(1) GATHER_STORE(2) GATHER_STORE(3)
+  if (bad) atomicOr(err, bad);
+}
+#undef GATHER_INDEX
+#undef GATHER_LOAD
+#undef GATHER_STORE
+
+__global__ __launch_bounds__(256) void gather_rows_kernel(gather_args a, const long long* __restrict__ idx, int* __restrict__ err) {
+  int s = 0;
+#pragma unroll
+  for (int i = 1; i < 4; ++i)
+    if (i < a.n && blockIdx.x >= a.seg[i].block0) s = i;
+  const gather_seg& g = a.seg[s];
+  const unsigned blk = blockIdx.x - g.block0;
+  const bool chan = g.chan != nullptr;
+  if (g.width == 16) {
+    if (chan) gather_copy<uint4, true>(g, idx, err, blk); else gather_copy<uint4, false>(g, idx, err, blk);
+  } else if (g.width == 4) {
+    if (chan) gather_copy<uint32_t, true>(g, idx, err, blk); else gather_copy<uint32_t, false>(g, idx, err, blk);
+  } else {
+    if (chan) gather_copy<uint8_t, true>(g, idx, err, blk); else gather_copy<uint8_t, false>(g, idx, err, blk);
+  }
+}
+
+}  // namespace tl
+
+using namespace tl;
+
+extern "C" int tl_gather_rows(const void* const* src, void* const* dst, const int64_t* src_rows, const int64_t* C,
+                              const int64_t* inner_bytes, const int32_t* const* chan, const int64_t* n_chan, int n_seg,
+                              const int64_t* idx, int64_t n_idx, int32_t* err, void* stream) {
+  TL_REQUIRE(n_seg >= 1 && n_seg <= 4, "gather_rows: 1 to 4 segments per launch, at most 4 (got %d)", n_seg);
+  TL_REQUIRE(src && dst && src_rows && C && inner_bytes && chan && n_chan, "gather_rows: null table");
+  TL_REQUIRE(idx && err, "gather_rows: null index vector or error word");
+  TL_REQUIRE(n_idx > 0 && n_idx < (1LL << 31), "gather_rows: n_idx must be in [1, 2^31) (got %lld)", (long long)n_idx);
+  gather_args a;
+  a.n = n_seg;
+  unsigned long long blocks = 0;
+  for (int i = 0; i < 4; ++i) {
+    gather_seg& g = a.seg[i];
+    if (i >= n_seg) {
+      g = gather_seg{};
+      g.block0 = 0xffffffffu;
+      continue;
+    }
+    TL_REQUIRE(src[i] && dst[i], "gather_rows: null tensor in segment %d", i);
+    TL_REQUIRE(src_rows[i] > 0 && C[i] > 0 && inner_bytes[i] > 0 && n_chan[i] >= 0,
+               "gather_rows: segment %d: src_rows, C and inner_bytes must be positive, n_chan non-negative", i);
+    TL_REQUIRE(n_chan[i] == 0 || chan[i], "gather_rows: segment %d: n_chan = %lld with a null chan", i, (long long)n_chan[i]);
+    TL_REQUIRE(!chan[i] || n_chan[i] > 0, "gather_rows: segment %d: a channel list needs n_chan > 0", i);
+    TL_REQUIRE(C[i] < (1LL << 31) && inner_bytes[i] < (1LL << 31) && n_chan[i] < (1LL << 31),
+               "gather_rows: segment %d: C, n_chan or inner_bytes too large", i);
+    g.src = (const char*)src[i];
+    g.dst = (char*)dst[i];
+    g.chan = chan[i];
+    g.src_rows = src_rows[i];
+    g.C = (int)C[i];
+    g.sample_bytes = C[i] * inner_bytes[i];
+    g.unit_bytes = chan[i] ? inner_bytes[i] : g.sample_bytes;
+    g.n_unit = chan[i] ? (unsigned)n_chan[i] : 1u;
+    const uintptr_t al = (uintptr_t)g.src | (uintptr_t)g.dst | (uintptr_t)g.unit_bytes;
+    g.width = (al & 15) == 0 ? 16 : (al & 3) == 0 ? 4 : 1;
+    const long long vpu = g.unit_bytes / g.width;
+    // n_idx, n_unit, C and inner_bytes are below 2^31: every product below fits 64 bits when taken one factor at a time
+    TL_REQUIRE(vpu < (1LL << 31) && (long long)g.n_unit * vpu < (1LL << 31) && n_idx * ((long long)g.n_unit * vpu) < (1LL << 31),
+               "gather_rows: segment %d: more than 2^31 vectors of %d bytes in one batch", i, g.width);
+    g.vec_per_unit = (unsigned)vpu;
+    g.n_vec = (unsigned)(n_idx * (long long)g.n_unit * vpu);
+    g.block0 = (unsigned)blocks;
+    blocks += (g.n_vec + (unsigned long long)GATHER_PER_BLOCK - 1) / GATHER_PER_BLOCK;
+    TL_REQUIRE(blocks < (1ULL << 31), "gather_rows: too many workgroups");
+  }
+  hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, (const long long*)idx, (int*)err);
+  return check_launch("gather_rows");
+}

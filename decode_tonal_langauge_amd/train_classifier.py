@@ -35,6 +35,8 @@ def run(config: dict) -> str:
         flat.update(train_cfg.get(section, {}))
     if "fused" in train_cfg:               # training.params.fused: the HIP train step of the classifiers that have one
         flat["fused"] = bool(train_cfg["fused"])
+    if "resident" in train_cfg:            # training.params.resident: batches gathered on the device (data_loading/resident.py)
+        flat["resident"] = bool(train_cfg["resident"])
     model_cfg = config.get("model", {})
     dataset_cfg = config.get("dataset", {})
     evaluation_cfg = config.get("evaluation", {})

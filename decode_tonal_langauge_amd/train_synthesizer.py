@@ -13,6 +13,7 @@ Inputs (reference :161-201): ``sample_path`` .npz with ``ecog (N,C,T)`` and eith
 librosa calls of the reference restated with NumPy / SciPy);
 ``channel_file`` JSON {active_channels, tone_discriminative, syllable_discriminative};
 ``config_file`` JSON {mel_kwargs, tone_dynamic_mapping, n_syllables, n_tones[, *_model_kwargs]}.
+``--resident`` (YAML: ``resident: true``; off by default) keeps the dataset on the GPU and gathers every batch there.
 Output: one CSV row per run with the reference's columns (:369-385).
 """
 from __future__ import annotations
@@ -65,6 +66,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--batch_size', type=int, default=8)
     p.add_argument('--epochs', type=int, default=100)
     p.add_argument('--lr', type=float, default=0.0005)
+    p.add_argument('--resident', action='store_true',
+                   help="keep the dataset on the GPU and gather every batch there (data_loading/resident.py); CUDA devices only")
     return p
 
 
@@ -123,9 +126,19 @@ def train(params: Namespace) -> dict:
 
     dataset = np.load(params.sample_path)
     ecog = dataset['ecog']
-    ecog_non = ecog[:, non_disc, :]
-    ecog_syl = ecog[:, channel_selections['syllable_discriminative'], :]
-    ecog_tone = ecog[:, channel_selections['tone_discriminative'], :]
+    syl_channels, tone_channels = channel_selections['syllable_discriminative'], channel_selections['tone_discriminative']
+    # resident: ecog is stored once on the device and read through the three channel lists by the batch gather; the three
+    # host copies ecog[:, channels, :] are not made
+    resident = bool(getattr(params, 'resident', False)) and 'cuda' in str(params.device)
+    if resident:
+        n_samples, n_timepoints = ecog.shape[0], ecog.shape[2]
+        n_channels, n_syl_channels, n_tone_channels = len(non_disc), len(syl_channels), len(tone_channels)
+    else:
+        ecog_non = ecog[:, non_disc, :]
+        ecog_syl = ecog[:, syl_channels, :]
+        ecog_tone = ecog[:, tone_channels, :]
+        n_samples, n_channels, n_timepoints = ecog_non.shape
+        n_syl_channels, n_tone_channels = ecog_syl.shape[1], ecog_tone.shape[1]
     mels = _mels_from_dataset(dataset, params, mel_kwargs)
     say('Number of Mel spectrogram coefficients', mels.shape[1:])
     mels_dim = mels.shape[1]
@@ -133,20 +146,25 @@ def train(params: Namespace) -> dict:
 
     syl_kwargs = config.get('syllable_model_kwargs', {})
     tone_kwargs = config.get('tone_model_kwargs', {})
-    syllable_model = _build_classifier(params.syllable_model_name, ecog_syl.shape[1], seq_length, n_syllables,
+    syllable_model = _build_classifier(params.syllable_model_name, n_syl_channels, seq_length, n_syllables,
                                        syl_kwargs, "syllable")
-    tone_model = _build_classifier(params.tone_model_name, ecog_tone.shape[1], seq_length, n_tones, tone_kwargs, "tone")
+    tone_model = _build_classifier(params.tone_model_name, n_tone_channels, seq_length, n_tones, tone_kwargs, "tone")
     if params.syllable_model_path is not None:
         syllable_model.load_state_dict(torch.load(params.syllable_model_path))
     if params.tone_model_path is not None:
         tone_model.load_state_dict(torch.load(params.tone_model_path))
     train_classifiers = not (params.syllable_model_path is not None and params.tone_model_path is not None)
 
-    n_samples, n_channels, n_timepoints = ecog_non.shape
     if params.verbose > 0:
         say(f"Prepared {n_samples} ECoG samples with shape {ecog.shape[1:]}")
-    tds = TensorDataset(torch.tensor(ecog_non, dtype=torch.float32), torch.tensor(ecog_syl, dtype=torch.float32),
-                        torch.tensor(ecog_tone, dtype=torch.float32), torch.tensor(mels, dtype=torch.float32))
+    if resident:
+        from .data_loading.resident import ResidentDataset
+        ecog_t = torch.tensor(ecog, dtype=torch.float32)
+        tds = ResidentDataset([(ecog_t, non_disc), (ecog_t, syl_channels), (ecog_t, tone_channels),
+                               (torch.tensor(mels, dtype=torch.float32), None)], device=params.device)
+    else:
+        tds = TensorDataset(torch.tensor(ecog_non, dtype=torch.float32), torch.tensor(ecog_syl, dtype=torch.float32),
+                            torch.tensor(ecog_tone, dtype=torch.float32), torch.tensor(mels, dtype=torch.float32))
 
     mcds, losses = [], []
     np.random.seed(params.seed)
@@ -155,7 +173,8 @@ def train(params: Namespace) -> dict:
     for i, seed in enumerate(seeds):
         set_seeds(int(seed))
         ratios = [params.train_ratio, 1 - params.train_ratio]
-        loaders = split_dataset(tds, ratios, shuffling=[True, False], batch_size=params.batch_size, seed=int(seed))
+        loaders = split_dataset(tds, ratios, shuffling=[True, False], batch_size=params.batch_size, seed=int(seed),
+                                resident=resident)
         if params.synthesis_model_name == 'SynthesisLite':
             model = SynthesisLite(output_dim=mels_dim, n_channels=n_channels, n_timepoints=n_timepoints)
         elif params.synthesis_model_name == 'SynthesisFull':

@@ -31,7 +31,8 @@ def _fit_one(params: Namespace, dataset, seed: int, n_classes: int, n_channels: 
     """Split, build, train, test and predict one model for one seed.  Returns (model, preds, true)."""
     verbose = getattr(params, "verbose", 1)
     loaders = split_dataset(dataset, [params.train_ratio, params.vali_ratio, params.test_ratio],
-                            shuffling=[True, False, False], batch_size=params.batch_size, seed=int(seed))
+                            shuffling=[True, False, False], batch_size=params.batch_size, seed=int(seed),
+                            resident=bool(getattr(params, "resident", False)), device=params.device)
     true = np.concatenate([b[1].cpu().numpy() for b in loaders[2]])
     model = get_classifier_by_name(params.model, params.device, n_classes, n_channels, seq_length,
                                    classifier_kwargs=getattr(params, "model_kwargs", None))

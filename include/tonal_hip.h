@@ -375,6 +375,19 @@ int tl_sum_slabs2(const float* srcA, float* dstA, int64_t nA, const float* srcB,
  * tuple of the loop)                                                                                                    */
 int tl_stage_step(float* scalars_dev, uint64_t* seed_dev, float coef_grad, float coef_mom, float bias_corr2, uint64_t seed,
                   const void* const* src, void* const* dst, const int64_t* nbytes, int n, void* stream);
+/* A batch of up to four tensors gathered by one index vector in ONE launch (data_loading/resident.py: the device-resident
+ * counterpart of the DataLoader's per-sample indexing + torch.stack).  Host tables of n_seg <= 4 entries, one per output
+ * tensor ("segment"): src (N = src_rows[s] samples of C[s] rows of inner_bytes[s] bytes, contiguous), dst, and an optional
+ * device list chan[s] of n_chan[s] int32 row numbers (chan[s] null: n_chan[s] = 0 and all C rows are taken in order).
+ * idx: n_idx int64 sample numbers in device memory, shared by the segments.  For segment s, batch row b, output row j:
+ *     dst[b][j][:] = src[idx[b]][chan ? chan[j] : j][:]          copied as bytes, any dtype; indices may repeat.
+ * 16-byte accesses when the copy unit (a whole sample without a list, one row with one) and both bases are multiples of
+ * 16 bytes, 4-byte ones when multiples of 4, bytes otherwise.  An idx[b] outside [0, src_rows) or a chan[j] outside [0, C)
+ * is never dereferenced: bit 0 (index) or bit 1 (channel) of *err (device int32, never cleared here) is set and nothing is
+ * written for that row.                                                                                              */
+int tl_gather_rows(const void* const* src, void* const* dst, const int64_t* src_rows, const int64_t* C,
+                   const int64_t* inner_bytes, const int32_t* const* chan, const int64_t* n_chan, int n_seg,
+                   const int64_t* idx, int64_t n_idx, int32_t* err, void* stream);
 int tl_nadam_multi_dev(const tl_nadam_entry* entries_dev, int count, int64_t total_blocks, const float* scalars_dev,
                        float beta1, float beta2, float eps, float weight_decay, float grad_scale, void* stream);
 /* the same update for a parameter (rows x cols) whose gradient is low rank, g = fa^T . fb with
