@@ -1,5 +1,6 @@
-"""The data-parallel side of the three classifier train engines (``_simple_classifier_engine``, ``_cnn_classifier_train_engine``,
-``_cnnrnn_classifier_train_engine``): one process per GPU, every rank is handed the GLOBAL batch and works on its rows.
+"""The data-parallel side of the three classifier train engines (``_classifier_train_engine.ClassifierTrainEngine`` and its
+subclasses): one process per GPU, every rank is handed the GLOBAL batch and works on its rows.  The free-standing parts live
+here, the per-step side (``_take`` / ``_exchange`` / ``epoch_stats``) in the base class.
 
   shard      ``shard_plan``: the rules of ``SynthesisTrainer._shard`` - contiguous ``parallel.shard_rows``; a ragged batch gives
              unequal shards, each weighted by its share of the rows; a batch with fewer rows than ranks leaves some ranks
@@ -11,11 +12,12 @@
              order, and every rank runs the same ``tl_nadam_lowrank`` on the same B_global rows;
   statistics ``reduce_stats_words``: one small collective per epoch over the process group on the raw int64 words.
 
-Nothing here runs without an active process group (``parallel.active()``): the single-process engines keep their launches."""
+No collective here runs without an active process group (``parallel.active()``); a single-process step is the plan
+``ShardPlan(B, 0, B, 1.0)`` on the same launches."""
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Tuple
+from typing import List
 
 import torch
 import torch.distributed as dist
@@ -112,99 +114,3 @@ class RowGather:
             dist.all_gather_into_tensor(ho, mine.to(dev))
             out.copy_(ho)
         return out if self.identity else out.index_select(0, self.pick)
-
-
-class ClassifierDP:
-    """Mixin of the classifier train engines.  ``_dp_setup`` once at construction (after ``self.model`` / ``self.stats`` /
-    ``self.device`` exist); ``_take`` at the top of every public step."""
-
-    dp = False
-
-    def _dp_setup(self) -> None:
-        self.dp = parallel.active()
-        self.rank, self.world = parallel.world()
-        self._plan: Optional[ShardPlan] = None
-        self._seed_fix = 0
-        self._arena: Optional[parallel.FlatGrads] = None
-        self._gathers: Dict[int, RowGather] = {}
-        self.exchange_events: Optional[list] = None      # a list: (start, end) HIP event pairs around every exchange
-        if not self.dp:
-            return
-        parallel.broadcast_parameters_(self.model)
-        if self.world > 1:
-            # the dropout seed of a step is rank 0's: its torch seed and its count of draws so far, broadcast once
-            box = [(int(torch.initial_seed()), int(getattr(self.model, "_drop_calls", 0)))]
-            dist.broadcast_object_list(box, src=0)
-            seed0, calls0 = box[0]
-            self._seed_fix = ((seed0 - int(torch.initial_seed())) * 0x9E3779B1) & 0xFFFFFFFFFFFFFFFF
-            if hasattr(self.model, "_drop_calls"):
-                self.model._drop_calls = calls0
-        self._void = torch.zeros_like(self.stats)        # where a weight-0 rank's duplicated row is counted
-
-    # ------------------------------------------------------------------ per step
-    def _take(self, x: torch.Tensor, y: Optional[torch.Tensor] = None):
-        """This rank's rows of the global batch (the whole batch without a process group) and the plan of the step."""
-        B = x.shape[0]
-        if not self.dp:
-            self._plan = ShardPlan(B, 0, B, 1.0)
-            return x, y
-        plan = self._plan = shard_plan(B, self.rank, self.world)
-        x = x[plan.slice]
-        if x.data_ptr() % 16:
-            x = x.clone()
-        return x, (None if y is None else y[plan.slice])
-
-    def _grad_scale(self) -> float:
-        return 1.0 / self._plan.B if self._plan.live else 0.0
-
-    def _stats_base(self) -> int:
-        return (self.stats if self._plan.live else self._void).data_ptr()
-
-    def _step_seed(self) -> int:
-        return (int(self.model._next_seed()) + self._seed_fix) & 0xFFFFFFFFFFFFFFFF
-
-    def _make_arena(self, shapes: Dict[str, torch.Size], order=()) -> Dict[str, torch.Tensor]:
-        """Dense gradient buffers as views of one flat arena (16-byte aligned: the optimiser's pointer table takes them)."""
-        self._arena = parallel.FlatGrads(shapes, list(order), self.device)
-        return self._arena.views
-
-    def _gather(self, t: torch.Tensor) -> torch.Tensor:
-        plan = self._plan
-        g = self._gathers.get(plan.B)
-        if g is None:
-            if len(self._gathers) > 4:
-                self._gathers.clear()
-            g = self._gathers[plan.B] = RowGather(plan.B, self.world, self.device)
-        return g(t, plan.rows_sent)
-
-    def _exchange(self, extra=(), lowrank: Optional[Dict[object, Tuple[torch.Tensor, torch.Tensor]]] = None):
-        """Sum the arena (and ``extra``: dense buffers allocated on demand) over the ranks - one bucketed all-reduce - and
-        gather the low-rank factor rows in global row order.  Returns the gathered ``lowrank``."""
-        ev = None
-        if self.exchange_events is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        parallel.allreduce_bucketed([self._arena.flat] + list(extra))
-        out = {k: (self._gather(fa), self._gather(fb)) for k, (fa, fb) in (lowrank or {}).items()}
-        if ev is not None:
-            ev[1].record()
-            self.exchange_events.append(ev)
-        return out
-
-    def _gather_pred(self, pred: torch.Tensor) -> torch.Tensor:
-        return self._gather(pred.view(-1, 1)).view(-1)
-
-    # ------------------------------------------------------------------ per epoch
-    def epoch_stats(self):
-        """(loss sum, samples counted, confusion matrix (N, N) int64 on the host) since the last call - ONE device-to-host
-        read - and zero them.  Under a process group the words of all ranks are summed first (one small collective), so every
-        rank returns the same values.  Raises ``ValueError`` if a label was outside [0, n_classes)."""
-        if self.dp:
-            host = reduce_stats_words(self.stats)
-            self._void.zero_()
-        else:
-            host = self.stats.cpu()
-        self.stats.zero_()
-        if int(host[2]) != 0:
-            raise ValueError(f"labels must lie in [0, {self.N}) for a model with {self.N} classes")
-        return float(host[0:1].view(torch.float64)[0]), int(host[1]), host[3:].reshape(self.N, self.N).clone()

@@ -5,7 +5,7 @@ with two decay groups, a confusion matrix per epoch).
 One train step of a batch (B, C, T):
   trunk     the six conv stages on ``ConvStack`` - the kernels, the layout and the three passes per stage of the synthesis
             model's ECoG block (F(6,3) / F(4,3) V form / direct MFMA by ``TONAL_KERNELS`` wino), with the arg-max and sign
-            planes (or V) the backward needs; ``tl_dropout_scale`` on the last pooled feature map in train mode;
+            planes (or V) the backward needs; ``tl_dropout_scale_at`` on the last pooled feature map in train mode;
   fc1       the feature map is gathered into torch's flatten order (B, K) by ``tl_permute_reduce`` and the NT GEMM runs on
             ``classifier[1].weight`` WHERE IT LIES (1.2 GB at 128 x 400: a re-packed copy is right for frozen weights only),
             split-K, bias and LeakyReLU behind it; the activations a1 are kept;
@@ -13,33 +13,28 @@ One train step of a batch (B, C, T):
             gradient, loss sum / count / confusion matrix ADDED to device words read once per epoch;
   head      ``tl_head_bwd`` (LeakyReLU' off the stored a1) gives da1, db1 (and dW2 when dense); dfeat = da1 . W1 is ONE read of
             W1 by the TN GEMM (A = da1^T); it is permuted back into the last stage's gradient rows (pad rows / columns zero) and
-            ``tl_dropout_scale`` with the forward's seed is dropout's backward;
+            ``tl_dropout_scale_at`` with the forward's seed is dropout's backward;
   trunk     per stage, last to first, ``stage_wgrad`` then ``stage_dgrad``; then the first stage's weight gradient;
   update    one ``FusedNAdam``; at B <= ``FusedNAdam.LOWRANK_MAX`` the two Linear weights go as rank-B factors (fc1's 1.2 GB
             gradient is never written), above that dW1 comes from the TN GEMM and dW2 from ``tl_head_bwd``.
 
 Under a process group (``parallel.active()``) every public step takes the GLOBAL batch and works on this rank's rows
-(``_classifier_dp``): the dropout mask is indexed by the element's position in the global batch (``tl_dropout_scale_at``, same
+(``_classifier_train_engine``, ``_classifier_dp``): the dropout mask is indexed by the element's position in the global batch
+(``tl_dropout_scale_at`` - without a process group the shard starts at row 0 and the mask is ``tl_dropout_scale``'s, bit for bit; same
 masks for 1 or N ranks), ``grad_scale`` is 1 / B_global, the conv and bias gradients are views of one arena summed by one bucketed
 all-reduce, and at B_global <= ``LOWRANK_MAX`` the two Linear weights travel as the gathered factor rows (da1, flat) and
-(dz, a1) - fc1's gradient is never reduced and never written.  Without one nothing changes.
+(dz, a1) - fc1's gradient is never reduced and never written.
 
 No host read happens in ``train_batch`` / ``eval_batch``.  There is no CPU fallback and no fallback to autograd."""
 from __future__ import annotations
 
-from typing import Dict, Optional, Tuple
-
 import torch
 import torch.nn as nn
 
-from . import _lib
-from ._classifier_dp import ClassifierDP
+from ._classifier_train_engine import SUPPORTED, ClassifierTrainEngine, check_common, refuse
 from ._conv_stack import ConvStack
 from ._launch import r4
-from ._lib import EPI_LRELU, EPI_MASK, EPI_STORE, LOAD_DIRECT, check, ptr
-from ._simple_classifier_engine import SUPPORTED, SimpleClassifierEngine
-from .models.utils import split_decay_groups
-from .optim import FusedNAdam
+from ._lib import EPI_LRELU, EPI_MASK, EPI_STORE, LOAD_DIRECT, ptr
 
 
 def _stage_defs(model):
@@ -57,24 +52,12 @@ def _stage_defs(model):
 def check_supported(model) -> None:
     """Raise ``ValueError`` (stating the supported set) unless ``model`` can be trained by ``CnnClassifierTrainEngine``."""
     from .models.deep_classifiers import CNNClassifier
-
-    def refuse(why: str):
-        raise ValueError(f"{why}: {SUPPORTED}")
     if not isinstance(model, CNNClassifier):
         refuse(f"model {type(model).__name__}")
-    for m in list(model.feature_extractor) + list(model.classifier):
-        if isinstance(m, nn.LeakyReLU) and m.negative_slope < 0:
-            refuse(f"negative_slope {m.negative_slope}")
-    if model.n_classes > 64:
-        refuse(f"n_classes {model.n_classes}")
-    p_drop = float(model.feature_extractor[-1].p)
-    if not p_drop < 1.0:
-        refuse(f"dropout {p_drop}")
-    if model.classifier[1].out_features % 4 != 0:
-        refuse(f"hidden width {model.classifier[1].out_features}")
-    for p in model.parameters():
-        if not p.is_cuda or p.dtype != torch.float32:
-            refuse(f"parameters on '{p.device}' in {p.dtype}")
+    hidden = model.classifier[1].out_features
+    check_common(model, [m.negative_slope for m in list(model.feature_extractor) + list(model.classifier)
+                         if isinstance(m, nn.LeakyReLU)], float(model.feature_extractor[-1].p),
+                 also=[(hidden % 4 != 0, f"hidden width {hidden}")])
 
 
 class _Head:
@@ -92,7 +75,9 @@ class _Head:
         self.pred = torch.empty(B, dtype=torch.int64, device=dev)
 
 
-class CnnClassifierTrainEngine(ClassifierDP, ConvStack):
+class CnnClassifierTrainEngine(ClassifierTrainEngine, ConvStack):
+    head_bias = "classifier.3.bias"
+
     def __init__(self, model, learning_rate: float = 0.0005, weight_decay: float = 0.0):
         check_supported(model)
         stage_defs, conv_at = _stage_defs(model)
@@ -102,11 +87,9 @@ class CnnClassifierTrainEngine(ClassifierDP, ConvStack):
         if len(flat_widths) > 1:
             raise ValueError(f"un-pooled conv stages of different widths {sorted(flat_widths)}: {SUPPORTED}")
         super().__init__(n_electrodes, n_timepoints, stage_defs, slope, flat_widths.pop() if flat_widths else stage_defs[-1][0])
-        self.model = model
         self.STAGE_NAMES = {st.idx: f"feature_extractor.{conv_at[st.idx - 1]}" for st in self.stages}
         self.name1 = f"feature_extractor.{conv_at[0]}"
         self.fc1, self.fc2 = model.classifier[1], model.classifier[3]
-        self.N = int(model.n_classes)
         self.hidden = int(self.fc1.out_features)
         last = self.stages[-1]
         self.c_last, self.tp_last = last.cout, last.tp_out
@@ -115,26 +98,11 @@ class CnnClassifierTrainEngine(ClassifierDP, ConvStack):
         if self.K != self.fc1.in_features:
             raise ValueError(f"classifier[1] takes {self.fc1.in_features} features, the conv stack gives {self.K}")
         self.p_drop = float(model.feature_extractor[-1].p)
-        self.device = self.fc1.weight.device
-        self.params: Dict[str, nn.Parameter] = dict(model.named_parameters())
-        decay, no_decay = split_decay_groups(model.named_parameters())
-        self.optimizer = FusedNAdam([{"params": decay, "weight_decay": float(weight_decay)},
-                                     {"params": no_decay, "weight_decay": 0.0}], lr=float(learning_rate), stored_beta2=True)
-        self.force_dense = False           # tests / the benchmark: dense dW1 / dW2 at a batch the low-rank update would take
-        # loss sum (the bits of a double), sample count, label-range flag, confusion matrix: one buffer, one read per epoch
-        self.stats = torch.zeros(3 + self.N * self.N, dtype=torch.int64, device=self.device)
-        # dense gradient buffers (kept: the optimiser caches its pointer table); the two Linear weights get one on demand
-        lin_w = (self.fc1.weight, self.fc2.weight)
-        self._dp_setup()
-        shapes = {k: p.shape for k, p in self.params.items() if all(p is not w for w in lin_w)}
-        if self.dp:            # ... as views of one arena, in the order the backward finishes them: one all-reduce
-            self.grads: Dict[str, torch.Tensor] = dict(self._make_arena(shapes, list(shapes)[::-1]))
-        else:
-            self.grads = {k: torch.zeros_like(self.params[k]) for k in shapes}
-        self._heads: Dict[int, _Head] = {}
+        self.input_shape = (self.C, self.T)
+        # the two Linear weights get a dense buffer on demand; the backward finishes the others last layer first
+        self._setup_training(model, learning_rate, weight_decay, lowrank_names=("classifier.1.weight", "classifier.3.weight"),
+                             arena_order=[k for k, _ in model.named_parameters()][::-1])
         self._eye = None
-        self.last_seed = 0                 # dropout seed of the last forward pass (0: no dropout applied)
-        self.last_lowrank: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
 
     # ------------------------------------------------------------------ stack shape
     def _v43(self, st) -> bool:
@@ -143,40 +111,20 @@ class CnnClassifierTrainEngine(ClassifierDP, ConvStack):
         return super()._v43(st) and (st.idx == 2 or self.stages[st.idx - 3].pool)
 
     # ------------------------------------------------------------------ plumbing
-    def _head(self, B: int) -> _Head:
-        ws = self._heads.get(B)
-        if ws is None:
-            if len(self._heads) > 2:
-                self._heads.clear()
-            ws = self._heads[B] = _Head(B, self.N, self.hidden, self.K, self.device)
-        return ws
+    def _make_workspace(self, B: int, dev) -> _Head:
+        return _Head(B, self.N, self.hidden, self.K, dev)
 
-    def _input(self, x: torch.Tensor) -> torch.Tensor:
-        _lib.require_gpu(x, "CnnClassifierTrainEngine")
-        if x.ndim != 3 or x.shape[1] != self.C or x.shape[2] != self.T:
-            raise ValueError(f"expected input (B, {self.C}, {self.T}), got {tuple(x.shape)}")
-        if x.shape[0] < 1:
-            raise ValueError("empty batch")
-        return x.float().contiguous()
-
-    def _labels(self, y: torch.Tensor, B: int) -> torch.Tensor:
-        _lib.require_gpu(y, "CnnClassifierTrainEngine")
-        if y.shape != (B,):
-            raise ValueError(f"expected {B} labels, got {tuple(y.shape)}")
-        return y.long().contiguous()
-
-    def _dense(self, name: str) -> torch.Tensor:
-        g = self.grads.get(name)
-        if g is None:
-            g = self.grads[name] = torch.empty_like(self.params[name])
-        return g
+    @property
+    def _heads(self):
+        """{B: the head buffers of batch ``B`` on the engine's device}: a read-only view of the workspace cache (the test
+        helpers read the kept fc1 activations ``_heads[B].a1`` of the last step)."""
+        return {B: ws for (B, dev), ws in self._workspaces.items() if dev == self.device}
 
     # ------------------------------------------------------------------ forward
     def _forward(self, x: torch.Tensor, dropout: bool) -> _Head:
         B = x.shape[0]
         self._alloc(B, x.device)
-        ws = self._head(B)
-        lib, st_ = self.lib, self._stream()
+        ws = self._workspace(B, x.device)
         prm = self.params
         self.generation += 1
         self.conv1_forward(x, prm[self.name1 + ".weight"].data, prm[self.name1 + ".bias"].data)
@@ -186,7 +134,7 @@ class CnnClassifierTrainEngine(ClassifierDP, ConvStack):
         feat = self.P[self.stages[-1].idx]                       # [S * tp_last][ld_last]
         self.last_seed = 0
         if dropout and self.p_drop > 0.0:
-            self.last_seed = self._step_seed() if self.dp else int(self.model._next_seed())
+            self.last_seed = self._step_seed()
             self._drop(feat)
         # torch's flatten of (B, ch, t, c): column ch * lat * C + t * C + c  <-  row (b * C + c) * tp + t, column ch
         lat, Cn, tp, ld = self.lat, self.C, self.tp_last, self.ld_last
@@ -199,45 +147,30 @@ class CnnClassifierTrainEngine(ClassifierDP, ConvStack):
         if sk > 1:
             slab = torch.empty(sk, B, H, dtype=torch.float32, device=x.device)
             self._nt(tag="fc1_fwd", out=ptr(slab), epilogue=EPI_STORE, splitk=sk, slab_stride=B * H, **kw)
-            check(lib.tl_splitk_bias_lrelu(ptr(slab), ptr(b1), ptr(ws.a1), sk, B * H, H, self.slope, st_),
-                  "tl_splitk_bias_lrelu")
+            self._call(None, "tl_splitk_bias_lrelu", ptr(slab), ptr(b1), ptr(ws.a1), sk, B * H, H, self.slope)
         else:
             self._nt(tag="fc1_fwd", bias=ptr(b1), out=ptr(ws.a1), epilogue=EPI_LRELU, slope=self.slope, **kw)
-        check(lib.tl_linear_rows(ptr(ws.a1), ptr(self.fc2.weight.data), ptr(self.fc2.bias.data), ptr(ws.scores), B, H, self.N,
-                                 H, 1, st_), "tl_linear_rows")
+        self._call(None, "tl_linear_rows", ptr(ws.a1), ptr(self.fc2.weight.data), ptr(self.fc2.bias.data), ptr(ws.scores), B, H,
+                   self.N, H, 1)
         return ws
 
     def _drop(self, rows: torch.Tensor) -> None:
         """Dropout (forward and backward alike) on the last stage's rows [(b * C + c) * tp + t][ld] with ``last_seed``; a shard
-        that starts at global row b0 draws its rows of the single-process mask."""
-        if self.dp:
-            index0 = self._plan.row0 * self.C * self.tp_last * self.ld_last
-            check(self.lib.tl_dropout_scale_at(ptr(rows), rows.numel(), self.p_drop, self.last_seed, index0, self._stream()),
-                  "tl_dropout_scale_at")
-        else:
-            check(self.lib.tl_dropout_scale(ptr(rows), rows.numel(), self.p_drop, self.last_seed, self._stream()),
-                  "tl_dropout_scale")
-
-    def _ce(self, ws: _Head, y: Optional[torch.Tensor], B: int, grad: bool, pred: bool) -> None:
-        base = self._stats_base()
-        check(self.lib.tl_ce_scores_loss(ptr(ws.scores), ptr(y), ptr(ws.dz) if grad else None,
-                                         ptr(self.grads["classifier.3.bias"]) if grad else None, ptr(ws.pred) if pred else None,
-                                         base, base + 8, base + 24, base + 16, B, self.N, self.N, ws.dz.shape[1],
-                                         self._grad_scale(), self._stream()), "tl_ce_scores_loss")
+        that starts at global row b0 draws its rows of the single-process mask (b0 = 0: ``tl_dropout_scale``'s, bit for bit)."""
+        index0 = self._plan.row0 * self.C * self.tp_last * self.ld_last
+        self._call(None, "tl_dropout_scale_at", ptr(rows), rows.numel(), self.p_drop, self.last_seed, index0)
 
     # ------------------------------------------------------------------ backward
     def _backward(self, ws: _Head, B: int, dense: bool) -> None:
         """Every gradient of the step from ``ws.dz``: dense ones into ``self.grads``, the two Linear weights as factors in
         ``self.last_lowrank`` unless ``dense``."""
         self._alloc_bwd()
-        lib, st_ = self.lib, self._stream()
         prm = self.params
         H, K, N = self.hidden, self.K, self.N
         f32 = dict(dtype=torch.float32, device=self._dev)
         w1, w2 = self.fc1.weight.data, self.fc2.weight.data
-        check(lib.tl_head_bwd(ptr(ws.dz), ptr(ws.a1), ptr(w2), ptr(ws.da1), ptr(self.grads["classifier.1.bias"]),
-                              ptr(self._dense("classifier.3.weight")) if dense else None, B, H, N, ws.dz.shape[1], 2, self.slope,
-                              st_), "tl_head_bwd")
+        self._call(None, "tl_head_bwd", ptr(ws.dz), ptr(ws.a1), ptr(w2), ptr(ws.da1), ptr(self.grads["classifier.1.bias"]),
+                   ptr(self._dense("classifier.3.weight")) if dense else None, B, H, N, ws.dz.shape[1], 2, self.slope)
         self.last_lowrank = {}
         if dense:
             self._tn(tag="fc1_wgrad", A=ptr(ws.da1), B=ptr(ws.flat), slab=ptr(self._dense("classifier.1.weight")), Krows=B,
@@ -247,13 +180,7 @@ class CnnClassifierTrainEngine(ClassifierDP, ConvStack):
         # dfeat (B, K) = da1 . W1: the TN GEMM reduces over the 1024 rows of W1 as stored, A = da1^T (pad columns zero)
         ldt = ws.ldt
         self._permute(ws.da1, ws.da1t, (1, 1, H, ldt), (0, 0, 1, H), (1, 1, H, B))
-        if ldt <= 32:                # skinny streaming kernel: 512-column tiles, 16-deep K stages
-            sk = self._splitk((K + 511) // 512, (H + 15) // 16, 1024)
-        else:
-            sk = self._splitk(((ldt + 127) // 128) * ((K + 127) // 128), (H + 31) // 32, 1024)
-        slab = torch.empty(sk, ldt, K, **f32)
-        self._tn(tag="fc1_dgrad", A=ptr(ws.da1t), B=ptr(w1), slab=ptr(slab), Krows=H, A_rows=H, B_rows=H, Mdim=ldt, Ndim=K,
-                 lda=ldt, ldb=K, ldc=K, loader=LOAD_DIRECT, splitk=sk, slab_stride=ldt * K)
+        slab, sk = self._tn_stored("fc1_dgrad", ws.da1t, ldt, w1, H, K)
         # ... summed over the splits and scattered into the last stage's gradient rows [(b * C + c) * tp + t][ch]; the source
         # limits leave the pad rows (t >= lat) and pad columns zero
         last = self.stages[-1]
@@ -281,74 +208,9 @@ class CnnClassifierTrainEngine(ClassifierDP, ConvStack):
             S = self.S
             nblk = int(min(2048, S))
             part = torch.empty(nblk, (self.k1 + 1) * self.c1, **f32)
-            check(lib.tl_conv1_wgrad(ptr(self._x), ptr(self.G[1]), ptr(self.bits[1]), ptr(part), nblk, S, self.T, self.k1,
-                                     self.c1, self.tp1, self.tout1, st_), "tl_conv1_wgrad")
+            self._call(None, "tl_conv1_wgrad", ptr(self._x), ptr(self.G[1]), ptr(self.bits[1]), ptr(part), nblk, S, self.T,
+                       self.k1, self.c1, self.tp1, self.tout1)
         self._reduce_c1_partials(part, self.grads[self.name1 + ".weight"], self.grads[self.name1 + ".bias"])
 
-    def _step(self, x: torch.Tensor, y: torch.Tensor, update: bool) -> _Head:
-        x = self._input(x)
-        y = self._labels(y, x.shape[0])
-        dense = self.force_dense or x.shape[0] > FusedNAdam.LOWRANK_MAX      # (from the GLOBAL batch: the same on every rank)
-        x, y = self._take(x, y)
-        B = x.shape[0]
-        ws = self._forward(x, dropout=self.model.training)
-        self._ce(ws, y, B, grad=True, pred=False)
-        self._backward(ws, B, dense)
-        if self.dp:
-            N = self.N
-            sent = {k: (ws.dz if k == "classifier.3.weight" else fa, fb) for k, (fa, fb) in self.last_lowrank.items()}
-            got = self._exchange(extra=[self.grads[k] for k in ("classifier.1.weight", "classifier.3.weight")] if dense else (),
-                                 lowrank=sent)
-            self.last_lowrank = {k: (fa[:, :N] if k == "classifier.3.weight" else fa, fb) for k, (fa, fb) in got.items()}
-        if update:
-            lin = ("classifier.1.weight", "classifier.3.weight")
-            grads = {self.params[k]: g for k, g in self.grads.items() if dense or k not in lin}
-            lowrank = {self.params[k]: f for k, f in self.last_lowrank.items()}
-            self.optimizer.step(grads=grads, lowrank=lowrank or None)
-            # FusedNAdam writes through data_ptr: the inference engine keys its packed weights on ``_version``, which did not move
-            hip = getattr(self.model, "_hip", None)
-            if hip is not None:
-                hip._packed.clear()
-        return ws
-
-    # ------------------------------------------------------------------ the public steps
-    @torch.no_grad()
-    def train_batch(self, x: torch.Tensor, y: torch.Tensor) -> None:
-        """Forward, loss, backward and update for one batch; everything stays on the stream (no host read)."""
-        self._step(x, y, update=True)
-
-    @torch.no_grad()
-    def backward_only(self, x: torch.Tensor, y: torch.Tensor) -> Dict[str, object]:
-        """Debug hook: forward, loss and backward of one batch WITHOUT the update.  {parameter name: gradient}, a Linear weight
-        on the low-rank path as its factors ``(fa (B, rows), fb (B, cols))`` with gradient ``fa^T . fb``.  The tensors are the
-        engine's buffers: valid until the next step.  The batch is counted in the epoch statistics like any other."""
-        self._step(x, y, update=False)
-        return self.step_gradients()
-
-    def step_gradients(self) -> Dict[str, object]:
-        """The gradients of the last ``train_batch`` / ``backward_only`` (see there)."""
-        out: Dict[str, object] = {k: g for k, g in self.grads.items() if k not in self.last_lowrank}
-        out.update(self.last_lowrank)
-        return out
-
-    @torch.no_grad()
-    def eval_batch(self, x: torch.Tensor, y: torch.Tensor) -> None:
-        """Forward (no dropout) and loss statistics of one batch (no gradients, no update)."""
-        x = self._input(x)
-        x, y = self._take(x, self._labels(y, x.shape[0]))
-        ws = self._forward(x, dropout=False)
-        self._ce(ws, y, x.shape[0], grad=False, pred=False)
-
-    @torch.no_grad()
-    def predict_batch(self, x: torch.Tensor) -> torch.Tensor:
-        """Arg-max class of every row (int64, on the device)."""
-        x, _ = self._take(self._input(x))
-        ws = self._forward(x, dropout=False)
-        self._ce(ws, None, x.shape[0], grad=False, pred=True)
-        return self._gather_pred(ws.pred) if self.dp else ws.pred.clone()
-
-    def scores(self, B: int) -> torch.Tensor:
-        """The float32 sigmoid scores (B, n_classes) of the last forward pass at batch ``B``."""
-        return self._heads[B].scores
-
-    epoch_stats = ClassifierDP.epoch_stats      # (the same statistics buffer: one read per epoch, zeroed afterwards)
+    def _lowrank_wire(self, ws: _Head):
+        return {"classifier.3.weight": ws.dz}                # dz travels at its stored width (the factor is its first N columns)

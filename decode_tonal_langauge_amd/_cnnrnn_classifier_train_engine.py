@@ -7,22 +7,23 @@ One train step of a batch (B, C, T); t1 = (T - 6) // 2, ta = t1 - 6, tb = ta - 6
             hs / cs / the activated gates of every step, rows time-major (t * B + b); h1 = hs[T - 1];
   trunk     two ``tl_conv1_fwd`` launches (7 taps) write one branch-major row matrix - the B * w1 sequences cut from h1, then
             the B * C electrode sequences - the two 7-tap stages run in the form ``TONAL_KERNELS conv7=`` selects (``wino63``:
-            ``tl_conv7_wino63v_nt``, or ``direct``), ``tl_pool3_fwd`` pools (3,1), applies the dropout mask and writes lstm2's
+            ``tl_conv7_wino63v_nt``, or ``direct``), ``tl_pool3_fwd_shard`` pools (3,1), applies the dropout mask and writes lstm2's
             input matrix in the reference's raw-view order, rows time-major;
   lstm2     as lstm1 over the t' steps; ``tl_linear_rows(act=1)`` on its last hidden state gives the sigmoid scores;
   loss      ``tl_ce_scores_loss``: dz with respect to the pre-sigmoid output, the output bias gradient, loss sum / count /
             confusion matrix ADDED to device words read once per epoch;
   backward  ``tl_head_bwd`` -> dh2; ``tl_lstm_bptt_seq`` (one fused launch per step) -> dgates and their transposed copy;
-            dW_hh, dW_ih, db and dX2 = dgates . W_ih (ONE read of the weight, A = dgates^T) on the TN GEMM; ``tl_pool3_bwd``;
+            dW_hh, dW_ih, db and dX2 = dgates . W_ih (ONE read of the weight, A = dgates^T) on the TN GEMM; ``tl_pool3_bwd_shard``;
             ``ConvStack.stage_wgrad`` / ``stage_dgrad`` for the two 7-tap stages (direct kernels, J = 7); ``tl_conv1_wgrad`` per
             branch; ``tl_conv1_dgrad`` on the LSTM branch -> dh1; lstm1's BPTT and GEMMs;
   update    one ``FusedNAdam`` over dense gradients (an LSTM weight gradient has rank T * B: no low-rank form).
 
 Under a process group (``parallel.active()``) every public step takes the GLOBAL batch and works on this rank's rows
-(``_classifier_dp``): the dropout mask of the (3,1) pool is indexed by the sequence's number in the global batch's branch-major
-order (``tl_pool3_fwd_shard`` / ``tl_pool3_bwd_shard``, same masks for 1 or N ranks), ``grad_scale`` is 1 / B_global, and all
+(``_classifier_train_engine``, ``_classifier_dp``): the dropout mask of the (3,1) pool is indexed by the sequence's number in the
+global batch's branch-major order (``tl_pool3_fwd_shard`` / ``tl_pool3_bwd_shard`` - without a process group the shard is the whole
+batch and they are ``tl_pool3_fwd`` / ``tl_pool3_bwd``, bit for bit; same masks for 1 or N ranks), ``grad_scale`` is 1 / B_global, and all
 gradients - views of one arena - are summed by one bucketed all-reduce (an LSTM weight gradient has no low-rank form, and
-``output.weight`` is 4 KB).  Without one nothing changes.
+``output.weight`` is 4 KB).
 
 No host read happens in ``train_batch`` / ``eval_batch``.  There is no CPU fallback and no fallback to autograd."""
 from __future__ import annotations
@@ -32,14 +33,11 @@ from typing import Dict, Optional
 import torch
 import torch.nn as nn
 
-from . import _kernels, _lib
-from ._classifier_dp import ClassifierDP
+from . import _kernels
+from ._classifier_train_engine import SUPPORTED, ClassifierTrainEngine, check_common, refuse
 from ._conv_stack import ConvStack
 from ._launch import r4
 from ._lib import EPI_LRELU, EPI_STORE, LOAD_DIRECT, LOAD_V, check, ptr
-from ._simple_classifier_engine import SUPPORTED, SimpleClassifierEngine
-from .models.utils import split_decay_groups
-from .optim import FusedNAdam
 
 K7 = 7            # taps of every convolution of the model
 C_FIRST, C_A, C_B = 1024, 512, 256
@@ -64,24 +62,11 @@ def lstm2_input_index(b: int, ch: int, s: int, w: int, B: int, tq: int, W: int, 
 def check_supported(model) -> None:
     """Raise ``ValueError`` (stating the supported set) unless ``model`` can be trained by ``CnnRnnClassifierTrainEngine``."""
     from .models.deep_classifiers import CNNRNNClassifier
-
-    def refuse(why: str):
-        raise ValueError(f"{why}: {SUPPORTED}")
     if not isinstance(model, CNNRNNClassifier):
         refuse(f"model {type(model).__name__}")
-    for m in model.modules():
-        if isinstance(m, nn.LeakyReLU) and m.negative_slope < 0:
-            refuse(f"negative_slope {m.negative_slope}")
-    if model.n_classes > 64:
-        refuse(f"n_classes {model.n_classes}")
-    p_drop = float(model.conv_block3[5].p)
-    if not p_drop < 1.0:
-        refuse(f"dropout {p_drop}")
-    if geometry(model.input_channels, model.input_length, model.lstm1.hidden_size)["tq"] < 1:
-        refuse(f"input_length {model.input_length} (no row is left behind the (3,1) pool)")
-    for p in model.parameters():
-        if not p.is_cuda or p.dtype != torch.float32:
-            refuse(f"parameters on '{p.device}' in {p.dtype}")
+    tq = geometry(model.input_channels, model.input_length, model.lstm1.hidden_size)["tq"]
+    check_common(model, [m.negative_slope for m in model.modules() if isinstance(m, nn.LeakyReLU)], float(model.conv_block3[5].p),
+                 also=[(tq < 1, f"input_length {model.input_length} (no row is left behind the (3,1) pool)")])
 
 
 class _Lstm:
@@ -131,8 +116,10 @@ class _Ws:
         self.pred = torch.empty(B, dtype=torch.int64, device=dev)
 
 
-class CnnRnnClassifierTrainEngine(ClassifierDP, ConvStack):
+class CnnRnnClassifierTrainEngine(ClassifierTrainEngine, ConvStack):
     F63_CAPABLE = False        # (the 3-tap F(6,3) stack does not apply: every stage here has 7 taps)
+    UPDATE_TAG = "update"
+    head_bias = "output.bias"
 
     def __init__(self, model, learning_rate: float = 0.0005, weight_decay: float = 0.0):
         check_supported(model)
@@ -151,32 +138,19 @@ class CnnRnnClassifierTrainEngine(ClassifierDP, ConvStack):
         for st in self.stages:
             st.tp_in = st.tp_out = self.Tp
         self.fuse_c1 = False
-        self.model = model
         self.STAGE_NAMES = {2: "conv_block3.0", 3: "conv_block3.2"}
-        self.N = int(model.n_classes)
         self.p_drop = float(model.conv_block3[5].p)
-        self.device = model.output.weight.device
+        self.input_shape = (Cn, T)
         if model.lstm2.hidden_size % 8 != 0 or model.lstm2.input_size != C_B * self.W:
             raise ValueError(f"lstm2 ({model.lstm2.input_size} -> {model.lstm2.hidden_size}): {SUPPORTED}")
-        self.params: Dict[str, nn.Parameter] = dict(model.named_parameters())
-        decay, no_decay = split_decay_groups(model.named_parameters())
-        self.optimizer = FusedNAdam([{"params": decay, "weight_decay": float(weight_decay)},
-                                     {"params": no_decay, "weight_decay": 0.0}], lr=float(learning_rate), stored_beta2=True)
-        # loss sum (the bits of a double), sample count, label-range flag, confusion matrix: one buffer, one read per epoch
-        self.stats = torch.zeros(3 + self.N * self.N, dtype=torch.int64, device=self.device)
-        self._dp_setup()
-        if self.dp:            # views of one arena, in the order the backward finishes them: one all-reduce, no staging copy
-            self.grads: Dict[str, torch.Tensor] = dict(self._make_arena(
-                {k: p.shape for k, p in self.params.items()},
-                ["output.bias", "output.weight"] + [k for k in self.params if k.startswith("lstm2.")]
-                + [k for k in self.params if k.startswith("conv_block3.")][::-1]
-                + [k for k in self.params if k.startswith("conv_pool_block")] + [k for k in self.params if k.startswith("lstm1.")]))
-        else:
-            self.grads = {k: torch.zeros_like(p) for k, p in self.params.items()}
-        self._ws: Dict[int, _Ws] = {}
+        # every gradient is dense (an LSTM weight gradient has rank T * B); the order the backward finishes them in
+        names = [k for k, _ in model.named_parameters()]
+        self._setup_training(model, learning_rate, weight_decay, arena_order=(
+            ["output.bias", "output.weight"] + [k for k in names if k.startswith("lstm2.")]
+            + [k for k in names if k.startswith("conv_block3.")][::-1]
+            + [k for k in names if k.startswith("conv_pool_block")] + [k for k in names if k.startswith("lstm1.")]))
         self._updates = 0                  # optimiser steps taken: part of the key of every weight pack
         self._packs: Dict[str, tuple] = {}
-        self.last_seed = 0                 # dropout seed of the last forward pass (0: no dropout applied)
 
     # ------------------------------------------------------------------ buffers
     def _alloc_rows(self):
@@ -201,33 +175,8 @@ class CnnRnnClassifierTrainEngine(ClassifierDP, ConvStack):
         self.G = {1: z(rows, C_FIRST), 2: z(rows, C_A), 3: z(rows, C_B)}
         return True
 
-    def _work(self, B: int) -> _Ws:
-        ws = self._ws.get(B)
-        if ws is None or ws.scores.device != self._dev:
-            if len(self._ws) > 2:
-                self._ws.clear()
-            ws = self._ws[B] = _Ws(self, B, self._dev)
-        return ws
-
-    def _input(self, x: torch.Tensor) -> torch.Tensor:
-        _lib.require_gpu(x, "CnnRnnClassifierTrainEngine")
-        if x.ndim != 3 or x.shape[1] != self.Cn or x.shape[2] != self.T:
-            raise ValueError(f"expected input (B, {self.Cn}, {self.T}), got {tuple(x.shape)}")
-        if x.shape[0] < 1:
-            raise ValueError("empty batch")
-        return x.float().contiguous()
-
-    def _labels(self, y: torch.Tensor, B: int) -> torch.Tensor:
-        _lib.require_gpu(y, "CnnRnnClassifierTrainEngine")
-        if y.shape != (B,):
-            raise ValueError(f"expected {B} labels, got {tuple(y.shape)}")
-        return y.long().contiguous()
-
-    def _call(self, tag: str, name: str, *args) -> None:
-        ev = self._tick(tag)
-        check(getattr(self.lib, name)(*args, self._stream()), name)
-        if ev:
-            ev[1].record()
+    def _make_workspace(self, B: int, dev) -> _Ws:
+        return _Ws(self, B, dev)
 
     # ------------------------------------------------------------------ LSTM
     def _version(self, *names) -> tuple:
@@ -301,14 +250,8 @@ class CnnRnnClassifierTrainEngine(ClassifierDP, ConvStack):
             return
         # dx (rows, in) = dgates . W_ih: the TN GEMM reduces over the 4 H rows of the weight as stored, A = dgates^T (pad
         # columns zero) - one read of the weight, no transposed copy
-        w, ldt, K = self._w_ih(l), l.ldt, l.Kp
-        if ldt <= 32:                # skinny streaming kernel: 512-column tiles, 16-deep K stages
-            sk = self._splitk((K + 511) // 512, (H4 + 15) // 16, 1024)
-        else:
-            sk = self._splitk(((ldt + 127) // 128) * ((K + 127) // 128), (H4 + 31) // 32, 1024)
-        slab = torch.empty(sk, ldt, K, dtype=torch.float32, device=self._dev)
-        self._tn(tag=f"{l.name}_dx", A=ptr(l.dgT), B=ptr(w), slab=ptr(slab), Krows=H4, A_rows=H4, B_rows=H4, Mdim=ldt, Ndim=K,
-                 lda=ldt, ldb=K, ldc=K, loader=LOAD_DIRECT, splitk=sk, slab_stride=ldt * K)
+        ldt, K = l.ldt, l.Kp
+        slab, sk = self._tn_stored(f"{l.name}_dx", l.dgT, ldt, self._w_ih(l), H4, K)
         self._permute(slab, dx, (1, 1, rows, l.in_dim), (0, 0, K, 1), nz=sk, zs=ldt * K)
 
     # ------------------------------------------------------------------ the 7-tap stages, forward
@@ -361,7 +304,7 @@ class CnnRnnClassifierTrainEngine(ClassifierDP, ConvStack):
     def _forward(self, x: torch.Tensor, dropout: bool) -> _Ws:
         B = x.shape[0]
         self._alloc(B, x.device)
-        ws = self._work(B)
+        ws = self._workspace(B, x.device)
         prm = self.params
         self.generation += 1
         self._x = x
@@ -384,44 +327,27 @@ class CnnRnnClassifierTrainEngine(ClassifierDP, ConvStack):
         self._conv7("conv3b_fwd", self.P[2], "conv_block3.2", self.P[3], C_A, C_B, self.ta)
         self.last_seed = 0
         if dropout and self.p_drop > 0.0:
-            self.last_seed = self._step_seed() if self.dp else int(self.model._next_seed())
-        if self.dp:
-            self._call("pool3_fwd", "tl_pool3_fwd_shard", ptr(self.P[3]), ptr(ws.X2), B, w1, Cn, C_B, Tp, self.tq, C_B, 1, B,
-                       self.p_drop if self.last_seed else 0.0, self.last_seed, self._plan.row0, self._plan.B)
-        else:
-            self._call("pool3_fwd", "tl_pool3_fwd", ptr(self.P[3]), ptr(ws.X2), B, w1, Cn, C_B, Tp, self.tq, C_B, 1, B,
-                       self.p_drop if self.last_seed else 0.0, self.last_seed)
+            self.last_seed = self._step_seed()
+        self._call("pool3_fwd", "tl_pool3_fwd_shard", ptr(self.P[3]), ptr(ws.X2), B, w1, Cn, C_B, Tp, self.tq, C_B, 1, B,
+                   self.p_drop if self.last_seed else 0.0, self.last_seed, self._plan.row0, self._plan.B)
         self._lstm_forward(l2, ws.X2)
         out = self.model.output
-        check(self.lib.tl_linear_rows(ptr(l2.h_last()), ptr(out.weight.data), ptr(out.bias.data), ptr(ws.scores), B, l2.Hp,
-                                      self.N, l2.Hp, 1, self._stream()), "tl_linear_rows")
+        self._call(None, "tl_linear_rows", ptr(l2.h_last()), ptr(out.weight.data), ptr(out.bias.data), ptr(ws.scores), B, l2.Hp,
+                   self.N, l2.Hp, 1)
         return ws
 
-    def _ce(self, ws: _Ws, y: Optional[torch.Tensor], B: int, grad: bool, pred: bool) -> None:
-        base = self._stats_base()
-        check(self.lib.tl_ce_scores_loss(ptr(ws.scores), ptr(y), ptr(ws.dz) if grad else None,
-                                         ptr(self.grads["output.bias"]) if grad else None, ptr(ws.pred) if pred else None,
-                                         base, base + 8, base + 24, base + 16, B, self.N, self.N, ws.dz.shape[1],
-                                         self._grad_scale(), self._stream()), "tl_ce_scores_loss")
-
     # ------------------------------------------------------------------ backward
-    def _backward(self, ws: _Ws, B: int) -> None:
+    def _backward(self, ws: _Ws, B: int, dense: bool) -> None:
         """Every gradient of the step from ``ws.dz`` into ``self.grads``."""
         self._alloc_bwd()
         prm, g = self.params, self.grads
         l1, l2 = ws.l1, ws.l2
         Cn, T, w1, Tp = self.Cn, self.T, self.w1, self.Tp
-        check(self.lib.tl_head_bwd(ptr(ws.dz), ptr(l2.h_last()), ptr(self.model.output.weight.data), ptr(l2.dh_last), None,
-                                   ptr(g["output.weight"]), B, l2.Hp, self.N, ws.dz.shape[1], 0, self.slope, self._stream()),
-              "tl_head_bwd")
+        self._call(None, "tl_head_bwd", ptr(ws.dz), ptr(l2.h_last()), ptr(self.model.output.weight.data), ptr(l2.dh_last), None,
+                   ptr(g["output.weight"]), B, l2.Hp, self.N, ws.dz.shape[1], 0, self.slope)
         self._lstm_backward(l2, ws.X2, ws.dX2)
-        if self.dp:
-            self._call("pool3_bwd", "tl_pool3_bwd_shard", ptr(self.P[3]), ptr(ws.dX2), ptr(self.G[3]), B, w1, Cn, C_B, Tp, self.tq,
-                       C_B, C_B, 1, B, self.p_drop if self.last_seed else 0.0, self.last_seed, self.slope, self._plan.row0,
-                       self._plan.B)
-        else:
-            self._call("pool3_bwd", "tl_pool3_bwd", ptr(self.P[3]), ptr(ws.dX2), ptr(self.G[3]), B, w1, Cn, C_B, Tp, self.tq, C_B,
-                       C_B, 1, B, self.p_drop if self.last_seed else 0.0, self.last_seed, self.slope)
+        self._call("pool3_bwd", "tl_pool3_bwd_shard", ptr(self.P[3]), ptr(ws.dX2), ptr(self.G[3]), B, w1, Cn, C_B, Tp, self.tq, C_B,
+                   C_B, 1, B, self.p_drop if self.last_seed else 0.0, self.last_seed, self.slope, self._plan.row0, self._plan.B)
         for st in reversed(self.stages):
             name = self.STAGE_NAMES[st.idx]
             self.stage_wgrad(st, g[name + ".weight"], g[name + ".bias"])
@@ -442,68 +368,9 @@ class CnnRnnClassifierTrainEngine(ClassifierDP, ConvStack):
                    C_FIRST, Tp, self.t1, w1, l1.Hp, w1, 1)
         self._lstm_backward(l1, ws.x1, None)
 
-    def _refresh_inference_packs(self) -> None:
-        # FusedNAdam writes through data_ptr: the module's inference engines key their packed weights on ``_version``, which
-        # did not move
-        m = self.model
-        if getattr(m, "_hip", None) is not None:
-            m._hip._packed.clear()
-            m._hip_lstm1._packed = None
-            m._hip_lstm2._packed = None
-
-    def _step(self, x: torch.Tensor, y: torch.Tensor, update: bool) -> _Ws:
-        x = self._input(x)
-        x, y = self._take(x, self._labels(y, x.shape[0]))
-        B = x.shape[0]
-        ws = self._forward(x, dropout=self.model.training)
-        self._ce(ws, y, B, grad=True, pred=False)
-        self._backward(ws, B)
-        if self.dp:
-            self._exchange()
-        if update:
-            ev = self._tick("update")
-            self.optimizer.step(grads={self.params[k]: g for k, g in self.grads.items()})
-            if ev:
-                ev[1].record()
-            self._updates += 1
-            self._refresh_inference_packs()
-        return ws
-
-    # ------------------------------------------------------------------ the public steps
-    @torch.no_grad()
-    def train_batch(self, x: torch.Tensor, y: torch.Tensor) -> None:
-        """Forward, loss, backward and update for one batch; everything stays on the stream (no host read)."""
-        self._step(x, y, update=True)
-
-    @torch.no_grad()
-    def backward_only(self, x: torch.Tensor, y: torch.Tensor) -> Dict[str, torch.Tensor]:
-        """Debug hook: forward, loss and backward of one batch WITHOUT the update.  {parameter name: gradient}; the tensors are
-        the engine's buffers: valid until the next step.  The batch is counted in the epoch statistics like any other."""
-        self._step(x, y, update=False)
-        return self.step_gradients()
-
-    def step_gradients(self) -> Dict[str, torch.Tensor]:
-        """The gradients of the last ``train_batch`` / ``backward_only`` (all dense)."""
-        return dict(self.grads)
-
-    @torch.no_grad()
-    def eval_batch(self, x: torch.Tensor, y: torch.Tensor) -> None:
-        """Forward (no dropout) and loss statistics of one batch (no gradients, no update)."""
-        x = self._input(x)
-        x, y = self._take(x, self._labels(y, x.shape[0]))
-        ws = self._forward(x, dropout=False)
-        self._ce(ws, y, x.shape[0], grad=False, pred=False)
-
-    @torch.no_grad()
-    def predict_batch(self, x: torch.Tensor) -> torch.Tensor:
-        """Arg-max class of every row (int64, on the device)."""
-        x, _ = self._take(self._input(x))
-        ws = self._forward(x, dropout=False)
-        self._ce(ws, None, x.shape[0], grad=False, pred=True)
-        return self._gather_pred(ws.pred) if self.dp else ws.pred.clone()
-
-    def scores(self, B: int) -> torch.Tensor:
-        """The float32 sigmoid scores (B, n_classes) of the last forward pass at batch ``B``."""
-        return self._ws[B].scores
-
-    epoch_stats = ClassifierDP.epoch_stats      # (the same statistics buffer: one read per epoch, zeroed afterwards)
+    def _after_update(self) -> None:
+        self._updates += 1
+        super()._after_update()
+        if getattr(self.model, "_hip", None) is not None:    # (made together with ``_hip``: the two LSTM packs are stale too)
+            self.model._hip_lstm1._packed = None
+            self.model._hip_lstm2._packed = None

@@ -190,6 +190,18 @@ class ConvStack(LaunchTimers):
     def _splitk(tiles: int, ksteps: int, target: int = 2048) -> int:
         return int(max(1, min(ksteps, (target + tiles - 1) // tiles, 1024)))
 
+    def _tn_stored(self, tag, At, ldt, W, rows, K):
+        """A . W on a weight ``W`` (rows, K) as it lies - one read of it, no transposed copy: the TN GEMM reduces over the rows,
+        its A operand is ``At`` = A^T (rows, ldt), pad columns zero.  Returns the split-K slabs ``(sk, ldt, K)`` and ``sk``."""
+        if ldt <= 32:                # skinny streaming kernel: 512-column tiles, 16-deep K stages
+            sk = self._splitk((K + 511) // 512, (rows + 15) // 16, 1024)
+        else:
+            sk = self._splitk(((ldt + 127) // 128) * ((K + 127) // 128), (rows + 31) // 32, 1024)
+        slab = torch.empty(sk, ldt, K, dtype=torch.float32, device=self._dev)
+        self._tn(tag=tag, A=ptr(At), B=ptr(W), slab=ptr(slab), Krows=rows, A_rows=rows, B_rows=rows, Mdim=ldt, Ndim=K, lda=ldt,
+                 ldb=K, ldc=K, loader=LOAD_DIRECT, splitk=sk, slab_stride=ldt * K)
+        return slab, sk
+
     # ------------------------------------------------------------------ weight packing
     def _pack_conv(self, w, cin_ld, flip_for_dgrad):
         """torch (O, I, J, 1) -> forward pack [J][O][cin_ld] or dgrad pack [J'][I_ld][O_ld] (J flipped)."""

@@ -14,38 +14,26 @@ One train step of a batch (B, K):
             ``tl_head_bwd`` (head) or the TN GEMM (hidden layer) and applied by ``tl_nadam``.
 
 Under a process group (``parallel.active()``) every public step takes the GLOBAL batch and works on this rank's rows
-(``_classifier_dp``): ``grad_scale`` is 1 / B_global, the bias gradients (and dense weight gradients) are summed by one bucketed
+(``_classifier_train_engine``, ``_classifier_dp``): ``grad_scale`` is 1 / B_global, the bias gradients (and dense weight gradients) are summed by one bucketed
 all-reduce, and at B_global <= ``LOWRANK_MAX`` the weights travel as the gathered factor rows - every rank applies the same
-rank-B_global update.  Without one nothing changes.
+rank-B_global update.  Without one the step is the same launches on the whole batch.
 
 There is no CPU fallback and no fallback to autograd: a model outside the supported set is refused."""
 from __future__ import annotations
-
-from typing import Dict, Optional, Tuple
 
 import torch
 import torch.nn as nn
 
 from . import _lib
-from ._classifier_dp import ClassifierDP
+from ._classifier_train_engine import SUPPORTED  # noqa: F401  (re-exported: it was defined here)
+from ._classifier_train_engine import ClassifierTrainEngine, check_common, refuse
 from ._launch import launch_nt, launch_tn, r4
-from ._lib import EPI_LRELU, LOAD_DIRECT, check, ptr
-from .models.utils import split_decay_groups
-from .optim import FusedNAdam
-
-SUPPORTED = ("the fused classifier step supports LogisticRegressionClassifier and ShallowNNClassifier with fp32 parameters on "
-             "a CUDA device, input_dim % 4 == 0, hidden_dim % 4 == 0, n_classes <= 64 and a ReLU or LeakyReLU activation; "
-             "CNNClassifier (_cnn_classifier_train_engine) with fp32 parameters on a CUDA device, negative_slope >= 0, "
-             "n_classes <= 64 and dropout < 1; CNNRNNClassifier (_cnnrnn_classifier_train_engine) under the same conditions with "
-             "at least one row left behind its (3,1) pool")
+from ._lib import EPI_LRELU, LOAD_DIRECT, ptr
 
 
 def check_supported(model) -> None:
     """Raise ``ValueError`` (stating the supported set) unless ``model`` can be trained by ``SimpleClassifierEngine``."""
     from .models.simple_classifiers import LogisticRegressionClassifier, ShallowNNClassifier
-
-    def refuse(why: str):
-        raise ValueError(f"{why}: {SUPPORTED}")
     if isinstance(model, LogisticRegressionClassifier):
         layers = [model.linear]
     elif isinstance(model, ShallowNNClassifier):
@@ -58,14 +46,7 @@ def check_supported(model) -> None:
         refuse(f"model {type(model).__name__}")
     if model.input_dim % 4 != 0:
         refuse(f"input_dim {model.input_dim}")
-    if model.n_classes > 64:
-        refuse(f"n_classes {model.n_classes}")
-    for layer in layers:
-        if layer.bias is None:
-            refuse("a layer without bias")
-        for p in (layer.weight, layer.bias):
-            if not p.is_cuda or p.dtype != torch.float32:
-                refuse(f"parameters on '{p.device}' in {p.dtype}")
+    check_common(model, also=[(layer.bias is None, "a layer without bias") for layer in layers])
 
 
 class _Workspace:
@@ -73,6 +54,7 @@ class _Workspace:
 
     def __init__(self, B: int, N: int, H: int, dev):
         f32 = dict(dtype=torch.float32, device=dev)
+        self.x = None                                   # the input rows of the last forward pass
         self.logits = torch.empty(B, N, **f32)
         self.dlogits = torch.zeros(B, r4(N), **f32)
         self.pred = torch.empty(B, dtype=torch.int64, device=dev)
@@ -80,152 +62,72 @@ class _Workspace:
         self.dh = torch.empty(B, H, **f32) if H else None
 
 
-class SimpleClassifierEngine(ClassifierDP):
+class SimpleClassifierEngine(ClassifierTrainEngine):
+    CE = "tl_ce_loss"
+    CE_BUFFERS = ("logits", "dlogits")
+    INPUT_ERROR = "Expected input dimension {}, got {got}."
+
     def __init__(self, model, learning_rate: float = 0.0005, weight_decay: float = 0.0):
         check_supported(model)
         self.lib = _lib.load()
-        self.model = model
-        self.N = int(model.n_classes)
         self.K = int(model.input_dim)
+        self.input_shape = (self.K,)
         self.shallow = hasattr(model, "hidden")
         if self.shallow:
             self.H = int(model.hidden.out_features)
             act = model.activation
             self.act, self.slope = (1, 0.0) if isinstance(act, nn.ReLU) else (2, float(act.negative_slope))
-            self.head = model.output
+            self.head_name, weights = "output", ("output.weight", "hidden.weight")
         else:
             self.H, self.act, self.slope = 0, 0, 0.0
-            self.head = model.linear
-        self.device = self.head.weight.device
-        decay, no_decay = split_decay_groups(model.named_parameters())
-        self.optimizer = FusedNAdam([{"params": decay, "weight_decay": float(weight_decay)},
-                                     {"params": no_decay, "weight_decay": 0.0}], lr=float(learning_rate), stored_beta2=True)
-        self.force_dense = False           # tests / the benchmark: materialise dW at a batch the low-rank update would take
-        # loss sum (the bits of a double), sample count, label-range flag, confusion matrix: one buffer, one read per epoch
-        self.stats = torch.zeros(3 + self.N * self.N, dtype=torch.int64, device=self.device)
-        self._dp_setup()
-        if self.dp:            # the always-dense gradients (the biases) as views of one arena: one all-reduce, no staging copy
-            named = {k: p for k, p in model.named_parameters() if any(p is q for q in no_decay)}
-            views = self._make_arena({k: p.shape for k, p in named.items()})
-            self.grads: Dict[nn.Parameter, torch.Tensor] = {named[k]: v for k, v in views.items()}
-        else:
-            self.grads = {p: torch.zeros_like(p) for p in no_decay}
-        self._ws: Dict[int, _Workspace] = {}
-        self.last_lowrank: Dict[nn.Parameter, Tuple[torch.Tensor, torch.Tensor]] = {}   # the factors of the last train step
+            self.head_name, weights = "linear", ("linear.weight",)
+        self.head_bias = self.head_name + ".bias"
+        # the biases are always dense; a weight gets its buffer on demand (dense path only)
+        self._setup_training(model, learning_rate, weight_decay, lowrank_names=weights)
 
     # ------------------------------------------------------------------ plumbing
-    def _workspace(self, B: int) -> _Workspace:
-        ws = self._ws.get(B)
-        if ws is None:
-            if len(self._ws) > 4:
-                self._ws.clear()
-            ws = self._ws[B] = _Workspace(B, self.N, self.H, self.device)
-        return ws
+    def _make_workspace(self, B: int, dev) -> _Workspace:
+        return _Workspace(B, self.N, self.H, dev)
 
     def _input(self, x: torch.Tensor) -> torch.Tensor:
-        _lib.require_gpu(x, "SimpleClassifierEngine")
-        if x.ndim > 2:
-            x = x.reshape(x.size(0), -1)
-        if x.ndim != 2 or x.shape[1] != self.K:
-            raise ValueError(f"Expected input dimension {self.K}, got {tuple(x.shape)}.")
-        if x.shape[0] < 1:
-            raise ValueError("empty batch")
-        x = x.float().contiguous()
+        x = super()._input(x.reshape(x.size(0), -1) if x.ndim > 2 else x)
         return x if x.data_ptr() % 16 == 0 else x.clone()
 
-    def _labels(self, y: torch.Tensor, B: int) -> torch.Tensor:
-        _lib.require_gpu(y, "SimpleClassifierEngine")
-        if y.shape != (B,):
-            raise ValueError(f"expected {B} labels, got {tuple(y.shape)}")
-        return y.long().contiguous()
-
-    def _stream(self) -> int:
-        return torch.cuda.current_stream().cuda_stream
-
-    def _forward(self, x: torch.Tensor, ws: _Workspace) -> None:
-        B, st = x.shape[0], self._stream()
+    def _forward(self, x: torch.Tensor, dropout: bool) -> _Workspace:
+        B, prm = x.shape[0], self.params
+        ws = self._workspace(B, x.device)
+        ws.x = x
         feat, kf = x, self.K
         if self.shallow:
-            hid = self.model.hidden
-            launch_nt(self.lib, A=ptr(x), Bw=ptr(hid.weight), bias=ptr(hid.bias), out=ptr(ws.h), M=B, A_rows=B, N=self.H,
-                      K=self.K, lda=self.K, ldb=self.K, ldo=self.H, Tvalid=1, loader=LOAD_DIRECT, epilogue=EPI_LRELU,
+            launch_nt(self.lib, A=ptr(x), Bw=ptr(prm["hidden.weight"]), bias=ptr(prm["hidden.bias"]), out=ptr(ws.h), M=B, A_rows=B,
+                      N=self.H, K=self.K, lda=self.K, ldb=self.K, ldo=self.H, Tvalid=1, loader=LOAD_DIRECT, epilogue=EPI_LRELU,
                       slope=self.slope)
             feat, kf = ws.h, self.H
-        check(self.lib.tl_linear_rows(ptr(feat), ptr(self.head.weight), ptr(self.head.bias), ptr(ws.logits), B, kf, self.N, kf,
-                                      0, st), "tl_linear_rows")
+        self._call(None, "tl_linear_rows", ptr(feat), ptr(prm[self.head_name + ".weight"]), ptr(prm[self.head_bias]),
+                   ptr(ws.logits), B, kf, self.N, kf, 0)
+        return ws
 
-    def _ce(self, ws: _Workspace, y: Optional[torch.Tensor], B: int, grad: bool, pred: bool) -> None:
-        base = self._stats_base()
-        check(self.lib.tl_ce_loss(ptr(ws.logits), ptr(y), ptr(ws.dlogits) if grad else None,
-                                  ptr(self.grads[self.head.bias]) if grad else None, ptr(ws.pred) if pred else None,
-                                  base, base + 8, base + 24, base + 16, B, self.N, self.N, ws.dlogits.shape[1],
-                                  self._grad_scale(), self._stream()), "tl_ce_loss")
-
-    def _dense(self, p: nn.Parameter) -> torch.Tensor:
-        g = self.grads.get(p)
-        if g is None:
-            g = self.grads[p] = torch.empty_like(p)
-        return g
-
-    # ------------------------------------------------------------------ the public steps
-    @torch.no_grad()
-    def train_batch(self, x: torch.Tensor, y: torch.Tensor) -> None:
-        """Forward, loss, backward and update for one batch; everything stays on the stream (no host read)."""
-        x = self._input(x)
-        y = self._labels(y, x.shape[0])
-        dense = self.force_dense or x.shape[0] > FusedNAdam.LOWRANK_MAX      # (from the GLOBAL batch: the same on every rank)
-        x, y = self._take(x, y)
-        B = x.shape[0]
-        ws = self._workspace(B)
-        st = self._stream()
-        self._forward(x, ws)
-        self._ce(ws, y, B, grad=True, pred=False)
-        ldd = ws.dlogits.shape[1]
-        hw = self.head.weight
-        grads = {p: g for p, g in self.grads.items() if p.ndim < 2}
-        lowrank: Dict[nn.Parameter, Tuple[torch.Tensor, torch.Tensor]] = {}
+    def _backward(self, ws: _Workspace, B: int, dense: bool) -> None:
+        """Every gradient of the step from ``ws.dlogits``: the biases (and, when ``dense``, the weights) into ``self.grads``,
+        otherwise the weights as factors in ``self.last_lowrank``."""
+        x, ldd = ws.x, ws.dlogits.shape[1]
+        hw = self.head_name + ".weight"
         dout = ws.dlogits[:, :self.N]
+        self.last_lowrank = {}
         if self.shallow:
-            hid = self.model.hidden
-            check(self.lib.tl_head_bwd(ptr(ws.dlogits), ptr(ws.h), ptr(hw), ptr(ws.dh), ptr(self.grads[hid.bias]),
-                                       ptr(self._dense(hw)) if dense else None, B, self.H, self.N, ldd, self.act, self.slope, st),
-                  "tl_head_bwd")
+            self._call(None, "tl_head_bwd", ptr(ws.dlogits), ptr(ws.h), ptr(self.params[hw]), ptr(ws.dh),
+                       ptr(self.grads["hidden.bias"]), ptr(self._dense(hw)) if dense else None, B, self.H, self.N, ldd, self.act,
+                       self.slope)
             if dense:
-                launch_tn(self.lib, A=ptr(ws.dh), B=ptr(x), slab=ptr(self._dense(hid.weight)), Krows=B, A_rows=B, B_rows=B,
+                launch_tn(self.lib, A=ptr(ws.dh), B=ptr(x), slab=ptr(self._dense("hidden.weight")), Krows=B, A_rows=B, B_rows=B,
                           Mdim=self.H, Ndim=self.K, lda=self.H, ldb=self.K, ldc=self.K, loader=LOAD_DIRECT)
-                grads[hw], grads[hid.weight] = self.grads[hw], self.grads[hid.weight]
             else:
-                lowrank[hw], lowrank[hid.weight] = (dout, ws.h), (ws.dh, x)
+                self.last_lowrank = {hw: (dout, ws.h), "hidden.weight": (ws.dh, x)}
         elif dense:
-            check(self.lib.tl_head_bwd(ptr(ws.dlogits), ptr(x), ptr(hw), None, None, ptr(self._dense(hw)), B, self.K, self.N, ldd,
-                                       0, 0.0, st), "tl_head_bwd")
-            grads[hw] = self.grads[hw]
+            self._call(None, "tl_head_bwd", ptr(ws.dlogits), ptr(x), ptr(self.params[hw]), None, None, ptr(self._dense(hw)), B,
+                       self.K, self.N, ldd, 0, 0.0)
         else:
-            lowrank[hw] = (dout, x)
-        if self.dp:
-            # dlogits travels at its stored width (the factor is its first N columns)
-            sent = {p: (ws.dlogits if fa is dout else fa, fb) for p, (fa, fb) in lowrank.items()}
-            got = self._exchange(extra=[g for p, g in grads.items() if p.ndim >= 2], lowrank=sent)
-            lowrank = {p: (fa[:, :self.N] if sent[p][0] is ws.dlogits else fa, fb) for p, (fa, fb) in got.items()}
-        self.last_lowrank = lowrank
-        self.optimizer.step(grads=grads, lowrank=lowrank or None)
+            self.last_lowrank = {hw: (dout, x)}
 
-    @torch.no_grad()
-    def eval_batch(self, x: torch.Tensor, y: torch.Tensor) -> None:
-        """Forward and loss statistics of one batch (no gradients, no update)."""
-        x = self._input(x)
-        x, y = self._take(x, self._labels(y, x.shape[0]))
-        ws = self._workspace(x.shape[0])
-        self._forward(x, ws)
-        self._ce(ws, y, x.shape[0], grad=False, pred=False)
-
-    @torch.no_grad()
-    def predict_batch(self, x: torch.Tensor) -> torch.Tensor:
-        """Arg-max class of every row (int64, on the device)."""
-        x, _ = self._take(self._input(x))
-        ws = self._workspace(x.shape[0])
-        self._forward(x, ws)
-        self._ce(ws, None, x.shape[0], grad=False, pred=True)
-        return self._gather_pred(ws.pred) if self.dp else ws.pred.clone()
-
-    epoch_stats = ClassifierDP.epoch_stats
+    def _lowrank_wire(self, ws: _Workspace):
+        return {self.head_name + ".weight": ws.dlogits}       # dlogits travels at its stored width (the factor is its first N columns)

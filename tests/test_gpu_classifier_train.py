@@ -198,7 +198,7 @@ def test_one_train_step_gradients_on_the_dense_path(kind):
     names = {p: k for k, p in eng.model.named_parameters()}
     eng.train_batch(x.to(DEV), y.to(DEV))
     torch.cuda.synchronize()
-    got = {names[p]: t for p, t in eng.grads.items()}
+    got = {k: t for k, t in eng.grads.items()}
     assert set(got) == set(r64)                                                            # all four (both) gradients exist
     ok = [_held("gradients", f"{kind}_{k}", ref.rel_l2(got[k], r64[k]), ref.rel_l2(r32[k], r64[k])) for k in sorted(r64)]
     assert all(ok), kind
@@ -250,6 +250,75 @@ def test_update_trajectory_lowrank_and_dense(kind):
     for k in sorted(low):
         ok.append(_held("trajectory", f"{kind}_lowrank_vs_dense_B64_{k}", ref.rel_l2(low[k], dense[k]), yards["lowrank_B64", k]))
     assert all(ok), kind
+
+
+def _snapshot(eng):
+    """Every parameter and every entry of the optimiser state (tensors cloned, the host scalars as they are)."""
+    prm = {k: v.detach().clone() for k, v in eng.model.named_parameters()}
+    names = {p: k for k, p in eng.model.named_parameters()}
+    state = {(names[p], k): (v.clone() if torch.is_tensor(v) else v) for p, st in eng.optimizer.state.items() for k, v in st.items()}
+    return prm, state
+
+
+def _same_bits(a, b):
+    return set(a) == set(b) and all(torch.equal(a[k], b[k]) if torch.is_tensor(a[k]) else a[k] == b[k] for k in a)
+
+
+@pytest.mark.parametrize("route", ["lowrank", "dense"])
+@pytest.mark.parametrize("kind", ["logistic", "shallow"])
+def test_backward_only_returns_the_step_gradients_and_updates_nothing(kind, route):
+    """``backward_only`` / ``step_gradients`` of the simple engine (inherited from the base class) at B = 5: the weights as
+    factor pairs whose product is the gradient on the low-rank route, as tensors under ``force_dense``; yardstick as above."""
+    from decode_tonal_langauge_amd.models.simple_classifiers import LogisticRegressionClassifier, ShallowNNClassifier
+    torch.manual_seed(11)
+    model = LogisticRegressionClassifier(8, 3) if kind == "logistic" else ShallowNNClassifier(8, 3, 8, "LeakyReLU")
+    g = torch.Generator().manual_seed(12)
+    x, y = torch.randn(5, 8, generator=g), torch.randint(0, 3, (5,), generator=g)
+    m64, _ = ref.as_double(model, [])
+    r64, r32 = ref.gradients(m64, x.double(), y), ref.gradients(model, x, y)
+
+    def fresh():
+        eng = _engine(model, 0.001, 0.01)
+        eng.force_dense = route == "dense"
+        return eng
+    eng = fresh()
+    before = _snapshot(eng)
+    got = eng.backward_only(x.to(DEV), y.to(DEV))
+    torch.cuda.synchronize()
+    assert got.keys() == eng.step_gradients().keys() == r64.keys()
+    got = {k: tuple(f.clone() for f in v) if isinstance(v, tuple) else v.clone() for k, v in got.items()}
+    after = _snapshot(eng)
+    assert _same_bits(before[0], after[0]) and before[1] == after[1] == {}             # no update, no optimiser state made
+    ok = []
+    for k in sorted(r64):
+        if k.endswith("weight") and route == "lowrank":
+            fa, fb = got[k]                                                                # (B, rows), (B, cols): dW = fa^T . fb
+            assert fa.shape == (5, r64[k].shape[0]) and fb.shape == (5, r64[k].shape[1])
+            full = fa.double().t() @ fb.double()
+        else:
+            assert torch.is_tensor(got[k])
+            full = got[k]
+        ok.append(_held("backward_only", f"{kind}_{route}_{k}", ref.rel_l2(full, r64[k]), ref.rel_l2(r32[k], r64[k])))
+    assert all(ok), (kind, route)
+    # with optimiser state in place: a second call moves neither it nor the parameters
+    eng.train_batch(x.to(DEV), y.to(DEV))
+    before = _snapshot(eng)
+    assert sum(torch.is_tensor(v) for v in before[1].values()) == 2 * len(r64)             # both moments of every parameter
+    eng.backward_only(x.to(DEV), y.to(DEV))
+    torch.cuda.synchronize()
+    after = _snapshot(eng)
+    assert _same_bits(before[0], after[0]) and _same_bits(before[1], after[1])
+    # a fresh engine on the same model: the gradients its train step applied are those bits
+    twin = fresh()
+    twin.train_batch(x.to(DEV), y.to(DEV))
+    torch.cuda.synchronize()
+    applied = twin.step_gradients()
+    assert applied.keys() == got.keys()
+    for k, v in got.items():
+        if isinstance(v, tuple):
+            assert all(torch.equal(a, b) for a, b in zip(applied[k], v)), k
+        else:
+            assert torch.equal(applied[k], v), k
 
 
 def test_train_batch_never_reads_the_device():
