@@ -302,7 +302,7 @@ class CnnRnnConvEngine:
         # transformed arrays exist); "direct" the 7-tap window GEMM (72.8 ms for the CNN-RNN forward at C5, batch 64, against
         # 46 ms).  The segmented F(4,3) forms of rounds 2-4 were retired in round 6
         _kernels.validate()
-        self.conv7_form = _kernels.get("conv7")
+        self.conv7_form = _kernels.conv7_forward()
         # rows per sequence: whole hexes for the F(6,3) form, whole quads for the others
         self.Tp = (self.t1 + 5) // 6 * 6 if self.conv7_form == "wino63" else (self.t1 + 3) // 4 * 4
         self._packed: Dict[str, Tuple[tuple, torch.Tensor]] = {}

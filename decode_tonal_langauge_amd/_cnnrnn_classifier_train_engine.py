@@ -14,8 +14,9 @@ One train step of a batch (B, C, T); t1 = (T - 6) // 2, ta = t1 - 6, tb = ta - 6
             confusion matrix ADDED to device words read once per epoch;
   backward  ``tl_head_bwd`` -> dh2; ``tl_lstm_bptt_seq`` (one fused launch per step) -> dgates and their transposed copy;
             dW_hh, dW_ih, db and dX2 = dgates . W_ih (ONE read of the weight, A = dgates^T) on the TN GEMM; ``tl_pool3_bwd_shard``;
-            ``ConvStack.stage_wgrad`` / ``stage_dgrad`` for the two 7-tap stages (direct kernels, J = 7); ``tl_conv1_wgrad`` per
-            branch; ``tl_conv1_dgrad`` on the LSTM branch -> dh1; lstm1's BPTT and GEMMs;
+            ``ConvStack.stage_wgrad`` / ``stage_dgrad`` for the two 7-tap stages (direct kernels, J = 7; under ``TONAL_KERNELS
+            conv7=wino63bwd`` both passes on F(6,3): ``_wgrad7`` / ``_dgrad7``); ``tl_conv1_wgrad`` per branch; ``tl_conv1_dgrad``
+            on the LSTM branch -> dh1; lstm1's BPTT and GEMMs;
   update    one ``FusedNAdam`` over dense gradients (an LSTM weight gradient has rank T * B: no low-rank form).
 
 Under a process group (``parallel.active()``) every public step takes the GLOBAL batch and works on this rank's rows
@@ -37,7 +38,7 @@ from . import _kernels
 from ._classifier_train_engine import SUPPORTED, ClassifierTrainEngine, check_common, refuse
 from ._conv_stack import ConvStack
 from ._launch import r4
-from ._lib import EPI_LRELU, EPI_STORE, LOAD_DIRECT, LOAD_V, check, ptr
+from ._lib import EPI_LRELU, EPI_MASK, EPI_STORE, LOAD_DIRECT, LOAD_V, LOAD_Y, check, ptr
 
 K7 = 7            # taps of every convolution of the model
 C_FIRST, C_A, C_B = 1024, 512, 256
@@ -132,7 +133,10 @@ class CnnRnnClassifierTrainEngine(ClassifierTrainEngine, ConvStack):
         self.t1, self.ta, self.tb, self.tq = geo["t1"], geo["ta"], geo["tb"], geo["tq"]
         assert self.t1 == self.tout1 and self.stages[1].tout == self.tb
         # rows per sequence: whole hexes for the F(6,3) form of the 7-tap forward, whole quads otherwise (CnnRnnConvEngine's)
-        self.conv7_form = _kernels.get("conv7")
+        self.conv7_form = _kernels.conv7_forward()
+        # conv7=wino63bwd: the weight and input gradients of the two wide stages on F(6,3) too (_wgrad7 / _dgrad7; needs whole
+        # 256-channel tiles of C_in for the transform-free weight-gradient kernel - the model's widths have them)
+        self.conv7_bwd = _kernels.get("conv7") == "wino63bwd"
         self.Tp = (self.t1 + 5) // 6 * 6 if self.conv7_form == "wino63" else (self.t1 + 3) // 4 * 4
         self.tp1 = self.Tp
         for st in self.stages:
@@ -164,8 +168,12 @@ class CnnRnnClassifierTrainEngine(ClassifierTrainEngine, ConvStack):
         self.sbits = {1: zi(rows, C_FIRST // 32)}
         self.V7 = None
         if self.conv7_form == "wino63":
-            nh_pad = (rows // 6 + 2 + 127) // 128 * 128
+            # whole 128-hex tiles of the NT kernel (+ 2: its third segment reads one hex on); under conv7=wino63bwd also whole
+            # 6-hex K-steps of the weight-gradient kernel, which the first rounding does not imply (253 hexes: 256 < 258)
+            nh_pad = (rows // 6 + (6 if self.conv7_bwd else 2) + 127) // 128 * 128
             self.V7 = (z(nh_pad, 8, C_FIRST), z(nh_pad, 8, C_FIRST))
+        self._v7_of = None                 # (generation, tag) of the transform V7 holds
+        self.Y7 = self.D7 = None           # conv7=wino63bwd: Y = A dz, and V0 / V1 of the moved dz (allocated with G)
 
     def _alloc_bwd(self) -> bool:
         if self.G is not None:
@@ -173,6 +181,11 @@ class CnnRnnClassifierTrainEngine(ClassifierTrainEngine, ConvStack):
         z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=self._dev)
         rows = self.S * self.Tp
         self.G = {1: z(rows, C_FIRST), 2: z(rows, C_A), 3: z(rows, C_B)}
+        if self.conv7_bwd:
+            # three hex arrays of the wider gradient (C_A channels; stage 3 re-views them): 32 x rows x C_A / 6 bytes each
+            nh_pad = self.V7[0].shape[0]
+            self.Y7 = z(nh_pad, 8, C_A)
+            self.D7 = (z(nh_pad, 8, C_A), z(nh_pad, 8, C_A))
         return True
 
     def _make_workspace(self, B: int, dev) -> _Ws:
@@ -262,18 +275,12 @@ class CnnRnnClassifierTrainEngine(ClassifierTrainEngine, ConvStack):
         w, b = self.params[name + ".weight"].data, self.params[name + ".bias"].data
         name = name + ".weight"
         if self.conv7_form == "wino63":
-            nhex = rows // 6
-            V0 = self.V7[0].view(-1)[: self.V7[0].shape[0] * 8 * cin].view(-1, 8, cin)
-            V1 = self.V7[1].view(-1)[: self.V7[1].shape[0] * 8 * cin].view(-1, 8, cin)
-            if cin != self.V7[0].shape[2]:
-                # a narrower layer re-views the storage: its pad hexes overlay the wider layer's transform data - zero them
-                # ("zero hexes appended", tl_conv7_wino63v_nt's contract)
-                h0 = (nhex + 1) // 2 * 2
-                V0[h0:].zero_()
-                V1[h0:].zero_()
+            # (a narrower layer re-views the storage: its pad hexes are zeroed - "zero hexes appended", tl_conv7_wino63v_nt's contract)
+            V0, V1 = (self._hex_view(v, cin, rows // 6) for v in self.V7)
             ev = self._tick(tag + "_xform")
             check(self.lib.tl_wino63_xform2(ptr(src), ptr(V0), ptr(V1), rows, self.Tp, tvalid, cin, src.shape[1], cin, st_),
                   "tl_wino63_xform2")
+            self._v7_of = (self.generation, tag)
             hit = self._packs.get(tag)
             if hit is None or hit[0] != self._version(name):
                 wp = hit[1] if hit is not None else torch.empty(3 * cin // 8, 8, cout, 8, dtype=torch.float32, device=w.device)
@@ -293,6 +300,110 @@ class CnnRnnClassifierTrainEngine(ClassifierTrainEngine, ConvStack):
         self._nt(tag=tag, A=ptr(src), Bw=ptr(wp), bias=ptr(b), out=ptr(dst), M=rows, A_rows=rows + 8, N=cout, K=cin, lda=cin,
                  ldb=cin, ldo=cout, J=K7, row_shift=0, Tp=self.Tp, Tvalid=self.Tp, slope=self.slope, loader=LOAD_DIRECT,
                  epilogue=EPI_LRELU)
+
+    # ------------------------------------------------------------------ the 7-tap stages, backward on F(6,3) (conv7=wino63bwd)
+    def _hex_view(self, buf: torch.Tensor, c: int, nhex: int) -> torch.Tensor:
+        """``buf`` (hexes, 8, wider) re-viewed for ``c`` channels; the pad hexes of a narrower view overlay data: zeroed - with
+        an odd ``nhex`` the second hex of the last pair too, which no transform kernel writes (the weight-gradient kernel reads
+        whole 6-hex K-steps of BOTH operands: a stale hex of Y against a stale hex of V is a term of the sum)."""
+        if c == buf.shape[2]:
+            return buf
+        v = buf.view(-1)[: buf.shape[0] * 8 * c].view(-1, 8, c)
+        v[(nhex + 1) // 2 * 2:].zero_()
+        if nhex % 2:
+            v.view(-1, c // 8, 8, 2, 8)[nhex // 2, :, :, 1].zero_()          # (pair layout: [hex / 2][c / 8][8][hex % 2][8])
+        return v
+
+    def _wgrad7(self, st, gw: torch.Tensor, gb: torch.Tensor) -> None:
+        """dW_j = sum_R dz[R] (x) x[R + j] as three 3-tap F(6,3) weight gradients: taps 3 s .. 3 s + 2 see x shifted by 3 s rows =
+        V0(x), V1(x) and V0(x) one hex on (``a_hex``), all against Y = A dz (``tl_wino63_ydz`` of G[idx]); the transform-free
+        kernel of the synthesis stack runs them.  V0 / V1 of the stage input are the forward's where V7 still holds them
+        (stage 3: the last transform of the forward), else recomputed (stage 2: V7 is one buffer pair for both stages - keeping
+        its transform would cost two more arrays of rows x C_FIRST / 6 x 32 bytes; the recompute is timed in ``_wgrad_xform``, the
+        split-K sums, the three finalize passes and the scatter into the seven taps in ``_wgrad_reduce``)."""
+        S, Tp = self.S, self.Tp
+        rows, nhex, cin, cout = S * Tp, S * Tp // 6, st.cin, st.cout
+        f32 = dict(dtype=torch.float32, device=self._dev)
+        src, Gs = self.P[st.idx - 1], self.G[st.idx]
+        tag = f"conv{st.idx}_wgrad"
+        fwd_tag = "conv3a_fwd" if st.idx == 2 else "conv3b_fwd"
+        kept = self._v7_of == (self.generation, fwd_tag)
+        V0, V1 = (self._hex_view(v, cin, nhex) for v in self.V7)
+        ev = self._tick(tag + "_xform")
+        if not kept:
+            check(self.lib.tl_wino63_xform2(ptr(src), ptr(V0), ptr(V1), rows, Tp, st.tin, cin, src.shape[1], cin, self._stream()),
+                  "tl_wino63_xform2")
+            self._v7_of = (self.generation, fwd_tag)
+        Y = self._hex_view(self.Y7, cout, nhex)
+        check(self.lib.tl_wino63_ydz(ptr(Gs), ptr(Y), rows, Tp, st.tout, cout, Gs.shape[1], cout, self._stream()), "tl_wino63_ydz")
+        if ev:
+            ev[1].record()
+        sk = self._splitk((cin // 64) * (cout // 64), (rows + 35) // 36, 4096)
+        slab = torch.empty(3, sk, 8 * cin, cout, **f32)
+        bias_part = torch.empty(sk, cout, **f32)
+        ev = self._tick(tag)
+        for s, (V, a_hex) in enumerate(((V0, 0), (V1, 0), (V0, 1))):
+            self._tn(fn="tl_conv3_wino63v_tn", A=ptr(V), B=ptr(Y), slab=ptr(slab[s]), Krows=rows, A_rows=V.shape[0],
+                     B_rows=Y.shape[0], Mdim=cin, Ndim=cout, lda=cin, ldb=cout, ldc=cout, J=3, Tp=Tp, splitk=sk,
+                     slab_stride=8 * cin * cout, loader=LOAD_Y, Tvalid=st.tout, a_hex=a_hex,
+                     colsum=ptr(bias_part) if s == 0 else None)
+        if ev:
+            ev[1].record()
+        # (slab: 3 sk x 32 cin cout bytes, 1.6 GB at the wider stage of 128 x 400, batch 64 - transient, back in torch's caching
+        # allocator behind the step; the direct form's slabs are sk x 28 cin cout bytes, 73 MB there)
+        n = 8 * cin * cout
+        ev = self._tick(tag + "_reduce")
+        red = torch.empty(8 * cin, cout, **f32) if sk > 1 else None
+        g3 = torch.empty(cout, cin, 3, **f32)
+        gw7 = gw.view(cout, cin, K7)
+        for s in range(3):
+            if sk > 1:
+                self._permute(slab[s], red, (1, 1, 1, n), (0, 0, 0, 1), nz=sk, zs=n)
+            check(self.lib.tl_wino63_wgrad_finalize(ptr(red if sk > 1 else slab[s]), ptr(g3), cout, cin, cout, self._stream()),
+                  "tl_wino63_wgrad_finalize")
+            nt = min(3, K7 - 3 * s)                    # (segment 2: tap 6 alone - its taps 7, 8 do not exist)
+            gw7[:, :, 3 * s:3 * s + nt].copy_(g3[:, :, :nt])
+        self._permute(bias_part, gb, (1, 1, 1, cout), (0, 0, 0, 1), nz=sk, zs=cout)
+        if ev:
+            ev[1].record()
+
+    def _dgrad7(self, st, w: torch.Tensor) -> None:
+        """G[idx - 1][t] = (sum_j W_j^T dz[t - j]) * LeakyReLU'(input): the forward kernel on dz moved down six rows inside its
+        sequence (``tl_wino63_xform2s``: t_out + 6 <= Tp, so no window leaves the sequence) with the taps of the flipped,
+        transposed weight; the mask from the sign words under stage 2 (its input came out of a pool), from P[2] under stage 3."""
+        S, Tp = self.S, self.Tp
+        rows, nhex, cin, cout = S * Tp, S * Tp // 6, st.cin, st.cout
+        Gs, out = self.G[st.idx], self.G[st.idx - 1]
+        tag = f"conv{st.idx}_dgrad"
+        name = self.STAGE_NAMES[st.idx] + ".weight"
+        D0, D1 = (self._hex_view(v, cout, nhex) for v in self.D7)
+        ev = self._tick(tag + "_xform")
+        check(self.lib.tl_wino63_xform2s(ptr(Gs), ptr(D0), ptr(D1), rows, Tp, st.tout, K7 - 1, cout, Gs.shape[1], cout,
+                                         self._stream()), "tl_wino63_xform2s")
+        hit = self._packs.get(tag)
+        if hit is None or hit[0] != self._version(name):
+            wp = hit[1] if hit is not None else torch.empty(3 * cout // 8, 8, cin, 8, dtype=torch.float32, device=w.device)
+            wf = w.reshape(cout, cin, K7).flip(2).permute(1, 0, 2).contiguous()        # (I, O, 7): wf[i][o][j] = w[o][i][6 - j]
+            check(self.lib.tl_wino63_weights7(ptr(wf), ptr(wp), cin, cout, K7, self._stream()), "tl_wino63_weights7")
+            self._packs[tag] = (self._version(name), wp)
+        wp = self._packs[tag][1]
+        if ev:
+            ev[1].record()
+        kw = dict(auxbits=ptr(self.sbits[1]), ld_auxbits=self.sbits[1].shape[1]) if st.idx == 2 else \
+            dict(mask=ptr(self.P[2]), ld_mask=self.P[2].shape[1])
+        self._nt(tag=tag, fn="tl_conv7_wino63v_dgrad_nt", A=ptr(D0), aux=ptr(D1), A_rows=D0.shape[0], lda=cout, Bw=ptr(wp),
+                 out=ptr(out), M=rows, N=cin, K=cout, ldb=3 * cout, ldo=out.shape[1], J=K7, row_shift=0, Tp=Tp, Tvalid=Tp,
+                 slope=self.slope, loader=LOAD_V, epilogue=EPI_MASK, **kw)
+
+    def stage_wgrad(self, st, gw, gb) -> None:
+        if self.conv7_bwd:
+            return self._wgrad7(st, gw, gb)
+        return super().stage_wgrad(st, gw, gb)
+
+    def stage_dgrad(self, st, w):
+        if self.conv7_bwd:
+            return self._dgrad7(st, w)
+        return super().stage_dgrad(st, w)
 
     # ------------------------------------------------------------------ forward
     def _branches(self, ws: _Ws, B: int):

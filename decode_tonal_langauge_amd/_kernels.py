@@ -43,7 +43,9 @@ KEYS: Dict[str, Tuple[str, _Allowed, str, str]] = {
                     "(no gradient rows, no tl_wino63_unpool_yvd); gemm: one-tap GEMM + tl_wino63_unpool_yvd"),
     "store_p1": ("TONAL_STORE_P1", _B, "0", "keep the raw pooled rows of stages 1 / 2 beside V, and Vd2 beside Y2 (tests)"),
     # ---- deep classifiers (_classifier_engine.py)
-    "conv7": ("TONAL_CONV7", frozenset({"wino63", "direct"}), "wino63", "the CNN-RNN classifier's 7-tap convolutions"),
+    "conv7": ("TONAL_CONV7", frozenset({"wino63", "wino63bwd", "direct"}), "wino63",
+              "the CNN-RNN classifier's 7-tap convolutions: wino63 three F(6,3) segments forward, direct kernels backward; "
+              "wino63bwd the same forward and, in training, both backward passes on F(6,3) as well; direct all direct"),
     # ---- optimiser / trainer
     "whh_dh": ("TONAL_WHH_DH", _B, "1", "single process: the W_hh NAdam pass also produces the last BPTT product dh_1 = dgates_2 . W_hh "
                                         "(0: a W_hh stream of its own for it)"),
@@ -105,6 +107,12 @@ def get(key: str, default: str = None) -> str:
                                f"TONAL_KERNELS={key}={os.environ[legacy]} (or set TONAL_AB=1 to run an A/B comparison)")
         return _check(key, os.environ[legacy])
     return table_default if default is None else default
+
+
+def conv7_forward() -> str:
+    """The form the 7-tap convolutions run FORWARD in: ``wino63bwd`` differs from ``wino63`` in the training backward only."""
+    form = get("conv7")
+    return "wino63" if form == "wino63bwd" else form
 
 
 def validate() -> None:

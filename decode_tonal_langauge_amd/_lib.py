@@ -37,6 +37,7 @@ class NtParams(C.Structure):
         ("c1x", C.c_void_p), ("c1bits", C.c_void_p), ("c1partial", C.c_void_p), ("c1T", C.c_int), ("c1kt", C.c_int),
         ("vout", C.c_void_p), ("vhalo", C.c_void_p), ("vout_quads", C.c_int64), ("ld_vout", C.c_int),
         ("out_tp", C.c_int), ("vout2", C.c_void_p),
+        ("mask", C.c_void_p), ("ld_mask", C.c_int),
     ]
 
 
@@ -50,6 +51,7 @@ class TnParams(C.Structure):
         ("splitk", C.c_int), ("slab_stride", C.c_int64),
         ("colsum", C.c_void_p),
         ("vd", C.c_void_p), ("ld_vd", C.c_int), ("part", C.c_int), ("bm", C.c_int), ("g_tp", C.c_int),
+        ("a_hex", C.c_int),
     ]
 
 
@@ -70,6 +72,9 @@ SIGNATURES = {
     "tl_wino63_xform2": (_I, [_P, _P, _P, _L, _I, _I, _I, _I, _I, _P]),
     "tl_wino63_weights7": (_I, [_P, _P, _I, _I, _I, _P]),
     "tl_conv7_wino63v_nt": (_I, [C.POINTER(NtParams), _P]),
+    "tl_wino63_ydz": (_I, [_P, _P, _L, _I, _I, _I, _I, _I, _P]),
+    "tl_wino63_xform2s": (_I, [_P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P]),
+    "tl_conv7_wino63v_dgrad_nt": (_I, [C.POINTER(NtParams), _P]),
     "tl_wino63_unpool_rows6": (_I, [_P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "tl_wino63_weights1": (_I, [_P, _P, _I, _I, _I, _P]),
     "tl_conv1_wino63v_dgrad_nt": (_I, [C.POINTER(NtParams), _P]),

@@ -142,8 +142,10 @@ __global__ void wino63_weights7_kernel(const float* __restrict__ w, float* __res
 // Rows P[seq * Tp + t][C] -> V0 = B^T (rows 6 h .. 6 h + 7) and V1 = B^T (rows 6 h + 3 .. 6 h + 10) of every hex, pair layout:
 // the operands of tl_conv7_wino63v_nt.  Rows from Tvalid on (and past the sequence) enter as zeros.  Thread = 4 channels x one
 // hex, lanes ordered (8-channel chunk, hex of the pair, half chunk) like wino63_unpool_yvd_kernel: whole 64-byte runs.
+// shift (tl_wino63_xform2s): the rows enter moved down by `shift` inside their sequence - row t as row t + shift, zeros in front.
 __global__ __launch_bounds__(256, 4) void wino63_xform2_kernel(const float* __restrict__ P, float* __restrict__ V0, float* __restrict__ V1,
-                                                             long long nhex, int hps, int Tp, int Tvalid, int C, int ldp, int ldv) {
+                                                             long long nhex, int hps, int Tp, int Tvalid, int C, int ldp, int ldv,
+                                                             int shift) {
   const int tpp = C >> 1;                                    // threads per hex pair
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long pair = idx / tpp;
@@ -159,7 +161,8 @@ __global__ __launch_bounds__(256, 4) void wino63_xform2_kernel(const float* __re
 #pragma unroll
   for (int j = 0; j < 11; ++j) {
     d[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (6 * hs + j < Tvalid) d[j] = *reinterpret_cast<const f32x4*>(src + (long long)j * ldp);
+    const int t = 6 * hs + j - shift;
+    if (t >= 0 && t < Tvalid) d[j] = *reinterpret_cast<const f32x4*>(src + (long long)(j - shift) * ldp);
   }
   f32x4 o0[8], o1[8];
 #pragma unroll
@@ -183,6 +186,44 @@ __global__ __launch_bounds__(256, 4) void wino63_xform2_kernel(const float* __re
   for (int j = 0; j < 8; ++j) *reinterpret_cast<f32x4*>(V0 + at + 16 * j) = o0[j];
 #pragma unroll
   for (int j = 0; j < 8; ++j) *reinterpret_cast<f32x4*>(V1 + at + 16 * j) = o1[j];
+}
+
+// Gradient rows dz[seq * Tp + t][C] of a stage WITHOUT a pool -> Y = A dz (rows 6 h .. 6 h + 5) of every hex, pair layout: the
+// second operand of tl_conv3_wino63v_tn with loader 3 for the three segments of a 7-tap weight gradient.  Rows from Tvalid on
+// enter as zeros.  Planes and their arithmetic are wino63_unpool_yvd_kernel's (plane 1 = the sum of the six rows); threads as above.
+__global__ __launch_bounds__(256, 4) void wino63_ydz_kernel(const float* __restrict__ G, float* __restrict__ Y, long long nhex, int hps,
+                                                          int Tp, int Tvalid, int C, int ldg, int ldv) {
+  const int tpp = C >> 1;                                    // threads per hex pair
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long pair = idx / tpp;
+  const int tl_ = (int)(idx - pair * tpp);
+  const int half = tl_ & 1, hpar = (tl_ >> 1) & 1, kc = tl_ >> 2;
+  const int c = 8 * kc + 4 * half;
+  const long long hg = 2 * pair + hpar;
+  if (hg >= nhex) return;
+  const long long seq = hg / hps;
+  const int hs = (int)(hg - seq * hps);
+  const float* src = G + (seq * Tp + 6LL * hs) * (long long)ldg + c;
+  f32x4 d[6];
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    d[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (6 * hs + j < Tvalid) d[j] = *reinterpret_cast<const f32x4*>(src + (long long)j * ldg);
+  }
+  f32x4 oy[8];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float d6[6] = {d[0][k], d[1][k], d[2][k], d[3][k], d[4][k], d[5][k]};
+    const float ev1 = (d6[0] + d6[2]) + d6[4], od1 = (d6[1] + d6[3]) + d6[5];
+    const float ev2 = fmaf(16.f, d6[4], fmaf(4.f, d6[2], d6[0])), od2 = fmaf(32.f, d6[5], fmaf(8.f, d6[3], 2.f * d6[1]));
+    const float ev3 = fmaf(0.0625f, d6[4], fmaf(0.25f, d6[2], d6[0])), od3 = fmaf(0.03125f, d6[5], fmaf(0.125f, d6[3], 0.5f * d6[1]));
+    const float y[8] = {d6[0], ev1 + od1, ev1 - od1, ev2 + od2, ev2 - od2, ev3 + od3, ev3 - od3, d6[5]};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) oy[j][k] = y[j];
+  }
+  const long long at = v6_at(hg, 0, c, ldv >> 3);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) *reinterpret_cast<f32x4*>(Y + at + 16 * j) = oy[j];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -256,7 +297,9 @@ __global__ __launch_bounds__(512, 2) void wino63v_nt_kernel(const tl_nt_params p
   // EPI == LRELU: a SEVEN-tap convolution as three 3-tap segments summed in the transform domain (tl_conv7_wino63v_nt): the K
   // loop runs over 3 K channels - segment 0 = V0 (A), hex H; segment 1 = V1 (aux: the transform of the rows shifted by 3);
   // segment 2 = V0 again, hex H + 1 (rows shifted by 6 ARE the next hex) - against taps [3 K / 8][8][N][8]
-  constexpr bool SEG3 = EPI == W_EPI_LRELU;
+  // (W6_EPI_MASK7 / _MASK7F, tl_conv7_wino63v_dgrad_nt: the same K loop under the MASK epilogue - the input gradient of such a
+  // convolution is a 7-tap convolution of the gradient rows moved down six rows, tl_wino63_xform2s)
+  constexpr bool SEG3 = EPI == W_EPI_LRELU || EPI == W6_EPI_MASK7 || EPI == W6_EPI_MASK7F;
   // EPI == GY (tl_conv1_wino63v_dgrad_nt): transforms 6, 7 of both operands are zero - the six-batch K loop (V6K6_*: half-set H =
   // transforms 4, 5; 24 MFMAs per K-step), and waves 6, 7 fetch through empty resources (their planes are never read)
   constexpr bool SIX = EPI == W_EPI_GY;
@@ -424,7 +467,8 @@ __global__ __launch_bounds__(512, 2) void wino63v_nt_kernel(const tl_nt_params p
     // What the epilogue reads from global memory is requested in front of the LAST K-step (tonal_wino43v.hip)
     auto prefetch = [&] {
       if constexpr (EPI == W_EPI_POOL || EPI == W_EPI_POOLV || EPI == W_EPI_LRELU) return v5_prefetch_pool(p, cur.n0, wn, lr);
-      else if constexpr (EPI == W_EPI_MASK) return v6_prefetch_mask(p, cur.R0, cur.n0, wm, wn, lr, lh);
+      else if constexpr (EPI == W_EPI_MASK || EPI == W6_EPI_MASK7) return v6_prefetch_mask(p, cur.R0, cur.n0, wm, wn, lr, lh);
+      else if constexpr (EPI == W6_EPI_MASK7F) return v6_pre_mask{{0u, 0u, 0u}};      // (float rows: read by the epilogue itself)
       else if constexpr (EPI == W_EPI_MASKY || EPI == W6_EPI_MASKY_Y) return v6_prefetch_masky(p, cur.R0, cur.n0, wm, wn, lr, lh);
       else if constexpr (EPI == W_EPI_GY) return v6_prefetch_masky<true>(p, cur.R0, cur.n0, wm, wn, lr, lh);
       else return v6_prefetch_c1w(p, cur.R0, cur.n0, wm, wn, lr, lh);
@@ -489,9 +533,12 @@ __global__ __launch_bounds__(512, 2) void wino63v_nt_kernel(const tl_nt_params p
     } else if constexpr (EPI == W_EPI_LRELU) {
       if (full) v6_epilogue_lrelu<true>(p, acc, pre, done.R0, done.n0, wm, wn, lr, lh);
       else v6_epilogue_lrelu<false>(p, acc, pre, done.R0, done.n0, wm, wn, lr, lh);
-    } else if constexpr (EPI == W_EPI_MASK) {
+    } else if constexpr (EPI == W_EPI_MASK || EPI == W6_EPI_MASK7) {
       if (full) v6_epilogue_mask<true>(p, acc, pre, done.R0, done.n0, wm, wn, lr, lh);
       else v6_epilogue_mask<false>(p, acc, pre, done.R0, done.n0, wm, wn, lr, lh);
+    } else if constexpr (EPI == W6_EPI_MASK7F) {
+      if (full) v6_epilogue_mask<true, true>(p, acc, pre, done.R0, done.n0, wm, wn, lr, lh);
+      else v6_epilogue_mask<false, true>(p, acc, pre, done.R0, done.n0, wm, wn, lr, lh);
     } else if constexpr (EPI == W_EPI_MASKY) {
       float* xch = reinterpret_cast<float*>(lds + 3 * V6_STAGE);
       if (full) v6_epilogue_masky<true>(p, acc, pre, xch, done.R0, done.n0, wm, wn, lr, lh, done.tm);
@@ -1382,7 +1429,7 @@ __global__ __launch_bounds__(512, 1) void wino63v_tn4y_kernel(const tl_tn_params
     const int quarter = (wave * 3 + t) / 6, pc = (wave * 3 + t) % 6;
     const int rho = 4 * pc + (lane >> 4), i = rho / 6, hx = rho % 6;
     const int chunk = (lane & 15) ^ ((hx & 1) << 3);
-    vvoff[t] = (unsigned)(v6_at(hx, i0 + i, m0 + quarter * 64 + chunk * 4, kc8) * 4);
+    vvoff[t] = (unsigned)(v6_at(hx + p.a_hex, i0 + i, m0 + quarter * 64 + chunk * 4, kc8) * 4);   // (a_hex: tl_tn_params)
     vdst[t] = (unsigned)((quarter * QT + pc * 256) * 4);
   }
   // the Y piece of wave w < 6: rows 4 w .. 4 w + 3 of the tile's 24 ([transform][hex] order), like a quarter-tile of V
@@ -1807,8 +1854,37 @@ extern "C" int tl_wino63_xform2(const float* P, float* V0, float* V1, int64_t ro
   const long long n = ((nhex + 1) / 2) * (C / 2);
   TL_REQUIRE((n + 255) / 256 < (1LL << 31), "wino63_xform2: grid too large");
   hipLaunchKernelGGL(wino63_xform2_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P, V0, V1, nhex,
-                     Tp / 6, Tp, Tvalid, C, ldp, ldv);
+                     Tp / 6, Tp, Tvalid, C, ldp, ldv, 0);
   return check_launch("wino63_xform2");
+}
+
+// ---- the backward of those 7-tap stages (TONAL_KERNELS conv7=wino63bwd; include/tonal_hip.h states the algebra) ----
+extern "C" int tl_wino63_xform2s(const float* P, float* V0, float* V1, int64_t rows, int Tp, int Tvalid, int shift, int C, int ldp,
+                                 int ldv, void* stream) {
+  using namespace tl;
+  TL_REQUIRE(P && V0 && V1, "wino63_xform2s: null pointer");
+  TL_REQUIRE(Tp > 0 && Tp % 6 == 0 && rows > 0 && rows % Tp == 0 && Tvalid >= 0 && Tvalid <= Tp, "wino63_xform2s: Tp %% 6 == 0, whole sequences, Tvalid <= Tp needed");
+  TL_REQUIRE(shift >= 0 && shift <= 6, "wino63_xform2s: shift must lie in 0..6");
+  TL_REQUIRE(C > 0 && C % 8 == 0 && ldp >= C && ldp % 4 == 0 && ldv >= C && ldv % 8 == 0, "wino63_xform2s: C %% 8, ldp %% 4, ldv %% 8 needed");
+  const long long nhex = rows / 6;
+  const long long n = ((nhex + 1) / 2) * (C / 2);
+  TL_REQUIRE((n + 255) / 256 < (1LL << 31), "wino63_xform2s: grid too large");
+  hipLaunchKernelGGL(wino63_xform2_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P, V0, V1, nhex,
+                     Tp / 6, Tp, Tvalid, C, ldp, ldv, shift);
+  return check_launch("wino63_xform2s");
+}
+
+extern "C" int tl_wino63_ydz(const float* G, float* Y, int64_t rows, int Tp, int Tvalid, int C, int ldg, int ldv, void* stream) {
+  using namespace tl;
+  TL_REQUIRE(G && Y, "wino63_ydz: null pointer");
+  TL_REQUIRE(Tp > 0 && Tp % 6 == 0 && rows > 0 && rows % Tp == 0 && Tvalid >= 0 && Tvalid <= Tp, "wino63_ydz: Tp %% 6 == 0, whole sequences, Tvalid <= Tp needed");
+  TL_REQUIRE(C > 0 && C % 8 == 0 && ldg >= C && ldg % 4 == 0 && ldv >= C && ldv % 8 == 0, "wino63_ydz: C %% 8, ldg %% 4, ldv %% 8 needed");
+  const long long nhex = rows / 6;
+  const long long n = ((nhex + 1) / 2) * (C / 2);
+  TL_REQUIRE((n + 255) / 256 < (1LL << 31), "wino63_ydz: grid too large");
+  hipLaunchKernelGGL(wino63_ydz_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, G, Y, nhex, Tp / 6, Tp,
+                     Tvalid, C, ldg, ldv);
+  return check_launch("wino63_ydz");
 }
 
 // out[R][n] = LeakyReLU(sum_{j < 7..9} sum_k w[n][k][j] x[R + j][k] + bias[n]) from A = V0, aux = V1 (tl_wino63_xform2 of x) and
@@ -1834,6 +1910,36 @@ extern "C" int tl_conv7_wino63v_nt(const tl_nt_params* pp, void* stream) {
   const long long ngrid = nwg < 256 ? nwg : 256;
   hipLaunchKernelGGL((wino63v_nt_kernel<W_EPI_LRELU>), dim3((unsigned)ngrid), dim3(512), 0, (hipStream_t)stream, p);
   return check_launch("conv7_wino63");
+}
+
+// out[R][n] = (sum_{j < 7} sum_k Bw-taps[n][k][j] dzs[R + j][k]) * LeakyReLU'(stage input at [R][n]) from A = V0, aux = V1
+// (tl_wino63_xform2s of dz with shift 6) and Bw = tl_wino63_weights7 of the flipped, transposed weight: K = C_out, N = C_in
+extern "C" int tl_conv7_wino63v_dgrad_nt(const tl_nt_params* pp, void* stream) {
+  using namespace tl;
+  TL_REQUIRE(pp != nullptr, "conv7_wino63_dgrad: null params");
+  const tl_nt_params& p = *pp;
+  TL_REQUIRE(p.A && p.aux && p.Bw && p.out, "conv7_wino63_dgrad: null V0 (A) / V1 (aux) / Bw / out");
+  TL_REQUIRE(p.loader == W_LOAD_V && p.epilogue == W_EPI_MASK && p.row_shift == 0 && p.splitk <= 1,
+             "conv7_wino63_dgrad: loader 2 (pre-transformed operands), MASK epilogue, row_shift 0 (the rows are moved by the transform), no split-K");
+  TL_REQUIRE((p.auxbits != nullptr) != (p.mask != nullptr), "conv7_wino63_dgrad: exactly one mask source - auxbits (sign words) or mask (float rows)");
+  TL_REQUIRE(p.J == 7, "conv7_wino63_dgrad: 7 taps");
+  TL_REQUIRE(p.M > 0 && p.M % 6 == 0 && p.N > 0 && p.N % 32 == 0 && p.K >= 16 && p.K % 8 == 0, "conv7_wino63_dgrad: M %% 6, N %% 32, K %% 8, K >= 16 needed");
+  TL_REQUIRE(p.lda >= p.K && p.lda % 8 == 0 && p.ldb >= 3 * p.K && p.ldb % 8 == 0 && p.ldo >= p.N, "conv7_wino63_dgrad: bad leading dimensions");
+  TL_REQUIRE(p.auxbits == nullptr || p.ld_auxbits * 32 >= p.N, "conv7_wino63_dgrad: ld_auxbits too small");
+  TL_REQUIRE(p.mask == nullptr || p.ld_mask >= p.N, "conv7_wino63_dgrad: ld_mask too small");
+  TL_REQUIRE(p.A_rows % 2 == 0 && p.Tp > 0 && p.Tp % 6 == 0 && p.M % p.Tp == 0, "conv7_wino63_dgrad: V holds hex pairs; Tp %% 6, whole sequences");
+  TL_REQUIRE(8LL * p.N * p.ldb * 4 < (1LL << 31), "conv7_wino63_dgrad: tap set larger than a buffer resource");
+  TL_REQUIRE(128LL * 8 * p.lda * 4 + 4LL * p.K < (1LL << 31) && p.M + V6_ROWS < (1LL << 31), "conv7_wino63_dgrad: tile span / M too large");
+  TL_REQUIRE(192LL * (p.ldo > p.ld_mask ? p.ldo : p.ld_mask) * 4 < (1LL << 31), "conv7_wino63_dgrad: ldo / ld_mask too large");
+  TL_REQUIRE(p.slope >= 0.f && p.slope <= 1.f, "conv7_wino63_dgrad: LeakyReLU slope must lie in [0, 1]");
+  const long long ntm = (p.M + V6_ROWS - 1) / V6_ROWS;
+  const long long nwg = ntm * ((p.N + V6_BN - 1) / V6_BN);
+  TL_REQUIRE(nwg < (1LL << 31), "conv7_wino63_dgrad: grid too large");
+  TL_REQUIRE(p.A_rows >= ntm * V6_BH, "conv7_wino63_dgrad: V0 / V1 must hold whole 128-hex tiles (pad them with zero hexes)");
+  const long long ngrid = nwg < 256 ? nwg : 256;
+  if (p.auxbits != nullptr) hipLaunchKernelGGL((wino63v_nt_kernel<W6_EPI_MASK7>), dim3((unsigned)ngrid), dim3(512), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL((wino63v_nt_kernel<W6_EPI_MASK7F>), dim3((unsigned)ngrid), dim3(512), 0, (hipStream_t)stream, p);
+  return check_launch("conv7_wino63_dgrad");
 }
 
 // NT passes on a pre-transformed operand: A = V[hex][8][lda], A_rows = hexes in V (whole 128-hex tiles), M = output rows
@@ -1980,6 +2086,7 @@ extern "C" int tl_conv3_wino63v_tn(const tl_tn_params* pp, void* stream) {
     TL_REQUIRE(p.Mdim % 256 == 0 && p.Ndim % 64 == 0 && p.lda % 8 == 0 && p.ldb % 8 == 0 && p.lda >= p.Mdim && p.ldb >= p.Ndim &&
                p.ldc >= p.Ndim, "wino63v_tn: loader 3 needs Mdim %% 256, Ndim %% 64, lda / ldb %% 8");
     TL_REQUIRE(p.A_rows % 2 == 0 && p.B_rows % 2 == 0 && p.vd == nullptr, "wino63v_tn: loader 3: whole hex pairs in V and Y, no Vd");
+    TL_REQUIRE(p.a_hex == 0 || p.a_hex == 1, "wino63v_tn: loader 3: a_hex must be 0 or 1");
     TL_REQUIRE(p.splitk <= 65535 && (p.splitk == 1 || p.slab_stride >= 8LL * p.Mdim * p.ldc), "wino63v_tn: bad splitk / slab_stride");
     const long long ks = (p.Krows / 6 + T6_H - 1) / T6_H;
     TL_REQUIRE(p.A_rows >= ks * T6_H && p.B_rows >= ks * T6_H, "wino63v_tn: V and Y must hold whole 6-hex K-steps (pad with zero hexes)");
@@ -1992,6 +2099,7 @@ extern "C" int tl_conv3_wino63v_tn(const tl_tn_params* pp, void* stream) {
     return check_launch("wino63v_tn (both operands pre-transformed)");
   }
   TL_REQUIRE(p.A && p.B && p.slab && p.bbits, "wino63v_tn: null V/B/bbits/slab");
+  TL_REQUIRE(p.a_hex == 0, "wino63v_tn: a_hex needs loader 3 (both operands pre-transformed)");
   TL_REQUIRE(p.J == 3 && p.loader == 1, "wino63v_tn: 3 taps, UNPOOL loader (1) or pre-transformed Y (3)");
   TL_REQUIRE(p.Tp > 0 && p.Tp % 6 == 0 && p.Tvalid % 2 == 0 && p.Tvalid <= p.Tp, "wino63v_tn: Tp %% 6 == 0 and an even Tvalid <= Tp needed");
   TL_REQUIRE(p.Krows > 0 && p.Krows % p.Tp == 0 && p.Mdim > 0 && p.Ndim > 0, "wino63v_tn: bad sizes (Krows must be whole sequences)");

@@ -15,7 +15,9 @@ namespace tl {
 
 // Instantiations of wino63v_nt_kernel beyond the numbering of tl_nt_params.epilogue; tl_conv3_wino63v_nt picks them from fields
 // the parameters have: epilogue 6 without vout2 / vhalo (Y only, no Vd), epilogue 4 with row_shift 0 (the operand is Y, not Vd)
-enum { W6_EPI_MASKY_Y = 8, W6_EPI_C1W_Y = 9 };
+// (10, 11: the MASK epilogue behind the three-segment K loop of a 7-tap convolution, tl_conv7_wino63v_dgrad_nt - the mask from
+// the sign words auxbits / from the float rows `mask`)
+enum { W6_EPI_MASKY_Y = 8, W6_EPI_C1W_Y = 9, W6_EPI_MASK7 = 10, W6_EPI_MASK7F = 11 };
 
 constexpr unsigned V6_DROP = 0x80000000u;     // added to any in-range byte offset (< 2^31) it stays past every resource
 constexpr unsigned long long V6_HI = 0xffffffff00000000ull;
@@ -367,12 +369,14 @@ __device__ __forceinline__ void v6_epilogue_pool(const tl_nt_params& p, const f3
 // (MASKY without Vd still issues 256 Y stores per wave and tile: the wait counter holds 63 at the most)
 template <int EPI>
 constexpr int v6_stores() {
-  return EPI == W_EPI_POOL ? 52 : EPI == W_EPI_POOLV ? 70 : (EPI == W_EPI_MASK || EPI == W_EPI_LRELU) ? 96
+  return EPI == W_EPI_POOL ? 52 : EPI == W_EPI_POOLV ? 70
+         : (EPI == W_EPI_MASK || EPI == W_EPI_LRELU || EPI == W6_EPI_MASK7 || EPI == W6_EPI_MASK7F) ? 96
          : (EPI == W_EPI_MASKY || EPI == W6_EPI_MASKY_Y || EPI == W_EPI_GY) ? 63 : 0;
 }
 
 // ------------------------------------------------------------------------------------------
-// Input gradient: out[R][col] = y * LeakyReLU'(stage input), the sign of the input from its 1-bit array (auxbits).
+// Input gradient: out[R][col] = y * LeakyReLU'(stage input), the sign of the input from its 1-bit array (auxbits) - or
+// (FMASK, tl_conv7_wino63v_dgrad_nt behind a stage without a pool) from its float rows p.mask, read here row by row.
 // ------------------------------------------------------------------------------------------
 struct v6_pre_mask {
   uint32_t s[3];               // sign words of the half's rows: lane lr holds those of rows lr, 32 + lr, 64 + lr
@@ -386,7 +390,7 @@ __device__ __forceinline__ v6_pre_mask v6_prefetch_mask(const tl_nt_params& p, l
     if (colbase < p.N && ra + 32 * k < p.M) r.s[k] = p.auxbits[(ra + 32 * k) * (long long)p.ld_auxbits + (colbase >> 5)];
   return r;
 }
-template <bool FULL>
+template <bool FULL, bool FMASK = false>
 __device__ __forceinline__ void v6_epilogue_mask(const tl_nt_params& p, const f32x16 (&acc)[8], const v6_pre_mask& pre, long long R0,
                                                  int n0, int wm, int wn, int lr_in, int lh) {
   int lr = lr_in;                                           // (opaque copy: see v6_epilogue_c1w)
@@ -403,9 +407,15 @@ __device__ __forceinline__ void v6_epilogue_mask(const tl_nt_params& p, const f3
     inA = v6_in_bits96(Rw, p.M);
     inB = v6_in_bits96(Rw + 96, p.M);
   }
-  uint32_t sT[3];                                           // bit j of sT[k]: sign of (row 32 k + j, this lane's column)
+  uint32_t sT[3] = {0u, 0u, 0u};                            // bit j of sT[k]: sign of (row 32 k + j, this lane's column)
+  if constexpr (!FMASK) {
 #pragma unroll
-  for (int k = 0; k < 3; ++k) sT[k] = bit_transpose32(pre.s[k], lr);
+    for (int k = 0; k < 3; ++k) sT[k] = bit_transpose32(pre.s[k], lr);
+  }
+  // FMASK: the rows of the stage input through a resource of their own (a load past it - V5_OOB - returns 0)
+  const __amdgpu_buffer_rsrc_t rsM = rsrc_of(FMASK ? p.mask + Rw * (long long)p.ld_mask : p.out, FMASK ? (p.M - Rw) * (long long)p.ld_mask * 4 : 0);
+  const unsigned mvoff = (FMASK && colok) ? ((unsigned)(96 * lh) * (unsigned)p.ld_mask + (unsigned)col) * 4u : V5_OOB;
+  const unsigned ldm4 = (unsigned)p.ld_mask * 4u;
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
     float y[6];
@@ -413,7 +423,14 @@ __device__ __forceinline__ void v6_epilogue_mask(const tl_nt_params& p, const f3
 #pragma unroll
     for (int h = 0; h < 6; ++h) {
       const int r = 6 * e + h;
-      const float o = y[h] * selbit(sT[r >> 5], r & 31, 1.f, p.slope);
+      float o;
+      if constexpr (FMASK) {
+        const unsigned mo = FULL ? mvoff : selmu(mask96(inA, inB, r), mvoff, V5_OOB);
+        const float x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsM, mo, (unsigned)r * ldm4, 0));
+        o = y[h] * (x > 0.f ? 1.f : p.slope);
+      } else {
+        o = y[h] * selbit(sT[r >> 5], r & 31, 1.f, p.slope);
+      }
       const unsigned vo = FULL ? ovoff : selmu(mask96(inA, inB, r), ovoff, V5_OOB);
       __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o), rsO, vo, (unsigned)r * ldo4, 0);
     }

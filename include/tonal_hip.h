@@ -94,6 +94,9 @@ typedef struct {
    * zero from Tvalid_in conv rows on; `out` is not written.  The first hex of every 768-row tile is finished by
    * tl_wino63_vd_fixup from vhalo[tile][2][N].                                                                        */
   float* vout2;
+  /* tl_conv7_wino63v_dgrad_nt: the LeakyReLU' mask of a stage input that did NOT come out of a pooling epilogue (no sign words):
+   * its float rows mask[R][ld_mask] (> 0 ? 1 : slope); exactly one of auxbits / mask is given                            */
+  const float* mask; int ld_mask;
 } tl_nt_params;
 int tl_gemm_nt_window(const tl_nt_params* p, void* stream);
 
@@ -128,6 +131,8 @@ typedef struct {
                          first / second of them (to put them on different streams)                                  */
   int bm;             /* tl_conv3_wino43v_tn: C_in tile, 0 = 128 when Mdim % 128 == 0 else 64; 64 / 128 force one   */
   int g_tp;           /* tl_conv3_wino63v_tn: rows per sequence of B / bbits, [seq * g_tp + t']; 0: Tp / 2           */
+  int a_hex;          /* tl_conv3_wino63v_tn, loader 3: 0 or 1 - hex h of B meets hex h + a_hex of A (the third segment of a
+                         7-tap weight gradient: rows shifted by 6 ARE the next hex; hexes past A_rows read as zero)     */
 } tl_tn_params;
 int tl_gemm_tn_window(const tl_tn_params* p, void* stream);
 
@@ -225,6 +230,24 @@ int tl_conv1_fwd_v6(const float* x, const float* w, const float* b, float* P, fl
 int tl_wino63_xform2(const float* P, float* V0, float* V1, int64_t rows, int Tp, int Tvalid, int C, int ldp, int ldv, void* stream);
 int tl_wino63_weights7(const float* w, float* fwd, int O, int I, int taps, void* stream);
 int tl_conv7_wino63v_nt(const tl_nt_params* p, void* stream);
+/* The backward of those 7-tap stages on the same kernels (TONAL_KERNELS conv7=wino63bwd).  dz = the gradient at the stage's
+ * pre-activation, rows [seq * Tp + t], zero from t_out = t_in - 6 <= Tp - 6 on.
+ *   weight gradient  dW_j = sum_R dz[R] (x) x[R + j]: segment s (taps 3s .. 3s+2) is a 3-tap F(6,3) weight gradient of x shifted by
+ *                    3s rows - three tl_conv3_wino63v_tn launches with loader 3 on (V0(x), Y), (V1(x), Y) and (V0(x) with
+ *                    a_hex = 1, Y), each followed by tl_wino63_wgrad_finalize; taps 7, 8 of the last one are dropped
+ *   tl_wino63_ydz    dz rows (ldg) -> Y[rows / 6][8][ldv] = A dz (rows 6h .. 6h+5; rows from Tvalid on taken as zero), pair layout,
+ *                    plane order of tl_wino63_unpool_yvd (plane 1 = the sum of the six rows: colsum stays the bias gradient)
+ *   input gradient   dx[t] = sum_j W_j^T dz[t - j] = conv7_forward(dz moved DOWN six rows inside its sequence; taps flipped,
+ *                    channels transposed)[t]: the moved rows still fit (t_out + 6 <= Tp), so no window leaves its sequence
+ *   tl_wino63_xform2s  tl_wino63_xform2 of the rows moved down by `shift` (0 <= shift <= 6): row t of a sequence enters as row
+ *                    t + shift, rows in front of it as zeros
+ *   tl_conv7_wino63v_dgrad_nt  tl_conv7_wino63v_nt on those V0 / V1 with Bw = tl_wino63_weights7 of the flipped, transposed
+ *                    weight (I, O, 7), epilogue MASK: out[R][n] = conv * (input > 0 ? 1 : slope), the sign of the stage input
+ *                    from auxbits (sign words, ld_auxbits) or from its float rows `mask` (ld_mask) - exactly one of the two */
+int tl_wino63_ydz(const float* G, float* Y, int64_t rows, int Tp, int Tvalid, int C, int ldg, int ldv, void* stream);
+int tl_wino63_xform2s(const float* P, float* V0, float* V1, int64_t rows, int Tp, int Tvalid, int shift, int C, int ldp, int ldv,
+                      void* stream);
+int tl_conv7_wino63v_dgrad_nt(const tl_nt_params* p, void* stream);
 /* Round 5 - the input gradient of a ONE-tap pooled stage whose input is the pooled output of a 3-tap F(6,3) stage (conv4 of the
  * reference stack: nn.Conv2d(512, 256, (1,1)) + LeakyReLU + MaxPool behind conv3, models/synthesis_models.py:96-101, backward in
  * loss.backward(), models/synthesis_trainer.py:226) on the F(6,3) NT kernel: its eight batched GEMMs take the six rows of a hex
