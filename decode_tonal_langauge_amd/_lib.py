@@ -176,6 +176,13 @@ SIGNATURES = {
     "tl_gl_synth": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _L, _P]),
     "tl_gl_analyse": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _L, _D, _I, _P]),
     "tl_gl_overlap_add": (_I, [_P, _P, _P, _I, _I, _I, _I, _L, _L, _P]),
+    "tl_gather_rows_group": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _L, _L, _I, _P, _P, _P]),
+    "tl_nadam_group": (_I, [_P, _P, _P, _P, _I, _L, _L, _L, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P]),
+    "tl_nadam_lowrank_group": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _L, _L, _F, _F, _F, _F, _F, _F, _F, _F, _P,
+                                    _P]),
+    "tl_linear_rows_group": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _L, _I, _L, _L, _L, _L, _P, _P]),
+    "tl_ce_loss_group": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _L, _L, _L, _L, _L, _L, _P, _P]),
+    "tl_head_bwd_group": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -31,7 +31,26 @@ __global__ __launch_bounds__(CE_WAVES * 64) void ce_loss_kernel(const float* __r
                                                                 float* __restrict__ dlogits, float* __restrict__ dbias,
                                                                 long long* __restrict__ pred, double* loss_sum, long long* count,
                                                                 unsigned long long* confusion, int32_t* err, int B, int N,
-                                                                int ldl, int ldd, float grad_scale) {
+                                                                int ldl, int ldd, float grad_scale,
+                                                                const int32_t* __restrict__ active, long long s_logits,
+                                                                long long s_labels, long long s_dlogits, long long s_dbias,
+                                                                long long s_pred, long long s_stats) {
+  // member blockIdx.x of a group (tl_ce_loss_group): one workgroup per member, whose arrays lie s_* elements behind member 0's
+  // (s_stats: 8-byte words, for loss_sum, count, confusion and err alike); a member whose active word is 0 writes nothing.
+  // The single launch is member 0 of a group of one.
+  const int mem = blockIdx.x;
+  if (active != nullptr && active[mem] == 0) return;
+  logits += mem * s_logits;
+  if (labels != nullptr) labels += mem * s_labels;
+  if (dlogits != nullptr) dlogits += mem * s_dlogits;
+  if (dbias != nullptr) dbias += mem * s_dbias;
+  if (pred != nullptr) pred += mem * s_pred;
+  if (labels != nullptr) {
+    loss_sum += mem * s_stats;
+    count += mem * s_stats;
+    confusion += mem * s_stats;
+    err += 2 * mem * s_stats;
+  }
   __shared__ double s_db[CE_WAVES][64];
   __shared__ double s_loss[CE_WAVES];
   __shared__ int s_cnt[CE_WAVES];
@@ -124,7 +143,17 @@ __device__ __forceinline__ f32x4 hb_dact(const f32x4 h, int act, float slope) {
 
 __global__ __launch_bounds__(64) void head_bwd_kernel(const float* __restrict__ dl, const float* __restrict__ h,
                                                       const float* __restrict__ W, float* dh, float* __restrict__ dbias_h,
-                                                      float* __restrict__ dw, int B, int K, int N, int ldd, int act, float slope) {
+                                                      float* __restrict__ dw, int B, int K, int N, int ldd, int act, float slope,
+                                                      const int32_t* __restrict__ active, long long s_dl, long long s_h,
+                                                      long long s_W, long long s_dw) {
+  // member blockIdx.y of a group (tl_head_bwd_group, dw only): its dl, h, W and dw lie s_* elements behind member 0's; a member
+  // whose active word is 0 writes nothing.  The single launch is member 0 of a group of one.
+  const int mem = blockIdx.y;
+  if (active != nullptr && active[mem] == 0) return;
+  dl += mem * s_dl;
+  h += mem * s_h;
+  W += mem * s_W;
+  if (dw != nullptr) dw += mem * s_dw;
   __shared__ __attribute__((aligned(16))) float sd[HB_RB][HB_NT];
   const int K4 = K >> 2;
   const int k4 = blockIdx.x * 64 + threadIdx.x;
@@ -196,7 +225,8 @@ using namespace tl;
 template <bool SCORES>
 static int ce_launch(const float* logits, const int64_t* labels, float* dlogits, float* dbias, int64_t* pred, double* loss_sum,
                      int64_t* count, int64_t* confusion, int32_t* err, int B, int N, int ldl, int ldd, float grad_scale,
-                     void* stream) {
+                     void* stream, int M = 1, int64_t s_logits = 0, int64_t s_labels = 0, int64_t s_dlogits = 0,
+                     int64_t s_dbias = 0, int64_t s_pred = 0, int64_t s_stats = 0, const int32_t* active = nullptr) {
   TL_REQUIRE(logits != nullptr, "ce_loss: null logits");
   TL_REQUIRE(labels != nullptr || pred != nullptr, "ce_loss: null labels (allowed only to get pred alone)");
   TL_REQUIRE(labels == nullptr || (loss_sum && count && confusion && err),
@@ -206,9 +236,10 @@ static int ce_launch(const float* logits, const int64_t* labels, float* dlogits,
   TL_REQUIRE(B >= 1, "ce_loss: the batch B must be at least 1");
   TL_REQUIRE(ldl >= N, "ce_loss: row stride ldl of logits below N");
   TL_REQUIRE(dlogits == nullptr || (ldd >= N && ldd <= 64), "ce_loss: row stride ldd of dlogits must lie in [N, 64]");
-  hipLaunchKernelGGL(ce_loss_kernel<SCORES>, dim3(1), dim3(CE_WAVES * 64), 0, (hipStream_t)stream, logits,
+  hipLaunchKernelGGL(ce_loss_kernel<SCORES>, dim3((unsigned)M), dim3(CE_WAVES * 64), 0, (hipStream_t)stream, logits,
                      (const long long*)labels, dlogits, dbias, (long long*)pred, loss_sum, (long long*)count,
-                     (unsigned long long*)confusion, err, B, N, ldl, ldd, grad_scale);
+                     (unsigned long long*)confusion, err, B, N, ldl, ldd, grad_scale, active, (long long)s_logits,
+                     (long long)s_labels, (long long)s_dlogits, (long long)s_dbias, (long long)s_pred, (long long)s_stats);
   return check_launch(SCORES ? "ce_scores_loss" : "ce_loss");
 }
 
@@ -217,6 +248,21 @@ extern "C" int tl_ce_loss(const float* logits, const int64_t* labels, float* dlo
                           float grad_scale, void* stream) {
   return ce_launch<false>(logits, labels, dlogits, dbias, pred, loss_sum, count, confusion, err, B, N, ldl, ldd, grad_scale,
                           stream);
+}
+
+extern "C" int tl_ce_loss_group(const float* logits, const int64_t* labels, float* dlogits, float* dbias, int64_t* pred,
+                                double* loss_sum, int64_t* count, int64_t* confusion, int32_t* err, int M, int B, int N, int ldl,
+                                int ldd, float grad_scale, int64_t s_logits, int64_t s_labels, int64_t s_dlogits, int64_t s_dbias,
+                                int64_t s_pred, int64_t s_stats, const int32_t* active, void* stream) {
+  TL_REQUIRE(M >= 1 && M <= 65535, "ce_loss_group: the number of members M must lie in [1, 65535] (got %d)", M);
+  TL_REQUIRE(B >= 1 && N >= 1 && s_logits >= 0 && s_labels >= 0, "ce_loss_group: bad sizes or a negative member stride");
+  // members must not share what they write: every output stride covers a member's extent
+  TL_REQUIRE(M == 1 || ((!dlogits || s_dlogits >= (int64_t)B * ldd) && (!dbias || s_dbias >= N) && (!pred || s_pred >= B)),
+             "ce_loss_group: member stride of dlogits / dbias / pred shorter than a member's B x ldd / N / B elements");
+  TL_REQUIRE(M == 1 || !labels || s_stats >= (int64_t)N * N,
+             "ce_loss_group: member stride of the statistics words shorter than the N x N confusion matrix");
+  return ce_launch<false>(logits, labels, dlogits, dbias, pred, loss_sum, count, confusion, err, B, N, ldl, ldd, grad_scale,
+                          stream, M, s_logits, s_labels, s_dlogits, s_dbias, s_pred, s_stats, active);
 }
 
 extern "C" int tl_ce_scores_loss(const float* scores, const int64_t* labels, float* dlogits, float* dbias, int64_t* pred,
@@ -238,6 +284,25 @@ extern "C" int tl_head_bwd(const float* dlogits, const float* h, const float* W,
              "head_bwd: h, W, dh, dbias_h and dw must be 16-byte aligned");
   const int blocks = (K / 4 + 63) / 64;
   hipLaunchKernelGGL(head_bwd_kernel, dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream, dlogits, h, W, dh, dbias_h, dw, B,
-                     K, N, ldd, act, act == 1 ? 0.f : slope);
+                     K, N, ldd, act, act == 1 ? 0.f : slope, (const int32_t*)nullptr, 0LL, 0LL, 0LL, 0LL);
   return check_launch("head_bwd");
+}
+
+extern "C" int tl_head_bwd_group(const float* dlogits, const float* h, const float* W, float* dw, int M, int B, int K, int N,
+                                 int ldd, int64_t s_dlogits, int64_t s_h, int64_t s_W, int64_t s_dw, const int32_t* active,
+                                 void* stream) {
+  TL_REQUIRE(dlogits && h && W && dw, "head_bwd_group: null dlogits / h / W / dw");
+  TL_REQUIRE(M >= 1 && M <= 65535, "head_bwd_group: the number of members M must lie in [1, 65535] (got %d)", M);
+  TL_REQUIRE(N >= 1 && N <= 64, "head_bwd_group: the number of outputs N must lie in [1, 64]");
+  TL_REQUIRE(B >= 1 && K >= 4 && K % 4 == 0, "head_bwd_group: B >= 1 and K a positive multiple of 4 needed (columns move as float4)");
+  TL_REQUIRE(ldd >= N, "head_bwd_group: row stride ldd of dlogits below N");
+  TL_REQUIRE((((uintptr_t)h | (uintptr_t)W | (uintptr_t)dw) & 15) == 0, "head_bwd_group: h, W and dw must be 16-byte aligned");
+  TL_REQUIRE(s_dlogits >= 0 && s_h >= 0 && s_W >= 0 && s_h % 4 == 0 && s_W % 4 == 0 && s_dw % 4 == 0,
+             "head_bwd_group: the member strides of h, W and dw must be non-negative multiples of 4 elements (16-byte aligned members)");
+  TL_REQUIRE(M == 1 || s_dw >= (int64_t)N * K, "head_bwd_group: member stride of dw shorter than the N x K elements of a member");
+  const int blocks = (K / 4 + 63) / 64;
+  hipLaunchKernelGGL(head_bwd_kernel, dim3((unsigned)blocks, (unsigned)M), dim3(64), 0, (hipStream_t)stream, dlogits, h, W,
+                     (float*)nullptr, (float*)nullptr, dw, B, K, N, ldd, 0, 0.f, active, (long long)s_dlogits, (long long)s_h,
+                     (long long)s_W, (long long)s_dw);
+  return check_launch("head_bwd_group");
 }

@@ -24,6 +24,7 @@ struct gather_seg {
   unsigned n_vec;          // n_idx * n_unit * vec_per_unit   (< 2^31)
   unsigned block0;         // first workgroup of the segment
   int width;
+  long long dst_stride;    // bytes between the destinations of two members of a group (tl_gather_rows_group; 0 alone)
 };
 struct gather_args {
   gather_seg seg[4];
@@ -56,11 +57,11 @@ struct gather_args {
       ok##u ? r##u * g.sample_bytes + (long long)c##u * g.unit_bytes + (long long)off##u * (long long)sizeof(V) : 0; \
   const V val##u = *reinterpret_cast<const V*>(g.src + so##u);
 #define GATHER_STORE(u) \
-  if (ok##u) *reinterpret_cast<V*>(g.dst + (long long)v##u * (long long)sizeof(V)) = val##u;
+  if (ok##u) *reinterpret_cast<V*>(dst + (long long)v##u * (long long)sizeof(V)) = val##u;
 
 template <typename V, bool CHAN>
 __device__ __forceinline__ void gather_copy(const gather_seg& g, const long long* __restrict__ idx, int* __restrict__ err,
-                                            unsigned blk) {
+                                            unsigned blk, char* __restrict__ dst) {
   static_assert(GATHER_UNROLL == 4, "the phases below are written out four times");
   const unsigned first = blk * GATHER_PER_BLOCK + threadIdx.x;
   int bad = 0;
@@ -73,7 +74,14 @@ __device__ __forceinline__ void gather_copy(const gather_seg& g, const long long
 #undef GATHER_LOAD
 #undef GATHER_STORE
 
-__global__ __launch_bounds__(256) void gather_rows_kernel(gather_args a, const long long* __restrict__ idx, int* __restrict__ err) {
+// Member blockIdx.y of a group (tl_gather_rows_group) reads its own index vector, idx_stride words behind member 0's, and writes
+// dst_stride bytes behind member 0's destination; a member whose active word is 0 loads and writes nothing.  The single launch
+// is member 0 of a group of one.
+__global__ __launch_bounds__(256) void gather_rows_kernel(gather_args a, const long long* __restrict__ idx, int* __restrict__ err,
+                                                          const int32_t* __restrict__ active, long long idx_stride) {
+  const int mem = blockIdx.y;
+  if (active != nullptr && active[mem] == 0) return;
+  idx += mem * idx_stride;
   int s = 0;
 #pragma unroll
   for (int i = 1; i < 4; ++i)
@@ -81,12 +89,13 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(gather_args a, const l
   const gather_seg& g = a.seg[s];
   const unsigned blk = blockIdx.x - g.block0;
   const bool chan = g.chan != nullptr;
+  char* dst = g.dst + mem * g.dst_stride;
   if (g.width == 16) {
-    if (chan) gather_copy<uint4, true>(g, idx, err, blk); else gather_copy<uint4, false>(g, idx, err, blk);
+    if (chan) gather_copy<uint4, true>(g, idx, err, blk, dst); else gather_copy<uint4, false>(g, idx, err, blk, dst);
   } else if (g.width == 4) {
-    if (chan) gather_copy<uint32_t, true>(g, idx, err, blk); else gather_copy<uint32_t, false>(g, idx, err, blk);
+    if (chan) gather_copy<uint32_t, true>(g, idx, err, blk, dst); else gather_copy<uint32_t, false>(g, idx, err, blk, dst);
   } else {
-    if (chan) gather_copy<uint8_t, true>(g, idx, err, blk); else gather_copy<uint8_t, false>(g, idx, err, blk);
+    if (chan) gather_copy<uint8_t, true>(g, idx, err, blk, dst); else gather_copy<uint8_t, false>(g, idx, err, blk, dst);
   }
 }
 
@@ -94,9 +103,11 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(gather_args a, const l
 
 using namespace tl;
 
-extern "C" int tl_gather_rows(const void* const* src, void* const* dst, const int64_t* src_rows, const int64_t* C,
-                              const int64_t* inner_bytes, const int32_t* const* chan, const int64_t* n_chan, int n_seg,
-                              const int64_t* idx, int64_t n_idx, int32_t* err, void* stream) {
+// dst_stride null: the single launch (M = 1)
+static int gather_launch(const void* const* src, void* const* dst, const int64_t* dst_stride, const int64_t* src_rows,
+                         const int64_t* C, const int64_t* inner_bytes, const int32_t* const* chan, const int64_t* n_chan, int n_seg,
+                         const int64_t* idx, int64_t idx_stride, int64_t n_idx, int M, const int32_t* active, int32_t* err,
+                         void* stream) {
   TL_REQUIRE(n_seg >= 1 && n_seg <= 4, "gather_rows: 1 to 4 segments per launch, at most 4 (got %d)", n_seg);
   TL_REQUIRE(src && dst && src_rows && C && inner_bytes && chan && n_chan, "gather_rows: null table");
   TL_REQUIRE(idx && err, "gather_rows: null index vector or error word");
@@ -126,7 +137,8 @@ extern "C" int tl_gather_rows(const void* const* src, void* const* dst, const in
     g.sample_bytes = C[i] * inner_bytes[i];
     g.unit_bytes = chan[i] ? inner_bytes[i] : g.sample_bytes;
     g.n_unit = chan[i] ? (unsigned)n_chan[i] : 1u;
-    const uintptr_t al = (uintptr_t)g.src | (uintptr_t)g.dst | (uintptr_t)g.unit_bytes;
+    g.dst_stride = dst_stride ? dst_stride[i] : 0;
+    const uintptr_t al = (uintptr_t)g.src | (uintptr_t)g.dst | (uintptr_t)g.unit_bytes | (uintptr_t)g.dst_stride;
     g.width = (al & 15) == 0 ? 16 : (al & 3) == 0 ? 4 : 1;
     const long long vpu = g.unit_bytes / g.width;
     // n_idx, n_unit, C and inner_bytes are below 2^31: every product below fits 64 bits when taken one factor at a time
@@ -137,7 +149,29 @@ extern "C" int tl_gather_rows(const void* const* src, void* const* dst, const in
     g.block0 = (unsigned)blocks;
     blocks += (g.n_vec + (unsigned long long)GATHER_PER_BLOCK - 1) / GATHER_PER_BLOCK;
     TL_REQUIRE(blocks < (1ULL << 31), "gather_rows: too many workgroups");
+    TL_REQUIRE(M == 1 || g.dst_stride >= n_idx * (long long)g.n_unit * g.unit_bytes,
+               "gather_rows_group: segment %d: member stride of dst shorter than the bytes of a member's batch", i);
   }
-  hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, (const long long*)idx, (int*)err);
+  hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)blocks, (unsigned)M), dim3(256), 0, (hipStream_t)stream, a,
+                     (const long long*)idx, (int*)err, active, (long long)idx_stride);
   return check_launch("gather_rows");
+}
+
+extern "C" int tl_gather_rows(const void* const* src, void* const* dst, const int64_t* src_rows, const int64_t* C,
+                              const int64_t* inner_bytes, const int32_t* const* chan, const int64_t* n_chan, int n_seg,
+                              const int64_t* idx, int64_t n_idx, int32_t* err, void* stream) {
+  return gather_launch(src, dst, nullptr, src_rows, C, inner_bytes, chan, n_chan, n_seg, idx, 0, n_idx, 1, nullptr, err, stream);
+}
+
+extern "C" int tl_gather_rows_group(const void* const* src, void* const* dst, const int64_t* dst_stride, const int64_t* src_rows,
+                                    const int64_t* C, const int64_t* inner_bytes, const int32_t* const* chan,
+                                    const int64_t* n_chan, int n_seg, const int64_t* idx, int64_t idx_stride, int64_t n_idx, int M,
+                                    const int32_t* active, int32_t* err, void* stream) {
+  TL_REQUIRE(M >= 1 && M <= 65535, "gather_rows_group: the number of members M must lie in [1, 65535] (got %d)", M);
+  TL_REQUIRE(dst_stride != nullptr, "gather_rows_group: null table of member strides");
+  TL_REQUIRE(M == 1 || idx_stride >= n_idx, "gather_rows_group: member stride of idx shorter than the n_idx indices of a batch");
+  for (int i = 0; i < n_seg && i < 4; ++i)
+    TL_REQUIRE(dst_stride[i] >= 0, "gather_rows_group: segment %d: negative member stride", i);
+  return gather_launch(src, dst, dst_stride, src_rows, C, inner_bytes, chan, n_chan, n_seg, idx, idx_stride, n_idx, M, active, err,
+                       stream);
 }

@@ -873,7 +873,16 @@ __device__ __forceinline__ void nadam_one(float& p, float g, float& m, float& v,
 __global__ __launch_bounds__(256) void nadam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v, long long n, float cg,
                                                     float cm, float b1, float b2, float bc2, float eps, float wd,
-                                                    float gscale) {
+                                                    float gscale, const int32_t* __restrict__ active, long long sp,
+                                                    long long sg) {
+  // member blockIdx.y of a group (tl_nadam_group): its tensors lie sp (p, m, v) / sg (g) elements behind member 0's; a member
+  // whose active word is 0 is left alone.  The single launch is member 0 of a group of one.
+  const int mem = blockIdx.y;
+  if (active != nullptr && active[mem] == 0) return;
+  p += mem * sp;
+  m += mem * sp;
+  v += mem * sp;
+  g += mem * sg;
   const long long n4 = n >> 2;
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += stride) {
@@ -961,8 +970,21 @@ __global__ __launch_bounds__(256) void nadam_lowrank_kernel(float* __restrict__ 
                                                             const float* __restrict__ fb, int kr, int rows, int cols,
                                                             int ldfa, int ldfb, float cg, float cm, float b1, float b2,
                                                             float bc2, float eps, float wd, float gscale,
-                                                            float* __restrict__ dh_slab, int U, int row_tiles) {
+                                                            float* __restrict__ dh_slab, int U, int row_tiles,
+                                                            const int32_t* __restrict__ active, long long sp, long long sfa,
+                                                            long long sfb) {
   extern __shared__ __attribute__((aligned(16))) float lr_lds[];
+  if constexpr (!DH) {
+    // member blockIdx.z of a group (tl_nadam_lowrank_group): parameter and moments sp elements, factors sfa / sfb elements
+    // behind member 0's; a member whose active word is 0 is left alone.  The single launch is member 0 of a group of one.
+    const int mem = blockIdx.z;
+    if (active != nullptr && active[mem] == 0) return;
+    p += mem * sp;
+    m += mem * sp;
+    v += mem * sp;
+    fa += mem * sfa;
+    fb += mem * sfb;
+  }
   float* sa = lr_lds;                        // [kr][LR_TR]
   float* sb = lr_lds + kr * LR_TR;           // [kr][LR_TC]
   const int c0 = blockIdx.y * LR_TC;
@@ -1114,7 +1136,16 @@ __global__ __launch_bounds__(256) void splitk_bias_lrelu_kernel(const float* __r
 // weight rows stream through 16-byte loads (the weights stay in L2 across rows), partial sums meet in a wave reduction.
 __global__ __launch_bounds__(256) void linear_rows_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                           const float* __restrict__ bias, float* __restrict__ out, int K, int N,
-                                                          long long ldx, int act) {
+                                                          long long ldx, int act, const int32_t* __restrict__ active,
+                                                          long long sx, long long sw, long long sb, long long so) {
+  // member blockIdx.y of a group (tl_linear_rows_group): its x, w, bias and out lie sx, sw, sb, so elements behind member 0's;
+  // a member whose active word is 0 writes nothing.  The single launch is member 0 of a group of one.
+  const int mem = blockIdx.y;
+  if (active != nullptr && active[mem] == 0) return;
+  x += mem * sx;
+  w += mem * sw;
+  if (bias != nullptr) bias += mem * sb;
+  out += mem * so;
   const int r = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float* xr = x + (long long)r * ldx;
   const int K4 = K >> 2;
@@ -1526,8 +1557,23 @@ extern "C" int tl_nadam(float* p, const float* g, float* m, float* v, int64_t n,
   TL_REQUIRE(p && g && m && v && n > 0, "nadam: bad arguments");
   TL_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "nadam: pointers must be 16-byte aligned");
   hipLaunchKernelGGL(nadam_kernel, dim3(grid_for(n / 4 + 1, 256, 256LL * 8)), dim3(256), 0, (hipStream_t)stream, p, g,
-                     m, v, (long long)n, coef_grad, coef_mom, beta1, beta2, bias_corr2, eps, weight_decay, grad_scale);
+                     m, v, (long long)n, coef_grad, coef_mom, beta1, beta2, bias_corr2, eps, weight_decay, grad_scale,
+                     (const int32_t*)nullptr, 0LL, 0LL);
   return check_launch("nadam");
+}
+
+extern "C" int tl_nadam_group(float* p, const float* g, float* m, float* v, int M, int64_t n, int64_t s_p, int64_t s_g,
+                              float coef_grad, float coef_mom, float beta1, float beta2, float bias_corr2, float eps,
+                              float weight_decay, float grad_scale, const int32_t* active, void* stream) {
+  TL_REQUIRE(p && g && m && v && n > 0, "nadam_group: bad arguments");
+  TL_REQUIRE(M >= 1 && M <= 65535, "nadam_group: the number of members M must lie in [1, 65535] (got %d)", M);
+  TL_REQUIRE(M == 1 || (s_p >= n && s_g >= n), "nadam_group: member strides shorter than the %lld elements of a member", (long long)n);
+  TL_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0 && s_p % 4 == 0 && s_g % 4 == 0,
+             "nadam_group: pointers must be 16-byte aligned and the member strides multiples of 4 elements");
+  hipLaunchKernelGGL(nadam_kernel, dim3(grid_for(n / 4 + 1, 256, 256LL * 8), (unsigned)M), dim3(256), 0, (hipStream_t)stream, p, g,
+                     m, v, (long long)n, coef_grad, coef_mom, beta1, beta2, bias_corr2, eps, weight_decay, grad_scale, active,
+                     (long long)s_p, (long long)s_g);
+  return check_launch("nadam_group");
 }
 
 extern "C" int tl_nadam_multi(const tl_nadam_entry* entries_dev, int count, int64_t total_blocks, float coef_grad,
@@ -1554,7 +1600,8 @@ extern "C" int tl_nadam_multi_chunk(void) { return NM_CHUNK; }
 static int nadam_lowrank_launch(float* p, float* m, float* v, const float* fa, const float* fb, int kr, int rows, int cols,
                                 int ldfa, int ldfb, float coef_grad, float coef_mom, float beta1, float beta2,
                                 float bias_corr2, float eps, float weight_decay, float grad_scale, float* dh_slab, int U,
-                                int row_tiles, void* stream) {
+                                int row_tiles, void* stream, int M = 1, int64_t s_p = 0, int64_t s_fa = 0, int64_t s_fb = 0,
+                                const int32_t* active = nullptr) {
   TL_REQUIRE(p && m && v && rows > 0 && cols > 0, "nadam_lowrank: bad arguments");
   TL_REQUIRE(kr >= 0 && kr <= LR_MAXK && (kr == 0 || (fa && fb)), "nadam_lowrank: rank must be 0..%d with both factors", LR_MAXK);
   TL_REQUIRE(cols % 4 == 0 && ldfb % 4 == 0 && ldfa >= rows && ldfb >= cols, "nadam_lowrank: cols / ldfb must be multiples of 4, ld >= extent");
@@ -1586,11 +1633,26 @@ static int nadam_lowrank_launch(float* p, float* m, float* v, const float* fa, c
   if (dh)
     hipLaunchKernelGGL(nadam_lowrank_kernel<true>, dim3(gx, gy), dim3(256), lds, (hipStream_t)stream, p, m, v, fa, fb, kr, rows,
                        cols, ldfa, ldfb, coef_grad, coef_mom, beta1, beta2, bias_corr2, eps, weight_decay, grad_scale, dh_slab, U,
-                       row_tiles);
+                       row_tiles, (const int32_t*)nullptr, 0LL, 0LL, 0LL);
   else
-    hipLaunchKernelGGL(nadam_lowrank_kernel<false>, dim3(gx, gy), dim3(256), lds, (hipStream_t)stream, p, m, v, fa, fb, kr, rows,
-                       cols, ldfa, ldfb, coef_grad, coef_mom, beta1, beta2, bias_corr2, eps, weight_decay, grad_scale, nullptr, 0, 1);
+    hipLaunchKernelGGL(nadam_lowrank_kernel<false>, dim3(gx, gy, (unsigned)M), dim3(256), lds, (hipStream_t)stream, p, m, v, fa, fb,
+                       kr, rows, cols, ldfa, ldfb, coef_grad, coef_mom, beta1, beta2, bias_corr2, eps, weight_decay, grad_scale,
+                       nullptr, 0, 1, active, (long long)s_p, (long long)s_fa, (long long)s_fb);
   return check_launch("nadam_lowrank");
+}
+
+extern "C" int tl_nadam_lowrank_group(float* p, float* m, float* v, const float* fa, const float* fb, int M, int kr, int rows,
+                                      int cols, int ldfa, int ldfb, int64_t s_p, int64_t s_fa, int64_t s_fb, float coef_grad,
+                                      float coef_mom, float beta1, float beta2, float bias_corr2, float eps, float weight_decay,
+                                      float grad_scale, const int32_t* active, void* stream) {
+  TL_REQUIRE(M >= 1 && M <= 65535, "nadam_lowrank_group: the number of members M must lie in [1, 65535] (got %d)", M);
+  TL_REQUIRE(rows > 0 && cols > 0 && (M == 1 || s_p >= (int64_t)rows * cols),
+             "nadam_lowrank_group: member stride of p, m, v shorter than the rows x cols elements of a member");
+  TL_REQUIRE(M == 1 || kr <= 0 || (s_fa >= 0 && s_fb >= 0), "nadam_lowrank_group: negative member stride of a factor");
+  TL_REQUIRE(s_p % 4 == 0 && s_fb % 4 == 0,
+             "nadam_lowrank_group: the member strides of p, m, v and fb must be multiples of 4 elements (16-byte aligned members)");
+  return nadam_lowrank_launch(p, m, v, fa, fb, kr, rows, cols, ldfa, ldfb, coef_grad, coef_mom, beta1, beta2, bias_corr2, eps,
+                              weight_decay, grad_scale, nullptr, 0, 1, stream, M, s_p, s_fa, s_fb, active);
 }
 
 extern "C" int tl_nadam_lowrank(float* p, float* m, float* v, const float* fa, const float* fb, int kr, int rows, int cols,
@@ -1625,8 +1687,27 @@ extern "C" int tl_linear_rows(const float* x, const float* w, const float* bias,
   TL_REQUIRE(act == 0 || act == 1, "linear_rows: act must be 0 (none) or 1 (sigmoid)");
   TL_REQUIRE(K % 4 == 0 && ldx >= K && ldx % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)w % 16) == 0,
              "linear_rows: K and ldx must be multiples of 4 and x, w 16-byte aligned (rows are read as float4)");
-  hipLaunchKernelGGL(linear_rows_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, x, w, bias, out, K, N, (long long)ldx, act);
+  hipLaunchKernelGGL(linear_rows_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, x, w, bias, out, K, N, (long long)ldx, act,
+                     (const int32_t*)nullptr, 0LL, 0LL, 0LL, 0LL);
   return check_launch("linear_rows");
+}
+
+extern "C" int tl_linear_rows_group(const float* x, const float* w, const float* bias, float* out, int M, int B, int K, int N,
+                                    int64_t ldx, int act, int64_t s_x, int64_t s_w, int64_t s_bias, int64_t s_out,
+                                    const int32_t* active, void* stream) {
+  using namespace tl;
+  TL_REQUIRE(x && w && out, "linear_rows_group: null pointer");
+  TL_REQUIRE(M >= 1 && M <= 65535, "linear_rows_group: the number of members M must lie in [1, 65535] (got %d)", M);
+  TL_REQUIRE(B > 0 && K > 0 && N > 0 && N <= 64, "linear_rows_group: bad sizes (1 <= N <= 64 output columns)");
+  TL_REQUIRE(act == 0 || act == 1, "linear_rows_group: act must be 0 (none) or 1 (sigmoid)");
+  TL_REQUIRE(K % 4 == 0 && ldx >= K && ldx % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)w % 16) == 0,
+             "linear_rows_group: K and ldx must be multiples of 4 and x, w 16-byte aligned (rows are read as float4)");
+  TL_REQUIRE(s_x % 4 == 0 && s_w % 4 == 0 && s_x >= 0 && s_w >= 0 && s_bias >= 0,
+             "linear_rows_group: the member strides of x and w must be non-negative multiples of 4 elements (16-byte aligned members)");
+  TL_REQUIRE(M == 1 || s_out >= (int64_t)B * N, "linear_rows_group: member stride of out shorter than the B x N elements of a member");
+  hipLaunchKernelGGL(linear_rows_kernel, dim3((unsigned)B, (unsigned)M), dim3(256), 0, (hipStream_t)stream, x, w, bias, out, K, N,
+                     (long long)ldx, act, active, (long long)s_x, (long long)s_w, (long long)s_bias, (long long)s_out);
+  return check_launch("linear_rows_group");
 }
 
 extern "C" int tl_labels_from_scores(const float* tone_scores, const float* syl_scores, const float* table, float* labels,

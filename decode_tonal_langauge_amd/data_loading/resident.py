@@ -106,15 +106,7 @@ class ResidentDataset:
         t, chan = self._tensors[k], self._lists[k]
         return (rows,) + tuple(t.shape[1:]) if chan is None else (rows, len(chan)) + tuple(t.shape[2:])
 
-    def gather(self, idx: torch.Tensor, start: int, stop: int, err: torch.Tensor) -> Tuple[torch.Tensor, ...]:
-        """Rows ``idx[start:stop]`` (int64, on the device, a pointer offset - no slice kernel) of every field, one launch on
-        the current stream.  ``err``: int32 device word, bit 0 / 1 set for an index / channel out of range."""
-        for t in self._tensors:
-            _lib.require_gpu(t, "ResidentDataset.gather")
-        if not (idx.is_cuda and idx.dtype == torch.int64 and idx.is_contiguous() and 0 <= start < stop <= idx.numel()):
-            raise ValueError("ResidentDataset.gather: idx must be a contiguous int64 device vector and 0 <= start < stop <= len")
-        rows, n = stop - start, self.n_fields
-        out = tuple(torch.empty(self.batch_shape(k, rows), dtype=self._tensors[k].dtype, device=self.device) for k in range(n))
+    def _tables(self):
         if self._abi is None:              # the tables of the launch that do not change from batch to batch
             src, chan = (C.c_void_p * 4)(), (C.c_void_p * 4)()
             src_rows, n_c, inner, n_chan = (C.c_int64 * 4)(), (C.c_int64 * 4)(), (C.c_int64 * 4)(), (C.c_int64 * 4)()
@@ -127,10 +119,44 @@ class ResidentDataset:
                     n_c[k], inner[k] = t.shape[1], sample_bytes // t.shape[1]
                     n_chan[k], chan[k] = len(self._lists[k]), self._chan[k].data_ptr()
             self._abi = (src, src_rows, n_c, inner, chan, n_chan, _lib.load().tl_gather_rows)
-        src, src_rows, n_c, inner, chan, n_chan, launch = self._abi
+        return self._abi
+
+    def gather(self, idx: torch.Tensor, start: int, stop: int, err: torch.Tensor) -> Tuple[torch.Tensor, ...]:
+        """Rows ``idx[start:stop]`` (int64, on the device, a pointer offset - no slice kernel) of every field, one launch on
+        the current stream.  ``err``: int32 device word, bit 0 / 1 set for an index / channel out of range."""
+        for t in self._tensors:
+            _lib.require_gpu(t, "ResidentDataset.gather")
+        if not (idx.is_cuda and idx.dtype == torch.int64 and idx.is_contiguous() and 0 <= start < stop <= idx.numel()):
+            raise ValueError("ResidentDataset.gather: idx must be a contiguous int64 device vector and 0 <= start < stop <= len")
+        rows, n = stop - start, self.n_fields
+        out = tuple(torch.empty(self.batch_shape(k, rows), dtype=self._tensors[k].dtype, device=self.device) for k in range(n))
+        src, src_rows, n_c, inner, chan, n_chan, launch = self._tables()
         dst = (C.c_void_p * 4)(*[t.data_ptr() for t in out])
         _lib.check(launch(src, dst, src_rows, n_c, inner, chan, n_chan, n, idx.data_ptr() + 8 * start, rows, err.data_ptr(),
                           _lib.stream_ptr()), "tl_gather_rows")
+        return out
+
+    def gather_group(self, table: torch.Tensor, start: int, stop: int, err: torch.Tensor,
+                     active: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, ...]:
+        """``gather`` for M index vectors at once (``tl_gather_rows_group``): ``table`` is an (M, n) int64 device table, member
+        m's batch is rows ``table[m][start:stop]``, and field k comes back stacked as (M, rows, ...).  ``active``: M int32
+        device words; the batch of a member whose word is 0 is neither read nor written (its rows are left uninitialised)."""
+        for t in self._tensors:
+            _lib.require_gpu(t, "ResidentDataset.gather_group")
+        if not (table.is_cuda and table.dtype == torch.int64 and table.dim() == 2 and table.is_contiguous()
+                and 0 <= start < stop <= table.shape[1]):
+            raise ValueError("ResidentDataset.gather_group: table must be a contiguous (M, n) int64 device table and "
+                             "0 <= start < stop <= n")
+        M, rows, n = table.shape[0], stop - start, self.n_fields
+        out = tuple(torch.empty((M,) + self.batch_shape(k, rows), dtype=self._tensors[k].dtype, device=self.device)
+                    for k in range(n))
+        src, src_rows, n_c, inner, chan, n_chan, _single = self._tables()
+        dst = (C.c_void_p * 4)(*[t.data_ptr() for t in out])
+        stride = (C.c_int64 * 4)(*[t.stride(0) * t.element_size() for t in out])
+        _lib.check(_lib.load().tl_gather_rows_group(src, dst, stride, src_rows, n_c, inner, chan, n_chan, n,
+                                                    table.data_ptr() + 8 * start, table.shape[1], rows, M,
+                                                    None if active is None else active.data_ptr(), err.data_ptr(),
+                                                    _lib.stream_ptr()), "tl_gather_rows_group")
         return out
 
 

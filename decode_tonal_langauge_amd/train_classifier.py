@@ -19,7 +19,7 @@ import numpy as np
 import yaml
 
 from . import parallel
-from .training.classifier_pipeline import save_and_plot_results, train_joint_targets, train_separate_targets
+from .training.classifier_pipeline import ensemble_wanted, save_and_plot_results, train_joint_targets, train_separate_targets
 from .utils.config import dict_to_namespace, generate_hash_name_from_config, load_config
 
 
@@ -37,6 +37,8 @@ def run(config: dict) -> str:
         flat["fused"] = bool(train_cfg["fused"])
     if "resident" in train_cfg:            # training.params.resident: batches gathered on the device (data_loading/resident.py)
         flat["resident"] = bool(train_cfg["resident"])
+    if "ensemble" in train_cfg:            # training.params.ensemble: all seeds of a (target, model) group in one pass (needs fused)
+        flat["ensemble"] = bool(train_cfg["ensemble"])
     model_cfg = config.get("model", {})
     dataset_cfg = config.get("dataset", {})
     evaluation_cfg = config.get("evaluation", {})
@@ -47,6 +49,7 @@ def run(config: dict) -> str:
         if not hasattr(params, key):
             setattr(params, key, default)
 
+    ensemble_wanted(params)                # (raises when the key is set without fused)
     sample_dir = getattr(params, "sample_dir", "data/samples")
     if not os.path.exists(sample_dir):
         raise FileNotFoundError(f"Sample directory {sample_dir} does not exist."

@@ -54,8 +54,83 @@ def _fit_one(params: Namespace, dataset, seed: int, n_classes: int, n_channels: 
     return model, preds, true
 
 
+def ensemble_wanted(params: Namespace) -> bool:
+    """``training.params.ensemble`` (off by default): all seeds of a (target, model) group trained in one pass
+    (``models/classifier_ensemble_trainer.py``).  It runs on the HIP path only and implies the device-resident dataset."""
+    if not getattr(params, "ensemble", False):
+        return False
+    if not getattr(params, "fused", False):
+        raise ValueError("training.params.ensemble: true needs training.params.fused: true - the classifier ensemble supports "
+                         "LogisticRegressionClassifier on the HIP train step only, in a single process; there is no autograd "
+                         "ensemble")
+    return True
+
+
+def _resident(dataset, device):
+    """The ONE device-resident dataset the splits of all seeds index (``split_dataset`` takes it as it is)."""
+    from ..data_loading.resident import ResidentDataset
+    if isinstance(dataset, ResidentDataset):
+        return dataset
+    return ResidentDataset.from_tensor_dataset(dataset, device if device is not None
+                                               else ("cuda" if not dataset.tensors[0].is_cuda else None))
+
+
+def _ensemble_prologue(params: Namespace, rds, seed: int, n_classes: int, n_channels: int, seq_length: int, announce: bool):
+    """What ``_fit_one`` does for a seed before its trainer exists, in its order: the split, the ``true`` pass over the test
+    loader (it draws a base seed BEFORE the model is built), the model.  Returns (loaders, true, model, generator state)."""
+    loaders = split_dataset(rds, [params.train_ratio, params.vali_ratio, params.test_ratio], shuffling=[True, False, False],
+                            batch_size=params.batch_size, seed=int(seed), resident=True, device=params.device)
+    true = np.concatenate([b[1].cpu().numpy() for b in loaders[2]])
+    model = get_classifier_by_name(params.model, params.device, n_classes, n_channels, seq_length,
+                                   classifier_kwargs=getattr(params, "model_kwargs", None))
+    if announce:
+        print(f"Number of trainable parameters: {model.get_layer_nparams()}")
+    return loaders, true, model, torch.get_rng_state()
+
+
+def _fit_ensemble(params: Namespace, rds, seeds, n_classes: int, n_channels: int, seq_length: int, tag: str, announce: bool,
+                  states=None):
+    """``_fit_one`` for all seeds of one (target, model) group at once.  ``states``: per seed the generator state its
+    prologue starts from (None: ``set_seeds(seed)``, the start of a seed's stream).  Returns (models, preds, trues, states at
+    the end of each seed's stream)."""
+    from ..models.classifier_ensemble_trainer import ClassifierEnsembleTrainer
+    verbose = getattr(params, "verbose", 1)
+    loaders, trues, models, entered = [], [], [], []
+    for i, seed in enumerate(seeds):
+        if states is None:
+            set_seeds(int(seed))
+        else:
+            torch.set_rng_state(states[i])
+        lo, true, model, state = _ensemble_prologue(params, rds, int(seed), n_classes, n_channels, seq_length,
+                                                    announce and i == 0)
+        loaders.append(lo)
+        trues.append(true)
+        models.append(model)
+        entered.append(state)
+    run_dirs = [os.path.join(params.log_dir, f"{tag}_csv", f"subject_{params.subject_id}", "seed_" + str(int(seed)))
+                for seed in seeds]
+    trainer = ClassifierEnsembleTrainer(models, learning_rate=params.lr, weight_decay=float(getattr(params, "weight_decay", 0.0)),
+                                        log_dirs=run_dirs, verbose=verbose > 1, rng_states=entered)
+    trainer.fit([lo[0] for lo in loaders], [lo[1] for lo in loaders], max_epochs=params.epochs, patience=params.patience)
+    trainer.test([lo[2] for lo in loaders])
+    preds = [p.cpu().numpy() for p in trainer.predict([lo[2] for lo in loaders])]
+    if getattr(params, "save_checkpoints", False) and parallel.is_writer():
+        model_dir = os.path.join(params.log_dir, "model_checkpoints")
+        os.makedirs(model_dir, exist_ok=True)
+        for seed, model in zip(seeds, models):
+            path = os.path.join(model_dir, f"{tag}_{params.model_name}_seed_{int(seed)}.pt")
+            state = model.state_dict()
+            for k in state:                # the parameters are views of the group's stacks: save the member, not the stack
+                state[k] = state[k].clone()
+            torch.save(state, path)
+            if verbose > 0:
+                print(f"Model saved to {path}")
+    return models, preds, trues, [trainer.rng_state(m) for m in range(len(models))]
+
+
 def train_joint_targets(params: Namespace, seeds: np.ndarray) -> Tuple[Dict, np.ndarray, List[str]]:
     verbose = getattr(params, "verbose", 1)
+    ensemble = ensemble_wanted(params)
     handler = ClassificationSampleHandler(params)
     data = handler.load_data()
     dataset = handler.prepare_torch_dataset(data["features"], data["labels"], params.device)
@@ -70,10 +145,16 @@ def train_joint_targets(params: Namespace, seeds: np.ndarray) -> Tuple[Dict, np.
     confusion = np.zeros((n_classes, n_classes)) if "confusion_matrix" in metrics else None
     model_size = 0
     tag = "_".join(params.targets) if len(params.targets) > 1 else params.targets[0]
+    if ensemble:       # every seed in one pass; the results then take the sequential loop's way, seed after seed
+        models, all_preds, all_true, _ = _fit_ensemble(params, _resident(dataset, params.device), seeds, n_classes, n_channels,
+                                                       seq_length, tag, announce=verbose > 0)
     for i, seed in enumerate(seeds):
-        set_seeds(int(seed))
-        model, preds, true = _fit_one(params, dataset, int(seed), n_classes, n_channels, seq_length, tag,
-                                      announce=verbose > 0 and i == 0)
+        if ensemble:
+            model, preds, true = models[i], all_preds[i], all_true[i]
+        else:
+            set_seeds(int(seed))
+            model, preds, true = _fit_one(params, dataset, int(seed), n_classes, n_channels, seq_length, tag,
+                                          announce=verbose > 0 and i == 0)
         model_size = model.get_nparams()
         got = compute_classification_metrics(true, preds, metrics=metrics, verbose=verbose > 1)
         if confusion is not None and "confusion_matrix" in got:
@@ -87,6 +168,7 @@ def train_joint_targets(params: Namespace, seeds: np.ndarray) -> Tuple[Dict, np.
 
 def train_separate_targets(params: Namespace, seeds: np.ndarray) -> Tuple[Dict, np.ndarray, List[str]]:
     verbose = getattr(params, "verbose", 1)
+    ensemble = ensemble_wanted(params)
     datasets, shapes, channels, n_cls, names = {}, {}, {}, {}, {}
     for target in params.targets:
         tp = Namespace(**vars(params))
@@ -110,14 +192,31 @@ def train_separate_targets(params: Namespace, seeds: np.ndarray) -> Tuple[Dict, 
     per_target_cm = ({t: np.zeros((n_cls[t], n_cls[t])) for t in params.targets}
                      if "confusion_matrix" in metrics else None)
     model_size = 0
-    for i, seed in enumerate(seeds):
-        set_seeds(int(seed))
-        all_true, all_preds = {}, {}
+    fitted = {}
+    if ensemble:
+        # One ensemble over the seeds per target, targets in order.  The stream of seed s is consumed only by seed s's own
+        # runs, so member s of the next target continues from the state member s had at the end of this one - the stream the
+        # seed-major loop below gives it.  (Nothing on this path draws from the NumPy or Python generators set_seeds also sets.)
+        states = None
         for target, dataset in datasets.items():
             if verbose > 1:
-                print(f"Training for target: {target} with seed {seed}...")
-            model, preds, true = _fit_one(params, dataset, int(seed), n_cls[target], shapes[target][0],
-                                          shapes[target][1], target, announce=verbose > 0 and i == 0)
+                print(f"Training for target: {target} with seeds {seeds.tolist()}...")
+            models, preds, trues, states = _fit_ensemble(params, _resident(dataset, params.device), seeds, n_cls[target],
+                                                         shapes[target][0], shapes[target][1], target, announce=verbose > 0,
+                                                         states=states)
+            fitted[target] = (models, preds, trues)
+    for i, seed in enumerate(seeds):
+        if not ensemble:
+            set_seeds(int(seed))
+        all_true, all_preds = {}, {}
+        for target, dataset in datasets.items():
+            if ensemble:
+                model, preds, true = (fitted[target][k][i] for k in range(3))
+            else:
+                if verbose > 1:
+                    print(f"Training for target: {target} with seed {seed}...")
+                model, preds, true = _fit_one(params, dataset, int(seed), n_cls[target], shapes[target][0],
+                                              shapes[target][1], target, announce=verbose > 0 and i == 0)
             model_size += model.get_nparams()
             all_true[target], all_preds[target] = true, preds
             got = compute_classification_metrics(true, preds, metrics=metrics)

@@ -411,6 +411,28 @@ int tl_stage_step(float* scalars_dev, uint64_t* seed_dev, float coef_grad, float
 int tl_gather_rows(const void* const* src, void* const* dst, const int64_t* src_rows, const int64_t* C,
                    const int64_t* inner_bytes, const int32_t* const* chan, const int64_t* n_chan, int n_seg,
                    const int64_t* idx, int64_t n_idx, int32_t* err, void* stream);
+/* ---- group launches: M models of equal shape ("members") trained side by side (_classifier_ensemble_engine.py) -----------
+ * Every tl_*_group entry is its single-model neighbour with a member dimension on the grid: member m works on pointers
+ * s_* ELEMENTS (of the pointer's type, unless stated otherwise) behind the ones given, which are member 0's.  It is the SAME
+ * kernel - the single entry launches it with M = 1 - so a member's outputs have the bits of the single launch on the same
+ * inputs.  `active` (M device int32 words, may be null = all): the workgroups of a member whose word is 0 return before their
+ * first load and write nothing - no parameter, moment, statistics word or output.  1 <= M <= 65535.  Where the single entry
+ * wants a pointer 16-byte aligned, the member stride must be a multiple of 16 bytes; the strides of everything a member
+ * writes must cover its extent (members never share an output).  Every other check is the single entry's.
+ *
+ * tl_gather_rows with M index vectors over the one dataset: idx is an (M, idx_stride) int64 table and member m's batch is
+ * rows idx[m][0 .. n_idx) (pass idx + start, as with the single entry), written dst_stride[s] BYTES behind member 0's
+ * destination of segment s: x as (M, B, ...), y as (M, B).  The access width also has to divide dst_stride[s].  One error word,
+ * ORed into as by the single entry.                                                                                       */
+int tl_gather_rows_group(const void* const* src, void* const* dst, const int64_t* dst_stride, const int64_t* src_rows,
+                         const int64_t* C, const int64_t* inner_bytes, const int32_t* const* chan, const int64_t* n_chan,
+                         int n_seg, const int64_t* idx, int64_t idx_stride, int64_t n_idx, int M, const int32_t* active,
+                         int32_t* err, void* stream);
+/* tl_nadam on M tensors of n elements each: p, m, v at member stride s_p, g at s_g (multiples of 4; a bias row of N floats is
+ * therefore stored at row stride 4 ceil(N / 4))                                                                            */
+int tl_nadam_group(float* p, const float* g, float* m, float* v, int M, int64_t n, int64_t s_p, int64_t s_g, float coef_grad,
+                   float coef_mom, float beta1, float beta2, float bias_corr2, float eps, float weight_decay, float grad_scale,
+                   const int32_t* active, void* stream);
 int tl_nadam_multi_dev(const tl_nadam_entry* entries_dev, int count, int64_t total_blocks, const float* scalars_dev,
                        float beta1, float beta2, float eps, float weight_decay, float grad_scale, void* stream);
 /* the same update for a parameter (rows x cols) whose gradient is low rank, g = fa^T . fb with
@@ -419,6 +441,12 @@ int tl_nadam_multi_dev(const tl_nadam_entry* entries_dev, int count, int64_t tot
 int tl_nadam_lowrank(float* p, float* m, float* v, const float* fa, const float* fb, int kr, int rows, int cols,
                      int ldfa, int ldfb, float coef_grad, float coef_mom, float beta1, float beta2,
                      float bias_corr2, float eps, float weight_decay, float grad_scale, void* stream);
+/* ... for M members (see the group launches above): grid (row tiles, column tiles, M); p, m, v at member stride s_p, the
+ * factors at s_fa (a member's dlogits, B x ldfa) and s_fb (a member's batch rows, B x ldfb); s_p and s_fb multiples of 4   */
+int tl_nadam_lowrank_group(float* p, float* m, float* v, const float* fa, const float* fb, int M, int kr, int rows, int cols,
+                           int ldfa, int ldfb, int64_t s_p, int64_t s_fa, int64_t s_fb, float coef_grad, float coef_mom,
+                           float beta1, float beta2, float bias_corr2, float eps, float weight_decay, float grad_scale,
+                           const int32_t* active, void* stream);
 /* ... and, in the same pass over p, dh = fa[0:U] . p_OLD (U x cols): the last step of the label LSTM's BPTT
  * (dh_1 = dgates_2 . W_hh reads the weight as it was BEFORE this update, and the W_hh gradient has no term for the first step,
  * so the update does not wait for it; torch's LSTM backward inside loss.backward(), models/synthesis_trainer.py:226, followed by
@@ -443,6 +471,10 @@ int tl_splitk_bias_lrelu(const float* slab, const float* bias, float* out, int n
  * with (models/deep_classifiers.py:97-99,265-267).  N <= 64, K % 4 == 0, 16-byte aligned rows.                        */
 int tl_linear_rows(const float* x, const float* w, const float* bias, float* out, int B, int K, int N, int64_t ldx, int act,
                    void* stream);
+/* ... for M members (see the group launches above): grid (B, M); x (M, B, K), w (M, N, K), bias and out at the member strides
+ * s_x, s_w, s_bias, s_out; s_x and s_w multiples of 4                                                                      */
+int tl_linear_rows_group(const float* x, const float* w, const float* bias, float* out, int M, int B, int K, int N, int64_t ldx,
+                         int act, int64_t s_x, int64_t s_w, int64_t s_bias, int64_t s_out, const int32_t* active, void* stream);
 /* the whole label pass of a train step (models/synthesis_trainer.py:207-218) in one launch: tone = argmax of tone_scores
  * (B, n_tone_cls), syl = argmax of syl_scores (B, n_syl_cls) (first maximum), the gather of tl_tone_dynamics (n_rows table
  * rows) and, if pair is given, pair[b] = tone * n_syl + syl                                                        */
@@ -466,6 +498,13 @@ int tl_labels_from_scores(const float* tone_scores, const float* syl_scores, con
  * labels = null: only pred is written (loss_sum, count, confusion and err are not touched and may be null).               */
 int tl_ce_loss(const float* logits, const int64_t* labels, float* dlogits, float* dbias, int64_t* pred, double* loss_sum,
                int64_t* count, int64_t* confusion, int32_t* err, int B, int N, int ldl, int ldd, float grad_scale, void* stream);
+/* ... for M members (see the group launches above): one 16-wave workgroup per member, so each member's sums keep the fixed
+ * order of the single launch.  s_stats is the member stride of loss_sum, count, confusion AND err alike, in 8-byte words (the
+ * engine keeps M x (3 + N N) int64 words: loss, count, err, confusion); dbias and pred are rows per member.                  */
+int tl_ce_loss_group(const float* logits, const int64_t* labels, float* dlogits, float* dbias, int64_t* pred, double* loss_sum,
+                     int64_t* count, int64_t* confusion, int32_t* err, int M, int B, int N, int ldl, int ldd, float grad_scale,
+                     int64_t s_logits, int64_t s_labels, int64_t s_dlogits, int64_t s_dbias, int64_t s_pred, int64_t s_stats,
+                     const int32_t* active, void* stream);
 /* the same step for the deep classifiers, whose forward ends in a sigmoid and whose trainer applies nn.CrossEntropyLoss to those
  * sigmoid outputs (models/deep_classifiers.py:97-99 under models/classifier_trainer.py:72-89): `scores` (B, N) are the fp32
  * s = sigmoid(z) exactly as tl_linear_rows(act = 1) writes them, the loss is CE(s), and
@@ -488,6 +527,10 @@ int tl_ce_scores_loss(const float* scores, const int64_t* labels, float* dlogits
  * aligned.  With dh null and h = x this is the weight gradient of LogisticRegressionClassifier's layer.                    */
 int tl_head_bwd(const float* dlogits, const float* h, const float* W, float* dh, float* dbias_h, float* dw, int B, int K, int N,
                 int ldd, int act, float slope, void* stream);
+/* ... for M members (see the group launches above), the logistic dense form only: dw[m] = dlogits[m]^T . h[m] (no dh, no
+ * dbias_h, no activation); grid (column blocks, M); s_h, s_W and s_dw multiples of 4                                        */
+int tl_head_bwd_group(const float* dlogits, const float* h, const float* W, float* dw, int M, int B, int K, int N, int ldd,
+                      int64_t s_dlogits, int64_t s_h, int64_t s_W, int64_t s_dw, const int32_t* active, void* stream);
 
 /* ---- training of CNNRNNClassifier (models/deep_classifiers.py:158-343 under models/classifier_trainer.py:72-89) ----------
  * The LSTM pair keeps ROWS TIME-MAJOR (row = t * B + b), so the kept arrays are directly the (T B)-row operands of the

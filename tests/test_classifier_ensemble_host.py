@@ -1,0 +1,249 @@
+"""CPU: the host side of the classifier ensemble - every member's epoch orders and the state of torch's global generator are
+those of stock loaders run seed after seed (one target, and two targets in the seed-major order of the pipeline), what the
+ensemble does not take is refused with the supported set, and the ``tl_*_group`` entry points are declared, exported and
+validate their arguments without a launch."""
+import ctypes as C
+import os
+import re
+from argparse import Namespace
+
+import pytest
+import torch
+from torch.utils.data import TensorDataset
+
+from decode_tonal_langauge_amd.data_loading.dataloaders import split_dataset
+from decode_tonal_langauge_amd.data_loading.resident import ResidentDataset, ResidentLoader
+from decode_tonal_langauge_amd.utils.utils import set_seeds
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RATIOS, SHUFFLE, BATCH = [0.7, 0.1, 0.2], [True, False, False], 8
+SEEDS, EPOCHS = (3, 11, 42), 3
+GROUP = ("tl_linear_rows_group", "tl_ce_loss_group", "tl_head_bwd_group", "tl_nadam_lowrank_group", "tl_nadam_group",
+         "tl_gather_rows_group")
+
+
+def _dataset(n):
+    return TensorDataset(torch.arange(n), torch.arange(n) * 2)        # the values are the global sample numbers
+
+
+def _sequential_run(tds, seed):
+    """What one sequential run of a seed draws (the caller has seeded the stream): the split, one pass over the test loader,
+    per epoch one train and one validation iteration, then a test and a predict pass.  Every batch, in order."""
+    train, val, test = split_dataset(tds, RATIOS, SHUFFLE, batch_size=BATCH, seed=seed)
+    passes = [test] + [train, val] * EPOCHS + [test, test]
+    return [[b[0].tolist() for b in loader] for loader in passes]
+
+
+def _ensemble_target(tds, states):
+    """The same passes for all seeds at once through the order helper.  ``states``: None (every seed starts its stream) or
+    the members' states at the end of the target before.  Returns (per seed the batches of every pass, the states after)."""
+    from decode_tonal_langauge_amd.models.classifier_ensemble_trainer import MemberStreams, check_loaders, draw_orders
+    rds = ResidentDataset.from_tensor_dataset(tds, device="cpu")                   # ONE dataset for all seeds
+    loaders, entered, got = [], [], [[] for _ in SEEDS]
+
+    def batches(order):
+        order = order.tolist()
+        return [order[i:i + BATCH] for i in range(0, len(order), BATCH)]
+
+    for i, seed in enumerate(SEEDS):                                               # the per-seed prologue, seed after seed
+        if states is None:
+            set_seeds(seed)
+        else:
+            torch.set_rng_state(states[i])
+        lo = split_dataset(rds, RATIOS, SHUFFLE, batch_size=BATCH, seed=seed, resident=True, device="cpu")
+        assert all(isinstance(l, ResidentLoader) and l.dataset is rds for l in lo)
+        got[i].append(list(lo[2].iter_indices()))                                  # the `true` pass
+        loaders.append(lo)
+        entered.append(torch.get_rng_state())
+    streams = MemberStreams(len(SEEDS), entered)
+    members = list(range(len(SEEDS)))
+    for which in [0, 1] * EPOCHS + [2, 2]:
+        group = [lo[which] for lo in loaders]
+        check_loaders(group, len(SEEDS))
+        for m, order in draw_orders(group, streams, members).items():
+            got[m].append(batches(order))
+    streams.leave()
+    return got, streams.states
+
+
+def test_orders_and_random_stream_match_stock_loaders_run_seed_after_seed():
+    tds = _dataset(53)
+    want = []
+    for seed in SEEDS:
+        set_seeds(seed)
+        want.append(_sequential_run(tds, seed))
+    state = torch.get_rng_state()
+    assert [len(b) for b in want[0][1]] == [8, 8, 8, 8, 5]                          # 37 train samples: four full batches, a ragged one
+    torch.manual_seed(12345)                                                       # (nothing may lean on the state left above)
+    got, states = _ensemble_target(tds, None)
+    for i, seed in enumerate(SEEDS):
+        assert got[i] == want[i], seed
+    assert torch.equal(torch.get_rng_state(), state)
+    assert torch.equal(states[-1], state)
+    assert len({tuple(map(tuple, g[1])) for g in got}) == len(SEEDS)                # the members do train on different orders
+
+
+def test_two_targets_continue_each_members_own_stream():
+    targets = [_dataset(53), _dataset(61)]
+    want = []
+    for seed in SEEDS:                                                             # the pipeline's loop: seeds outside, targets inside
+        set_seeds(seed)
+        want.append([_sequential_run(tds, seed) for tds in targets])
+    state = torch.get_rng_state()
+    torch.manual_seed(999)
+    states = None
+    for t, tds in enumerate(targets):                                              # the ensemble: targets outside
+        got, states = _ensemble_target(tds, states)
+        for i, seed in enumerate(SEEDS):
+            assert got[i] == want[i][t], (seed, t)
+    assert torch.equal(torch.get_rng_state(), state)
+
+
+def test_a_stopped_member_draws_nothing():
+    from decode_tonal_langauge_amd.models.classifier_ensemble_trainer import MemberStreams, draw_orders
+    rds = ResidentDataset.from_tensor_dataset(_dataset(53), device="cpu")
+    loaders = [ResidentLoader(rds, range(40), batch_size=BATCH, shuffle=True) for _ in range(3)]
+    torch.manual_seed(5)
+    streams = MemberStreams(3)
+    before = [s.clone() for s in streams.states]
+    orders = draw_orders(loaders, streams, [0, 2])
+    assert sorted(orders) == [0, 2] and torch.equal(orders[0], orders[2])          # equal states, equal draws
+    assert torch.equal(streams.states[1], before[1]) and not torch.equal(streams.states[0], before[0])
+    with pytest.raises(ValueError, match="3 generator states"):
+        MemberStreams(3, before[:2])
+
+
+# ------------------------------------------------------------------ refusals
+def test_engine_refuses_what_it_does_not_take(monkeypatch):
+    from decode_tonal_langauge_amd import parallel
+    from decode_tonal_langauge_amd._classifier_ensemble_engine import ClassifierEnsembleEngine
+    from decode_tonal_langauge_amd.models.classifier_ensemble_trainer import ClassifierEnsembleTrainer
+    from decode_tonal_langauge_amd.models.simple_classifiers import LogisticRegressionClassifier as LR, ShallowNNClassifier
+    cases = (([LR(40, 3), ShallowNNClassifier(40, 3, 20, "ReLU")], "model ShallowNNClassifier"),
+             ([LR(40, 3), LR(44, 3)], "member 1 has shape (44 -> 3)"),
+             ([LR(40, 3), LR(40, 4)], "member 1 has shape (40 -> 4)"),
+             ([LR(42, 3)], "input_dim 42"),
+             ([LR(40, 65)], "n_classes 65"),
+             ([], "no models"),
+             ([LR(40, 3), LR(40, 3)], "cpu"))                                      # parameters on the CPU: no fallback
+    for build in (ClassifierEnsembleEngine, ClassifierEnsembleTrainer):
+        for models, what in cases:
+            with pytest.raises(ValueError, match="classifier ensemble supports one or more LogisticRegressionClassifier") as e:
+                build(models)
+            assert what in str(e.value), (what, str(e.value))
+    monkeypatch.setattr(parallel, "world", lambda: (0, 2))
+    with pytest.raises(ValueError, match="classifier ensemble supports") as e:
+        ClassifierEnsembleEngine([LR(40, 3), LR(40, 3)])
+    assert "process group of 2 ranks" in str(e.value) and "single process" in str(e.value)
+
+
+def test_loaders_must_share_one_dataset_subset_size_and_batch_size():
+    from decode_tonal_langauge_amd.models.classifier_ensemble_trainer import check_loaders
+    tds = _dataset(53)
+    rds, other = ResidentDataset.from_tensor_dataset(tds, device="cpu"), ResidentDataset.from_tensor_dataset(tds, device="cpu")
+    good = [ResidentLoader(rds, range(m, m + 20), batch_size=8) for m in range(3)]
+    check_loaders(good, 3)
+    stock = split_dataset(tds, RATIOS, SHUFFLE, batch_size=8, seed=1)[0]
+    for bad, what in (([good[0], good[1]], "2 loaders for 3 members"),
+                      ([good[0], stock, good[2]], "loader 1 is a DataLoader"),
+                      ([good[0], good[1], ResidentLoader(other, range(20), batch_size=8)], "loader 2 reads another dataset"),
+                      ([good[0], ResidentLoader(rds, range(19), batch_size=8), good[2]], "loader 1 has 19 samples"),
+                      ([good[0], good[1], ResidentLoader(rds, range(20), batch_size=4)], "loader 2 has batch size 4"),
+                      ([ResidentLoader(rds, [], batch_size=8)] * 3, "empty subset")):
+        with pytest.raises(ValueError, match="SAME ResidentDataset object, with equal subset sizes and equal batch size") as e:
+            check_loaders(bad, 3)
+        assert what in str(e.value), (what, str(e.value))
+
+
+def test_ensemble_needs_fused_and_is_off_by_default():
+    from decode_tonal_langauge_amd import train_classifier
+    from decode_tonal_langauge_amd.training.classifier_pipeline import ensemble_wanted
+    assert ensemble_wanted(Namespace()) is False and ensemble_wanted(Namespace(ensemble=False)) is False
+    assert ensemble_wanted(Namespace(ensemble=True, fused=True)) is True
+    for params in (Namespace(ensemble=True), Namespace(ensemble=True, fused=False, resident=True)):
+        with pytest.raises(ValueError, match="supports LogisticRegressionClassifier on the HIP train step only"):
+            ensemble_wanted(params)
+    with pytest.raises(ValueError, match="needs training.params.fused: true"):
+        train_classifier.run({"training": {"params": {"ensemble": True, "io": {"sample_dir": "/nonexistent"}}}})
+    with pytest.raises(FileNotFoundError):                                          # with fused the key is accepted
+        train_classifier.run({"training": {"params": {"ensemble": True, "fused": True, "io": {"sample_dir": "/nonexistent"}}}})
+
+
+# ------------------------------------------------------------------ ABI
+def test_group_entry_points_are_declared_typed_and_exported():
+    from decode_tonal_langauge_amd import _lib
+    lib = _lib.load()
+    header = open(os.path.join(ROOT, "include", "tonal_hip.h")).read()
+    for name in GROUP:
+        m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*?)\)\s*;", header, re.S)
+        assert m, f"{name} is not declared in include/tonal_hip.h"
+        assert name in _lib.SIGNATURES and hasattr(lib, name), name
+        assert len(m.group(1).split(",")) == len(_lib.SIGNATURES[name][1]), name
+
+
+def test_group_argument_validation_without_gpu():
+    from decode_tonal_langauge_amd import _lib
+    lib = _lib.load()
+    err = lib.tl_last_error
+
+    def lin(x=16, w=16, b=16, out=16, M=3, B=4, K=8, N=3, ldx=8, sx=32, sw=24, sb=4, so=12):
+        return lib.tl_linear_rows_group(x, w, b, out, M, B, K, N, ldx, 0, sx, sw, sb, so, None, None)
+    for name in ("x", "w", "out"):
+        assert lin(**{name: None}) == -1 and b"null pointer" in err(), name
+    assert lin(M=0) == -1 and b"[1, 65535]" in err()
+    assert lin(sx=34) == -1 and lin(sw=26) == -1 and b"multiples of 4 elements" in err()
+    assert lin(so=11) == -1 and b"member stride of out" in err()
+    assert lin(K=6) == -1 and lin(x=20) == -1 and b"16-byte aligned" in err()
+
+    def ce(logits=16, labels=16, dl=16, db=16, pred=16, ls=16, cnt=24, cm=40, er=32, M=3, B=4, N=3, ldl=3, ldd=4, sl=12, sy=4,
+           sdl=16, sdb=4, sp=4, ss=12):
+        return lib.tl_ce_loss_group(logits, labels, dl, db, pred, ls, cnt, cm, er, M, B, N, ldl, ldd, 0.25, sl, sy, sdl, sdb, sp,
+                                    ss, None, None)
+    assert ce(logits=None) == -1 and b"null logits" in err()
+    assert ce(labels=None, pred=None) == -1 and b"null labels" in err()
+    for name in ("ls", "cnt", "cm", "er"):
+        assert ce(**{name: None}) == -1 and b"not optional" in err(), name
+    assert ce(M=0) == -1 and b"[1, 65535]" in err()
+    assert ce(sdl=15) == -1 and ce(sdb=2) == -1 and ce(sp=3) == -1 and b"member stride of dlogits / dbias / pred" in err()
+    assert ce(ss=8) == -1 and b"statistics words" in err()
+    assert ce(N=65, ldl=65, sdb=68, ss=4225) == -1 and b"[1, 64]" in err()
+
+    def hb(dl=16, h=16, W=16, dw=16, M=3, B=4, K=8, N=3, ldd=4, sdl=16, sh=32, sW=24, sdw=24):
+        return lib.tl_head_bwd_group(dl, h, W, dw, M, B, K, N, ldd, sdl, sh, sW, sdw, None, None)
+    for name in ("dl", "h", "W", "dw"):
+        assert hb(**{name: None}) == -1 and b"null" in err(), name
+    assert hb(M=0) == -1 and b"[1, 65535]" in err()
+    assert hb(sh=30) == -1 and hb(sW=22) == -1 and hb(sdw=26) == -1 and b"multiples of 4 elements" in err()
+    assert hb(sdw=20) == -1 and b"member stride of dw" in err()
+    assert hb(K=6) == -1 and b"multiple of 4" in err()
+
+    def low(p=16, m=16, v=16, fa=16, fb=16, M=3, kr=4, rows=3, cols=8, ldfa=4, ldfb=8, sp=24, sfa=16, sfb=32):
+        return lib.tl_nadam_lowrank_group(p, m, v, fa, fb, M, kr, rows, cols, ldfa, ldfb, sp, sfa, sfb, 1e-3, 1e-3, 0.9, 0.999, 0.5,
+                                          1e-8, 0.0, 1.0, None, None)
+    for name in ("p", "m", "v", "fa", "fb"):
+        assert low(**{name: None}) == -1, name
+    assert low(M=0) == -1 and b"[1, 65535]" in err()
+    assert low(sp=26) == -1 and low(sfb=34) == -1 and b"multiples of 4 elements" in err()
+    assert low(sp=20) == -1 and b"shorter than the rows x cols" in err()
+    assert low(kr=65) == -1 and b"rank must be" in err()
+
+    def nad(p=16, g=16, m=16, v=16, M=3, n=3, sp=4, sg=4):
+        return lib.tl_nadam_group(p, g, m, v, M, n, sp, sg, 1e-3, 1e-3, 0.9, 0.999, 0.5, 1e-8, 0.0, 1.0, None, None)
+    for name in ("p", "g", "m", "v"):
+        assert nad(**{name: None}) == -1 and b"bad arguments" in err(), name
+    assert nad(M=0) == -1 and b"[1, 65535]" in err()
+    assert nad(sp=3, sg=3) == -1 and b"multiples of 4 elements" in err()        # a bias row of 3 floats: store it at stride 4
+    assert nad(n=5) == -1 and b"shorter than the 5 elements" in err()
+
+    P4, L4 = C.c_void_p * 4, C.c_int64 * 4
+    ptrs, ones, none, zeros = P4(16, 16, 16, 16), L4(1, 1, 1, 1), P4(), L4()
+
+    def gat(dst_stride=L4(64, 64, 64, 64), n_seg=2, idx=16, idx_stride=40, n_idx=8, M=3, er=16, inner=L4(8, 8, 8, 8)):
+        return lib.tl_gather_rows_group(ptrs, ptrs, dst_stride, ones, ones, inner, none, zeros, n_seg, idx, idx_stride, n_idx, M,
+                                        None, er, None)
+    assert gat(M=0) == -1 and b"[1, 65535]" in err()
+    assert gat(dst_stride=None) == -1 and b"member strides" in err()
+    assert gat(idx=None) == -1 and gat(er=None) == -1 and b"null index vector or error word" in err()
+    assert gat(idx_stride=7) == -1 and b"member stride of idx" in err()
+    assert gat(dst_stride=L4(63, 64, 64, 64)) == -1 and b"member stride of dst" in err()
+    assert gat(n_seg=5) == -1 and b"at most 4" in err()
