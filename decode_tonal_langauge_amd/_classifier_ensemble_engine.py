@@ -1,62 +1,103 @@
-"""All seeds of a classifier experiment in one pass: M ``LogisticRegressionClassifier``s of equal shape ("members") trained
-side by side by the launches that train one (``_simple_classifier_engine``).
+"""All seeds of a classifier experiment in one pass: M ``LogisticRegressionClassifier``s or M ``ShallowNNClassifier``s of equal
+shape ("members") trained side by side by the launches that train one (``_simple_classifier_engine``).
 
 A step of the single engine is a handful of launches that occupy a few of the 256 CUs for a few microseconds each; the group
 kernels (``tl_*_group``, include/tonal_hip.h) are the same kernels with a member dimension on the grid, so the step of M
 members costs the same number of launches.  They are the SAME kernels - the single entry points launch them with M = 1 - and
 every member therefore gets the bits ``SimpleClassifierEngine`` would give it on the same batches.
 
-Storage is stacked: W (M, N, K), the biases (M, r4(N)) (a row of N floats is not 16-byte aligned, which the update kernels
-want), moments, gradients, logits, dlogits, pred and the statistics words (M, 3 + N^2) likewise.  Each module's parameters
-become views of the stacks, so ``state_dict()``, ``torch.save`` and inference through the module keep working.
+Storage is stacked, per Linear layer: the weight (M, out, in), the bias (M, r4(out)) (a row of N floats is not 16-byte aligned,
+which the update kernels want), moments and the bias gradient likewise; logits, dlogits, pred, the hidden activations and their
+gradient (M, B, ...) and the statistics words (M, 3 + N^2).  Each module's parameters become views of the stacks, so
+``state_dict()``, ``torch.save`` and inference through the module keep working.
+
+The shallow step mirrors the single engine's low-rank route launch for launch: the hidden layer on the NT GEMM's group form
+(bias and ReLU / LeakyReLU in its epilogue), the output layer on ``tl_linear_rows_group``, ``tl_ce_loss_group``,
+``tl_head_bwd_act_group`` (dh with the activation derivative, the hidden bias gradient - it reads the output weight BEFORE its
+update), then the two weights as rank-B updates and the two biases.  Its training batches hold at most
+``FusedNAdam.LOWRANK_MAX`` rows: above that the single engine forms the hidden weight gradient on TN GEMM kernels that have no
+member dimension.  Evaluation and prediction take any batch size.  The logistic group keeps its dense route.
 
 ``set_active(mask)``: the workgroups of a member whose mask word is 0 return before their first load - a member that stopped
 early stays frozen, to the bit, while the others go on.  The NAdam schedule is one counter shared by the active members: they
 advance in lockstep from step 0, and a member never resumes, so its step count freezes with its parameters.
 
-Out of scope (refused with the supported set): every other model class, members of differing shape, a multi-rank process
-group.  There is no CPU fallback."""
+Out of scope (refused with the supported set): every other model class, a group mixing the two classes, members of differing
+shape or activation, a multi-rank process group.  There is no CPU fallback."""
 from __future__ import annotations
 
 from typing import List, Optional, Sequence, Tuple
 
 import torch
+import torch.nn as nn
 
 from . import _lib, parallel
-from ._launch import r4
-from ._lib import check, ptr
+from ._launch import launch_nt_group, r4
+from ._lib import EPI_LRELU, LOAD_DIRECT, check, ptr
 from .models.utils import split_decay_groups
 from .optim import FusedNAdam
 
-SUPPORTED = ("the classifier ensemble supports one or more LogisticRegressionClassifier of equal input_dim and n_classes with "
-             "fp32 parameters on one CUDA device, input_dim % 4 == 0 and n_classes <= 64, in a single process (no multi-rank "
-             "process group); ShallowNNClassifier and the deep classifiers train one model at a time (ClassifierTrainer)")
+SUPPORTED = ("the classifier ensemble supports one or more LogisticRegressionClassifier of equal input_dim and n_classes, or one or "
+             "more ShallowNNClassifier of equal input_dim, hidden_dim and n_classes with the same ReLU or LeakyReLU activation "
+             "(equal negative_slope), hidden_dim % 4 == 0 and training batches of at most 64 rows - never a mix of the two "
+             "classes - with biases and fp32 parameters on one CUDA device, input_dim % 4 == 0 and n_classes <= 64, in a single "
+             "process (no multi-rank process group); the deep classifiers train one model at a time (ClassifierTrainer)")
 
 
 def refuse(why: str):
     raise ValueError(f"{why}: {SUPPORTED}")
 
 
+def _shape(m) -> tuple:
+    hidden = getattr(m, "hidden", None)
+    return (int(m.input_dim),) + ((int(hidden.out_features),) if hidden is not None else ()) + (int(m.n_classes),)
+
+
+def _arrow(shape: tuple) -> str:
+    return "(" + " -> ".join(str(s) for s in shape) + ")"
+
+
+def _activation(m) -> Tuple[int, float]:
+    """(act code of ``tl_head_bwd``, slope) of a shallow member's activation."""
+    return (1, 0.0) if isinstance(m.activation, nn.ReLU) else (2, float(m.activation.negative_slope))
+
+
 def check_supported(models: Sequence) -> None:
     """Raise ``ValueError`` (stating the supported set) unless ``models`` can be trained by ``ClassifierEnsembleEngine``."""
-    from .models.simple_classifiers import LogisticRegressionClassifier
+    from .models.simple_classifiers import LogisticRegressionClassifier, ShallowNNClassifier
     models = list(models)
     if not models:
         refuse("no models")
-    for m in models:
-        if not isinstance(m, LogisticRegressionClassifier):
-            refuse(f"model {type(m).__name__}")
     first = models[0]
+    for m in models:
+        if not isinstance(m, (LogisticRegressionClassifier, ShallowNNClassifier)):
+            refuse(f"model {type(m).__name__}")
+        if type(m) is not type(first):
+            refuse(f"model {type(m).__name__} in a group of {type(first).__name__}")
+    shallow = isinstance(first, ShallowNNClassifier)
     for i, m in enumerate(models):
-        if (int(m.input_dim), int(m.n_classes)) != (int(first.input_dim), int(first.n_classes)):
-            refuse(f"member {i} has shape ({m.input_dim} -> {m.n_classes}), member 0 ({first.input_dim} -> {first.n_classes})")
+        if _shape(m) != _shape(first):
+            refuse(f"member {i} has shape {_arrow(_shape(m))}, member 0 {_arrow(_shape(first))}")
+    if shallow:
+        for i, m in enumerate(models):
+            if not isinstance(m.activation, (nn.ReLU, nn.LeakyReLU)):
+                refuse(f"activation {type(m.activation).__name__}")
+            if type(m.activation) is not type(first.activation):
+                refuse(f"member {i} has activation {type(m.activation).__name__}, member 0 {type(first.activation).__name__}")
+            if _activation(m) != _activation(first):
+                refuse(f"member {i} has negative_slope {_activation(m)[1]}, member 0 {_activation(first)[1]}")
+        if _activation(first)[1] < 0:
+            refuse(f"negative_slope {_activation(first)[1]}")
+        if first.hidden.out_features % 4 != 0:
+            refuse(f"hidden_dim {first.hidden.out_features}")
     if first.input_dim % 4 != 0:
         refuse(f"input_dim {first.input_dim}")
     if first.n_classes > 64:
         refuse(f"n_classes {first.n_classes}")
     for m in models:
-        if m.linear.bias is None:
-            refuse("a layer without bias")
+        for layer in ((m.hidden, m.output) if shallow else (m.linear,)):
+            if layer.bias is None:
+                refuse("a layer without bias")
     if parallel.world()[1] > 1:
         refuse(f"a process group of {parallel.world()[1]} ranks")
     dev = None
@@ -69,14 +110,50 @@ def check_supported(models: Sequence) -> None:
             dev = p.device
 
 
+def check_train_batch(shallow: bool, B: int) -> None:
+    """Raise ``ValueError`` for a training batch size the group cannot take (shallow members: the low-rank route only)."""
+    if shallow and B > FusedNAdam.LOWRANK_MAX:
+        raise ValueError(f"a training batch of {B} rows: the ShallowNNClassifier ensemble trains batches of at most "
+                         f"{FusedNAdam.LOWRANK_MAX} rows (above that the hidden layer's weight gradient needs the TN GEMM "
+                         "kernels, which have no member dimension); evaluation and prediction take any batch size")
+
+
+class _Layer:
+    """One Linear layer of all members: weight (M, rows, cols), bias (M, r4(rows)), their moments, the bias gradient."""
+
+    def __init__(self, name: str, layers: Sequence[nn.Linear], dev):
+        self.name = name
+        M, (rows, cols) = len(layers), layers[0].weight.shape
+        self.rows, self.cols, self.ldb = int(rows), int(cols), r4(int(rows))
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.W = torch.empty(M, rows, cols, **f32)
+        self.b = torch.zeros(M, self.ldb, **f32)
+        with torch.no_grad():
+            for m, layer in enumerate(layers):
+                # parameters move into the stacks; the modules keep views of them
+                self.W[m].copy_(layer.weight.detach())
+                self.b[m, :rows].copy_(layer.bias.detach())
+                layer.weight.data = self.W[m]
+                layer.bias.data = self.b[m, :rows]
+        self.mW, self.vW = torch.zeros_like(self.W), torch.zeros_like(self.W)
+        self.mb, self.vb = torch.zeros_like(self.b), torch.zeros_like(self.b)
+        self.db = torch.zeros_like(self.b)
+
+    def moments(self, m: int):
+        return {self.name + ".weight": (self.mW[m], self.vW[m]),
+                self.name + ".bias": (self.mb[m, :self.rows], self.vb[m, :self.rows])}
+
+
 class _Workspace:
     """Buffers of one batch size (a loader has two: the full batch and the ragged last one)."""
 
-    def __init__(self, M: int, B: int, N: int, dev):
+    def __init__(self, M: int, B: int, N: int, H: int, dev):
         f32 = dict(dtype=torch.float32, device=dev)
         self.logits = torch.empty(M, B, N, **f32)
         self.dlogits = torch.zeros(M, B, r4(N), **f32)
         self.pred = torch.zeros(M, B, dtype=torch.int64, device=dev)
+        self.h = torch.zeros(M, B, H, **f32) if H else None          # the hidden activations, kept for the backward
+        self.dh = torch.zeros(M, B, H, **f32) if H else None
 
 
 class ClassifierEnsembleEngine:
@@ -86,33 +163,33 @@ class ClassifierEnsembleEngine:
         self.lib = _lib.load()
         M = self.M = len(self.models)
         first = self.models[0]
+        self.shallow = hasattr(first, "hidden")
         K, N = self.K, self.N = int(first.input_dim), int(first.n_classes)
-        self.ldb = r4(N)
-        dev = self.device = first.linear.weight.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        # parameters move into the stacks; the modules keep views of them
-        self.W = torch.empty(M, N, K, **f32)
-        self.b = torch.zeros(M, self.ldb, **f32)
-        with torch.no_grad():
-            for m, model in enumerate(self.models):
-                self.W[m].copy_(model.linear.weight.detach())
-                self.b[m, :N].copy_(model.linear.bias.detach())
-                model.linear.weight.data = self.W[m]
-                model.linear.bias.data = self.b[m, :N]
-        self.mW, self.vW = torch.zeros_like(self.W), torch.zeros_like(self.W)
-        self.mb, self.vb = torch.zeros_like(self.b), torch.zeros_like(self.b)
-        self.db = torch.zeros_like(self.b)
-        self._dW: Optional[torch.Tensor] = None          # on demand (dense path only)
+        dev = self.device = next(first.parameters()).device
+        if self.shallow:
+            self.H = int(first.hidden.out_features)
+            self.act, self.slope = _activation(first)
+            self.hidden = _Layer("hidden", [m.hidden for m in self.models], dev)
+            self.head = _Layer("output", [m.output for m in self.models], dev)
+            self.layers = [self.hidden, self.head]
+        else:
+            self.H, self.act, self.slope = 0, 0, 0.0
+            self.hidden = None
+            self.head = _Layer("linear", [m.linear for m in self.models], dev)
+            self.layers = [self.head]
+        self.ldb = self.head.ldb
+        self._dW: Optional[torch.Tensor] = None          # on demand (the logistic dense path only)
         # loss sum (the bits of a double), sample count, label-range flag, confusion matrix per member: one read per epoch
         self.words = 3 + N * N
         self.stats = torch.zeros(M, self.words, dtype=torch.int64, device=dev)
         # the schedule and the hyper-parameters are the single engine's: the two decay groups of ``_setup_training`` (the
-        # weight decays, the bias does not), ``stored_beta2`` scalars; member 0's parameters stand for the group
+        # weights decay, the biases do not), ``stored_beta2`` scalars; member 0's parameters stand for the group
         decay, no_decay = split_decay_groups(first.named_parameters())
         self.optimizer = FusedNAdam([{"params": decay, "weight_decay": float(weight_decay)},
                                      {"params": no_decay, "weight_decay": 0.0}], lr=float(learning_rate), stored_beta2=True)
         self.step_no, self.mu_product = 0, 1.0
-        self.force_dense = False           # tests / the benchmark: materialise dW at a batch the low-rank update would take
+        # tests / the benchmark: materialise dW at a batch the low-rank update would take (logistic members only)
+        self.force_dense = False
         self._mask = [1] * M
         self._active: Optional[torch.Tensor] = None      # device words; None while every member is active
         self._workspaces = {}
@@ -129,7 +206,7 @@ class ClassifierEnsembleEngine:
         if ws is None:
             if len(self._workspaces) > 4:
                 self._workspaces.clear()
-            ws = self._workspaces[B] = _Workspace(self.M, B, self.N, self.device)
+            ws = self._workspaces[B] = _Workspace(self.M, B, self.N, self.H, self.device)
         return ws
 
     def set_active(self, mask: Sequence) -> None:
@@ -166,22 +243,47 @@ class ClassifierEnsembleEngine:
     def _forward(self, x: torch.Tensor) -> _Workspace:
         B = x.shape[1]
         ws = self._workspace(B)
-        self._call("tl_linear_rows_group", ptr(x), ptr(self.W), ptr(self.b), ptr(ws.logits), self.M, B, self.K, self.N, self.K, 0,
-                   B * self.K, self.N * self.K, self.ldb, B * self.N)
+        feat, kf = x, self.K
+        if self.shallow:
+            hid, H = self.hidden, self.H
+            # the launch of ``SimpleClassifierEngine._forward`` with the member on grid.z
+            launch_nt_group(self.lib, self.M, B * self.K, H * self.K, hid.ldb, B * H, self._active, A=ptr(x), Bw=ptr(hid.W),
+                            bias=ptr(hid.b), out=ptr(ws.h), M=B, A_rows=B, N=H, K=self.K, lda=self.K, ldb=self.K, ldo=H, Tvalid=1,
+                            loader=LOAD_DIRECT, epilogue=EPI_LRELU, slope=self.slope)
+            feat, kf = ws.h, H
+        self._call("tl_linear_rows_group", ptr(feat), ptr(self.head.W), ptr(self.head.b), ptr(ws.logits), self.M, B, kf, self.N, kf,
+                   0, B * kf, self.N * kf, self.ldb, B * self.N)
         return ws
 
     def _ce(self, ws: _Workspace, y: Optional[torch.Tensor], B: int, grad: bool, pred: bool) -> None:
         base, ldd = self.stats.data_ptr(), ws.dlogits.shape[2]
-        self._call("tl_ce_loss_group", ptr(ws.logits), ptr(y), ptr(ws.dlogits) if grad else None, ptr(self.db) if grad else None,
-                   ptr(ws.pred) if pred else None, base, base + 8, base + 24, base + 16, self.M, B, self.N, self.N, ldd, 1.0 / B,
-                   B * self.N, B, B * ldd, self.ldb, B, self.words)
+        self._call("tl_ce_loss_group", ptr(ws.logits), ptr(y), ptr(ws.dlogits) if grad else None,
+                   ptr(self.head.db) if grad else None, ptr(ws.pred) if pred else None, base, base + 8, base + 24, base + 16, self.M,
+                   B, self.N, self.N, ldd, 1.0 / B, B * self.N, B, B * ldd, self.ldb, B, self.words)
 
     def _scalars(self):
         """The step's (coef_grad, coef_mom, bias_corr2): ``FusedNAdam._scalars``, as the single path computes them (both groups
-        share lr, betas and momentum_decay, so one set serves weight and bias)."""
+        share lr, betas and momentum_decay, so one set serves weights and biases)."""
         self.step_no += 1
         cg, cm, bc2, self.mu_product = self.optimizer._scalars(self.step_no, self.mu_product, self.optimizer.param_groups[0])
         return cg, cm, bc2
+
+    def _update_lowrank(self, layer: _Layer, fa: torch.Tensor, fb: torch.Tensor, B: int, scalars) -> None:
+        """``layer``'s weights by the rank-B gradient fa^T . fb, fa (M, B, ld >= rows), fb (M, B, cols)."""
+        gw = self.optimizer.param_groups[0]
+        b1, b2 = gw["betas"]
+        cg, cm, bc2 = scalars
+        ldfa = fa.shape[2]
+        self._call("tl_nadam_lowrank_group", ptr(layer.W), ptr(layer.mW), ptr(layer.vW), ptr(fa), ptr(fb), self.M, B, layer.rows,
+                   layer.cols, ldfa, layer.cols, layer.rows * layer.cols, B * ldfa, B * layer.cols, cg, cm, b1, b2, bc2, gw["eps"],
+                   gw["weight_decay"], 1.0)
+
+    def _update_bias(self, layer: _Layer, scalars) -> None:
+        gb = self.optimizer.param_groups[1]
+        b1, b2 = gb["betas"]
+        cg, cm, bc2 = scalars
+        self._call("tl_nadam_group", ptr(layer.b), ptr(layer.db), ptr(layer.mb), ptr(layer.vb), self.M, layer.rows, layer.ldb,
+                   layer.ldb, cg, cm, b1, b2, bc2, gb["eps"], gb["weight_decay"], 1.0)
 
     # ------------------------------------------------------------------ the public steps
     @torch.no_grad()
@@ -191,27 +293,38 @@ class ClassifierEnsembleEngine:
         x = self._input(x)
         B = x.shape[1]
         y = self._labels(y, B)
+        check_train_batch(self.shallow, B)
+        if self.shallow and self.force_dense:
+            raise ValueError(f"force_dense: the ShallowNNClassifier ensemble has no dense route (training batches of at most "
+                             f"{FusedNAdam.LOWRANK_MAX} rows, always as rank-B updates)")
         dense = self.force_dense or B > FusedNAdam.LOWRANK_MAX          # the single engine's decision: B alone
         ws = self._forward(x)
         self._ce(ws, y, B, grad=True, pred=False)
         ldd = ws.dlogits.shape[2]
-        gw, gb = self.optimizer.param_groups
-        b1, b2 = gw["betas"]
-        cg, cm, bc2 = self._scalars()
-        NK = self.N * self.K
-        if dense:
+        scalars = self._scalars()
+        head = self.head
+        if self.shallow:
+            H, NH = self.H, self.N * self.H
+            # dh (activation derivative applied) and the hidden bias gradient, off the output weight as it is BEFORE its update
+            self._call("tl_head_bwd_act_group", ptr(ws.dlogits), ptr(ws.h), ptr(head.W), ptr(ws.dh), ptr(self.hidden.db), None,
+                       self.M, B, H, self.N, ldd, self.act, self.slope, B * ldd, B * H, NH, B * H, self.hidden.ldb, 0)
+            self._update_lowrank(self.hidden, ws.dh, x, B, scalars)
+            self._update_lowrank(head, ws.dlogits, ws.h, B, scalars)
+            self._update_bias(self.hidden, scalars)
+        elif dense:
+            gw = self.optimizer.param_groups[0]
+            b1, b2 = gw["betas"]
+            cg, cm, bc2 = scalars
+            NK = self.N * self.K
             if self._dW is None:
-                self._dW = torch.empty_like(self.W)
-            self._call("tl_head_bwd_group", ptr(ws.dlogits), ptr(x), ptr(self.W), ptr(self._dW), self.M, B, self.K, self.N, ldd,
+                self._dW = torch.empty_like(head.W)
+            self._call("tl_head_bwd_group", ptr(ws.dlogits), ptr(x), ptr(head.W), ptr(self._dW), self.M, B, self.K, self.N, ldd,
                        B * ldd, B * self.K, NK, NK)
-            self._call("tl_nadam_group", ptr(self.W), ptr(self._dW), ptr(self.mW), ptr(self.vW), self.M, NK, NK, NK, cg, cm, b1, b2,
+            self._call("tl_nadam_group", ptr(head.W), ptr(self._dW), ptr(head.mW), ptr(head.vW), self.M, NK, NK, NK, cg, cm, b1, b2,
                        bc2, gw["eps"], gw["weight_decay"], 1.0)
         else:
-            self._call("tl_nadam_lowrank_group", ptr(self.W), ptr(self.mW), ptr(self.vW), ptr(ws.dlogits), ptr(x), self.M, B, self.N,
-                       self.K, ldd, self.K, NK, B * ldd, B * self.K, cg, cm, b1, b2, bc2, gw["eps"], gw["weight_decay"], 1.0)
-        b1, b2 = gb["betas"]
-        self._call("tl_nadam_group", ptr(self.b), ptr(self.db), ptr(self.mb), ptr(self.vb), self.M, self.N, self.ldb, self.ldb, cg,
-                   cm, b1, b2, bc2, gb["eps"], gb["weight_decay"], 1.0)
+            self._update_lowrank(head, ws.dlogits, x, B, scalars)
+        self._update_bias(head, scalars)
         for model in self.models:
             # the update wrote through data_ptr: an inference engine of the module keys its packed weights on ``_version``
             hip = getattr(model, "_hip", None)
@@ -239,7 +352,10 @@ class ClassifierEnsembleEngine:
 
     def moments(self, m: int):
         """Member m's NAdam moments {parameter name: (exp_avg, exp_avg_sq)} (views of the stacks)."""
-        return {"linear.weight": (self.mW[m], self.vW[m]), "linear.bias": (self.mb[m, :self.N], self.vb[m, :self.N])}
+        out = {}
+        for layer in self.layers:
+            out.update(layer.moments(m))
+        return out
 
     def epoch_stats(self) -> List[Tuple[float, int, torch.Tensor]]:
         """Per member (loss sum, samples counted, confusion matrix (N, N) int64 on the host) since the last call - ONE

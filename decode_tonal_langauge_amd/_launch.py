@@ -36,6 +36,16 @@ def launch_nt(lib, fn: str = "tl_gemm_nt_window", **fields) -> None:
     _launch(lib, fn, NtParams, _NT_FIELDS, _NT_DEFAULTS, fields)
 
 
+def launch_nt_group(lib, members: int, s_A: int, s_Bw: int, s_bias: int, s_out: int, active, /, **fields) -> None:
+    """``launch_nt`` for ``members`` members (positional: ``M`` is a field, the rows of one member): the fields describe member
+    0, member m lies ``s_*`` elements behind it (``tl_gemm_nt_window_group``; ``active``: the device mask words or None)."""
+    if not _NT_FIELDS.issuperset(fields):
+        raise TypeError(f"NtParams has no field {', '.join(sorted(set(fields) - _NT_FIELDS))}")
+    p = NtParams(**{**_NT_DEFAULTS, **fields})
+    check(lib.tl_gemm_nt_window_group(C.byref(p), members, s_A, s_Bw, s_bias, s_out, ptr(active), _stream()),
+          "tl_gemm_nt_window_group")
+
+
 def launch_tn(lib, fn: str = "tl_gemm_tn_window", **fields) -> None:
     """One TN windowed-GEMM launch (fields of ``TnParams`` by keyword; the rest: splitk = J = Tp = Tvalid = 1, else 0)."""
     _launch(lib, fn, TnParams, _TN_FIELDS, _TN_DEFAULTS, fields)

@@ -183,6 +183,8 @@ SIGNATURES = {
     "tl_linear_rows_group": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _L, _I, _L, _L, _L, _L, _P, _P]),
     "tl_ce_loss_group": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _L, _L, _L, _L, _L, _L, _P, _P]),
     "tl_head_bwd_group": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P]),
+    "tl_head_bwd_act_group": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _L, _L, _L, _L, _L, _L, _P, _P]),
+    "tl_gemm_nt_window_group": (_I, [C.POINTER(NtParams), _I, _L, _L, _L, _L, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

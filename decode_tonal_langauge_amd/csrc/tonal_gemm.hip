@@ -136,241 +136,35 @@ struct nt_cfg {
   static constexpr int WN = (NTHR / 64) / WM;                            // waves along N
 };
 
+// Each NT kernel body is a file of statements (tonal_gemm_nt_*_body.h) included into two __global__ functions: the single
+// launch (tl_gemm_nt_window) and the group launch (tl_gemm_nt_window_group: member blockIdx.z works on pointers moved by its
+// strides), so a member's tile runs the arithmetic of the single launch's tile in its order.  Text, not a __device__ function:
+// inlined from a function the single kernels came out with other registers and another schedule than they had.
+struct nt_group {
+  long long s_A, s_Bw, s_bias, s_out;   // member strides, elements
+  const int32_t* active;                // M words or null; 0: the member's workgroups return at once
+};
+
+// member blockIdx.z's parameters; false: the member is masked out (uniform over the workgroup - before any load or barrier)
+__device__ __forceinline__ bool nt_member(tl_nt_params& p, const nt_group& g) {
+  const int mem = blockIdx.z;
+  if (g.active != nullptr && g.active[mem] == 0) return false;
+  p.A += mem * g.s_A;
+  p.Bw += mem * g.s_Bw;
+  p.bias += mem * g.s_bias;
+  p.out += mem * g.s_out;
+  return true;
+}
+
 template <int BM, int LOADER, int EPI>
 __global__ __launch_bounds__(nt_cfg<BM>::NTHR, 2) void nt_window_kernel(const tl_nt_params p) {
-  constexpr int NTHR = nt_cfg<BM>::NTHR;
-  constexpr int WM = nt_cfg<BM>::WM;
-  constexpr int WN = nt_cfg<BM>::WN;
-  constexpr int MI = BM / (32 * WM);               // 32x32 tiles per wave along M
-  constexpr int NI = BN / (32 * WN);
-  constexpr int AROWS = BM + 6;                    // staged rows incl. the tap window (J <= 7)
-  constexpr int A_F4 = (LOADER == LOAD_DIRECT) ? ((AROWS * 8 + NTHR - 1) / NTHR) : ((AROWS / 2 * 8 + NTHR - 1) / NTHR);
-  constexpr int B_F4 = BN * 8 / NTHR;
+#include "tonal_gemm_nt_window_body.h"
+}
 
-  __shared__ __attribute__((aligned(16))) float lds[2 * AROWS * LDS_LD + 2 * BN * LDS_LD];
-  float* As = lds;                                 // [2][AROWS][LDS_LD]
-  float* Bs = lds + 2 * AROWS * LDS_LD;            // [2][BN][LDS_LD]
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wm = wave / WN, wn = wave % WN;
-  const int lr = lane & 31, lh = lane >> 5;
-
-  // XCD-aware tile order: blocks b and b+8 share an XCD/L2, so give each XCD a contiguous
-  // run of logical tiles; consecutive logical tiles walk N first and share the A panel.
-  const int ntn = (p.N + BN - 1) / BN;
-  const long long ntm = (p.M + BM - 1) / BM;
-  const long long nwg = ntm * ntn;
-  long long bid = blockIdx.x;
-  {
-    const long long q = nwg / 8, r = nwg % 8, x = bid % 8, i = bid / 8;
-    bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-  }
-  const long long tm = bid / ntn;
-  const int tn = (int)(bid % ntn);
-  const long long R0 = tm * BM;
-  const int n0 = tn * BN;
-  const int J = p.J;
-  const int arows_used = BM + J - 1;
-
-  // K range (split-K only meaningful for J == 1 plain GEMMs, but handled generally)
-  const int nkc_all = (p.K + BK - 1) / BK;
-  const int z = blockIdx.y;
-  const int kc_per = (nkc_all + p.splitk - 1) / p.splitk;
-  const int kc_begin = z * kc_per;
-  const int kc_end = min(nkc_all, kc_begin + kc_per);
-  const int nchunks = max(0, kc_end - kc_begin);
-  const int nsteps = nchunks * J;
-
-  f32x16 acc[MI][NI];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-  f32x4 ra[A_F4];          // staged A (DIRECT) or G (UNPOOL)
-  uint32_t rbits[A_F4];    // UNPOOL: raw 32-bit arg word (bit set -> odd row of the pair); the
-                           // nibble is extracted at LDS-store time so the load stays in flight
-  f32x4 rbP[B_F4], rbQ[B_F4];    // two B staging sets: B is prefetched TWO K-steps ahead (HBM/L2 latency
-                           // under full load exceeds one 64-MFMA step; measured in scripts/mfma_ablate.hip)
-
-  const long long Abase = R0 + p.row_shift;        // first staged A row (even for UNPOOL)
-
-  // Per-thread row pointers and validity are loop-invariant (a thread stages the same rows of
-  // every K-chunk): hoist them, so a K-step issues its global loads with one 64-bit add each.
-  const float* aptr[A_F4];
-  const uint32_t* abptr[A_F4];
-  bool aok[A_F4];
-  (void)abptr;
-#pragma unroll
-  for (int i = 0; i < A_F4; ++i) {
-    const int idx = tid + i * NTHR;
-    const int r = idx >> 3, c4 = idx & 7;
-    if constexpr (LOADER == LOAD_DIRECT) {
-      const long long row = Abase + r;
-      aok[i] = r < arows_used && row >= 0 && row < p.A_rows;
-      aptr[i] = p.A + (aok[i] ? row : 0) * (long long)p.lda + c4 * 4;
-      abptr[i] = nullptr;
-    } else {
-      const long long prow = (Abase >> 1) + r;     // Abase is even
-      aok[i] = (r < (arows_used + 1) / 2) && prow >= 0 && prow < p.A_rows &&
-               (int)((2 * prow) % p.Tp) < p.Tvalid_in;
-      aptr[i] = p.A + (aok[i] ? prow : 0) * (long long)p.lda + c4 * 4;
-      abptr[i] = p.abits + (aok[i] ? prow : 0) * (long long)p.ld_abits;
-    }
-  }
-  const float* bptr[B_F4];
-  bool bok[B_F4];
-#pragma unroll
-  for (int i = 0; i < B_F4; ++i) {
-    const int idx = tid + i * NTHR;
-    const int r = idx >> 3, c4 = idx & 7;
-    bok[i] = (n0 + r) < p.N;
-    bptr[i] = p.Bw + (long long)(bok[i] ? n0 + r : 0) * p.ldb + c4 * 4;
-  }
-  const bool ktail = (p.K % BK) != 0;             // wave-uniform: the hot shapes have K % 32 == 0
-  const int kq = (tid & 7) * 4;
-  const long long tap_stride = (long long)p.N * p.ldb;
-
-  auto load_a = [&](int chunk) {
-    const int kc = (kc_begin + chunk) * BK;
-    const bool kok = !ktail || (kc + kq) < p.K;
-#pragma unroll
-    for (int i = 0; i < A_F4; ++i) {
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      uint32_t nib = 0;
-      if (aok[i] && kok) {
-        v = *reinterpret_cast<const f32x4*>(aptr[i] + kc);
-        if constexpr (LOADER == LOAD_UNPOOL) nib = abptr[i][kc >> 5];
-      }
-      ra[i] = v;
-      rbits[i] = nib;
-    }
-  };
-  auto store_a = [&](int buf) {
-    float* dst = As + buf * AROWS * LDS_LD;
-#pragma unroll
-    for (int i = 0; i < A_F4; ++i) {
-      const int idx = tid + i * NTHR;
-      const int r = idx >> 3, c4 = idx & 7;
-      if constexpr (LOADER == LOAD_DIRECT) {
-        if (r < AROWS) *reinterpret_cast<f32x4*>(dst + r * LDS_LD + c4 * 4) = ra[i];
-      } else {
-        if (r < AROWS / 2) {
-          f32x4 e, o;
-          const uint32_t nibv = rbits[i] >> ((c4 * 4) & 31);     // kc is a multiple of 32
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const bool odd = (nibv >> q) & 1u;
-            e[q] = odd ? 0.f : ra[i][q];
-            o[q] = odd ? ra[i][q] : 0.f;
-          }
-          *reinterpret_cast<f32x4*>(dst + (2 * r) * LDS_LD + c4 * 4) = e;
-          *reinterpret_cast<f32x4*>(dst + (2 * r + 1) * LDS_LD + c4 * 4) = o;
-        }
-      }
-    }
-  };
-  auto load_b = [&](f32x4 (&rb)[B_F4], int chunk, int j) {
-    const int kc = (kc_begin + chunk) * BK;
-    const bool kok = !ktail || (kc + kq) < p.K;
-    const long long off = (long long)j * tap_stride + kc;     // wave-uniform
-#pragma unroll
-    for (int i = 0; i < B_F4; ++i) {
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (bok[i] && kok) v = *reinterpret_cast<const f32x4*>(bptr[i] + off);
-      rb[i] = v;
-    }
-  };
-  auto store_b = [&](const f32x4 (&rb)[B_F4], int buf) {
-    float* dst = Bs + buf * BN * LDS_LD;
-#pragma unroll
-    for (int i = 0; i < B_F4; ++i) {
-      const int idx = tid + i * NTHR;
-      const int r = idx >> 3, c4 = idx & 7;
-      *reinterpret_cast<f32x4*>(dst + r * LDS_LD + c4 * 4) = rb[i];
-    }
-  };
-
-  // Fragment sets F0 / F1 (statically named): while the MFMAs of one 8-deep k-group run, the
-  // ds_read_b128 of the next group are in flight; the last group of a K-step is carried in
-  // registers ACROSS the barrier, so the matrix pipe has work the moment the barrier opens, and
-  // the LDS stores of the next stage are issued mid-step (their target buffer was released at
-  // the previous barrier), leaving nothing but the barrier itself at the end of a step.
-  f32x4 fa0[MI], fb0[NI], fa1[MI], fb1[NI];
-  auto load_frag = [&](f32x4 (&fa)[MI], f32x4 (&fb)[NI], int abuf, int bbuf, int j, int kk) {
-    const float* a_s = As + abuf * AROWS * LDS_LD + (wm * (MI * 32) + lr + j) * LDS_LD + lh * 4 + kk * 8;
-    const float* b_s = Bs + bbuf * BN * LDS_LD + (wn * (NI * 32) + lr) * LDS_LD + lh * 4 + kk * 8;
-#pragma unroll
-    for (int i = 0; i < MI; ++i) fa[i] = *reinterpret_cast<const f32x4*>(a_s + i * 32 * LDS_LD);
-#pragma unroll
-    for (int i = 0; i < NI; ++i) fb[i] = *reinterpret_cast<const f32x4*>(b_s + i * 32 * LDS_LD);
-  };
-  auto mfma_group = [&](const f32x4 (&fa)[MI], const f32x4 (&fb)[NI]) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[mi][q], fb[ni][q], acc[mi][ni], 0, 0, 0);
-  };
-
-  // One K-step.  `rb_ld` receives B(s+2); `rb_st` holds B(s+1) (loaded one step ago) and is written
-  // to LDS mid-step.  A(chunk+1) is loaded at the first tap of a chunk and stored at its last tap.
-  // (chunk, tap) counters advanced without divisions
-  int c_cur = 0, j_cur = 0;          // step s
-  int c_ld = 0, j_ld = 0;            // step s + 2 (next B tile to load)
-  auto advance = [&](int& c, int& j) {
-    if (++j == J) {
-      j = 0;
-      ++c;
-    }
-  };
-  auto kstep = [&](int s, f32x4 (&rb_ld)[B_F4], const f32x4 (&rb_st)[B_F4]) {
-    const int chunk = c_cur, j = j_cur;
-    const int abuf = chunk & 1, bbuf = s & 1;
-    const bool more = s + 1 < nsteps;
-    const bool has_next_chunk = chunk + 1 < nchunks;
-    load_frag(fa0, fb0, abuf, bbuf, j, 0);
-    if (s + 2 < nsteps) load_b(rb_ld, c_ld, j_ld);
-    if (j == 0 && has_next_chunk) load_a(chunk + 1);
-    if (s > 0) mfma_group(fa1, fb1);             // k-group 3 of the previous step (registers)
-    load_frag(fa1, fb1, abuf, bbuf, j, 1);
-    mfma_group(fa0, fb0);
-    load_frag(fa0, fb0, abuf, bbuf, j, 2);
-    mfma_group(fa1, fb1);
-    if (more) store_b(rb_st, bbuf ^ 1);
-    if (j == J - 1 && has_next_chunk) store_a(abuf ^ 1);
-    load_frag(fa1, fb1, abuf, bbuf, j, 3);
-    mfma_group(fa0, fb0);
-    advance(c_cur, j_cur);
-    advance(c_ld, j_ld);
-    __syncthreads();
-  };
-
-  if (nsteps > 0) {
-    load_a(0);
-    load_b(rbP, 0, 0);
-    store_a(0);
-    store_b(rbP, 0);
-    advance(c_ld, j_ld);
-    if (nsteps > 1) load_b(rbQ, c_ld, j_ld);
-    advance(c_ld, j_ld);
-  }
-  __syncthreads();
-  int s = 0;
-  for (; s + 1 < nsteps; s += 2) {
-    kstep(s, rbP, rbQ);
-    kstep(s + 1, rbQ, rbP);
-  }
-  if (s < nsteps) kstep(s, rbP, rbQ);
-  if (nsteps > 0) mfma_group(fa1, fb1);
-
-  nt_epilogue<EPI, MI, NI>(p, acc, R0, n0, wm, wn, lr, lh, z);
+template <int BM, int LOADER, int EPI>
+__global__ __launch_bounds__(nt_cfg<BM>::NTHR, 2) void nt_window_group_kernel(tl_nt_params p, const nt_group g) {
+  if (!nt_member(p, g)) return;
+#include "tonal_gemm_nt_window_body.h"
 }
 
 
@@ -392,196 +186,13 @@ constexpr int G_NB = 4;                // B ring slots
 // conv5: with the 128-column tile half of their MFMAs were masked columns)
 template <int EPI, int NI>
 __global__ __launch_bounds__(256, 2) void nt_glds_kernel(const tl_nt_params p) {
-  constexpr int BM = 128, MI = 2, WN = 2, BN = 64 * NI;          // (shadows the file's 128-column constant)
-  __shared__ __attribute__((aligned(16))) float lds[2 * G_AROWS * GK + G_NB * BN * GK];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave / WN, wn = wave % WN;
-  const int lr = lane & 31, lh = lane >> 5;
+#include "tonal_gemm_nt_glds_body.h"
+}
 
-  const int ntn = (p.N + BN - 1) / BN;
-  const long long ntm = (p.M + BM - 1) / BM;
-  const long long nwg = ntm * ntn;
-  long long bid = blockIdx.x;
-  {
-    const long long q = nwg / 8, r = nwg % 8, x = bid % 8, i = bid / 8;
-    bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-  }
-  const long long tm = bid / ntn;
-  const int tn = (int)(bid % ntn);
-  const long long R0 = tm * BM;
-  const int n0 = tn * BN;
-  const int J = p.J;
-
-  const int nkc_all = p.K / GK;
-  const int z = blockIdx.y;
-  const int kc_per = (nkc_all + p.splitk - 1) / p.splitk;
-  const int kc_begin = z * kc_per;
-  const int kc_end = min(nkc_all, kc_begin + kc_per);
-  const int nchunks = max(0, kc_end - kc_begin);
-  const int nsteps = nchunks * J;
-
-  f32x16 acc[MI][NI];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-  // DMA piece = 16 rows x 64 B; lane -> (row = lane >> 2, physical chunk = lane & 3), and the source
-  // chunk is the swizzled one: chunk ^ ((row >> 2) & 3) with row % 16 == lane >> 2
-  const int prow = lane >> 2;
-  const int src_chunk = (lane & 3) ^ ((lane >> 4) & 3);
-  // A pieces: every wave issues 3 (pieces w, w+4 and 8); B pieces: 2 (w, w+4)
-  const float* asrc[3];
-  unsigned adst[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const int piece = (i < 2) ? wave + 4 * i : 8;
-    long long row = R0 + piece * 16 + prow;
-    if (row > p.A_rows - 1) row = p.A_rows - 1;          // clamped rows only feed masked outputs
-    asrc[i] = p.A + row * (long long)p.lda + src_chunk * 4;
-    adst[i] = (unsigned)(piece * 16 * GK * 4);
-  }
-  const float* bsrc[NI];
-  unsigned bdst[NI];
-#pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    const int piece = wave + 4 * i;
-    int n = n0 + piece * 16 + prow;
-    if (n > p.N - 1) n = p.N - 1;                         // clamped columns are masked by the epilogue
-    bsrc[i] = p.Bw + (long long)n * p.ldb + src_chunk * 4;
-    bdst[i] = (unsigned)(piece * 16 * GK * 4);
-  }
-  const long long tap_stride = (long long)p.N * p.ldb;
-  char* const lds_a = reinterpret_cast<char*>(lds);
-  char* const lds_b = reinterpret_cast<char*>(lds) + 2 * G_AROWS * GK * 4;
-
-  auto dma = [&](const float* g, char* l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-  };
-  auto issue_a = [&](int chunk) {
-    const int kc = (kc_begin + chunk) * GK;
-    char* base = lds_a + (chunk & 1) * (G_AROWS * GK * 4);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) dma(asrc[i] + kc, base + adst[i]);
-  };
-  auto issue_b = [&](int step, int chunk, int j) {
-    const long long off = (long long)j * tap_stride + (long long)(kc_begin + chunk) * GK;
-    char* base = lds_b + (step & (G_NB - 1)) * (BN * GK * 4);
-#pragma unroll
-    for (int i = 0; i < NI; ++i) dma(bsrc[i] + off, base + bdst[i]);
-  };
-
-  // fragment read offsets (bytes): row r, logical chunk c -> r*64 + ((c ^ ((r >> 2) & 3)) * 16)
-  f32x4 fa0[MI], fb0[NI], fa1[MI], fb1[NI];
-  auto load_frag = [&](f32x4 (&fa)[MI], f32x4 (&fb)[NI], int abuf, int bslot, int j, int kk) {
-    const int c = 2 * kk + lh;
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-      const int r = wm * 64 + i * 32 + lr + j;
-      fa[i] = *reinterpret_cast<const f32x4*>(lds_a + abuf * (G_AROWS * GK * 4) + r * 64 + ((c ^ ((r >> 2) & 3)) << 4));
-    }
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const int r = wn * (NI * 32) + i * 32 + lr;
-      fb[i] = *reinterpret_cast<const f32x4*>(lds_b + bslot * (BN * GK * 4) + r * 64 + ((c ^ ((r >> 2) & 3)) << 4));
-    }
-  };
-  auto mfma_group = [&](const f32x4 (&fa)[MI], const f32x4 (&fb)[NI]) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[mi][q], fb[ni][q], acc[mi][ni], 0, 0, 0);
-  };
-
-  // ---- prologue: A(0), B(0..2) in flight; wait for A(0) and B(0)
-  int c_ld = 0, j_ld = 0;
-  auto advance = [&](int& c, int& j) {
-    if (++j == J) {
-      j = 0;
-      ++c;
-    }
-  };
-  if (nsteps > 0) {
-    issue_a(0);
-    issue_b(0, 0, 0);
-    advance(c_ld, j_ld);
-    if (nsteps > 1) issue_b(1, c_ld, j_ld);
-    advance(c_ld, j_ld);
-    if (nsteps > 2) issue_b(2, c_ld, j_ld);
-    advance(c_ld, j_ld);
-    // everything but the last two B pieces-pairs must have landed (A(0), B(0))
-    if (nsteps > 2) {
-      if constexpr (NI == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    } else if (nsteps > 1) {
-      if constexpr (NI == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-  }
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-
-  // s_waitcnt needs an immediate: dispatch the (wave-uniform) count over the few values it takes
-  auto wait_all_but = [&](int n) {
-    switch (n) {
-      case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-      case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-      case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-      case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-      case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-      case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-      case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-      default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-  };
-
-  int c_cur = 0, j_cur = 0;
-  for (int s = 0; s < nsteps; ++s) {
-    const int chunk = c_cur, j = j_cur;
-    const int abuf = chunk & 1, bslot = s & (G_NB - 1);
-    load_frag(fa0, fb0, abuf, bslot, j, 0);
-    // DMA issue order inside a step: A(chunk+1) (first tap of a chunk; its slot held chunk-1), then
-    // B(s+3) (its ring slot held B(s-1), released at the last barrier)
-    const bool has_next = chunk + 1 < nchunks;
-    const bool lda_ = (j == 0) && has_next;
-    const bool ldb = s + 3 < nsteps;
-    if (lda_) issue_a(chunk + 1);
-    if (ldb) issue_b(s + 3, c_ld, j_ld);
-    if (s > 0) mfma_group(fa1, fb1);             // k-group 1 of the previous step (registers)
-    load_frag(fa1, fb1, abuf, bslot, j, 1);
-    mfma_group(fa0, fb0);
-    advance(c_cur, j_cur);
-    advance(c_ld, j_ld);
-    if (s + 1 < nsteps) {
-      // The next step reads B(s+1) and, when it opens a chunk, A(chunk+1).  vmcnt retires this
-      // wave's pieces in issue order, so allow exactly the pieces issued AFTER the youngest needed
-      // one to stay in flight: this step's own, B(s+2) (issued one step ago) and - when the next
-      // step stays in this chunk - an A(chunk+1) issued one step ago.
-      int n = (ldb ? NI : 0);                              // (NI B pieces per wave and step)
-      if (J == 1) {
-        // A(chunk+1) was issued this step (before B(s+3)) and is needed next step
-      } else {
-        n += (lda_ ? 3 : 0) + ((s + 2 < nsteps) ? NI : 0);
-        if (j == 1 && j != J - 1 && has_next) n += 3;
-      }
-      wait_all_but(n);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-    }
-  }
-  if (nsteps > 0) mfma_group(fa1, fb1);
-  nt_epilogue<EPI, MI, NI>(p, acc, R0, n0, wm, wn, lr, lh, z);
+template <int EPI, int NI>
+__global__ __launch_bounds__(256, 2) void nt_glds_group_kernel(tl_nt_params p, const nt_group g) {
+  if (!nt_member(p, g)) return;
+#include "tonal_gemm_nt_glds_body.h"
 }
 
 template <int EPI>
@@ -1201,10 +812,9 @@ __global__ __launch_bounds__(256, 2) void tn_skinny_kernel(const tl_tn_params p)
 
 }  // namespace tl
 
-extern "C" int tl_gemm_nt_window(const tl_nt_params* pp, void* stream) {
+// the argument checks of tl_gemm_nt_window (shared with tl_gemm_nt_window_group); fills in the defaults of splitk and bm
+static int nt_check(tl_nt_params& p) {
   using namespace tl;
-  TL_REQUIRE(pp != nullptr, "nt_window: null params");
-  tl_nt_params p = *pp;
   if (p.splitk < 1) p.splitk = 1;
   if (p.bm == 0) p.bm = 128;
   TL_REQUIRE(p.A && p.Bw && p.out, "nt_window: null A/Bw/out");
@@ -1229,6 +839,27 @@ extern "C" int tl_gemm_nt_window(const tl_nt_params* pp, void* stream) {
     TL_REQUIRE(p.N % 32 == 0 && p.ld_obits * 32 >= p.N, "nt_window: POOL needs N %% 32 == 0");
   }
   if (p.epilogue == EPI_MASK) TL_REQUIRE(p.aux != nullptr || p.auxbits != nullptr, "nt_window: MASK epilogue needs aux or auxbits");
+  return TL_OK;
+}
+
+// TONAL_GLDS=0 under TONAL_AB=1 selects the register-staged kernel (see tl_gemm_nt_window)
+static bool nt_glds_on() {
+  const char* ab = getenv("TONAL_AB");
+  const char* genv = (ab != nullptr && ab[0] == '1') ? getenv("TONAL_GLDS") : nullptr;
+  return genv == nullptr || genv[0] != '0';
+}
+
+// does tl_gemm_nt_window run these (checked) parameters on the direct-to-LDS kernel?
+static bool nt_takes_glds(const tl_nt_params& p) {
+  return nt_glds_on() && p.J <= 3 && p.bm == 128 && p.loader == tl::LOAD_DIRECT && p.row_shift == 0 && (p.K % tl::GK) == 0 &&
+         p.A_rows > 0;
+}
+
+extern "C" int tl_gemm_nt_window(const tl_nt_params* pp, void* stream) {
+  using namespace tl;
+  TL_REQUIRE(pp != nullptr, "nt_window: null params");
+  tl_nt_params p = *pp;
+  if (const int rc = nt_check(p)) return rc;
   hipStream_t st = (hipStream_t)stream;
   // Direct-to-LDS staging variant.  Round 1 measured it equal to the register-staged kernel on the conv2 forward (129.6 vs
   // 128.6 TFLOP/s) and kept the simpler one; on what is left for this entry point since the Winograd kernels took the 3-tap
@@ -1236,10 +867,7 @@ extern "C" int tl_gemm_nt_window(const tl_nt_params* pp, void* stream) {
   // same-call A/B, round 4): default on; TONAL_GLDS=0 selects the register-staged kernel (the A/B partner,
   // tests/test_gpu_parity.py holds the two against each other).
   // (an A/B switch of the test suite: honoured only under TONAL_AB=1, like the per-switch variables of _kernels.py)
-  const char* ab = getenv("TONAL_AB");
-  const char* genv = (ab != nullptr && ab[0] == '1') ? getenv("TONAL_GLDS") : nullptr;
-  const bool glds_on = genv == nullptr || genv[0] != '0';
-  if (glds_on && p.J <= 3 && p.bm == 128 && p.loader == LOAD_DIRECT && p.row_shift == 0 && (p.K % GK) == 0 && p.A_rows > 0) {
+  if (nt_takes_glds(p)) {
     switch (p.epilogue) {
       case EPI_STORE: return launch_glds<EPI_STORE>(p, st);
       case EPI_LRELU: return launch_glds<EPI_LRELU>(p, st);
@@ -1249,6 +877,48 @@ extern "C" int tl_gemm_nt_window(const tl_nt_params* pp, void* stream) {
   }
   if (p.bm == 256) return dispatch_nt<256>(p, st);
   return p.bm == 128 ? dispatch_nt<128>(p, st) : dispatch_nt<32>(p, st);
+}
+
+// tl_gemm_nt_window for M members of equal shape - what the hidden layer of the shallow-classifier ensemble launches: a plain
+// GEMM (J = 1, DIRECT, no split-K, 128-row tiles) with bias and LeakyReLU in the epilogue.  The kernel is chosen exactly as
+// tl_gemm_nt_window chooses it for *pp, and its body is that kernel's: a member's bits are the single launch's.
+extern "C" int tl_gemm_nt_window_group(const tl_nt_params* pp, int M, int64_t s_A, int64_t s_Bw, int64_t s_bias, int64_t s_out,
+                                       const int32_t* active, void* stream) {
+  using namespace tl;
+  TL_REQUIRE(pp != nullptr, "nt_window_group: null params");
+  tl_nt_params p = *pp;
+  TL_REQUIRE(M >= 1 && M <= 65535, "nt_window_group: the number of members M must lie in [1, 65535] (got %d)", M);
+  TL_REQUIRE(p.J == 1 && p.loader == LOAD_DIRECT && p.row_shift == 0,
+             "nt_window_group: only the plain GEMM has a group form (J = 1, DIRECT loader, row_shift = 0; got J %d, loader %d, "
+             "row_shift %d)", p.J, p.loader, p.row_shift);
+  TL_REQUIRE(p.splitk <= 1, "nt_window_group: no split-K (got splitk %d)", p.splitk);
+  TL_REQUIRE(p.bm == 0 || p.bm == 128, "nt_window_group: bm must be 0 or 128 (got %d)", p.bm);
+  TL_REQUIRE(p.epilogue == EPI_LRELU, "nt_window_group: only the LRELU epilogue has a group form (ReLU is slope 0; got %d)", p.epilogue);
+  TL_REQUIRE(p.bias != nullptr, "nt_window_group: null bias");
+  TL_REQUIRE(!p.aux && !p.auxbits && !p.abits && !p.obits && !p.osign && !p.vout && !p.vout2 && !p.vhalo && !p.c1x && !p.c1bits &&
+                 !p.c1partial && !p.mask,
+             "nt_window_group: aux / auxbits / abits / obits / osign / vout / c1 / mask pointers have no member stride: pass null");
+  if (const int rc = nt_check(p)) return rc;
+  TL_REQUIRE(s_A >= 0 && s_Bw >= 0 && s_bias >= 0 && s_A % 4 == 0 && s_Bw % 4 == 0,
+             "nt_window_group: the member strides of A and Bw must be non-negative multiples of 4 elements (16-byte aligned "
+             "members), that of bias non-negative");
+  TL_REQUIRE(M == 1 || s_out >= p.M * (int64_t)p.ldo,
+             "nt_window_group: member stride of out shorter than the M x ldo elements of a member");
+  hipStream_t st = (hipStream_t)stream;
+  const nt_group g = {(long long)s_A, (long long)s_Bw, (long long)s_bias, (long long)s_out, active};
+  const bool glds = nt_takes_glds(p), narrow = glds && p.N <= 64;
+  const int bn = narrow ? 64 : BN;
+  const long long nwg = ((p.M + 127) / 128) * ((p.N + bn - 1) / bn);
+  if (nwg <= 0) return TL_OK;
+  TL_REQUIRE(nwg < (1LL << 31), "nt_window_group: grid too large");
+  const dim3 grid((unsigned)nwg, 1, (unsigned)M);
+  if (narrow)
+    hipLaunchKernelGGL((nt_glds_group_kernel<EPI_LRELU, 1>), grid, dim3(256), 0, st, p, g);
+  else if (glds)
+    hipLaunchKernelGGL((nt_glds_group_kernel<EPI_LRELU, 2>), grid, dim3(256), 0, st, p, g);
+  else
+    hipLaunchKernelGGL((nt_window_group_kernel<128, LOAD_DIRECT, EPI_LRELU>), grid, dim3(nt_cfg<128>::NTHR), 0, st, p, g);
+  return check_launch("nt_window_group");
 }
 
 namespace tl {

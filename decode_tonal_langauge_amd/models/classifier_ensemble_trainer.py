@@ -1,6 +1,8 @@
-"""``ClassifierTrainer(fused=True)``'s loop for M ``LogisticRegressionClassifier``s at once (the seeds of one experiment): every
-step of the group is the launches of one model's step (``_classifier_ensemble_engine``), every batch of the group one gather
-launch (``tl_gather_rows_group``) over the ONE ``ResidentDataset`` the members' splits index.
+"""``ClassifierTrainer(fused=True)``'s loop for M ``LogisticRegressionClassifier``s or M ``ShallowNNClassifier``s at once (the
+seeds of one experiment): every step of the group is the launches of one model's step (``_classifier_ensemble_engine``), every
+batch of the group one gather launch (``tl_gather_rows_group``) over the ONE ``ResidentDataset`` the members' splits index.
+Shallow members train batches of at most ``FusedNAdam.LOWRANK_MAX`` (64) rows: ``fit`` refuses larger training loaders before
+the first epoch; validation, test and predict loaders may have any batch size.
 
 Member m's result is what a sequential ``ClassifierTrainer(fused=True)`` run of that member over its ``ResidentLoader``s gives:
 the same kernels on the same batches, early stopping per member (own ``best``, own ``wait``; a member that stops is masked out
@@ -142,6 +144,7 @@ class ClassifierEnsembleTrainer:
                     "confusion_matrix": stats[m][2]} for m in members}
 
     def fit(self, train_loaders, val_loaders, max_epochs: int, patience: int) -> List[List[Dict[str, float]]]:
+        from .._classifier_ensemble_engine import check_train_batch
         if self._fitted:
             raise RuntimeError("ClassifierEnsembleTrainer.fit runs once: the members share one NAdam schedule from step 0 and a "
                                "stopped member does not resume")
@@ -149,6 +152,8 @@ class ClassifierEnsembleTrainer:
         M = self.M
         check_loaders(train_loaders, M)
         check_loaders(val_loaders, M)
+        # shallow members train batches of at most FusedNAdam.LOWRANK_MAX rows: refused here, before the first epoch
+        check_train_batch(self.engine.shallow, int(train_loaders[0].batch_size))
         best, wait, step = [float("inf")] * M, [0] * M, 0
         active = [True] * M
         try:

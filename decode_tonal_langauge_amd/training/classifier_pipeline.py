@@ -61,8 +61,8 @@ def ensemble_wanted(params: Namespace) -> bool:
         return False
     if not getattr(params, "fused", False):
         raise ValueError("training.params.ensemble: true needs training.params.fused: true - the classifier ensemble supports "
-                         "LogisticRegressionClassifier on the HIP train step only, in a single process; there is no autograd "
-                         "ensemble")
+                         "LogisticRegressionClassifier on the HIP train step only (and ShallowNNClassifier there, at training "
+                         "batches of at most 64 rows), in a single process; there is no autograd ensemble")
     return True
 
 

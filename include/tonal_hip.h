@@ -531,6 +531,21 @@ int tl_head_bwd(const float* dlogits, const float* h, const float* W, float* dh,
  * dbias_h, no activation); grid (column blocks, M); s_h, s_W and s_dw multiples of 4                                        */
 int tl_head_bwd_group(const float* dlogits, const float* h, const float* W, float* dw, int M, int B, int K, int N, int ldd,
                       int64_t s_dlogits, int64_t s_h, int64_t s_W, int64_t s_dw, const int32_t* active, void* stream);
+/* ... and the full tl_head_bwd for M members (the output layer of ShallowNNClassifier): any subset of dh, dbias_h, dw, act 0 / 1
+ * / 2; the strides of h, W, dh, dbias_h and dw non-negative multiples of 4, and with M > 1 those of the outputs asked for at
+ * least a member's B K, K and N K elements                                                                                 */
+int tl_head_bwd_act_group(const float* dlogits, const float* h, const float* W, float* dh, float* dbias_h, float* dw, int M, int B,
+                          int K, int N, int ldd, int act, float slope, int64_t s_dlogits, int64_t s_h, int64_t s_W, int64_t s_dh,
+                          int64_t s_dbias_h, int64_t s_dw, const int32_t* active, void* stream);
+/* tl_gemm_nt_window for M members (the hidden layer of ShallowNNClassifier): *p describes member 0; member m works on A + m s_A,
+ * Bw + m s_Bw, bias + m s_bias and out + m s_out (elements).  Only the plain GEMM with bias and LeakyReLU has a group form:
+ * J = 1, loader DIRECT, row_shift 0, splitk <= 1, bm 0 or 128, epilogue LRELU (ReLU is slope 0), bias given, and none of aux /
+ * auxbits / abits / obits / osign / vout* / vhalo / c1* / mask; everything else is refused.  s_A and s_Bw non-negative multiples
+ * of 4, s_bias non-negative, s_out >= p->M * ldo when M > 1.  The kernel is chosen as tl_gemm_nt_window chooses it for *p
+ * (direct-to-LDS when K % 16 == 0, in its 64-column form for N <= 64, else register-staged) and runs that kernel's body with
+ * the member on grid.z, so a member's out has the bits of the single launch.                                                */
+int tl_gemm_nt_window_group(const tl_nt_params* p, int M, int64_t s_A, int64_t s_Bw, int64_t s_bias, int64_t s_out,
+                            const int32_t* active, void* stream);
 
 /* ---- training of CNNRNNClassifier (models/deep_classifiers.py:158-343 under models/classifier_trainer.py:72-89) ----------
  * The LSTM pair keeps ROWS TIME-MAJOR (row = t * B + b), so the kept arrays are directly the (T B)-row operands of the
