@@ -32,8 +32,10 @@ import torch
 import torch.nn as nn
 
 from . import _lib, parallel
+from ._classifier_train_engine import invalidate_packed, parameter_unmet
 from ._launch import launch_nt_group, r4
 from ._lib import EPI_LRELU, LOAD_DIRECT, check, ptr
+from ._simple_classifier_engine import activation_code, unmet
 from .models.utils import split_decay_groups
 from .optim import FusedNAdam
 
@@ -57,13 +59,9 @@ def _arrow(shape: tuple) -> str:
     return "(" + " -> ".join(str(s) for s in shape) + ")"
 
 
-def _activation(m) -> Tuple[int, float]:
-    """(act code of ``tl_head_bwd``, slope) of a shallow member's activation."""
-    return (1, 0.0) if isinstance(m.activation, nn.ReLU) else (2, float(m.activation.negative_slope))
-
-
 def check_supported(models: Sequence) -> None:
-    """Raise ``ValueError`` (stating the supported set) unless ``models`` can be trained by ``ClassifierEnsembleEngine``."""
+    """Raise ``ValueError`` (stating the supported set) unless ``models`` can be trained by ``ClassifierEnsembleEngine``: the
+    conditions of the single engine on every member (``_simple_classifier_engine.unmet``) and, between them, the group's."""
     from .models.simple_classifiers import LogisticRegressionClassifier, ShallowNNClassifier
     models = list(models)
     if not models:
@@ -74,37 +72,31 @@ def check_supported(models: Sequence) -> None:
             refuse(f"model {type(m).__name__}")
         if type(m) is not type(first):
             refuse(f"model {type(m).__name__} in a group of {type(first).__name__}")
-    shallow = isinstance(first, ShallowNNClassifier)
     for i, m in enumerate(models):
         if _shape(m) != _shape(first):
             refuse(f"member {i} has shape {_arrow(_shape(m))}, member 0 {_arrow(_shape(first))}")
-    if shallow:
+    misses = [unmet(m) for m in models]
+    if hasattr(first, "hidden"):
         for i, m in enumerate(models):
-            if not isinstance(m.activation, (nn.ReLU, nn.LeakyReLU)):
-                refuse(f"activation {type(m.activation).__name__}")
+            if "activation" in misses[i]:
+                refuse(misses[i]["activation"])
             if type(m.activation) is not type(first.activation):
                 refuse(f"member {i} has activation {type(m.activation).__name__}, member 0 {type(first.activation).__name__}")
-            if _activation(m) != _activation(first):
-                refuse(f"member {i} has negative_slope {_activation(m)[1]}, member 0 {_activation(first)[1]}")
-        if _activation(first)[1] < 0:
-            refuse(f"negative_slope {_activation(first)[1]}")
-        if first.hidden.out_features % 4 != 0:
-            refuse(f"hidden_dim {first.hidden.out_features}")
-    if first.input_dim % 4 != 0:
-        refuse(f"input_dim {first.input_dim}")
-    if first.n_classes > 64:
-        refuse(f"n_classes {first.n_classes}")
-    for m in models:
-        for layer in ((m.hidden, m.output) if shallow else (m.linear,)):
-            if layer.bias is None:
-                refuse("a layer without bias")
+            if activation_code(m) != activation_code(first):
+                refuse(f"member {i} has negative_slope {activation_code(m)[1]}, member 0 {activation_code(first)[1]}")
+        if activation_code(first)[1] < 0:
+            refuse(f"negative_slope {activation_code(first)[1]}")
+    for condition in ("hidden_dim", "input_dim", "n_classes", "bias"):
+        for miss in misses:
+            if condition in miss:
+                refuse(miss[condition])
     if parallel.world()[1] > 1:
         refuse(f"a process group of {parallel.world()[1]} ranks")
     dev = None
     for m in models:
         for p in m.parameters():
-            if not p.is_cuda or p.dtype != torch.float32:
-                refuse(f"parameters on '{p.device}' in {p.dtype}")
+            if parameter_unmet(p):
+                refuse(parameter_unmet(p))
             if dev is not None and p.device != dev:
                 refuse(f"parameters on '{p.device}' and '{dev}'")
             dev = p.device
@@ -118,16 +110,26 @@ def check_train_batch(shallow: bool, B: int) -> None:
                          "kernels, which have no member dimension); evaluation and prediction take any batch size")
 
 
+def _member_stride(t: torch.Tensor, *same) -> int:
+    """The member stride of a stacked buffer, read off the tensor whose pointer a group launch is given - once, where the
+    buffer is made.  Every member must be one dense block (the launches take the leading dimensions from the sizes), and the
+    buffers in ``same`` - moments, a gradient - are passed with the same stride."""
+    if not t[0].is_contiguous() or any(u.stride() != t.stride() for u in same):
+        raise RuntimeError(f"a stacked buffer {tuple(t.shape)} with strides {t.stride()}: members not dense, or not laid out "
+                           "like the buffers that share its member stride")
+    return t.stride(0)
+
+
 class _Layer:
     """One Linear layer of all members: weight (M, rows, cols), bias (M, r4(rows)), their moments, the bias gradient."""
 
     def __init__(self, name: str, layers: Sequence[nn.Linear], dev):
         self.name = name
         M, (rows, cols) = len(layers), layers[0].weight.shape
-        self.rows, self.cols, self.ldb = int(rows), int(cols), r4(int(rows))
+        self.rows, self.cols = int(rows), int(cols)
         f32 = dict(dtype=torch.float32, device=dev)
         self.W = torch.empty(M, rows, cols, **f32)
-        self.b = torch.zeros(M, self.ldb, **f32)
+        self.b = torch.zeros(M, r4(self.rows), **f32)
         with torch.no_grad():
             for m, layer in enumerate(layers):
                 # parameters move into the stacks; the modules keep views of them
@@ -138,6 +140,8 @@ class _Layer:
         self.mW, self.vW = torch.zeros_like(self.W), torch.zeros_like(self.W)
         self.mb, self.vb = torch.zeros_like(self.b), torch.zeros_like(self.b)
         self.db = torch.zeros_like(self.b)
+        self.s_W = _member_stride(self.W, self.mW, self.vW)
+        self.s_b = _member_stride(self.b, self.mb, self.vb, self.db)
 
     def moments(self, m: int):
         return {self.name + ".weight": (self.mW[m], self.vW[m]),
@@ -154,6 +158,8 @@ class _Workspace:
         self.pred = torch.zeros(M, B, dtype=torch.int64, device=dev)
         self.h = torch.zeros(M, B, H, **f32) if H else None          # the hidden activations, kept for the backward
         self.dh = torch.zeros(M, B, H, **f32) if H else None
+        self.s_logits, self.s_dlogits, self.s_pred = (_member_stride(t) for t in (self.logits, self.dlogits, self.pred))
+        self.s_h = _member_stride(self.h, self.dh) if H else 0
 
 
 class ClassifierEnsembleEngine:
@@ -166,22 +172,22 @@ class ClassifierEnsembleEngine:
         self.shallow = hasattr(first, "hidden")
         K, N = self.K, self.N = int(first.input_dim), int(first.n_classes)
         dev = self.device = next(first.parameters()).device
+        self.act, self.slope = activation_code(first)
         if self.shallow:
             self.H = int(first.hidden.out_features)
-            self.act, self.slope = _activation(first)
             self.hidden = _Layer("hidden", [m.hidden for m in self.models], dev)
             self.head = _Layer("output", [m.output for m in self.models], dev)
             self.layers = [self.hidden, self.head]
         else:
-            self.H, self.act, self.slope = 0, 0, 0.0
+            self.H = 0
             self.hidden = None
             self.head = _Layer("linear", [m.linear for m in self.models], dev)
             self.layers = [self.head]
-        self.ldb = self.head.ldb
-        self._dW: Optional[torch.Tensor] = None          # on demand (the logistic dense path only)
+        self._dW: Optional[torch.Tensor] = None          # on demand (the logistic dense path only), with its member stride
+        self._s_dW = 0
         # loss sum (the bits of a double), sample count, label-range flag, confusion matrix per member: one read per epoch
-        self.words = 3 + N * N
-        self.stats = torch.zeros(M, self.words, dtype=torch.int64, device=dev)
+        self.stats = torch.zeros(M, 3 + N * N, dtype=torch.int64, device=dev)
+        self.s_stats = _member_stride(self.stats)        # in 8-byte words
         # the schedule and the hyper-parameters are the single engine's: the two decay groups of ``_setup_training`` (the
         # weights decay, the biases do not), ``stored_beta2`` scalars; member 0's parameters stand for the group
         decay, no_decay = split_decay_groups(first.named_parameters())
@@ -240,26 +246,34 @@ class ClassifierEnsembleEngine:
             raise ValueError(f"expected ({self.M}, {B}) labels, got {tuple(y.shape)}")
         return y.long().contiguous()
 
+    def _input_stride(self, t: torch.Tensor) -> int:
+        """The member stride of a batch ``_input`` / ``_labels`` made dense.  A group of one has none: the leading stride of a
+        dense (1, ...) tensor is arbitrary, and the kernels multiply it by member 0."""
+        return t.stride(0) if self.M > 1 else 0
+
     def _forward(self, x: torch.Tensor) -> _Workspace:
         B = x.shape[1]
         ws = self._workspace(B)
-        feat, kf = x, self.K
+        s_x = self._input_stride(x)
+        feat, s_feat, kf = x, s_x, self.K
         if self.shallow:
             hid, H = self.hidden, self.H
             # the launch of ``SimpleClassifierEngine._forward`` with the member on grid.z
-            launch_nt_group(self.lib, self.M, B * self.K, H * self.K, hid.ldb, B * H, self._active, A=ptr(x), Bw=ptr(hid.W),
+            launch_nt_group(self.lib, self.M, s_x, hid.s_W, hid.s_b, ws.s_h, self._active, A=ptr(x), Bw=ptr(hid.W),
                             bias=ptr(hid.b), out=ptr(ws.h), M=B, A_rows=B, N=H, K=self.K, lda=self.K, ldb=self.K, ldo=H, Tvalid=1,
                             loader=LOAD_DIRECT, epilogue=EPI_LRELU, slope=self.slope)
-            feat, kf = ws.h, H
-        self._call("tl_linear_rows_group", ptr(feat), ptr(self.head.W), ptr(self.head.b), ptr(ws.logits), self.M, B, kf, self.N, kf,
-                   0, B * kf, self.N * kf, self.ldb, B * self.N)
+            feat, s_feat, kf = ws.h, ws.s_h, H
+        head = self.head
+        self._call("tl_linear_rows_group", ptr(feat), ptr(head.W), ptr(head.b), ptr(ws.logits), self.M, B, kf, self.N, kf, 0,
+                   s_feat, head.s_W, head.s_b, ws.s_logits)
         return ws
 
     def _ce(self, ws: _Workspace, y: Optional[torch.Tensor], B: int, grad: bool, pred: bool) -> None:
         base, ldd = self.stats.data_ptr(), ws.dlogits.shape[2]
         self._call("tl_ce_loss_group", ptr(ws.logits), ptr(y), ptr(ws.dlogits) if grad else None,
                    ptr(self.head.db) if grad else None, ptr(ws.pred) if pred else None, base, base + 8, base + 24, base + 16, self.M,
-                   B, self.N, self.N, ldd, 1.0 / B, B * self.N, B, B * ldd, self.ldb, B, self.words)
+                   B, self.N, self.N, ldd, 1.0 / B, ws.s_logits, 0 if y is None else self._input_stride(y), ws.s_dlogits, self.head.s_b,
+                   ws.s_pred, self.s_stats)
 
     def _scalars(self):
         """The step's (coef_grad, coef_mom, bias_corr2): ``FusedNAdam._scalars``, as the single path computes them (both groups
@@ -268,22 +282,22 @@ class ClassifierEnsembleEngine:
         cg, cm, bc2, self.mu_product = self.optimizer._scalars(self.step_no, self.mu_product, self.optimizer.param_groups[0])
         return cg, cm, bc2
 
-    def _update_lowrank(self, layer: _Layer, fa: torch.Tensor, fb: torch.Tensor, B: int, scalars) -> None:
-        """``layer``'s weights by the rank-B gradient fa^T . fb, fa (M, B, ld >= rows), fb (M, B, cols)."""
+    def _update_lowrank(self, layer: _Layer, fa: torch.Tensor, s_fa: int, fb: torch.Tensor, s_fb: int, B: int, scalars) -> None:
+        """``layer``'s weights by the rank-B gradient fa^T . fb, fa (M, B, ld >= rows), fb (M, B, cols), at their member
+        strides."""
         gw = self.optimizer.param_groups[0]
         b1, b2 = gw["betas"]
         cg, cm, bc2 = scalars
-        ldfa = fa.shape[2]
         self._call("tl_nadam_lowrank_group", ptr(layer.W), ptr(layer.mW), ptr(layer.vW), ptr(fa), ptr(fb), self.M, B, layer.rows,
-                   layer.cols, ldfa, layer.cols, layer.rows * layer.cols, B * ldfa, B * layer.cols, cg, cm, b1, b2, bc2, gw["eps"],
+                   layer.cols, fa.shape[2], layer.cols, layer.s_W, s_fa, s_fb, cg, cm, b1, b2, bc2, gw["eps"],
                    gw["weight_decay"], 1.0)
 
     def _update_bias(self, layer: _Layer, scalars) -> None:
         gb = self.optimizer.param_groups[1]
         b1, b2 = gb["betas"]
         cg, cm, bc2 = scalars
-        self._call("tl_nadam_group", ptr(layer.b), ptr(layer.db), ptr(layer.mb), ptr(layer.vb), self.M, layer.rows, layer.ldb,
-                   layer.ldb, cg, cm, b1, b2, bc2, gb["eps"], gb["weight_decay"], 1.0)
+        self._call("tl_nadam_group", ptr(layer.b), ptr(layer.db), ptr(layer.mb), ptr(layer.vb), self.M, layer.rows, layer.s_b,
+                   layer.s_b, cg, cm, b1, b2, bc2, gb["eps"], gb["weight_decay"], 1.0)
 
     # ------------------------------------------------------------------ the public steps
     @torch.no_grad()
@@ -300,36 +314,34 @@ class ClassifierEnsembleEngine:
         dense = self.force_dense or B > FusedNAdam.LOWRANK_MAX          # the single engine's decision: B alone
         ws = self._forward(x)
         self._ce(ws, y, B, grad=True, pred=False)
-        ldd = ws.dlogits.shape[2]
+        ldd, s_x = ws.dlogits.shape[2], self._input_stride(x)
         scalars = self._scalars()
         head = self.head
         if self.shallow:
-            H, NH = self.H, self.N * self.H
             # dh (activation derivative applied) and the hidden bias gradient, off the output weight as it is BEFORE its update
             self._call("tl_head_bwd_act_group", ptr(ws.dlogits), ptr(ws.h), ptr(head.W), ptr(ws.dh), ptr(self.hidden.db), None,
-                       self.M, B, H, self.N, ldd, self.act, self.slope, B * ldd, B * H, NH, B * H, self.hidden.ldb, 0)
-            self._update_lowrank(self.hidden, ws.dh, x, B, scalars)
-            self._update_lowrank(head, ws.dlogits, ws.h, B, scalars)
+                       self.M, B, self.H, self.N, ldd, self.act, self.slope, ws.s_dlogits, ws.s_h, head.s_W, ws.s_h,
+                       self.hidden.s_b, 0)
+            self._update_lowrank(self.hidden, ws.dh, ws.s_h, x, s_x, B, scalars)
+            self._update_lowrank(head, ws.dlogits, ws.s_dlogits, ws.h, ws.s_h, B, scalars)
             self._update_bias(self.hidden, scalars)
         elif dense:
             gw = self.optimizer.param_groups[0]
             b1, b2 = gw["betas"]
             cg, cm, bc2 = scalars
-            NK = self.N * self.K
             if self._dW is None:
                 self._dW = torch.empty_like(head.W)
-            self._call("tl_head_bwd_group", ptr(ws.dlogits), ptr(x), ptr(head.W), ptr(self._dW), self.M, B, self.K, self.N, ldd,
-                       B * ldd, B * self.K, NK, NK)
-            self._call("tl_nadam_group", ptr(head.W), ptr(self._dW), ptr(head.mW), ptr(head.vW), self.M, NK, NK, NK, cg, cm, b1, b2,
-                       bc2, gw["eps"], gw["weight_decay"], 1.0)
+                self._s_dW = _member_stride(self._dW)
+            dW = self._dW
+            # the weight gradient alone: the arguments ``SimpleClassifierEngine._backward`` gives ``tl_head_bwd`` on this route
+            self._call("tl_head_bwd_group", ptr(ws.dlogits), ptr(x), ptr(head.W), ptr(dW), self.M, B, self.K, self.N, ldd,
+                       ws.s_dlogits, s_x, head.s_W, self._s_dW)
+            self._call("tl_nadam_group", ptr(head.W), ptr(dW), ptr(head.mW), ptr(head.vW), self.M, self.N * self.K, head.s_W,
+                       self._s_dW, cg, cm, b1, b2, bc2, gw["eps"], gw["weight_decay"], 1.0)
         else:
-            self._update_lowrank(head, ws.dlogits, x, B, scalars)
+            self._update_lowrank(head, ws.dlogits, ws.s_dlogits, x, s_x, B, scalars)
         self._update_bias(head, scalars)
-        for model in self.models:
-            # the update wrote through data_ptr: an inference engine of the module keys its packed weights on ``_version``
-            hip = getattr(model, "_hip", None)
-            if hip is not None:
-                hip._packed.clear()
+        invalidate_packed(*self.models)
 
     @torch.no_grad()
     def eval_batch(self, x: torch.Tensor, y: torch.Tensor) -> None:

@@ -35,6 +35,11 @@ def refuse(why: str):
     raise ValueError(f"{why}: {SUPPORTED}")
 
 
+def parameter_unmet(p) -> Optional[str]:
+    """The reason to refuse a parameter that is not fp32 on a CUDA device (None: it is)."""
+    return None if p.is_cuda and p.dtype == torch.float32 else f"parameters on '{p.device}' in {p.dtype}"
+
+
 def check_common(model, slopes=(), dropout: float = 0.0, also=()) -> None:
     """The conditions every engine sets, in the order the refusals are reported: ``negative_slope >= 0``, ``n_classes <= 64``,
     ``dropout < 1``, then the engine's own ``also`` [(refused, why)], last fp32 parameters on a CUDA device."""
@@ -49,8 +54,17 @@ def check_common(model, slopes=(), dropout: float = 0.0, also=()) -> None:
         if refused:
             refuse(why)
     for p in model.parameters():
-        if not p.is_cuda or p.dtype != torch.float32:
-            refuse(f"parameters on '{p.device}' in {p.dtype}")
+        if parameter_unmet(p):
+            refuse(parameter_unmet(p))
+
+
+def invalidate_packed(*models) -> None:
+    """Drop the packed inference weights of the models' HIP engines.  The update kernels write through ``data_ptr``: the
+    ``_version`` those weights are keyed on did not move."""
+    for model in models:
+        hip = getattr(model, "_hip", None)
+        if hip is not None:
+            hip._packed.clear()
 
 
 class ClassifierTrainEngine(LaunchTimers):
@@ -159,11 +173,7 @@ class ClassifierTrainEngine(LaunchTimers):
         return {}
 
     def _after_update(self) -> None:
-        # FusedNAdam writes through data_ptr: the module's inference engine keys its packed weights on ``_version``, which did
-        # not move
-        hip = getattr(self.model, "_hip", None)
-        if hip is not None:
-            hip._packed.clear()
+        invalidate_packed(self.model)
 
     # ------------------------------------------------------------------ data parallel, per step
     def _take(self, x: torch.Tensor, y: Optional[torch.Tensor] = None):

@@ -21,32 +21,56 @@ rank-B_global update.  Without one the step is the same launches on the whole ba
 There is no CPU fallback and no fallback to autograd: a model outside the supported set is refused."""
 from __future__ import annotations
 
+from typing import Dict, Tuple
+
 import torch
 import torch.nn as nn
 
 from . import _lib
 from ._classifier_train_engine import SUPPORTED  # noqa: F401  (re-exported: it was defined here)
-from ._classifier_train_engine import ClassifierTrainEngine, check_common, refuse
+from ._classifier_train_engine import ClassifierTrainEngine, parameter_unmet, refuse
 from ._launch import launch_nt, launch_tn, r4
 from ._lib import EPI_LRELU, LOAD_DIRECT, ptr
+
+
+def activation_code(model) -> Tuple[int, float]:
+    """(act code of ``tl_head_bwd``, slope) of a ``ShallowNNClassifier``'s activation; (0, 0.0) without a hidden layer."""
+    if not hasattr(model, "hidden"):
+        return 0, 0.0
+    act = model.activation
+    return (1, 0.0) if isinstance(act, nn.ReLU) else (2, float(act.negative_slope))
+
+
+def unmet(model) -> Dict[str, str]:
+    """What a simple classifier misses of the conditions the HIP step sets per model: {condition: the reason to refuse it
+    with}.  The keys - "activation", "hidden_dim", "input_dim", "n_classes", "bias", "parameters" - come in the order in
+    which the refusals are reported."""
+    out, shallow = {}, hasattr(model, "hidden")
+    layers = (model.hidden, model.output) if shallow else (model.linear,)
+    if shallow:
+        if not isinstance(model.activation, (nn.ReLU, nn.LeakyReLU)):
+            out["activation"] = f"activation {type(model.activation).__name__}"
+        if model.hidden.out_features % 4 != 0:
+            out["hidden_dim"] = f"hidden_dim {model.hidden.out_features}"
+    if model.input_dim % 4 != 0:
+        out["input_dim"] = f"input_dim {model.input_dim}"
+    if model.n_classes > 64:
+        out["n_classes"] = f"n_classes {model.n_classes}"
+    if any(layer.bias is None for layer in layers):
+        out["bias"] = "a layer without bias"
+    whys = [why for why in map(parameter_unmet, model.parameters()) if why]
+    if whys:
+        out["parameters"] = whys[0]
+    return out
 
 
 def check_supported(model) -> None:
     """Raise ``ValueError`` (stating the supported set) unless ``model`` can be trained by ``SimpleClassifierEngine``."""
     from .models.simple_classifiers import LogisticRegressionClassifier, ShallowNNClassifier
-    if isinstance(model, LogisticRegressionClassifier):
-        layers = [model.linear]
-    elif isinstance(model, ShallowNNClassifier):
-        layers = [model.hidden, model.output]
-        if not isinstance(model.activation, (nn.ReLU, nn.LeakyReLU)):
-            refuse(f"activation {type(model.activation).__name__}")
-        if model.hidden.out_features % 4 != 0:
-            refuse(f"hidden_dim {model.hidden.out_features}")
-    else:
+    if not isinstance(model, (LogisticRegressionClassifier, ShallowNNClassifier)):
         refuse(f"model {type(model).__name__}")
-    if model.input_dim % 4 != 0:
-        refuse(f"input_dim {model.input_dim}")
-    check_common(model, also=[(layer.bias is None, "a layer without bias") for layer in layers])
+    for why in unmet(model).values():
+        refuse(why)
 
 
 class _Workspace:
@@ -73,13 +97,12 @@ class SimpleClassifierEngine(ClassifierTrainEngine):
         self.K = int(model.input_dim)
         self.input_shape = (self.K,)
         self.shallow = hasattr(model, "hidden")
+        self.act, self.slope = activation_code(model)
         if self.shallow:
             self.H = int(model.hidden.out_features)
-            act = model.activation
-            self.act, self.slope = (1, 0.0) if isinstance(act, nn.ReLU) else (2, float(act.negative_slope))
             self.head_name, weights = "output", ("output.weight", "hidden.weight")
         else:
-            self.H, self.act, self.slope = 0, 0, 0.0
+            self.H = 0
             self.head_name, weights = "linear", ("linear.weight",)
         self.head_bias = self.head_name + ".bias"
         # the biases are always dense; a weight gets its buffer on demand (dense path only)

@@ -146,9 +146,8 @@ __global__ __launch_bounds__(64) void head_bwd_kernel(const float* __restrict__ 
                                                       float* __restrict__ dw, int B, int K, int N, int ldd, int act, float slope,
                                                       const int32_t* __restrict__ active, long long s_dl, long long s_h,
                                                       long long s_W, long long s_dh, long long s_dbh, long long s_dw) {
-  // member blockIdx.y of a group (tl_head_bwd_act_group; tl_head_bwd_group asks for dw only): its dl, h, W, dh, dbias_h and dw
-  // lie s_* elements behind member 0's; a member whose active word is 0 writes nothing.  The single launch is member 0 of a
-  // group of one.
+  // member blockIdx.y of a group (tl_head_bwd_act_group): its dl, h, W, dh, dbias_h and dw lie s_* elements behind member 0's; a
+  // member whose active word is 0 writes nothing.  The single launch is member 0 of a group of one.
   const int mem = blockIdx.y;
   if (active != nullptr && active[mem] == 0) return;
   dl += mem * s_dl;
@@ -257,7 +256,7 @@ extern "C" int tl_ce_loss_group(const float* logits, const int64_t* labels, floa
                                 double* loss_sum, int64_t* count, int64_t* confusion, int32_t* err, int M, int B, int N, int ldl,
                                 int ldd, float grad_scale, int64_t s_logits, int64_t s_labels, int64_t s_dlogits, int64_t s_dbias,
                                 int64_t s_pred, int64_t s_stats, const int32_t* active, void* stream) {
-  TL_REQUIRE(M >= 1 && M <= 65535, "ce_loss_group: the number of members M must lie in [1, 65535] (got %d)", M);
+  TL_REQUIRE_MEMBERS("ce_loss_group", M);
   TL_REQUIRE(B >= 1 && N >= 1 && s_logits >= 0 && s_labels >= 0, "ce_loss_group: bad sizes or a negative member stride");
   // members must not share what they write: every output stride covers a member's extent
   TL_REQUIRE(M == 1 || ((!dlogits || s_dlogits >= (int64_t)B * ldd) && (!dbias || s_dbias >= N) && (!pred || s_pred >= B)),
@@ -275,8 +274,10 @@ extern "C" int tl_ce_scores_loss(const float* scores, const int64_t* labels, flo
                          stream);
 }
 
-extern "C" int tl_head_bwd(const float* dlogits, const float* h, const float* W, float* dh, float* dbias_h, float* dw, int B,
-                           int K, int N, int ldd, int act, float slope, void* stream) {
+static int head_bwd_launch(const float* dlogits, const float* h, const float* W, float* dh, float* dbias_h, float* dw, int B,
+                           int K, int N, int ldd, int act, float slope, void* stream, int M = 1, int64_t s_dlogits = 0,
+                           int64_t s_h = 0, int64_t s_W = 0, int64_t s_dh = 0, int64_t s_dbias_h = 0, int64_t s_dw = 0,
+                           const int32_t* active = nullptr) {
   TL_REQUIRE(dlogits && h && W, "head_bwd: null dlogits / h / W");
   TL_REQUIRE(dh || dbias_h || dw, "head_bwd: null dh, dbias_h and dw (nothing to compute)");
   TL_REQUIRE(N >= 1 && N <= 64, "head_bwd: the number of outputs N must lie in [1, 64]");
@@ -285,56 +286,39 @@ extern "C" int tl_head_bwd(const float* dlogits, const float* h, const float* W,
   TL_REQUIRE(act >= 0 && act <= 2, "head_bwd: act must be 0 (none), 1 (ReLU) or 2 (LeakyReLU)");
   TL_REQUIRE((((uintptr_t)h | (uintptr_t)W | (uintptr_t)dh | (uintptr_t)dbias_h | (uintptr_t)dw) & 15) == 0,
              "head_bwd: h, W, dh, dbias_h and dw must be 16-byte aligned");
+  // members must not share what they write: every output stride covers a member's extent (products of the sizes checked above)
+  TL_REQUIRE(M == 1 || !dh || s_dh >= (int64_t)B * K, "head_bwd: member stride of dh shorter than the B x K elements of a member");
+  TL_REQUIRE(M == 1 || !dbias_h || s_dbias_h >= K, "head_bwd: member stride of dbias_h shorter than the K elements of a member");
+  TL_REQUIRE(M == 1 || !dw || s_dw >= (int64_t)N * K, "head_bwd: member stride of dw shorter than the N x K elements of a member");
   const int blocks = (K / 4 + 63) / 64;
-  hipLaunchKernelGGL(head_bwd_kernel, dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream, dlogits, h, W, dh, dbias_h, dw, B,
-                     K, N, ldd, act, act == 1 ? 0.f : slope, (const int32_t*)nullptr, 0LL, 0LL, 0LL, 0LL, 0LL, 0LL);
+  hipLaunchKernelGGL(head_bwd_kernel, dim3((unsigned)blocks, (unsigned)M), dim3(64), 0, (hipStream_t)stream, dlogits, h, W, dh,
+                     dbias_h, dw, B, K, N, ldd, act, act == 1 ? 0.f : slope, active, (long long)s_dlogits, (long long)s_h,
+                     (long long)s_W, (long long)s_dh, (long long)s_dbias_h, (long long)s_dw);
   return check_launch("head_bwd");
 }
 
-extern "C" int tl_head_bwd_group(const float* dlogits, const float* h, const float* W, float* dw, int M, int B, int K, int N,
-                                 int ldd, int64_t s_dlogits, int64_t s_h, int64_t s_W, int64_t s_dw, const int32_t* active,
-                                 void* stream) {
-  TL_REQUIRE(dlogits && h && W && dw, "head_bwd_group: null dlogits / h / W / dw");
-  TL_REQUIRE(M >= 1 && M <= 65535, "head_bwd_group: the number of members M must lie in [1, 65535] (got %d)", M);
-  TL_REQUIRE(N >= 1 && N <= 64, "head_bwd_group: the number of outputs N must lie in [1, 64]");
-  TL_REQUIRE(B >= 1 && K >= 4 && K % 4 == 0, "head_bwd_group: B >= 1 and K a positive multiple of 4 needed (columns move as float4)");
-  TL_REQUIRE(ldd >= N, "head_bwd_group: row stride ldd of dlogits below N");
-  TL_REQUIRE((((uintptr_t)h | (uintptr_t)W | (uintptr_t)dw) & 15) == 0, "head_bwd_group: h, W and dw must be 16-byte aligned");
-  TL_REQUIRE(s_dlogits >= 0 && s_h >= 0 && s_W >= 0 && s_h % 4 == 0 && s_W % 4 == 0 && s_dw % 4 == 0,
-             "head_bwd_group: the member strides of h, W and dw must be non-negative multiples of 4 elements (16-byte aligned members)");
-  TL_REQUIRE(M == 1 || s_dw >= (int64_t)N * K, "head_bwd_group: member stride of dw shorter than the N x K elements of a member");
-  const int blocks = (K / 4 + 63) / 64;
-  hipLaunchKernelGGL(head_bwd_kernel, dim3((unsigned)blocks, (unsigned)M), dim3(64), 0, (hipStream_t)stream, dlogits, h, W,
-                     (float*)nullptr, (float*)nullptr, dw, B, K, N, ldd, 0, 0.f, active, (long long)s_dlogits, (long long)s_h,
-                     (long long)s_W, 0LL, 0LL, (long long)s_dw);
-  return check_launch("head_bwd_group");
+extern "C" int tl_head_bwd(const float* dlogits, const float* h, const float* W, float* dh, float* dbias_h, float* dw, int B,
+                           int K, int N, int ldd, int act, float slope, void* stream) {
+  return head_bwd_launch(dlogits, h, W, dh, dbias_h, dw, B, K, N, ldd, act, slope, stream);
 }
 
 extern "C" int tl_head_bwd_act_group(const float* dlogits, const float* h, const float* W, float* dh, float* dbias_h, float* dw,
                                      int M, int B, int K, int N, int ldd, int act, float slope, int64_t s_dlogits, int64_t s_h,
                                      int64_t s_W, int64_t s_dh, int64_t s_dbias_h, int64_t s_dw, const int32_t* active,
                                      void* stream) {
-  TL_REQUIRE(dlogits && h && W, "head_bwd_act_group: null dlogits / h / W");
-  TL_REQUIRE(dh || dbias_h || dw, "head_bwd_act_group: null dh, dbias_h and dw (nothing to compute)");
-  TL_REQUIRE(M >= 1 && M <= 65535, "head_bwd_act_group: the number of members M must lie in [1, 65535] (got %d)", M);
-  TL_REQUIRE(N >= 1 && N <= 64, "head_bwd_act_group: the number of outputs N must lie in [1, 64]");
-  TL_REQUIRE(B >= 1 && K >= 4 && K % 4 == 0,
-             "head_bwd_act_group: B >= 1 and K a positive multiple of 4 needed (columns move as float4)");
-  TL_REQUIRE(ldd >= N, "head_bwd_act_group: row stride ldd of dlogits below N");
-  TL_REQUIRE(act >= 0 && act <= 2, "head_bwd_act_group: act must be 0 (none), 1 (ReLU) or 2 (LeakyReLU)");
-  TL_REQUIRE((((uintptr_t)h | (uintptr_t)W | (uintptr_t)dh | (uintptr_t)dbias_h | (uintptr_t)dw) & 15) == 0,
-             "head_bwd_act_group: h, W, dh, dbias_h and dw must be 16-byte aligned");
+  TL_REQUIRE_MEMBERS("head_bwd_act_group", M);
   TL_REQUIRE(s_dlogits >= 0 && s_h >= 0 && s_W >= 0 && s_dh >= 0 && s_dbias_h >= 0 && s_dw >= 0 && s_h % 4 == 0 && s_W % 4 == 0 &&
                  s_dh % 4 == 0 && s_dbias_h % 4 == 0 && s_dw % 4 == 0,
              "head_bwd_act_group: the member strides of h, W, dh, dbias_h and dw must be non-negative multiples of 4 elements "
              "(16-byte aligned members)");
-  // members must not share what they write: every output stride covers a member's extent
-  TL_REQUIRE(M == 1 || !dh || s_dh >= (int64_t)B * K, "head_bwd_act_group: member stride of dh shorter than the B x K elements of a member");
-  TL_REQUIRE(M == 1 || !dbias_h || s_dbias_h >= K, "head_bwd_act_group: member stride of dbias_h shorter than the K elements of a member");
-  TL_REQUIRE(M == 1 || !dw || s_dw >= (int64_t)N * K, "head_bwd_act_group: member stride of dw shorter than the N x K elements of a member");
-  const int blocks = (K / 4 + 63) / 64;
-  hipLaunchKernelGGL(head_bwd_kernel, dim3((unsigned)blocks, (unsigned)M), dim3(64), 0, (hipStream_t)stream, dlogits, h, W, dh,
-                     dbias_h, dw, B, K, N, ldd, act, act == 1 ? 0.f : slope, active, (long long)s_dlogits, (long long)s_h,
-                     (long long)s_W, (long long)s_dh, (long long)s_dbias_h, (long long)s_dw);
-  return check_launch("head_bwd_act_group");
+  return head_bwd_launch(dlogits, h, W, dh, dbias_h, dw, B, K, N, ldd, act, slope, stream, M, s_dlogits, s_h, s_W, s_dh, s_dbias_h,
+                         s_dw, active);
+}
+
+// the dw-only form (the dense route of the logistic group): tl_head_bwd_act_group without dh and dbias_h, act 0
+extern "C" int tl_head_bwd_group(const float* dlogits, const float* h, const float* W, float* dw, int M, int B, int K, int N,
+                                 int ldd, int64_t s_dlogits, int64_t s_h, int64_t s_W, int64_t s_dw, const int32_t* active,
+                                 void* stream) {
+  return tl_head_bwd_act_group(dlogits, h, W, nullptr, nullptr, dw, M, B, K, N, ldd, 0, 0.f, s_dlogits, s_h, s_W, 0, 0, s_dw, active,
+                               stream);
 }

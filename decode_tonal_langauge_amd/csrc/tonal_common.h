@@ -27,6 +27,10 @@ inline int check_launch(const char* what) {
     }                                        \
   } while (0)
 
+// the member count of a group entry (tl_*_group): the members are a grid dimension
+#define TL_REQUIRE_MEMBERS(entry, M) \
+  TL_REQUIRE((M) >= 1 && (M) <= 65535, "%s: the number of members M must lie in [1, 65535] (got %d)", entry, M)
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 

@@ -887,7 +887,7 @@ extern "C" int tl_gemm_nt_window_group(const tl_nt_params* pp, int M, int64_t s_
   using namespace tl;
   TL_REQUIRE(pp != nullptr, "nt_window_group: null params");
   tl_nt_params p = *pp;
-  TL_REQUIRE(M >= 1 && M <= 65535, "nt_window_group: the number of members M must lie in [1, 65535] (got %d)", M);
+  TL_REQUIRE_MEMBERS("nt_window_group", M);
   TL_REQUIRE(p.J == 1 && p.loader == LOAD_DIRECT && p.row_shift == 0,
              "nt_window_group: only the plain GEMM has a group form (J = 1, DIRECT loader, row_shift = 0; got J %d, loader %d, "
              "row_shift %d)", p.J, p.loader, p.row_shift);

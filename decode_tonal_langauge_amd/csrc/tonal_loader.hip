@@ -167,7 +167,7 @@ extern "C" int tl_gather_rows_group(const void* const* src, void* const* dst, co
                                     const int64_t* C, const int64_t* inner_bytes, const int32_t* const* chan,
                                     const int64_t* n_chan, int n_seg, const int64_t* idx, int64_t idx_stride, int64_t n_idx, int M,
                                     const int32_t* active, int32_t* err, void* stream) {
-  TL_REQUIRE(M >= 1 && M <= 65535, "gather_rows_group: the number of members M must lie in [1, 65535] (got %d)", M);
+  TL_REQUIRE_MEMBERS("gather_rows_group", M);
   TL_REQUIRE(dst_stride != nullptr, "gather_rows_group: null table of member strides");
   TL_REQUIRE(M == 1 || idx_stride >= n_idx, "gather_rows_group: member stride of idx shorter than the n_idx indices of a batch");
   for (int i = 0; i < n_seg && i < 4; ++i)

@@ -1551,29 +1551,31 @@ extern "C" int tl_l1_mcd(const float* out, const float* targets, float* dout, fl
   return check_launch("l1_mcd");
 }
 
+static int nadam_launch(float* p, const float* g, float* m, float* v, int64_t n, float coef_grad, float coef_mom, float beta1,
+                        float beta2, float bias_corr2, float eps, float weight_decay, float grad_scale, void* stream, int M = 1,
+                        int64_t s_p = 0, int64_t s_g = 0, const int32_t* active = nullptr) {
+  TL_REQUIRE(p && g && m && v && n > 0, "nadam: bad arguments");
+  TL_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "nadam: pointers must be 16-byte aligned");
+  hipLaunchKernelGGL(nadam_kernel, dim3(grid_for(n / 4 + 1, 256, 256LL * 8), (unsigned)M), dim3(256), 0, (hipStream_t)stream, p, g,
+                     m, v, (long long)n, coef_grad, coef_mom, beta1, beta2, bias_corr2, eps, weight_decay, grad_scale, active,
+                     (long long)s_p, (long long)s_g);
+  return check_launch("nadam");
+}
+
 extern "C" int tl_nadam(float* p, const float* g, float* m, float* v, int64_t n, float coef_grad, float coef_mom,
                         float beta1, float beta2, float bias_corr2, float eps, float weight_decay, float grad_scale,
                         void* stream) {
-  TL_REQUIRE(p && g && m && v && n > 0, "nadam: bad arguments");
-  TL_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "nadam: pointers must be 16-byte aligned");
-  hipLaunchKernelGGL(nadam_kernel, dim3(grid_for(n / 4 + 1, 256, 256LL * 8)), dim3(256), 0, (hipStream_t)stream, p, g,
-                     m, v, (long long)n, coef_grad, coef_mom, beta1, beta2, bias_corr2, eps, weight_decay, grad_scale,
-                     (const int32_t*)nullptr, 0LL, 0LL);
-  return check_launch("nadam");
+  return nadam_launch(p, g, m, v, n, coef_grad, coef_mom, beta1, beta2, bias_corr2, eps, weight_decay, grad_scale, stream);
 }
 
 extern "C" int tl_nadam_group(float* p, const float* g, float* m, float* v, int M, int64_t n, int64_t s_p, int64_t s_g,
                               float coef_grad, float coef_mom, float beta1, float beta2, float bias_corr2, float eps,
                               float weight_decay, float grad_scale, const int32_t* active, void* stream) {
-  TL_REQUIRE(p && g && m && v && n > 0, "nadam_group: bad arguments");
-  TL_REQUIRE(M >= 1 && M <= 65535, "nadam_group: the number of members M must lie in [1, 65535] (got %d)", M);
+  TL_REQUIRE_MEMBERS("nadam_group", M);
   TL_REQUIRE(M == 1 || (s_p >= n && s_g >= n), "nadam_group: member strides shorter than the %lld elements of a member", (long long)n);
-  TL_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0 && s_p % 4 == 0 && s_g % 4 == 0,
-             "nadam_group: pointers must be 16-byte aligned and the member strides multiples of 4 elements");
-  hipLaunchKernelGGL(nadam_kernel, dim3(grid_for(n / 4 + 1, 256, 256LL * 8), (unsigned)M), dim3(256), 0, (hipStream_t)stream, p, g,
-                     m, v, (long long)n, coef_grad, coef_mom, beta1, beta2, bias_corr2, eps, weight_decay, grad_scale, active,
-                     (long long)s_p, (long long)s_g);
-  return check_launch("nadam_group");
+  TL_REQUIRE(s_p % 4 == 0 && s_g % 4 == 0, "nadam_group: the member strides must be multiples of 4 elements (16-byte aligned members)");
+  return nadam_launch(p, g, m, v, n, coef_grad, coef_mom, beta1, beta2, bias_corr2, eps, weight_decay, grad_scale, stream, M, s_p,
+                      s_g, active);
 }
 
 extern "C" int tl_nadam_multi(const tl_nadam_entry* entries_dev, int count, int64_t total_blocks, float coef_grad,
@@ -1645,7 +1647,7 @@ extern "C" int tl_nadam_lowrank_group(float* p, float* m, float* v, const float*
                                       int cols, int ldfa, int ldfb, int64_t s_p, int64_t s_fa, int64_t s_fb, float coef_grad,
                                       float coef_mom, float beta1, float beta2, float bias_corr2, float eps, float weight_decay,
                                       float grad_scale, const int32_t* active, void* stream) {
-  TL_REQUIRE(M >= 1 && M <= 65535, "nadam_lowrank_group: the number of members M must lie in [1, 65535] (got %d)", M);
+  TL_REQUIRE_MEMBERS("nadam_lowrank_group", M);
   TL_REQUIRE(rows > 0 && cols > 0 && (M == 1 || s_p >= (int64_t)rows * cols),
              "nadam_lowrank_group: member stride of p, m, v shorter than the rows x cols elements of a member");
   TL_REQUIRE(M == 1 || kr <= 0 || (s_fa >= 0 && s_fb >= 0), "nadam_lowrank_group: negative member stride of a factor");
@@ -1679,35 +1681,33 @@ extern "C" int tl_splitk_bias_lrelu(const float* slab, const float* bias, float*
   return check_launch("splitk_bias_lrelu");
 }
 
-extern "C" int tl_linear_rows(const float* x, const float* w, const float* bias, float* out, int B, int K, int N, int64_t ldx,
-                              int act, void* stream) {
+static int linear_rows_launch(const float* x, const float* w, const float* bias, float* out, int B, int K, int N, int64_t ldx,
+                              int act, void* stream, int M = 1, int64_t s_x = 0, int64_t s_w = 0, int64_t s_bias = 0,
+                              int64_t s_out = 0, const int32_t* active = nullptr) {
   using namespace tl;
   TL_REQUIRE(x && w && out, "linear_rows: null pointer");
   TL_REQUIRE(B > 0 && K > 0 && N > 0 && N <= 64, "linear_rows: bad sizes (1 <= N <= 64 output columns)");
   TL_REQUIRE(act == 0 || act == 1, "linear_rows: act must be 0 (none) or 1 (sigmoid)");
   TL_REQUIRE(K % 4 == 0 && ldx >= K && ldx % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)w % 16) == 0,
              "linear_rows: K and ldx must be multiples of 4 and x, w 16-byte aligned (rows are read as float4)");
-  hipLaunchKernelGGL(linear_rows_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, x, w, bias, out, K, N, (long long)ldx, act,
-                     (const int32_t*)nullptr, 0LL, 0LL, 0LL, 0LL);
+  hipLaunchKernelGGL(linear_rows_kernel, dim3((unsigned)B, (unsigned)M), dim3(256), 0, (hipStream_t)stream, x, w, bias, out, K, N,
+                     (long long)ldx, act, active, (long long)s_x, (long long)s_w, (long long)s_bias, (long long)s_out);
   return check_launch("linear_rows");
+}
+
+extern "C" int tl_linear_rows(const float* x, const float* w, const float* bias, float* out, int B, int K, int N, int64_t ldx,
+                              int act, void* stream) {
+  return linear_rows_launch(x, w, bias, out, B, K, N, ldx, act, stream);
 }
 
 extern "C" int tl_linear_rows_group(const float* x, const float* w, const float* bias, float* out, int M, int B, int K, int N,
                                     int64_t ldx, int act, int64_t s_x, int64_t s_w, int64_t s_bias, int64_t s_out,
                                     const int32_t* active, void* stream) {
-  using namespace tl;
-  TL_REQUIRE(x && w && out, "linear_rows_group: null pointer");
-  TL_REQUIRE(M >= 1 && M <= 65535, "linear_rows_group: the number of members M must lie in [1, 65535] (got %d)", M);
-  TL_REQUIRE(B > 0 && K > 0 && N > 0 && N <= 64, "linear_rows_group: bad sizes (1 <= N <= 64 output columns)");
-  TL_REQUIRE(act == 0 || act == 1, "linear_rows_group: act must be 0 (none) or 1 (sigmoid)");
-  TL_REQUIRE(K % 4 == 0 && ldx >= K && ldx % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)w % 16) == 0,
-             "linear_rows_group: K and ldx must be multiples of 4 and x, w 16-byte aligned (rows are read as float4)");
+  TL_REQUIRE_MEMBERS("linear_rows_group", M);
   TL_REQUIRE(s_x % 4 == 0 && s_w % 4 == 0 && s_x >= 0 && s_w >= 0 && s_bias >= 0,
              "linear_rows_group: the member strides of x and w must be non-negative multiples of 4 elements (16-byte aligned members)");
   TL_REQUIRE(M == 1 || s_out >= (int64_t)B * N, "linear_rows_group: member stride of out shorter than the B x N elements of a member");
-  hipLaunchKernelGGL(linear_rows_kernel, dim3((unsigned)B, (unsigned)M), dim3(256), 0, (hipStream_t)stream, x, w, bias, out, K, N,
-                     (long long)ldx, act, active, (long long)s_x, (long long)s_w, (long long)s_bias, (long long)s_out);
-  return check_launch("linear_rows_group");
+  return linear_rows_launch(x, w, bias, out, B, K, N, ldx, act, stream, M, s_x, s_w, s_bias, s_out, active);
 }
 
 extern "C" int tl_labels_from_scores(const float* tone_scores, const float* syl_scores, const float* table, float* labels,

@@ -18,15 +18,12 @@ method the global generator holds the LAST member's state, as a sequential loop 
 The order drawing (``MemberStreams``, ``draw_orders``, ``check_loaders``) is host only and needs no GPU."""
 from __future__ import annotations
 
-import csv
-import os
 from typing import Dict, List, Optional, Sequence
 
-import numpy as np
 import torch
 
 from ..data_loading.resident import ResidentLoader
-from .classifier_trainer import macro_scores
+from .classifier_trainer import EarlyStopping, epoch_line, epoch_row, macro_scores, write_confusion, write_metrics
 
 LOADERS = ("the classifier ensemble takes one ResidentLoader per member, all over the SAME ResidentDataset object, with equal "
            "subset sizes and equal batch size")
@@ -154,7 +151,7 @@ class ClassifierEnsembleTrainer:
         check_loaders(val_loaders, M)
         # shallow members train batches of at most FusedNAdam.LOWRANK_MAX rows: refused here, before the first epoch
         check_train_batch(self.engine.shallow, int(train_loaders[0].batch_size))
-        best, wait, step = [float("inf")] * M, [0] * M, 0
+        stopping, step = [EarlyStopping(patience) for _ in range(M)], 0
         active = [True] * M
         try:
             for epoch in range(max_epochs):
@@ -166,22 +163,15 @@ class ClassifierEnsembleTrainer:
                 step += len(train_loaders[0])
                 va = self._run_epoch(val_loaders, False, members)
                 for m in members:
-                    row = {"epoch": epoch, "step": step - 1, "train/loss_epoch": tr[m]["loss"],
-                           "train/accuracy": tr[m]["accuracy"], "val/loss": va[m]["loss"], "val/accuracy": va[m]["accuracy"],
-                           "train/weight_norm": self._weight_norm(m)}
+                    row = epoch_row(epoch, step, tr[m], va[m], self.models[m])
                     self.history[m].append(row)
                     if self.verbose:
-                        print(f"member {m} epoch {epoch}: train/loss {tr[m]['loss']:.4f}  val/loss {va[m]['loss']:.4f}  "
-                              f"val/accuracy {va[m]['accuracy']:.3f}")
-                    if va[m]["loss"] < best[m]:
-                        best[m], wait[m] = va[m]["loss"], 0
-                    else:
-                        wait[m] += 1
-                        if wait[m] >= patience:
-                            self.stopped_epoch[m] = epoch
-                            active[m] = False
+                        print(f"member {m} {epoch_line(row)}")
+                    if stopping[m].stops(va[m]["loss"]):
+                        self.stopped_epoch[m] = epoch
+                        active[m] = False
             for m in range(M):
-                self._write_metrics(m)
+                write_metrics(self.log_dirs[m], self.history[m])
         finally:
             self.engine.set_active([True] * M)               # evaluation takes every member; nothing updates from here on
             self.streams.leave()
@@ -200,9 +190,7 @@ class ClassifierEnsembleTrainer:
             cm = got[m]["confusion_matrix"]
             scores = macro_scores(cm)
             self.test_accuracy[m], self.test_f1[m], self.confusion_matrix[m] = scores["accuracy"], scores["f1"], cm
-            if self.log_dirs[m] is not None:
-                os.makedirs(self.log_dirs[m], exist_ok=True)
-                np.savetxt(os.path.join(self.log_dirs[m], "confusion_matrix_test.csv"), cm.numpy(), fmt="%d", delimiter=",")
+            write_confusion(self.log_dirs[m], cm)
             out.append({"accuracy": scores["accuracy"], "f1": scores["f1"], "confusion_matrix": cm})
         return out
 
@@ -217,16 +205,3 @@ class ClassifierEnsembleTrainer:
         finally:
             self.streams.leave()
         return [preds[m].clone() for m in members]
-
-    # ------------------------------------------------------------------ helpers
-    def _weight_norm(self, m: int) -> float:
-        return float(sum(float(p.detach().norm(2)) ** 2 for p in self.models[m].parameters() if p.requires_grad) ** 0.5)
-
-    def _write_metrics(self, m: int) -> None:
-        if self.log_dirs[m] is None or not self.history[m]:
-            return
-        os.makedirs(self.log_dirs[m], exist_ok=True)
-        with open(os.path.join(self.log_dirs[m], "metrics.csv"), "w", newline="") as f:
-            w = csv.DictWriter(f, fieldnames=list(self.history[m][0].keys()))
-            w.writeheader()
-            w.writerows(self.history[m])

@@ -56,6 +56,56 @@ def macro_scores(cm: torch.Tensor) -> Dict[str, float]:
     return {"accuracy": float(recall[present].sum() / k), "f1": float(f1[present].sum() / k)}
 
 
+# ---------------------------------------------------------------------- shared with ``ClassifierEnsembleTrainer``
+def epoch_row(epoch: int, step: int, tr: Dict[str, float], va: Dict[str, float], model: nn.Module) -> Dict[str, float]:
+    """The ``metrics.csv`` row of one epoch (Lightning's column names); ``step``: optimiser steps taken so far."""
+    return {"epoch": epoch, "step": step - 1, "train/loss_epoch": tr["loss"], "train/accuracy": tr["accuracy"],
+            "val/loss": va["loss"], "val/accuracy": va["accuracy"], "train/weight_norm": weight_norm(model)}
+
+
+def epoch_line(row: Dict[str, float]) -> str:
+    return (f"epoch {row['epoch']}: train/loss {row['train/loss_epoch']:.4f}  val/loss {row['val/loss']:.4f}  "
+            f"val/accuracy {row['val/accuracy']:.3f}")
+
+
+class EarlyStopping:
+    """Early stopping of one model on ``val/loss``: ``patience`` consecutive epochs without a new minimum."""
+
+    def __init__(self, patience: int) -> None:
+        self.patience, self.best, self.wait = patience, float("inf"), 0
+
+    def stops(self, val_loss: float) -> bool:
+        """Record an epoch's ``val/loss``; true when training stops after it."""
+        if val_loss < self.best:
+            self.best, self.wait = val_loss, 0
+            return False
+        self.wait += 1
+        return self.wait >= self.patience
+
+
+def weight_norm(model: nn.Module) -> float:
+    return float(sum(float(p.detach().norm(2)) ** 2 for p in model.parameters() if p.requires_grad) ** 0.5)
+
+
+def write_metrics(log_dir: Optional[str], history: List[Dict[str, float]]) -> None:
+    """``metrics.csv`` of one run (the writing rank only)."""
+    if log_dir is None or not history or not parallel.is_writer():
+        return
+    os.makedirs(log_dir, exist_ok=True)
+    with open(os.path.join(log_dir, "metrics.csv"), "w", newline="") as f:
+        w = csv.DictWriter(f, fieldnames=list(history[0].keys()))
+        w.writeheader()
+        w.writerows(history)
+
+
+def write_confusion(log_dir: Optional[str], cm: torch.Tensor) -> None:
+    """``confusion_matrix_test.csv`` of one run (the writing rank only)."""
+    if log_dir is None or not parallel.is_writer():
+        return
+    os.makedirs(log_dir, exist_ok=True)
+    np.savetxt(os.path.join(log_dir, "confusion_matrix_test.csv"), cm.numpy(), fmt="%d", delimiter=",")
+
+
 class ClassifierTrainer:
     def __init__(self, model: ClassifierModel, learning_rate: float = 0.0005, weight_decay: float = 0.0,
                  log_dir: Optional[str] = None, verbose: bool = False, fused: bool = False) -> None:
@@ -126,26 +176,23 @@ class ClassifierTrainer:
         return {"loss": loss_sum / max(n_seen, 1), "accuracy": macro_scores(cm)["accuracy"]}
 
     def fit(self, train_loader, val_loader, max_epochs: int, patience: int) -> List[Dict[str, float]]:
-        best, wait, step = float("inf"), 0, 0
+        stopping, step = EarlyStopping(patience), 0
         for epoch in range(max_epochs):
             tr = self._run_epoch(train_loader, True)
             step += len(train_loader)
             va = self._run_epoch(val_loader, False)
-            row = {"epoch": epoch, "step": step - 1, "train/loss_epoch": tr["loss"], "train/accuracy": tr["accuracy"],
-                   "val/loss": va["loss"], "val/accuracy": va["accuracy"], "train/weight_norm": self._weight_norm()}
+            row = epoch_row(epoch, step, tr, va, self.model)
             self.history.append(row)
             if self.verbose:
-                print(f"epoch {epoch}: train/loss {tr['loss']:.4f}  val/loss {va['loss']:.4f}  "
-                      f"val/accuracy {va['accuracy']:.3f}")
-            if va["loss"] < best:
-                best, wait = va["loss"], 0
-            else:
-                wait += 1
-                if wait >= patience:
-                    self.stopped_epoch = epoch
-                    break
+                print(epoch_line(row))
+            if stopping.stops(va["loss"]):
+                self.stopped_epoch = epoch
+                break
         self._write_metrics()
         return self.history
+
+    def _write_metrics(self) -> None:
+        write_metrics(self.log_dir, self.history)
 
     # ------------------------------------------------------------------ evaluation
     @torch.no_grad()
@@ -162,9 +209,7 @@ class ClassifierTrainer:
                 cm += _confusion(y.long().cpu(), self.model(x).argmax(1).cpu(), n_cls)
         scores = macro_scores(cm)
         self.test_accuracy, self.test_f1, self.confusion_matrix = scores["accuracy"], scores["f1"], cm
-        if self.log_dir is not None and parallel.is_writer():
-            os.makedirs(self.log_dir, exist_ok=True)
-            np.savetxt(os.path.join(self.log_dir, "confusion_matrix_test.csv"), cm.numpy(), fmt="%d", delimiter=",")
+        write_confusion(self.log_dir, cm)
         return {"accuracy": self.test_accuracy, "f1": self.test_f1, "confusion_matrix": cm}
 
     @torch.no_grad()
@@ -180,15 +225,3 @@ class ClassifierTrainer:
 
     def get_layer_nparams(self) -> Dict[str, int]:
         return self.model.get_layer_nparams()
-
-    def _weight_norm(self) -> float:
-        return float(sum(float(p.detach().norm(2)) ** 2 for p in self.model.parameters() if p.requires_grad) ** 0.5)
-
-    def _write_metrics(self) -> None:
-        if self.log_dir is None or not self.history or not parallel.is_writer():
-            return
-        os.makedirs(self.log_dir, exist_ok=True)
-        with open(os.path.join(self.log_dir, "metrics.csv"), "w", newline="") as f:
-            w = csv.DictWriter(f, fieldnames=list(self.history[0].keys()))
-            w.writeheader()
-            w.writerows(self.history)

@@ -26,31 +26,52 @@ from ..utils.utils import set_seeds
 from ..utils.visualise import plot_confusion_matrix
 
 
-def _fit_one(params: Namespace, dataset, seed: int, n_classes: int, n_channels: int, seq_length: int, tag: str,
-             announce: bool):
-    """Split, build, train, test and predict one model for one seed.  Returns (model, preds, true)."""
-    verbose = getattr(params, "verbose", 1)
+def _prologue(params: Namespace, dataset, seed: int, n_classes: int, n_channels: int, seq_length: int, announce: bool,
+              resident: bool):
+    """What a seed's run does before its trainer exists, in the order its draws from torch's global generator depend on: the
+    split, the ``true`` pass over the test loader (it draws a base seed BEFORE the model is built), the model.  Returns
+    (loaders, true, model)."""
     loaders = split_dataset(dataset, [params.train_ratio, params.vali_ratio, params.test_ratio],
-                            shuffling=[True, False, False], batch_size=params.batch_size, seed=int(seed),
-                            resident=bool(getattr(params, "resident", False)), device=params.device)
+                            shuffling=[True, False, False], batch_size=params.batch_size, seed=int(seed), resident=resident,
+                            device=params.device)
     true = np.concatenate([b[1].cpu().numpy() for b in loaders[2]])
     model = get_classifier_by_name(params.model, params.device, n_classes, n_channels, seq_length,
                                    classifier_kwargs=getattr(params, "model_kwargs", None))
     if announce:
         print(f"Number of trainable parameters: {model.get_layer_nparams()}")
-    run_dir = os.path.join(params.log_dir, f"{tag}_csv", f"subject_{params.subject_id}", "seed_" + str(seed))
+    return loaders, true, model
+
+
+def _run_dir(params: Namespace, tag: str, seed: int) -> str:
+    return os.path.join(params.log_dir, f"{tag}_csv", f"subject_{params.subject_id}", f"seed_{int(seed)}")
+
+
+def _save_checkpoint(params: Namespace, tag: str, seed: int, model, stacked: bool = False) -> None:
+    """``model``'s state dict under ``model_checkpoints`` (on request, the writing rank only).  ``stacked``: the parameters are
+    views of an ensemble's stacks - save the member, not the stack."""
+    if not getattr(params, "save_checkpoints", False) or not parallel.is_writer():
+        return
+    model_dir = os.path.join(params.log_dir, "model_checkpoints")
+    os.makedirs(model_dir, exist_ok=True)
+    path = os.path.join(model_dir, f"{tag}_{params.model_name}_seed_{int(seed)}.pt")
+    state = model.state_dict()
+    torch.save({k: v.clone() for k, v in state.items()} if stacked else state, path)
+    if getattr(params, "verbose", 1) > 0:
+        print(f"Model saved to {path}")
+
+
+def _fit_one(params: Namespace, dataset, seed: int, n_classes: int, n_channels: int, seq_length: int, tag: str,
+             announce: bool):
+    """Split, build, train, test and predict one model for one seed.  Returns (model, preds, true)."""
+    loaders, true, model = _prologue(params, dataset, seed, n_classes, n_channels, seq_length, announce,
+                                     resident=bool(getattr(params, "resident", False)))
     trainer = ClassifierTrainer(model, learning_rate=params.lr, weight_decay=float(getattr(params, "weight_decay", 0.0)),
-                                log_dir=run_dir, verbose=verbose > 1, fused=bool(getattr(params, "fused", False)))
+                                log_dir=_run_dir(params, tag, seed), verbose=getattr(params, "verbose", 1) > 1,
+                                fused=bool(getattr(params, "fused", False)))
     trainer.fit(loaders[0], loaders[1], max_epochs=params.epochs, patience=params.patience)
     trainer.test(loaders[2])
     preds = trainer.predict(loaders[2]).cpu().numpy()
-    if getattr(params, "save_checkpoints", False) and parallel.is_writer():
-        model_dir = os.path.join(params.log_dir, "model_checkpoints")
-        os.makedirs(model_dir, exist_ok=True)
-        path = os.path.join(model_dir, f"{tag}_{params.model_name}_seed_{seed}.pt")
-        torch.save(model.state_dict(), path)
-        if verbose > 0:
-            print(f"Model saved to {path}")
+    _save_checkpoint(params, tag, seed, model)
     return model, preds, true
 
 
@@ -75,56 +96,31 @@ def _resident(dataset, device):
                                                else ("cuda" if not dataset.tensors[0].is_cuda else None))
 
 
-def _ensemble_prologue(params: Namespace, rds, seed: int, n_classes: int, n_channels: int, seq_length: int, announce: bool):
-    """What ``_fit_one`` does for a seed before its trainer exists, in its order: the split, the ``true`` pass over the test
-    loader (it draws a base seed BEFORE the model is built), the model.  Returns (loaders, true, model, generator state)."""
-    loaders = split_dataset(rds, [params.train_ratio, params.vali_ratio, params.test_ratio], shuffling=[True, False, False],
-                            batch_size=params.batch_size, seed=int(seed), resident=True, device=params.device)
-    true = np.concatenate([b[1].cpu().numpy() for b in loaders[2]])
-    model = get_classifier_by_name(params.model, params.device, n_classes, n_channels, seq_length,
-                                   classifier_kwargs=getattr(params, "model_kwargs", None))
-    if announce:
-        print(f"Number of trainable parameters: {model.get_layer_nparams()}")
-    return loaders, true, model, torch.get_rng_state()
-
-
 def _fit_ensemble(params: Namespace, rds, seeds, n_classes: int, n_channels: int, seq_length: int, tag: str, announce: bool,
                   states=None):
     """``_fit_one`` for all seeds of one (target, model) group at once.  ``states``: per seed the generator state its
     prologue starts from (None: ``set_seeds(seed)``, the start of a seed's stream).  Returns (models, preds, trues, states at
     the end of each seed's stream)."""
     from ..models.classifier_ensemble_trainer import ClassifierEnsembleTrainer
-    verbose = getattr(params, "verbose", 1)
     loaders, trues, models, entered = [], [], [], []
     for i, seed in enumerate(seeds):
         if states is None:
             set_seeds(int(seed))
         else:
             torch.set_rng_state(states[i])
-        lo, true, model, state = _ensemble_prologue(params, rds, int(seed), n_classes, n_channels, seq_length,
-                                                    announce and i == 0)
+        lo, true, model = _prologue(params, rds, seed, n_classes, n_channels, seq_length, announce and i == 0, resident=True)
         loaders.append(lo)
         trues.append(true)
         models.append(model)
-        entered.append(state)
-    run_dirs = [os.path.join(params.log_dir, f"{tag}_csv", f"subject_{params.subject_id}", "seed_" + str(int(seed)))
-                for seed in seeds]
+        entered.append(torch.get_rng_state())                # where the seed's ``fit`` is entered
     trainer = ClassifierEnsembleTrainer(models, learning_rate=params.lr, weight_decay=float(getattr(params, "weight_decay", 0.0)),
-                                        log_dirs=run_dirs, verbose=verbose > 1, rng_states=entered)
+                                        log_dirs=[_run_dir(params, tag, seed) for seed in seeds],
+                                        verbose=getattr(params, "verbose", 1) > 1, rng_states=entered)
     trainer.fit([lo[0] for lo in loaders], [lo[1] for lo in loaders], max_epochs=params.epochs, patience=params.patience)
     trainer.test([lo[2] for lo in loaders])
     preds = [p.cpu().numpy() for p in trainer.predict([lo[2] for lo in loaders])]
-    if getattr(params, "save_checkpoints", False) and parallel.is_writer():
-        model_dir = os.path.join(params.log_dir, "model_checkpoints")
-        os.makedirs(model_dir, exist_ok=True)
-        for seed, model in zip(seeds, models):
-            path = os.path.join(model_dir, f"{tag}_{params.model_name}_seed_{int(seed)}.pt")
-            state = model.state_dict()
-            for k in state:                # the parameters are views of the group's stacks: save the member, not the stack
-                state[k] = state[k].clone()
-            torch.save(state, path)
-            if verbose > 0:
-                print(f"Model saved to {path}")
+    for seed, model in zip(seeds, models):
+        _save_checkpoint(params, tag, seed, model, stacked=True)
     return models, preds, trues, [trainer.rng_state(m) for m in range(len(models))]
 
 

@@ -527,16 +527,16 @@ int tl_ce_scores_loss(const float* scores, const int64_t* labels, float* dlogits
  * aligned.  With dh null and h = x this is the weight gradient of LogisticRegressionClassifier's layer.                    */
 int tl_head_bwd(const float* dlogits, const float* h, const float* W, float* dh, float* dbias_h, float* dw, int B, int K, int N,
                 int ldd, int act, float slope, void* stream);
-/* ... for M members (see the group launches above), the logistic dense form only: dw[m] = dlogits[m]^T . h[m] (no dh, no
- * dbias_h, no activation); grid (column blocks, M); s_h, s_W and s_dw multiples of 4                                        */
-int tl_head_bwd_group(const float* dlogits, const float* h, const float* W, float* dw, int M, int B, int K, int N, int ldd,
-                      int64_t s_dlogits, int64_t s_h, int64_t s_W, int64_t s_dw, const int32_t* active, void* stream);
-/* ... and the full tl_head_bwd for M members (the output layer of ShallowNNClassifier): any subset of dh, dbias_h, dw, act 0 / 1
- * / 2; the strides of h, W, dh, dbias_h and dw non-negative multiples of 4, and with M > 1 those of the outputs asked for at
- * least a member's B K, K and N K elements                                                                                 */
+/* ... for M members (see the group launches above; the output layer of ShallowNNClassifier): grid (column blocks, M), any subset
+ * of dh, dbias_h, dw, act 0 / 1 / 2; the strides of h, W, dh, dbias_h and dw non-negative multiples of 4, and with M > 1 those of
+ * the outputs asked for at least a member's B K, K and N K elements                                                        */
 int tl_head_bwd_act_group(const float* dlogits, const float* h, const float* W, float* dh, float* dbias_h, float* dw, int M, int B,
                           int K, int N, int ldd, int act, float slope, int64_t s_dlogits, int64_t s_h, int64_t s_W, int64_t s_dh,
                           int64_t s_dbias_h, int64_t s_dw, const int32_t* active, void* stream);
+/* ... and its dw-only form (the dense route of the logistic group): tl_head_bwd_act_group with dh = dbias_h = NULL and act 0,
+ * dw[m] = dlogits[m]^T . h[m]                                                                                               */
+int tl_head_bwd_group(const float* dlogits, const float* h, const float* W, float* dw, int M, int B, int K, int N, int ldd,
+                      int64_t s_dlogits, int64_t s_h, int64_t s_W, int64_t s_dw, const int32_t* active, void* stream);
 /* tl_gemm_nt_window for M members (the hidden layer of ShallowNNClassifier): *p describes member 0; member m works on A + m s_A,
  * Bw + m s_Bw, bias + m s_bias and out + m s_out (elements).  Only the plain GEMM with bias and LeakyReLU has a group form:
  * J = 1, loader DIRECT, row_shift 0, splitk <= 1, bm 0 or 128, epilogue LRELU (ReLU is slope 0), bias given, and none of aux /

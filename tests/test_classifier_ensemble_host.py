@@ -1,7 +1,7 @@
 """CPU: the host side of the classifier ensemble - every member's epoch orders and the state of torch's global generator are
 those of stock loaders run seed after seed (one target, and two targets in the seed-major order of the pipeline), what the
-ensemble does not take is refused with the supported set, and the ``tl_*_group`` entry points are declared, exported and
-validate their arguments without a launch."""
+ensemble does not take (logistic or shallow members) is refused with the supported set, and the ``tl_*_group`` entry points
+are declared, typed and exported and validate their arguments without a launch."""
 import ctypes as C
 import os
 import re
@@ -9,6 +9,7 @@ from argparse import Namespace
 
 import pytest
 import torch
+import torch.nn as nn
 from torch.utils.data import TensorDataset
 
 from decode_tonal_langauge_amd.data_loading.dataloaders import split_dataset
@@ -20,6 +21,9 @@ RATIOS, SHUFFLE, BATCH = [0.7, 0.1, 0.2], [True, False, False], 8
 SEEDS, EPOCHS = (3, 11, 42), 3
 GROUP = ("tl_linear_rows_group", "tl_ce_loss_group", "tl_head_bwd_group", "tl_nadam_lowrank_group", "tl_nadam_group",
          "tl_gather_rows_group")
+NEW = ("tl_gemm_nt_window_group", "tl_head_bwd_act_group")
+LOAD_DIRECT, LOAD_UNPOOL = 0, 1
+EPI_STORE, EPI_LRELU, EPI_POOL = 0, 1, 2
 
 
 def _dataset(n):
@@ -169,6 +173,59 @@ def test_ensemble_needs_fused_and_is_off_by_default():
         train_classifier.run({"training": {"params": {"ensemble": True, "fused": True, "io": {"sample_dir": "/nonexistent"}}}})
 
 
+def test_check_supported_refuses_with_the_supported_set(monkeypatch):
+    from decode_tonal_langauge_amd import parallel
+    from decode_tonal_langauge_amd._classifier_ensemble_engine import ClassifierEnsembleEngine, check_supported
+    from decode_tonal_langauge_amd.models.classifier_ensemble_trainer import ClassifierEnsembleTrainer
+    from decode_tonal_langauge_amd.models.simple_classifiers import LogisticRegressionClassifier as LR, ShallowNNClassifier as NN
+
+    def leaky(slope):
+        m = NN(40, 3, 20, "LeakyReLU")
+        assert isinstance(m.activation, nn.LeakyReLU)
+        m.activation.negative_slope = slope
+        return m
+
+    tanh = NN(40, 3, 20, "ReLU")
+    tanh.activation = nn.Tanh()                        # (the model's own constructor does not build one)
+    nobias = NN(40, 3, 20, "ReLU")
+    nobias.output.bias = None
+    cases = (([LR(40, 3), NN(40, 3, 20, "ReLU")], "model ShallowNNClassifier in a group of LogisticRegressionClassifier"),
+             ([NN(40, 3, 20, "ReLU"), LR(40, 3)], "model LogisticRegressionClassifier in a group of ShallowNNClassifier"),
+             ([NN(40, 3, 20, "ReLU"), NN(40, 3, 24, "ReLU")], "member 1 has shape (40 -> 24 -> 3), member 0 (40 -> 20 -> 3)"),
+             ([NN(40, 3, 20, "ReLU"), NN(40, 4, 20, "ReLU")], "member 1 has shape (40 -> 20 -> 4)"),
+             ([tanh], "activation Tanh"),
+             ([NN(40, 3, 20, "ReLU"), tanh], "activation Tanh"),
+             ([NN(40, 3, 20, "ReLU"), NN(40, 3, 20, "LeakyReLU")], "member 1 has activation LeakyReLU, member 0 ReLU"),
+             ([leaky(0.01), leaky(0.2)], "member 1 has negative_slope 0.2, member 0 0.01"),
+             ([NN(40, 3, 18, "ReLU")], "hidden_dim 18"),
+             ([NN(42, 3, 20, "ReLU")], "input_dim 42"),
+             ([NN(40, 65, 20, "ReLU")], "n_classes 65"),
+             ([nobias], "a layer without bias"),
+             ([NN(40, 3, 20, "ReLU"), NN(40, 3, 20, "ReLU")], "cpu"))                  # parameters on the CPU: no fallback
+    for models, what in cases:
+        for build in (check_supported, ClassifierEnsembleEngine, ClassifierEnsembleTrainer):
+            with pytest.raises(ValueError, match="classifier ensemble supports one or more LogisticRegressionClassifier") as e:
+                build(models)
+            msg = str(e.value)
+            assert what in msg, (what, msg)
+            assert "ShallowNNClassifier of equal input_dim, hidden_dim and n_classes" in msg and "at most 64 rows" in msg
+    monkeypatch.setattr(parallel, "world", lambda: (0, 2))
+    with pytest.raises(ValueError, match="classifier ensemble supports") as e:
+        check_supported([NN(40, 3, 20, "ReLU"), NN(40, 3, 20, "ReLU")])
+    assert "process group of 2 ranks" in str(e.value) and "single process" in str(e.value)
+
+
+def test_training_batches_above_the_low_rank_limit_are_refused_for_shallow_members_only():
+    from decode_tonal_langauge_amd._classifier_ensemble_engine import check_train_batch
+    from decode_tonal_langauge_amd.optim import FusedNAdam
+    assert FusedNAdam.LOWRANK_MAX == 64
+    check_train_batch(True, 64)
+    check_train_batch(False, 65)
+    check_train_batch(False, 4096)
+    with pytest.raises(ValueError, match="at most 64 rows"):
+        check_train_batch(True, 65)
+
+
 # ------------------------------------------------------------------ ABI
 def test_group_entry_points_are_declared_typed_and_exported():
     from decode_tonal_langauge_amd import _lib
@@ -247,3 +304,79 @@ def test_group_argument_validation_without_gpu():
     assert gat(idx_stride=7) == -1 and b"member stride of idx" in err()
     assert gat(dst_stride=L4(63, 64, 64, 64)) == -1 and b"member stride of dst" in err()
     assert gat(n_seg=5) == -1 and b"at most 4" in err()
+
+
+# the entries the shallow members added
+def test_new_entry_points_are_declared_typed_and_exported():
+    from decode_tonal_langauge_amd import _lib
+    lib = _lib.load()
+    header = open(os.path.join(ROOT, "include", "tonal_hip.h")).read()
+    for name in NEW:
+        m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*?)\)\s*;", header, re.S)
+        assert m, f"{name} is not declared in include/tonal_hip.h"
+        assert name in _lib.SIGNATURES and hasattr(lib, name), name
+        assert len(m.group(1).split(",")) == len(_lib.SIGNATURES[name][1]), name
+
+
+def test_nt_window_group_argument_validation_without_gpu():
+    from decode_tonal_langauge_amd import _lib
+    from decode_tonal_langauge_amd._launch import _NT_DEFAULTS
+    lib = _lib.load()
+    err = lib.tl_last_error
+
+    def nt(M=3, sA=32, sBw=96, sb=12, so=48, null_params=False, **fields):
+        # member 0: A (4, 8), Bw (12, 8), bias (12), out (4, 12); nothing is launched, the pointers are never followed
+        base = dict(A=16, Bw=16, bias=16, out=16, M=4, A_rows=4, N=12, K=8, lda=8, ldb=8, ldo=12, Tvalid=1, loader=LOAD_DIRECT,
+                    epilogue=EPI_LRELU, slope=0.01)
+        p = _lib.NtParams(**{**_NT_DEFAULTS, **base, **fields})
+        return lib.tl_gemm_nt_window_group(None if null_params else C.byref(p), M, sA, sBw, sb, so, None, None)
+
+    assert nt(null_params=True) == -1 and b"null params" in err()
+    for name in ("A", "Bw", "out"):
+        assert nt(**{name: None}) == -1 and b"null A/Bw/out" in err(), name
+    assert nt(bias=None) == -1 and b"null bias" in err()
+    assert nt(M=0) == -1 and b"[1, 65535]" in err()
+    assert nt(M=65536) == -1 and b"[1, 65535]" in err()
+    assert nt(J=3) == -1 and b"J = 1" in err()
+    assert nt(J=3, row_shift=-2) == -1 and b"row_shift" in err()
+    assert nt(loader=LOAD_UNPOOL, abits=16) == -1 and b"DIRECT" in err()
+    for epi in (EPI_STORE, EPI_POOL):
+        assert nt(epilogue=epi, obits=16) == -1 and b"LRELU" in err(), epi
+    assert nt(epilogue=EPI_STORE) == -1 and b"LRELU" in err()
+    assert nt(splitk=2) == -1 and b"split-K" in err()
+    assert nt(bm=32) == -1 and b"bm must be 0 or 128" in err()
+    assert nt(bm=256) == -1 and b"bm must be 0 or 128" in err()
+    for name in ("aux", "auxbits", "abits", "obits", "osign", "vout", "vout2", "vhalo", "c1x", "c1bits", "c1partial", "mask"):
+        assert nt(**{name: 16}) == -1 and b"no member stride" in err(), name
+    assert nt(sA=34) == -1 and b"multiples of 4 elements" in err()
+    assert nt(sBw=98) == -1 and b"multiples of 4 elements" in err()
+    assert nt(sA=-4) == -1 and nt(sBw=-4) == -1 and nt(sb=-1) == -1 and b"non-negative" in err()
+    assert nt(so=47) == -1 and b"member stride of out" in err()
+    assert nt(K=6, lda=8, ldb=8) == -1 and b"multiples of 4" in err()            # a check of tl_gemm_nt_window itself
+    assert nt(lda=4) == -1 and b"smaller than K" in err()
+
+
+def test_head_bwd_act_group_argument_validation_without_gpu():
+    from decode_tonal_langauge_amd import _lib
+    lib = _lib.load()
+    err = lib.tl_last_error
+
+    def hb(dl=16, h=16, W=16, dh=16, dbh=16, dw=16, M=3, B=4, K=8, N=3, ldd=4, act=2, sdl=16, sh=32, sW=24, sdh=32, sdbh=8,
+           sdw=24):
+        return lib.tl_head_bwd_act_group(dl, h, W, dh, dbh, dw, M, B, K, N, ldd, act, 0.01, sdl, sh, sW, sdh, sdbh, sdw, None, None)
+
+    for name in ("dl", "h", "W"):
+        assert hb(**{name: None}) == -1 and b"null dlogits / h / W" in err(), name
+    assert hb(dh=None, dbh=None, dw=None) == -1 and b"nothing to compute" in err()
+    assert hb(M=0) == -1 and b"[1, 65535]" in err()
+    assert hb(act=3) == -1 and hb(act=-1) == -1 and b"act must be" in err()
+    for name in ("sh", "sW", "sdh", "sdbh", "sdw"):
+        assert hb(**{name: 34}) == -1 and b"multiples of 4 elements" in err(), name
+        assert hb(**{name: -4}) == -1 and b"multiples of 4 elements" in err(), name
+    assert hb(sdh=28) == -1 and b"member stride of dh" in err()
+    assert hb(sdbh=4) == -1 and b"member stride of dbias_h" in err()
+    assert hb(sdw=20) == -1 and b"member stride of dw" in err()
+    assert hb(K=6) == -1 and b"multiple of 4" in err()
+    assert hb(N=65, ldd=68) == -1 and b"[1, 64]" in err()
+    assert hb(ldd=2) == -1 and b"below N" in err()
+    assert hb(h=20) == -1 and hb(dbh=24) == -1 and b"16-byte aligned" in err()

@@ -6,52 +6,18 @@ epochs, and the pipeline key against the sequential pipeline.
 
 All comparisons are exact (``torch.equal`` on the raw buffers): a group kernel IS the single kernel, launched with a member
 dimension, and the single engine's own tests tie it to the float64 reference."""
-import copy
 import ctypes as C
-import filecmp
-import os
-import sys
 
-import numpy as np
 import pytest
 import torch
 from torch.utils.data import TensorDataset
 
+from tests import ensemble_cases as ec
+from tests.ensemble_cases import CANARY, CASES, DEV, IDS
+from tests.ensemble_cases import (canary as _canary, gen as _gen, lib as _lib, mask_words as _mask, on as _on, r4 as _r4,
+                                  stream as _stream)
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-CANARY = -777.25
-MASKS = {1: [None], 3: [None, (1, 0, 1)]}
-CASES = [(M, mask) for M in (1, 3) for mask in MASKS[M]]
-IDS = [f"M{M}" + ("" if mask is None else "_masked") for M, mask in CASES]
-
-
-def _r4(n):
-    return (n + 3) // 4 * 4
-
-
-def _lib():
-    from decode_tonal_langauge_amd import _lib as L
-    return L, L.load()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _mask(mask):
-    return None if mask is None else torch.tensor(mask, dtype=torch.int32, device=DEV)
-
-
-def _on(mask, m):
-    return mask is None or bool(mask[m])
-
-
-def _canary(*shape, dtype=torch.float32):
-    return torch.full(shape, CANARY if dtype.is_floating_point else -7, dtype=dtype, device=DEV)
-
-
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
 
 
 # ---------------------------------------------------------------------------------------------- forward and loss
@@ -255,240 +221,21 @@ def test_gather_group_of_the_resident_dataset():
         assert torch.equal(gx[m].cpu(), x[table[m, 8:13]])
 
 
-# ---------------------------------------------------------------------------------------------- engine
-def _member_models(n, K=12, N=3):
-    from decode_tonal_langauge_amd.models.simple_classifiers import LogisticRegressionClassifier
-    out = []
-    for m in range(n):
-        torch.manual_seed(100 + m)
-        out.append(LogisticRegressionClassifier(K, N).to(DEV))
-    return out
-
-
-def _moments(eng):
-    return {k: (eng.optimizer.state[p]["exp_avg"], eng.optimizer.state[p]["exp_avg_sq"]) for k, p in eng.params.items()}
-
-
-@pytest.mark.parametrize("sizes", [(8, 8), (65, 65), (65, 19)], ids=["lowrank", "dense", "dense_then_lowrank"])
+# ---------------------------------------------------------------------------------------------- engine, trainer, pipeline
+# (the bodies are tests/ensemble_cases.py's, shared with the shallow members' module)
+@pytest.mark.parametrize("sizes", ec.KINDS["logistic"]["sizes"], ids=["lowrank", "dense", "dense_then_lowrank"])
 def test_engine_steps_equal_the_single_engine(sizes):
-    from decode_tonal_langauge_amd._classifier_ensemble_engine import ClassifierEnsembleEngine
-    from decode_tonal_langauge_amd._simple_classifier_engine import SimpleClassifierEngine
-    models = _member_models(3)
-    singles = [SimpleClassifierEngine(copy.deepcopy(m), 0.01, 0.02) for m in models]
-    ens = ClassifierEnsembleEngine(models, 0.01, 0.02)
-    assert all(torch.equal(a.linear.weight, s.model.linear.weight) for a, s in zip(models, singles))     # the views hold the values
-    g = _gen(9)
-    for B in sizes:
-        x = torch.randn(3, B, 2, 6, generator=g).to(DEV)
-        y = torch.randint(0, 3, (3, B), generator=g).float().to(DEV)
-        ens.train_batch(x, y)
-        for m, s in enumerate(singles):
-            s.train_batch(x[m], y[m])
-    torch.cuda.synchronize()
-    mode = torch.cuda.get_sync_debug_mode()
-    torch.cuda.set_sync_debug_mode("error")                    # warm: no step reads the device
-    try:
-        ens.eval_batch(x, y)
-        ens.train_batch(x, y)
-    finally:
-        torch.cuda.set_sync_debug_mode(mode)
-    for m, s in enumerate(singles):
-        s.eval_batch(x[m], y[m])
-        s.train_batch(x[m], y[m])
-    stats = ens.epoch_stats()
-    for m, s in enumerate(singles):
-        for k, v in s.model.state_dict().items():
-            assert torch.equal(models[m].state_dict()[k], v), (m, k)
-        for k, (ma, va) in _moments(s).items():
-            assert torch.equal(ens.moments(m)[k][0], ma) and torch.equal(ens.moments(m)[k][1], va), (m, k)
-        loss, count, cm = s.epoch_stats()
-        assert stats[m][0] == loss and stats[m][1] == count == sum(sizes) + 2 * sizes[-1] and torch.equal(stats[m][2], cm), m
-    assert len({float(m.linear.weight.detach().sum()) for m in models}) == 3
-    # inference through the module reads the stacked storage
-    with torch.no_grad():
-        assert torch.equal(models[1](x[1]).argmax(1), ens.predict_batch(x)[1])
+    ec.engine_steps_equal_the_single_engine("logistic", sizes)
 
 
 def test_engine_mask_freezes_a_member_and_names_the_member_with_a_bad_label():
-    from decode_tonal_langauge_amd._classifier_ensemble_engine import ClassifierEnsembleEngine
-    from decode_tonal_langauge_amd._simple_classifier_engine import SimpleClassifierEngine
-    models = _member_models(3)
-    singles = [SimpleClassifierEngine(copy.deepcopy(m), 0.01, 0.0) for m in models]
-    ens = ClassifierEnsembleEngine(models, 0.01, 0.0)
-    g = _gen(2)
-    batches = [(torch.randn(3, B, 12, generator=g).to(DEV), torch.randint(0, 3, (3, B), generator=g).to(DEV)) for B in (8, 65, 8)]
-    ens.train_batch(*batches[0])
-    frozen = copy.deepcopy(models[1].state_dict())
-    ens.set_active([True, False, True])
-    for x, y in batches[1:]:
-        ens.train_batch(x, y)
-    stats = ens.epoch_stats()
-    for m, s in enumerate(singles):
-        for x, y in batches[:1] if m == 1 else batches:
-            s.train_batch(x[m], y[m])
-        for k, v in s.model.state_dict().items():
-            assert torch.equal(models[m].state_dict()[k], v), (m, k)
-        assert stats[m][:2] == s.epoch_stats()[:2], m
-    assert all(torch.equal(frozen[k], v) for k, v in models[1].state_dict().items())
-    ens.set_active([True] * 3)
-    x, y = batches[0][0], batches[0][1].clone()
-    y[2, 3] = 3
-    ens.eval_batch(x, y)
-    with pytest.raises(ValueError, match=r"\[0, 3\).*member 2"):
-        ens.epoch_stats()
-    with pytest.raises(ValueError, match="expected input"):
-        ens.train_batch(x[:2], y[:2])
-
-
-# ---------------------------------------------------------------------------------------------- trainer
-SEEDS, LR, WD = (3, 11, 42), 0.1, 0.01       # the float32 CPU loop stops these seeds after epochs 3, 2 and 1 (val/loss turns by > 4 %)
-
-
-def _planted():
-    g = _gen(1)
-    y = torch.randint(0, 3, (53,), generator=g)
-    x = torch.randn(53, 2, 6, generator=g)
-    for k in range(3):
-        x.view(53, 12)[y == k, 4 * k:4 * k + 4] += 1.0
-    return TensorDataset(x, y.float())
-
-
-def _prologue(dataset, seed):
-    from decode_tonal_langauge_amd.data_loading.dataloaders import split_dataset
-    from decode_tonal_langauge_amd.models.simple_classifiers import LogisticRegressionClassifier
-    from decode_tonal_langauge_amd.utils.utils import set_seeds
-    set_seeds(seed)
-    loaders = split_dataset(dataset, [0.7, 0.1, 0.2], [True, False, False], batch_size=8, seed=seed, resident=True, device=DEV)
-    list(loaders[2])                                           # the pipeline's `true` pass draws before the model is built
-    return loaders, LogisticRegressionClassifier(12, 3).to(DEV), torch.get_rng_state()
+    ec.engine_mask_freezes_a_member("logistic")
 
 
 def test_trainer_equals_sequential_fused_runs_with_members_stopping_apart(tmp_path):
-    from decode_tonal_langauge_amd.data_loading.resident import ResidentDataset
-    from decode_tonal_langauge_amd.models.classifier_ensemble_trainer import ClassifierEnsembleTrainer
-    from decode_tonal_langauge_amd.models.classifier_trainer import ClassifierTrainer
-    tds = _planted()
-    seq = []
-    for seed in SEEDS:
-        loaders, model, state = _prologue(tds, seed)
-        assert len(loaders[0]) == 5 and len(loaders[0].sampler.indices) == 37  # four full batches and a ragged one
-        tr = ClassifierTrainer(model, LR, WD, log_dir=str(tmp_path / f"seq_{seed}"), fused=True)
-        hist = tr.fit(loaders[0], loaders[1], max_epochs=6, patience=1)
-        seq.append(dict(hist=hist, stopped=tr.stopped_epoch, test=tr.test(loaders[2]), pred=tr.predict(loaders[2]),
-                        sd=copy.deepcopy(model.state_dict()), entered=state))
-    final = torch.get_rng_state()
-    print("stopped_epoch of the sequential runs:", [s["stopped"] for s in seq])
-    assert len({s["stopped"] for s in seq}) > 1                # the masked path is exercised
-
-    rds = ResidentDataset.from_tensor_dataset(tds, device=DEV)
-    torch.manual_seed(777)
-    pro = [_prologue(rds, seed) for seed in SEEDS]
-    assert all(torch.equal(p[2], s["entered"]) for p, s in zip(pro, seq))
-    torch.manual_seed(778)                                     # the trainer works from the states it is given
-    dirs = [str(tmp_path / f"ens_{seed}") for seed in SEEDS]
-    ens = ClassifierEnsembleTrainer([p[1] for p in pro], LR, WD, log_dirs=dirs, rng_states=[p[2] for p in pro])
-    hists = ens.fit([p[0][0] for p in pro], [p[0][1] for p in pro], max_epochs=6, patience=1)
-    tests = ens.test([p[0][2] for p in pro])
-    preds = ens.predict([p[0][2] for p in pro])
-    assert torch.equal(torch.get_rng_state(), final)
-    for m, (seed, s) in enumerate(zip(SEEDS, seq)):
-        assert ens.stopped_epoch[m] == s["stopped"] and len(hists[m]) == len(s["hist"]), seed
-        for a, b in zip(hists[m], s["hist"]):
-            assert list(a) == list(b)
-            for key in a:
-                if key == "train/weight_norm":
-                    assert abs(a[key] - b[key]) <= 1e-6 * abs(b[key]), (seed, key)
-                else:
-                    assert a[key] == b[key], (seed, key, a[key], b[key])
-        assert tests[m]["accuracy"] == s["test"]["accuracy"] == ens.test_accuracy[m] and tests[m]["f1"] == s["test"]["f1"]
-        assert torch.equal(tests[m]["confusion_matrix"], s["test"]["confusion_matrix"])
-        assert torch.equal(ens.confusion_matrix[m], s["test"]["confusion_matrix"]) and ens.test_f1[m] == s["test"]["f1"]
-        assert preds[m].dtype == torch.int64 and preds[m].is_cuda and torch.equal(preds[m], s["pred"])
-        sd = pro[m][1].state_dict()
-        assert list(sd) == list(s["sd"]) and all(torch.equal(sd[k], v) for k, v in s["sd"].items()), seed
-        for name in ("metrics.csv", "confusion_matrix_test.csv"):
-            assert filecmp.cmp(os.path.join(dirs[m], name), str(tmp_path / f"seq_{seed}" / name), shallow=False), (seed, name)
-    assert torch.equal(ens.rng_state(len(SEEDS) - 1), final)
-    with pytest.raises(RuntimeError, match="runs once"):
-        ens.fit([p[0][0] for p in pro], [p[0][1] for p in pro], max_epochs=1, patience=1)
-
-
-# ---------------------------------------------------------------------------------------------- pipeline
-def _run_pipeline(tmp_path, monkeypatch, tag, separate, ensemble):
-    from decode_tonal_langauge_amd import train_classifier
-    from decode_tonal_langauge_amd.data_loading import synthetic
-    root = tmp_path / "data"
-    if not root.exists():
-        synthetic.write_dataset(str(root), n_samples=240, n_channels=8, n_timepoints=50)     # every joint class in every test split
-    got = {}
-    for name in ("train_joint_targets", "train_separate_targets"):
-        fn = getattr(train_classifier, name)
-        monkeypatch.setattr(train_classifier, name, lambda p, s, fn=fn: got.setdefault("out", fn(p, s)))
-    params = {"fused": True, "resident": True,
-              "io": {"log_dir": str(tmp_path / f"logs_{tag}"), "sample_dir": str(root / "samples"),
-                     "channel_selection_dir": str(root / "channels"), "save_checkpoints": True},
-              "experiment": {"targets": ["syllable", "tone"] if separate else ["tone"], "features": "ecog",
-                             "separate_models": separate, "seed": 1, "repeat": 3, "verbose": 0, "device": DEV},
-              "training": {"train_ratio": 0.7, "vali_ratio": 0.1, "test_ratio": 0.2, "batch_size": 16, "epochs": 4, "lr": 0.05,
-                           "patience": 1, "weight_decay": 0.01, "log_every_n_steps": 10}}
-    if ensemble is not None:
-        params["ensemble"] = ensemble
-    config = {"model": {"model": "models.simple_classifiers.LogisticRegressionClassifier", "model_name": "logistic",
-                        "model_kwargs": {}},
-              "dataset": {"class_labels": {"tone": None, "syllable": ["i", "a"]}},
-              "training": {"module": "train_classifier", "params": params},
-              "evaluation": {"metrics": ["accuracy", "f1_score", "confusion_matrix"], "aggregates": ["mean", "std"]}}
-    log_dir = train_classifier.run(config)
-    monkeypatch.undo()
-    return log_dir, got["out"], torch.get_rng_state()
-
-
-def _same(a, b, where=""):
-    if isinstance(a, dict):
-        assert isinstance(b, dict) and list(a) == list(b), where
-        for k in a:
-            _same(a[k], b[k], f"{where}/{k}")
-    elif isinstance(a, np.ndarray):
-        assert np.array_equal(a, b), where
-    elif isinstance(a, (list, tuple)) and a and isinstance(a[0], (dict, np.ndarray)):
-        assert len(a) == len(b), where
-        for i, (x, y) in enumerate(zip(a, b)):
-            _same(x, y, f"{where}/{i}")
-    else:
-        assert a == b or (a is None and b is None), (where, a, b)
-
-
-def _files(log_dir):
-    out = []
-    for base, _dirs, names in os.walk(log_dir):
-        out += [os.path.relpath(os.path.join(base, n), log_dir) for n in names]
-    return sorted(out)
+    ec.trainer_equals_sequential_fused_runs(tmp_path, "logistic")
 
 
 @pytest.mark.parametrize("separate", [False, True], ids=["joint", "separate"])
 def test_pipeline_with_the_key_equals_the_sequential_pipeline(tmp_path, monkeypatch, separate):
-    import pandas as pd
-    mods = ("decode_tonal_langauge_amd._classifier_ensemble_engine", "decode_tonal_langauge_amd.models.classifier_ensemble_trainer")
-    kept = {k: sys.modules.pop(k) for k in mods if k in sys.modules}
-    try:
-        off_dir, off, off_state = _run_pipeline(tmp_path, monkeypatch, "off", separate, None)
-        assert not any(k in sys.modules for k in mods)         # without the key nothing of the ensemble is imported
-    finally:
-        sys.modules.update(kept)
-    on_dir, on, on_state = _run_pipeline(tmp_path, monkeypatch, "on", separate, True)
-    assert all(k in sys.modules for k in mods) and on_dir != off_dir
-    assert torch.equal(on_state, off_state)
-    _same(on[0], off[0], "result_info")
-    assert np.array_equal(on[1], off[1]) and list(on[2]) == list(off[2])
-    assert int(on[1].sum()) == 3 * 48                          # 3 seeds x 20 % of 240
-    files = _files(on_dir)
-    assert files == _files(off_dir) and sum(f.endswith(".pt") for f in files) == (6 if separate else 3)
-    assert sum(f.endswith("metrics.csv") for f in files) == (6 if separate else 3)
-    for f in files:
-        a, b = os.path.join(on_dir, f), os.path.join(off_dir, f)
-        if f.endswith(".pt"):
-            sa, sb = torch.load(a), torch.load(b)
-            assert list(sa) == list(sb) and all(torch.equal(sa[k], sb[k]) for k in sa), f
-        elif f.endswith(".csv") and os.path.basename(f) != "results.csv":
-            assert filecmp.cmp(a, b, shallow=False), f
-    assert pd.read_csv(os.path.join(on_dir, "results.csv")).equals(pd.read_csv(os.path.join(off_dir, "results.csv")))
+    ec.pipeline_with_the_key_equals_the_sequential_pipeline(tmp_path, monkeypatch, "logistic", separate)
