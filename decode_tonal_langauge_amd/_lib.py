@@ -125,6 +125,7 @@ SIGNATURES = {
     "tl_set_step_scalars": (_I, [_P, _P, _F, _F, _F, C.c_uint64, _P]),
     "tl_stage_step": (_I, [_P, _P, _F, _F, _F, C.c_uint64, _P, _P, _P, _I, _P]),
     "tl_gather_rows": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _L, _P, _P]),
+    "tl_extract_windows": (_I, [_P, _L, _L, _L, _P, _L, _L, _I, _P, _P, _P]),
     "tl_nadam_multi_dev": (_I, [_P, _I, _L, _P, _F, _F, _F, _F, _F, _P]),
     "tl_nadam_lowrank": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F, _P]),
     "tl_nadam_lowrank_dh": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F, _P, _I, _I, _P]),

@@ -1,6 +1,7 @@
 // Device-resident batch loader: a batch of up to four tensors gathered by one index vector in ONE launch
 // (data_loading/resident.py; the stock DataLoader indexes sample by sample in Python and stacks B views).
-// See include/tonal_hip.h for the contract.
+// Window extraction: n windows cut from one (C, T) recording by a table of starts in ONE launch (data_loading/epoching.py).
+// See include/tonal_hip.h for the contracts.
 #include "tonal_common.h"
 
 namespace tl {
@@ -99,6 +100,76 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(gather_args a, const l
   }
 }
 
+// ---- tl_extract_windows: dst[i][c][:] = src[c][starts[i] : starts[i] + L] -----------------------------------------------------------
+// A window starts at an arbitrary sample, so every (window, channel) row has its own source alignment and no width above
+// the element's holds for all of them: one element per lane per copy, WINDOW_UNROLL copies per thread, all loads issued
+// before the first store (gather_copy's phases).  Lanes run along the flat (window, channel, sample) index: a row shorter
+// than a wave shares it with the next row, and the destination is written front to back in whole cache lines.
+// The flat index is 64-bit; it is divided once per thread (the workgroup's first element, uniform) and once more in 32 bits,
+// and a thread's further copies, 256 elements apart, advance (window, channel, sample) by the host's split of 256.
+struct window_args {
+  const char* src;
+  char* dst;
+  long long C, T, ld_src, L;
+  unsigned long long total;  // n * C * L elements
+  unsigned q256, r256;       // 256 = q256 * L + r256
+  unsigned qC, rC;           // q256 = qC * C + rC
+};
+
+#define WINDOW_UNROLL 8
+#define WINDOW_PER_BLOCK (256 * WINDOW_UNROLL)
+
+// a thread past the end reads starts[0], a thread of a bad window src[0] (both there: n, C, T >= 1); neither stores
+#define WINDOW_INDEX(u)                                                             \
+  const unsigned long long v##u = first + u * 256ull;                               \
+  bool ok##u = v##u < a.total;                                                      \
+  const unsigned i##u = ok##u ? i : 0u, c##u = c, j##u = j;                         \
+  {                                                                                 \
+    j += a.r256;                                                                    \
+    const unsigned carry = j >= L ? 1u : 0u;                                        \
+    j -= carry ? L : 0u;                                                            \
+    c += a.rC + carry;                                                              \
+    const unsigned wrap = c >= C ? 1u : 0u;                                         \
+    c -= wrap ? C : 0u;                                                             \
+    i += a.qC + wrap;                                                               \
+  }                                                                                 \
+  const long long s##u = starts[i##u];
+#define WINDOW_LOAD(u)                                                              \
+  {                                                                                 \
+    const bool s_ok = s##u >= 0 && s##u <= a.T - a.L;                               \
+    if (ok##u && !s_ok) bad = 2;                                                    \
+    ok##u = ok##u && s_ok;                                                          \
+  }                                                                                 \
+  const long long so##u = ok##u ? (long long)c##u * a.ld_src + s##u + (long long)j##u : 0; \
+  const E val##u = src[so##u];
+#define WINDOW_STORE(u) \
+  if (ok##u) dst[v##u] = val##u;
+
+template <typename E>
+__global__ __launch_bounds__(256) void extract_windows_kernel(window_args a, const long long* __restrict__ starts,
+                                                              int* __restrict__ err) {
+  static_assert(WINDOW_UNROLL == 8, "the phases below are written out eight times");
+  const E* __restrict__ src = reinterpret_cast<const E*>(a.src);
+  E* __restrict__ dst = reinterpret_cast<E*>(a.dst);
+  const unsigned L = (unsigned)a.L, C = (unsigned)a.C;              // both below 2^30 (host check)
+  const unsigned long long base = (unsigned long long)blockIdx.x * WINDOW_PER_BLOCK;
+  const unsigned long long row0 = base / (unsigned long long)a.L;    // uniform: rows (window, channel) before the workgroup
+  const unsigned o = (unsigned)(base - row0 * (unsigned long long)a.L) + threadIdx.x;   // < L + 256
+  const unsigned dq = o / L;
+  const unsigned row = (unsigned)row0 + dq;                         // n * C < 2^31
+  unsigned j = o - dq * L, i = row / C;
+  unsigned c = row - i * C;
+  const unsigned long long first = base + threadIdx.x;
+  int bad = 0;
+  WINDOW_INDEX(0) WINDOW_INDEX(1) WINDOW_INDEX(2) WINDOW_INDEX(3) WINDOW_INDEX(4) WINDOW_INDEX(5) WINDOW_INDEX(6) WINDOW_INDEX(7)
+  WINDOW_LOAD(0) WINDOW_LOAD(1) WINDOW_LOAD(2) WINDOW_LOAD(3) WINDOW_LOAD(4) WINDOW_LOAD(5) WINDOW_LOAD(6) WINDOW_LOAD(7)
+  WINDOW_STORE(0) WINDOW_STORE(1) WINDOW_STORE(2) WINDOW_STORE(3) WINDOW_STORE(4) WINDOW_STORE(5) WINDOW_STORE(6) WINDOW_STORE(7)
+  if (bad) atomicOr(err, bad);
+}
+#undef WINDOW_INDEX
+#undef WINDOW_LOAD
+#undef WINDOW_STORE
+
 }  // namespace tl
 
 using namespace tl;
@@ -174,4 +245,44 @@ extern "C" int tl_gather_rows_group(const void* const* src, void* const* dst, co
     TL_REQUIRE(dst_stride[i] >= 0, "gather_rows_group: segment %d: negative member stride", i);
   return gather_launch(src, dst, dst_stride, src_rows, C, inner_bytes, chan, n_chan, n_seg, idx, idx_stride, n_idx, M, active, err,
                        stream);
+}
+
+extern "C" int tl_extract_windows(const void* src, int64_t C, int64_t T, int64_t ld_src, const int64_t* starts, int64_t n,
+                                  int64_t L, int elem_bytes, void* dst, int32_t* err, void* stream) {
+  TL_REQUIRE(n >= 0, "extract_windows: n must not be negative (got %lld)", (long long)n);
+  TL_REQUIRE(C >= 1 && T >= 1 && L >= 1, "extract_windows: C, T and L must be positive (got %lld, %lld, %lld)", (long long)C,
+             (long long)T, (long long)L);
+  TL_REQUIRE(ld_src >= T, "extract_windows: row stride %lld shorter than the %lld samples of a row", (long long)ld_src,
+             (long long)T);
+  TL_REQUIRE(L <= T, "extract_windows: window length %lld exceeds the %lld samples of the recording", (long long)L,
+             (long long)T);
+  TL_REQUIRE(elem_bytes == 1 || elem_bytes == 2 || elem_bytes == 4 || elem_bytes == 8,
+             "extract_windows: elem_bytes must be 1, 2, 4 or 8 (got %d)", elem_bytes);
+  if (n == 0) return TL_OK;
+  TL_REQUIRE(src && starts && dst && err, "extract_windows: null src, starts, dst or error word");
+  TL_REQUIRE((((uintptr_t)src | (uintptr_t)dst) & (uintptr_t)(elem_bytes - 1)) == 0,
+             "extract_windows: src and dst must be aligned to the %d bytes of an element", elem_bytes);
+  TL_REQUIRE(((uintptr_t)starts & 7) == 0 && ((uintptr_t)err & 3) == 0, "extract_windows: misaligned starts or error word");
+  TL_REQUIRE(L < (1LL << 30) && C < (1LL << 30) && n < (1LL << 31) && n * C < (1LL << 31),
+             "extract_windows: L and C must be below 2^30 and n * C below 2^31 (got L %lld, C %lld, n %lld)", (long long)L,
+             (long long)C, (long long)n);
+  TL_REQUIRE(ld_src < (1LL << 40) && T < (1LL << 40), "extract_windows: T and ld_src must be below 2^40");
+  window_args a;
+  a.src = (const char*)src;
+  a.dst = (char*)dst;
+  a.C = C, a.T = T, a.ld_src = ld_src, a.L = L;
+  a.total = (unsigned long long)(n * C) * (unsigned long long)L;   // < 2^61
+  a.q256 = (unsigned)(256 / L), a.r256 = (unsigned)(256 % L);
+  a.qC = (unsigned)(a.q256 / C), a.rC = (unsigned)(a.q256 % C);
+  const unsigned long long blocks = (a.total + WINDOW_PER_BLOCK - 1) / WINDOW_PER_BLOCK;
+  TL_REQUIRE(blocks < (1ULL << 31), "extract_windows: too many workgroups (%llu elements in one launch)", a.total);
+  const dim3 grid((unsigned)blocks), block(256);
+  const long long* st = (const long long*)starts;
+  switch (elem_bytes) {
+    case 1: hipLaunchKernelGGL(extract_windows_kernel<uint8_t>, grid, block, 0, (hipStream_t)stream, a, st, (int*)err); break;
+    case 2: hipLaunchKernelGGL(extract_windows_kernel<uint16_t>, grid, block, 0, (hipStream_t)stream, a, st, (int*)err); break;
+    case 4: hipLaunchKernelGGL(extract_windows_kernel<uint32_t>, grid, block, 0, (hipStream_t)stream, a, st, (int*)err); break;
+    default: hipLaunchKernelGGL(extract_windows_kernel<uint64_t>, grid, block, 0, (hipStream_t)stream, a, st, (int*)err); break;
+  }
+  return check_launch("extract_windows");
 }

@@ -8,6 +8,8 @@ Schemas:
                            (reference channel_selection_main.py:86-88)
   * ``config.json``        ``{mel_kwargs, n_syllables, n_tones, tone_dynamic_mapping}`` (reference train_synthesizer.py:171-177)
   * ``B<block>_<modality>.npz``  ``data (C, T)``, ``sf`` (reference preprocess/io/tdt_blocks.py:33-34)
+  * ``B<block>.TextGrid``  one interval tier whose reading intervals are marked ``<tone digit><syllable character>``
+                           (read by data_loading/text_align.py)
 
 The ECoG carries a learnable class pattern: tone k lifts a group of channels, syllable 1 adds a slow
 ramp, so classifiers and the synthesiser have something to fit."""
@@ -15,7 +17,7 @@ from __future__ import annotations
 
 import json
 import os
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
@@ -78,3 +80,26 @@ def write_raw_block(root: str, block: int = 1, modality: str = "ecog", n_channel
     path = os.path.join(root, f"B{block}_{modality}.npz")
     np.savez(path, data=data, sf=sf)
     return path
+
+
+def write_block_annotations(root: str, block: int, events: Sequence, tier: str = "words", seconds: Optional[float] = None,
+                            short: bool = False, encoding: str = "utf-8") -> str:
+    """``B<block>.TextGrid`` for a ``write_raw_block`` recording: ``events`` are ``(start_s, end_s, tone, syllable)`` in
+    time order, without overlap; each becomes an interval marked ``f"{tone}{syllable}"`` on the tier ``tier`` and the gaps
+    between them (and up to ``seconds``, the recording's length) are filled with empty intervals, as Praat writes them."""
+    from .textgrid_io import write_textgrid
+    rows, at = [], 0.0
+    for start, end, tone, syllable in events:
+        start, end = float(start), float(end)
+        if start < at or end <= start:
+            raise ValueError(f"write_block_annotations: event ({start}, {end}) overlaps its predecessor or is empty")
+        if not 0 <= int(tone) <= 9 or len(str(syllable)) != 1:
+            raise ValueError("write_block_annotations: a tone is one digit and a syllable one character")
+        if start > at:
+            rows.append((at, start, ""))
+        rows.append((start, end, f"{int(tone)}{syllable}"))
+        at = end
+    if seconds is not None and float(seconds) > at:
+        rows.append((at, float(seconds), ""))
+    os.makedirs(root, exist_ok=True)
+    return write_textgrid(os.path.join(root, f"B{block}.TextGrid"), [(tier, rows)], short=short, encoding=encoding)

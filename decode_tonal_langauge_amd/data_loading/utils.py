@@ -1,7 +1,22 @@
-"""Label helpers of the train loop (mirror of reference data_loading/utils.py:32-79,119-156)."""
-from typing import Dict, List
+"""Label and file-name helpers (mirror of reference data_loading/utils.py)."""
+import re
+from typing import Dict, List, Optional
 
 import numpy as np
+
+
+def extract_block_id(filename: str) -> int:
+    """The block number of a file name: the digits behind the first ``B`` that has digits behind it (``HS25_B1.wav`` -> 1,
+    ``B5_16000.TextGrid`` -> 5).  ``ValueError`` when there is none."""
+    found = re.search(r"B(\d+)", filename)
+    if found is None:
+        raise ValueError(f"No block ID found in filename: {filename}")
+    return int(found.group(1))
+
+
+def match_filename(file: str, file_format: str, kwords: Optional[List[str]] = None) -> bool:
+    """True when ``file`` ends with ``file_format`` and contains every keyword."""
+    return file.endswith(file_format) and all(word in file for word in (kwords or ()))
 
 
 def prepare_tone_dynamics(tone_dynamic_mapping: Dict[str, List[int]], tone_labels: np.ndarray,

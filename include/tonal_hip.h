@@ -411,6 +411,17 @@ int tl_stage_step(float* scalars_dev, uint64_t* seed_dev, float coef_grad, float
 int tl_gather_rows(const void* const* src, void* const* dst, const int64_t* src_rows, const int64_t* C,
                    const int64_t* inner_bytes, const int32_t* const* chan, const int64_t* n_chan, int n_seg,
                    const int64_t* idx, int64_t n_idx, int32_t* err, void* stream);
+/* ---- window extraction (data_loading/epoching.py): n windows of L samples cut from one (C, T) recording in ONE launch --------
+ * src: C rows of T elements of elem_bytes (1, 2, 4 or 8) bytes each, row stride ld_src >= T elements.  starts: n int64 first
+ * samples in device memory, read on the device (no host synchronisation).  dst: (n, C, L), contiguous:
+ *     dst[i][c][j] = src[c * ld_src + starts[i] + j]               copied as bytes, any dtype; windows may overlap or repeat.
+ * One element per access: nothing but elem_bytes alignment of src and dst is assumed, and only bytes that are copied are
+ * read (lanes of a bad window, or past the end, read src[0]).  A window with starts[i] < 0 or starts[i] + L > T is never
+ * dereferenced: bit 1 (value 2) of *err (device int32, never cleared here) is set, its (C, L) destination is left as it was,
+ * and every other window of the launch is copied.  All offsets are 64-bit: src and dst may exceed 4 GiB.
+ * Limits: L <= T, L and C below 2^30, n * C below 2^31.  n = 0 returns TL_OK without a launch.                            */
+int tl_extract_windows(const void* src, int64_t C, int64_t T, int64_t ld_src, const int64_t* starts, int64_t n, int64_t L,
+                       int elem_bytes, void* dst, int32_t* err, void* stream);
 /* ---- group launches: M models of equal shape ("members") trained side by side (_classifier_ensemble_engine.py) -----------
  * Every tl_*_group entry is its single-model neighbour with a member dimension on the grid: member m works on pointers
  * s_* ELEMENTS (of the pointer's type, unless stated otherwise) behind the ones given, which are member 0's.  It is the SAME
