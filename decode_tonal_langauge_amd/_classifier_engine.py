@@ -15,17 +15,8 @@ import torch
 
 from . import _kernels, _lib
 from ._conv_stack import ConvStack
-from ._launch import launch_nt, r4
+from ._launch import LaunchTimers, PackCache, launch_nt, permute_reduce, r4
 from ._lib import EPI_LRELU, EPI_POOL, EPI_POOLV, EPI_STORE, LOAD_DIRECT, LOAD_V, check, ptr
-
-
-def _cached(packed: dict, key: str, param: torch.Tensor, build):
-    """Packed copies of the (usually frozen) classifier weights in ``packed``, rebuilt when the parameter changes."""
-    ver = (param._version, param.data_ptr())
-    hit = packed.get(key)
-    if hit is None or hit[0] != ver:
-        hit = packed[key] = (ver, build())
-    return hit[1]
 
 
 class CnnClassifierEngine(ConvStack):
@@ -42,7 +33,7 @@ class CnnClassifierEngine(ConvStack):
         self.tp_last = last.tp_out
         self.ld_last = last.cout if last.pool else self.ld5
         self.kflat_cls = n_electrodes * self.tp_last * self.ld_last
-        self._packed: Dict[str, Tuple[int, torch.Tensor]] = {}
+        self.packs = PackCache()
         # Round 5: the leading pooled 3-tap stages on the F(6,3) V-form kernels of the synthesis stack (tonal_wino63.hip: conv1
         # writes V1 in hex form, every stage but the last writes the next stage's V from its forward epilogue, the last one
         # pooled rows in this engine's own row geometry through out_tp) - forward only.  n63 = how many stages after the first
@@ -89,7 +80,7 @@ class CnnClassifierEngine(ConvStack):
             st, (w, b) = self.stages[i], convs[1 + i]
             tp_in = self.tp63[i]
             last = i == self.n63 - 1
-            wp = self._cached(f"conv{st.idx}w63", w, lambda w=w: self._pack_wino63(w, True))
+            wp = self.packs.get(f"conv{st.idx}w63", w, lambda w=w: self._pack_wino63(w, True))
             rows_in = S * tp_in
             if st.idx not in buf:
                 buf[st.idx] = zi(S * (st.tp_out if last else tp_in // 2), st.cout // 32)
@@ -126,9 +117,6 @@ class CnnClassifierEngine(ConvStack):
             if st.pool:
                 self.bits[st.idx] = zi(rows, st.cout // 32)
 
-    def _cached(self, key, param, build):
-        return _cached(self._packed, key, param, build)
-
     def forward_scores(self, convs: List[Tuple[torch.Tensor, torch.Tensor]], fc1, fc2, x: torch.Tensor,
                        p_drop: float = 0.0, seed: int = 0) -> torch.Tensor:
         """``p_drop`` > 0: the module's ``nn.Dropout`` after the last pool (reference :81) is active - applied in place on
@@ -151,9 +139,9 @@ class CnnClassifierEngine(ConvStack):
             # kernel of the synthesis engine (half the direct form's MFMA work); everything else on the direct MFMA kernel
             v43 = self._v43(st)
             if v43:
-                wp = self._cached(f"conv{st.idx}w43", w, lambda w=w: self._pack_wino43(w, True))
+                wp = self.packs.get(f"conv{st.idx}w43", w, lambda w=w: self._pack_wino43(w, True))
             else:
-                wp = self._cached(f"conv{st.idx}", w, lambda w=w, st=st: self._pack_conv(w, st.cin, False))
+                wp = self.packs.get(f"conv{st.idx}", w, lambda w=w, st=st: self._pack_conv(w, st.cin, False))
             src, dst = self.P[st.idx - 1], self.P[st.idx]
             kw = dict(A=ptr(src), Bw=ptr(wp), bias=ptr(b), out=ptr(dst), M=S * st.tp_in, A_rows=src.shape[0],
                       N=st.cout, K=st.cin, lda=src.shape[1], ldb=st.cin, ldo=dst.shape[1], J=st.k, row_shift=0,
@@ -178,7 +166,7 @@ class CnnClassifierEngine(ConvStack):
             self._permute(w_fc1, dst, (self.hidden, self.C, self.tp_last, self.ld_last),
                           (self.c_last * latC, 1, self.C, latC), (self.hidden, self.C, lat, self.c_last))
             return dst
-        wp1 = self._cached("fc1", w_fc1, pack_fc1)
+        wp1 = self.packs.get("fc1", w_fc1, pack_fc1)
         f32 = dict(dtype=torch.float32, device=dev)
         nkc = (self.kflat_cls + 31) // 32
         tiles = ((B + 127) // 128) * ((self.hidden + 127) // 128)
@@ -225,21 +213,16 @@ class LstmInferEngine:
         self.lib = _lib.load()
         self.in_dim, self.H = in_dim, hidden
         self.Kp, self.Hp = r4(in_dim), (hidden + 7) // 8 * 8
-        self._packed = None
+        self.packs = PackCache()
 
-    def _weights(self, w_ih, w_hh, b_ih, b_hh):
-        ver = tuple((t._version, t.data_ptr()) for t in (w_ih, w_hh, b_ih, b_hh))
-        if self._packed is None or self._packed[0] != ver:
-            H, Hp, Kp, dev = self.H, self.Hp, self.Kp, w_hh.device
-            wi = torch.zeros(4, Hp, Kp, dtype=torch.float32, device=dev)
-            wi[:, :H, :self.in_dim] = w_ih.detach().float().view(4, H, self.in_dim)
-            wh = torch.zeros(4, Hp, Hp, dtype=torch.float32, device=dev)
-            wh[:, :H, :H] = w_hh.detach().float().view(4, H, H)
-            bs = torch.zeros(4, Hp, dtype=torch.float32, device=dev)
-            bs[:, :H] = (b_ih.detach().float() + b_hh.detach().float()).view(4, H)
-            whp = wh.permute(1, 0, 2).contiguous().view(4 * Hp, Hp)      # unit-major: row 4 u + g
-            self._packed = (ver, wi.view(4 * Hp, Kp), wh.view(4 * Hp, Hp), bs.view(4 * Hp), whp)
-        return self._packed[1:]
+    def _weights(self, *weights):
+        """(W_ih as the projection GEMM reads it, b_ih + b_hh, W_hh unit-major) of (w_ih, w_hh, b_ih, b_hh)."""
+        def build():
+            w = [t.detach().float().contiguous() for t in weights]
+            wi, bs, whp, _ = lstm_pack_buffers(self.in_dim, self.H, w[0].device)
+            lstm_pack(self.lib, (wi, bs, whp, None), *w)
+            return (w[0] if wi is None else wi), bs, whp
+        return self.packs.get("lstm", weights, build)
 
     @torch.no_grad()
     def last_hidden(self, x_seq: torch.Tensor, w_ih, w_hh, b_ih, b_hh) -> torch.Tensor:
@@ -248,7 +231,7 @@ class LstmInferEngine:
         if D != self.in_dim:
             raise ValueError(f"expected input width {self.in_dim}, got {D}")
         dev = x_seq.device
-        wi, wh, bs, whp = self._weights(w_ih, w_hh, b_ih, b_hh)
+        wi, bs, whp = self._weights(w_ih, w_hh, b_ih, b_hh)
         H, Hp, Kp = self.H, self.Hp, self.Kp
         f32 = dict(dtype=torch.float32, device=dev)
         x = x_seq.float()
@@ -273,30 +256,49 @@ class LstmInferEngine:
         return h[:, :H] if Hp != H else h
 
 
-class CnnRnnConvEngine:
-    """Convolutional trunk of ``CNNRNNClassifier`` (reference models/deep_classifiers.py:230-259, 294-312)
-    on the HIP kernels, forward only: the two (7,1) conv + LeakyReLU + (2,1) max-pool branches
-    (``tl_conv1_fwd``, C_in = 1), the width-wise concatenation, the two 7-tap convolutions
-    1024 -> 512 -> 256 with LeakyReLU (``tl_gemm_nt_window``, J = 7) and the (3,1) max-pool.  The two
-    LSTMs and the output layer stay library calls of the owning module.
+def lstm_pack_buffers(in_dim: int, hidden: int, dev, train: bool = False) -> tuple:
+    """Zeroed (wi, bs, whp, whT) for ``lstm_pack``: hidden padded to 8, the input width to 4.  ``wi`` is None when nothing is
+    padded (``weight_ih_l0`` is used where it lies); ``whT`` (W_hh^T: row u', column g Hp + u) only for training."""
+    Kp, Hp = r4(in_dim), (hidden + 7) // 8 * 8
+    z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+    padded = Kp != in_dim or Hp != hidden
+    return z(4 * Hp, Kp) if padded else None, z(4 * Hp), z(4 * Hp, Hp), z(Hp, 4 * Hp) if train else None
 
-    Layout as everywhere else: one *sequence* per (batch element, width column), rows = time,
-    channels last; the LSTM branch comes first in the width order, as ``torch.cat((x1, x), dim=3)``."""
 
-    K = 7
+def lstm_pack(lib, packs: tuple, w_ih, w_hh, b_ih, b_hh) -> None:
+    """Fill ``packs`` from the (fp32, contiguous) weights of one ``nn.LSTM``: W_ih gate-major (row g Hp + u), the bias sum the
+    same, W_hh unit-major (row 4 u + g); pad rows and columns stay zero."""
+    wi, bs, whp, whT = packs
+    H, D, Hp, Kp = w_hh.shape[1], w_ih.shape[1], whp.shape[1], r4(w_ih.shape[1])
+    if wi is not None:
+        permute_reduce(lib, w_ih, wi, (1, 4, Hp, Kp), (0, H * D, D, 1), (1, 4, H, D))
+    permute_reduce(lib, w_hh, whp, (1, Hp, 4, Hp), (0, H, H * H, 1), (1, H, 4, H))
+    if whT is not None:
+        permute_reduce(lib, w_hh, whT, (1, Hp, 4, Hp), (0, 1, H * H, H), (1, H, 4, H))
+    bs.view(4, Hp)[:, :H] = (b_ih + b_hh).view(4, H)
 
-    def __init__(self, input_channels: int, input_length: int, lstm_dim: int, negative_slope: float):
-        self.lib = _lib.load()
-        self.C, self.T = input_channels, input_length
-        self.w1 = lstm_dim // input_length
-        self.W = self.w1 + input_channels
-        self.slope = float(negative_slope)
-        self.t1 = (input_length - self.K + 1) // 2           # after conv (7,1) + pool (2,1)
-        self.ta = self.t1 - self.K + 1                        # after the 1024 -> 512 convolution
-        self.tb = self.ta - self.K + 1                        # after the 512 -> 256 convolution
-        self.tq = self.tb // 3                                # after pool (3,1)
-        if self.tq < 1:
-            raise ValueError("input_length too small for the CNN-RNN convolution stack")
+
+K7 = 7            # taps of every convolution of CNNRNNClassifier
+C_FIRST, C_A, C_B = 1024, 512, 256
+
+
+def geometry(n_channels: int, n_timepoints: int, lstm_dim: int) -> Dict[str, int]:
+    """Row counts of the CNN-RNN trunk: after block 1 / 2 (t1), the two 7-tap stages (ta, tb), the (3,1) pool (tq)."""
+    t1 = (n_timepoints - K7 + 1) // 2
+    ta = t1 - K7 + 1
+    tb = ta - K7 + 1
+    w1 = lstm_dim // n_timepoints
+    return dict(t1=t1, ta=ta, tb=tb, tq=tb // 3, w1=w1, W=w1 + n_channels)
+
+
+class Conv7Trunk:
+    """What the forward-only trunk of ``CNNRNNClassifier`` (below) and the training one (``_cnnrnn_classifier_train_engine``)
+    share: the geometry, the rows per sequence, the transform buffers and the forward of a 7-tap stage.  The host class brings
+    ``lib``, ``slope``, ``_nt(tag=, fn=, **fields)`` and ``_tick(tag)``."""
+
+    def _trunk_geometry(self, n_channels: int, n_timepoints: int, lstm_dim: int) -> None:
+        geo = geometry(n_channels, n_timepoints, lstm_dim)
+        self.t1, self.ta, self.tb, self.tq, self.w1, self.W = (geo[k] for k in ("t1", "ta", "tb", "tq", "w1", "W"))
         # 7-tap stack: "wino63" (default since round 5) three F(6,3) segments summed in the transform domain by ONE launch of
         # the V-form NT kernel of the synthesis stack (tl_conv7_wino63v_nt: segment 2 re-reads V0 one hex on, so only two
         # transformed arrays exist); "direct" the 7-tap window GEMM (72.8 ms for the CNN-RNN forward at C5, batch 64, against
@@ -305,71 +307,104 @@ class CnnRnnConvEngine:
         self.conv7_form = _kernels.conv7_forward()
         # rows per sequence: whole hexes for the F(6,3) form, whole quads for the others
         self.Tp = (self.t1 + 5) // 6 * 6 if self.conv7_form == "wino63" else (self.t1 + 3) // 4 * 4
-        self._packed: Dict[str, Tuple[tuple, torch.Tensor]] = {}
+        self.packs = PackCache()
+
+    def _alloc_v7(self, rows: int, extra_hexes: int, dev):
+        """V0 / V1 of a 7-tap layer's input (hex transforms of the rows and of the rows shifted by 3, pair layout), shared by
+        the two layers (1024, then 512 channels: the second fits into the first's storage): whole 128-hex tiles of the NT
+        kernel behind ``extra_hexes`` - 2: its third segment reads one hex past a tile; 6 under conv7=wino63bwd: also whole
+        6-hex K-steps of the weight-gradient kernel, which the rounding does not imply (253 hexes: 256 < 258)."""
+        if self.conv7_form != "wino63":
+            return None
+        nh_pad = (rows // 6 + extra_hexes + 127) // 128 * 128
+        return tuple(torch.zeros(nh_pad, 8, C_FIRST, dtype=torch.float32, device=dev) for _ in range(2))
+
+    def _hex_view(self, buf: torch.Tensor, c: int, nhex: int) -> torch.Tensor:
+        """``buf`` (hexes, 8, wider) re-viewed for ``c`` channels; the pad hexes of a narrower view (whole pairs behind the last
+        hex, which the third segment and the rows past M of the last tile read) overlay the wider layer's data: zeroed, as
+        tl_conv7_wino63v_nt's contract says ("zero hexes appended") - with an odd ``nhex`` the second hex of the last pair too,
+        which no transform kernel writes (the weight-gradient kernel reads whole 6-hex K-steps of BOTH operands: a stale hex
+        of Y against a stale hex of V is a term of the sum)."""
+        if c == buf.shape[2]:
+            return buf
+        v = buf.view(-1)[: buf.shape[0] * 8 * c].view(-1, 8, c)
+        v[(nhex + 1) // 2 * 2:].zero_()
+        if nhex % 2:
+            v.view(-1, c // 8, 8, 2, 8)[nhex // 2, :, :, 1].zero_()          # (pair layout: [hex / 2][c / 8][8][hex % 2][8])
+        return v
+
+    def _conv7(self, key, src, w, b, dst, cin, cout, tvalid, rows, tag=None) -> None:
+        """dst[r] = lrelu(sum_j w[:, :, j] src[r + j] + b) for r < rows; src holds rows + 8 rows, of which ``tvalid`` per
+        sequence are data (the rows behind them enter as zeros: they only feed rows nobody reads).  ``w`` carries the
+        parameter's version counter (the parameter or its ``.detach()``): the weight pack ``key`` follows it."""
+        st_ = torch.cuda.current_stream().cuda_stream
+        w7 = w.reshape(cout, cin, K7)
+        if self.conv7_form == "wino63":
+            V0, V1 = (self._hex_view(v, cin, rows // 6) for v in self.V7)
+            ev = self._tick(tag and tag + "_xform")
+            check(self.lib.tl_wino63_xform2(ptr(src), ptr(V0), ptr(V1), rows, self.Tp, tvalid, cin, src.shape[1], cin, st_),
+                  "tl_wino63_xform2")
+            wp = self.packs.get(key, w, lambda: torch.empty(3 * cin // 8, 8, cout, 8, dtype=torch.float32, device=w.device),
+                                into=lambda wp: check(self.lib.tl_wino63_weights7(ptr(w7), ptr(wp), cout, cin, K7, st_),
+                                                      "tl_wino63_weights7"))
+            if ev:
+                ev[1].record()
+            self._nt(tag=tag, fn="tl_conv7_wino63v_nt", A=ptr(V0), aux=ptr(V1), A_rows=V0.shape[0], lda=cin, Bw=ptr(wp),
+                     bias=ptr(b), out=ptr(dst), M=rows, N=cout, K=cin, ldb=3 * cin, ldo=dst.shape[1], J=K7, row_shift=0,
+                     Tp=self.Tp, Tvalid=self.Tp, slope=self.slope, loader=LOAD_V, epilogue=EPI_LRELU)
+            return
+        # "direct": the 7-tap window GEMM, which reads rows + 8 input rows
+        if src.shape[0] < rows + 8:
+            raise RuntimeError("conv7: the input buffer is shorter than the rows the 7-tap window reads")
+        wp = self.packs.get(key, w, lambda: torch.empty(K7, cout, cin, dtype=torch.float32, device=w.device),     # [J][O][I]
+                            into=lambda wp: permute_reduce(self.lib, w7, wp, (1, K7, cout, cin), (0, 1, cin * K7, K7)))
+        self._nt(tag=tag, A=ptr(src), Bw=ptr(wp), bias=ptr(b), out=ptr(dst), M=rows, A_rows=rows + 8, N=cout, K=cin, lda=cin,
+                 ldb=cin, ldo=cout, J=K7, row_shift=0, Tp=self.Tp, Tvalid=self.Tp, slope=self.slope, loader=LOAD_DIRECT,
+                 epilogue=EPI_LRELU)
+
+
+class CnnRnnConvEngine(Conv7Trunk, LaunchTimers):
+    """Convolutional trunk of ``CNNRNNClassifier`` (reference models/deep_classifiers.py:230-259, 294-312)
+    on the HIP kernels, forward only: the two (7,1) conv + LeakyReLU + (2,1) max-pool branches
+    (``tl_conv1_fwd``, C_in = 1), the width-wise concatenation, the two 7-tap convolutions
+    1024 -> 512 -> 256 with LeakyReLU (``Conv7Trunk._conv7``) and the (3,1) max-pool.  The two
+    LSTMs and the output layer stay library calls of the owning module.
+
+    Layout as everywhere else: one *sequence* per (batch element, width column), rows = time,
+    channels last; the LSTM branch comes first in the width order, as ``torch.cat((x1, x), dim=3)``."""
+
+    K = K7
+
+    def __init__(self, input_channels: int, input_length: int, lstm_dim: int, negative_slope: float):
+        self.lib = _lib.load()
+        self.C, self.T = input_channels, input_length
+        self.slope = float(negative_slope)
+        self._trunk_geometry(input_channels, input_length, lstm_dim)
+        if self.tq < 1:
+            raise ValueError("input_length too small for the CNN-RNN convolution stack")
         self._B = None
 
-    def _cached(self, key, param, build):
-        return _cached(self._packed, key, param, build)
+    def _nt(self, tag=None, fn="tl_gemm_nt_window", **fields):
+        launch_nt(self.lib, fn, **fields)
 
     def _alloc(self, B: int, dev):
         if self._B == B and self._dev == dev:
             return
+        if self._B is not None and self._dev != dev:
+            self.packs = PackCache()           # (a stale pack is refilled where it lies: on the device left behind)
         self._B, self._dev = B, dev
         z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
         zi = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
         rows = B * self.W * self.Tp
         # + 8 rows: the segmented convolution reads up to 6 rows past the last row it is asked about
-        self.P, self.Y1, self.Y2 = z(rows + 8, 1024), z(rows + 8, 512), z(rows, 256)
+        self.P, self.Y1, self.Y2 = z(rows + 8, C_FIRST), z(rows + 8, C_A), z(rows, C_B)
         # sequences are stored branch-major - all LSTM-branch columns of all batch elements, then all electrode
         # columns - so both first-stage convolutions write straight into P (the stack is per sequence; only the
         # final feature map needs the reference's (batch, width) order)
         nb = B * self.w1 * self.Tp
         self.Pb, self.Pa = self.P[:nb], self.P[nb:rows]
         self.bits_a, self.bits_b = zi(B * self.C * self.Tp, 32), zi(B * self.w1 * self.Tp, 32)
-        self.V7 = None
-        if self.conv7_form == "wino63":
-            # V0 / V1 of a 7-tap layer's input (hex transforms of the rows and of the rows shifted by 3, pair layout, whole
-            # 128-hex tiles + one pair: the third segment reads one hex past a tile); shared by the two layers (1024, then 512
-            # channels: the second fits into the first's storage)
-            nh_pad = (rows // 6 + 2 + 127) // 128 * 128
-            self.V7 = (z(nh_pad, 8, 1024), z(nh_pad, 8, 1024))
-
-    def _conv7(self, src, w, b, dst, cin, cout, key, rows):
-        """dst[r] = lrelu(sum_j w[:, :, j] src[r + j] + b) for r < rows; src holds rows + 8 rows."""
-        st_ = torch.cuda.current_stream().cuda_stream
-        if self.conv7_form == "wino63" and cin % 8 == 0 and cout % 32 == 0:
-            nhex = rows // 6
-            V0 = self.V7[0].view(-1)[: self.V7[0].shape[0] * 8 * cin].view(-1, 8, cin)
-            V1 = self.V7[1].view(-1)[: self.V7[1].shape[0] * 8 * cin].view(-1, 8, cin)
-            # rows from the valid length of THIS layer's input on enter as zeros (they only feed rows nobody reads)
-            tvalid = self.t1 if cin == 1024 else self.ta
-            if V0.shape[2] != self.V7[0].shape[2]:
-                # a narrower layer re-views the storage: its pad hexes (whole pairs behind the last hex, which the third
-                # segment and the rows past M of the last tile read) overlay the wider layer's transform data - zero them, as
-                # tl_conv7_wino63v_nt's contract says ("zero hexes appended"); ~2 MB per array
-                h0 = (nhex + 1) // 2 * 2
-                V0[h0:].zero_()
-                V1[h0:].zero_()
-            check(self.lib.tl_wino63_xform2(ptr(src), ptr(V0), ptr(V1), rows, self.Tp, tvalid, cin, src.shape[1], cin, st_),
-                  "tl_wino63_xform2")
-
-            def pack63():
-                wp = torch.empty(3 * cin // 8, 8, cout, 8, dtype=torch.float32, device=w.device)
-                check(self.lib.tl_wino63_weights7(ptr(w.detach().reshape(cout, cin, self.K).contiguous()), ptr(wp), cout, cin,
-                                                  self.K, st_), "tl_wino63_weights7")
-                return wp
-            wp = self._cached(key + "wino63", w, pack63)
-            launch_nt(self.lib, fn="tl_conv7_wino63v_nt", A=ptr(V0), aux=ptr(V1), A_rows=V0.shape[0], lda=cin, Bw=ptr(wp),
-                      bias=ptr(b.detach()), out=ptr(dst), M=rows, N=cout, K=cin, ldb=3 * cin, ldo=dst.shape[1], J=self.K,
-                      row_shift=0, Tp=self.Tp, Tvalid=self.Tp, slope=self.slope, loader=LOAD_V, epilogue=EPI_LRELU)
-            return
-        # "direct" (or a width the F(6,3) form does not take): the 7-tap window GEMM, which reads rows + 8 input rows
-        if src.shape[0] < rows + 8:
-            raise RuntimeError("conv7: the input buffer is shorter than the rows the 7-tap window reads")
-        wp = self._cached(key + "direct", w, lambda: w.detach().reshape(cout, cin, self.K).permute(2, 0, 1).contiguous())   # [J][O][I]
-        launch_nt(self.lib, A=ptr(src), Bw=ptr(wp), bias=ptr(b.detach()), out=ptr(dst), M=rows, A_rows=rows + 8, N=cout, K=cin,
-                  lda=cin, ldb=cin, ldo=cout, J=self.K, row_shift=0, Tp=self.Tp, Tvalid=self.Tp, slope=self.slope,
-                  loader=LOAD_DIRECT, epilogue=EPI_LRELU)
+        self.V7 = self._alloc_v7(rows, 2, dev)
 
     @torch.no_grad()
     def linear(self, a: torch.Tensor, w: torch.Tensor, b: torch.Tensor, sigmoid: bool = False) -> torch.Tensor:
@@ -406,8 +441,8 @@ class CnnRnnConvEngine:
                                    ptr(bits), None, n, self.T, self.K, 1024, self.Tp, self.t1, self.slope, st_),
                   "tl_conv1_fwd")
         rows = B * self.W * self.Tp
-        self._conv7(self.P, conv3a[0], conv3a[1], self.Y1, 1024, 512, "conv3a", rows)
-        self._conv7(self.Y1, conv3b[0], conv3b[1], self.Y2, 512, 256, "conv3b", rows)
+        self._conv7("conv3a", self.P, *conv3a, self.Y1, C_FIRST, C_A, self.t1, rows)
+        self._conv7("conv3b", self.Y1, *conv3b, self.Y2, C_A, C_B, self.ta, rows)
         y = self.Y2.view(B * self.W, self.Tp, 256)[:, :3 * self.tq]
         y = y.reshape(B * self.W, self.tq, 3, 256).amax(dim=2).contiguous()            # MaxPool (3,1), per sequence
         if p_drop > 0.0:                   # the block's nn.Dropout (reference :258), train mode: in place on (seq, t', 256)

@@ -32,7 +32,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, parallel
-from ._classifier_train_engine import invalidate_packed, parameter_unmet
+from ._classifier_train_engine import parameter_unmet
 from ._launch import launch_nt_group, r4
 from ._lib import EPI_LRELU, LOAD_DIRECT, check, ptr
 from ._simple_classifier_engine import activation_code, unmet
@@ -341,7 +341,6 @@ class ClassifierEnsembleEngine:
         else:
             self._update_lowrank(head, ws.dlogits, ws.s_dlogits, x, s_x, B, scalars)
         self._update_bias(head, scalars)
-        invalidate_packed(*self.models)
 
     @torch.no_grad()
     def eval_batch(self, x: torch.Tensor, y: torch.Tensor) -> None:

@@ -3,8 +3,7 @@
 statistics, gradient buffers), input / label validation, the workspace cache, the loss launch, the public steps and the
 data-parallel side of them (``_classifier_dp`` keeps the free-standing parts of that).
 
-An engine supplies ``_make_workspace``, ``_forward``, ``_backward`` and, where it has them, ``_lowrank_wire`` / ``_after_update``;
-it names its loss kernel (``CE``), the buffers of its workspace that kernel reads and writes (``CE_BUFFERS``) and its head bias
+An engine supplies ``_make_workspace``, ``_forward``, ``_backward`` and, where it has one, ``_lowrank_wire``; it names its loss kernel (``CE``), the buffers of its workspace that kernel reads and writes (``CE_BUFFERS``) and its head bias
 (``head_bias``), and says in ``_setup_training`` which Linear weights take the low-rank update.
 
 Under a process group (``parallel.active()``) every public step takes the GLOBAL batch and works on this rank's rows; without
@@ -56,15 +55,6 @@ def check_common(model, slopes=(), dropout: float = 0.0, also=()) -> None:
     for p in model.parameters():
         if parameter_unmet(p):
             refuse(parameter_unmet(p))
-
-
-def invalidate_packed(*models) -> None:
-    """Drop the packed inference weights of the models' HIP engines.  The update kernels write through ``data_ptr``: the
-    ``_version`` those weights are keyed on did not move."""
-    for model in models:
-        hip = getattr(model, "_hip", None)
-        if hip is not None:
-            hip._packed.clear()
 
 
 class ClassifierTrainEngine(LaunchTimers):
@@ -166,14 +156,11 @@ class ClassifierTrainEngine(LaunchTimers):
                    ptr(self.grads[self.head_bias]) if grad else None, ptr(ws.pred) if pred else None, base, base + 8, base + 24,
                    base + 16, B, self.N, self.N, dz.shape[1], 1.0 / self._plan.B if self._plan.live else 0.0)
 
-    # ------------------------------------------------------------------ the engine's hooks
+    # ------------------------------------------------------------------ the engine's hook
     def _lowrank_wire(self, ws) -> Dict[str, torch.Tensor]:
         """{name: buffer}: a low-rank weight whose first factor is the leading columns of a wider stored buffer, which is what
         travels between the ranks."""
         return {}
-
-    def _after_update(self) -> None:
-        invalidate_packed(self.model)
 
     # ------------------------------------------------------------------ data parallel, per step
     def _take(self, x: torch.Tensor, y: Optional[torch.Tensor] = None):
@@ -236,7 +223,6 @@ class ClassifierTrainEngine(LaunchTimers):
             self.optimizer.step(grads=grads, lowrank={self.params[k]: f for k, f in self.last_lowrank.items()} or None)
             if ev:
                 ev[1].record()
-            self._after_update()
 
     @torch.no_grad()
     def train_batch(self, x: torch.Tensor, y: torch.Tensor) -> None:

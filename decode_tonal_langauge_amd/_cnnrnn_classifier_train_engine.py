@@ -29,29 +29,17 @@ gradients - views of one arena - are summed by one bucketed all-reduce (an LSTM 
 No host read happens in ``train_batch`` / ``eval_batch``.  There is no CPU fallback and no fallback to autograd."""
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Optional
 
 import torch
 import torch.nn as nn
 
 from . import _kernels
+from ._classifier_engine import C_A, C_B, C_FIRST, K7, Conv7Trunk, geometry, lstm_pack, lstm_pack_buffers
 from ._classifier_train_engine import SUPPORTED, ClassifierTrainEngine, check_common, refuse
 from ._conv_stack import ConvStack
 from ._launch import r4
-from ._lib import EPI_LRELU, EPI_MASK, EPI_STORE, LOAD_DIRECT, LOAD_V, LOAD_Y, check, ptr
-
-K7 = 7            # taps of every convolution of the model
-C_FIRST, C_A, C_B = 1024, 512, 256
-
-
-def geometry(n_channels: int, n_timepoints: int, lstm_dim: int) -> Dict[str, int]:
-    """Row counts of the trunk: after block 1 / 2 (t1), the two 7-tap stages (ta, tb), the (3,1) pool (tq)."""
-    t1 = (n_timepoints - K7 + 1) // 2
-    ta = t1 - K7 + 1
-    tb = ta - K7 + 1
-    w1 = lstm_dim // n_timepoints
-    return dict(t1=t1, ta=ta, tb=tb, tq=tb // 3, w1=w1, W=w1 + n_channels)
-
+from ._lib import EPI_MASK, EPI_STORE, LOAD_DIRECT, LOAD_V, LOAD_Y, check, ptr
 
 def lstm2_input_index(b: int, ch: int, s: int, w: int, B: int, tq: int, W: int, channels: int = C_B):
     """(row, column) of element (b, ch, s, w) of the contiguous (B, channels, tq, W) activation in lstm2's input matrix as this
@@ -71,19 +59,16 @@ def check_supported(model) -> None:
 
 
 class _Lstm:
-    """Packed weights and the kept state of one ``nn.LSTM`` for one batch size; rows are time-major (t * B + b)."""
+    """The kept state of one ``nn.LSTM`` for one batch size, rows time-major (t * B + b), and the packs of its weights the last
+    forward ran on (``_lstm_pack``)."""
 
     def __init__(self, name: str, mod: nn.LSTM, T: int, B: int, dev, want_dx: bool):
         f32 = dict(dtype=torch.float32, device=dev)
         self.name, self.T, self.B = name, T, B
         self.in_dim, self.H = mod.input_size, mod.hidden_size
         self.Kp, self.Hp = r4(self.in_dim), (self.H + 7) // 8 * 8
-        self.padded = self.Kp != self.in_dim or self.Hp != self.H
         H4, rows = 4 * self.Hp, T * B
-        self.wi = torch.zeros(H4, self.Kp, **f32) if self.padded else None      # (lstm2: weight_ih_l0 is used where it lies)
-        self.bs = torch.zeros(H4, **f32)
-        self.whp = torch.zeros(H4, self.Hp, **f32)                               # unit-major: row 4 u + g
-        self.whT = torch.zeros(self.Hp, H4, **f32)                               # W_hh^T: row u', column g Hp + u
+        self.wi = self.bs = self.whp = self.whT = None
         self.xp = torch.empty(rows, H4, **f32)
         self.hs = torch.empty(rows, self.Hp, **f32)
         self.cs = torch.empty(rows, self.Hp, **f32)
@@ -94,7 +79,6 @@ class _Lstm:
         self.ldt = (rows + 31) // 32 * 32
         self.dgT = torch.zeros(H4, self.ldt, **f32) if want_dx else None         # pad columns stay zero
         self.colsum = torch.empty(H4, **f32)
-        self.packed = None                                                       # weight version the packs were made from
 
     def h_last(self) -> torch.Tensor:
         return self.hs[(self.T - 1) * self.B:]
@@ -117,7 +101,7 @@ class _Ws:
         self.pred = torch.empty(B, dtype=torch.int64, device=dev)
 
 
-class CnnRnnClassifierTrainEngine(ClassifierTrainEngine, ConvStack):
+class CnnRnnClassifierTrainEngine(ClassifierTrainEngine, Conv7Trunk, ConvStack):
     F63_CAPABLE = False        # (the 3-tap F(6,3) stack does not apply: every stage here has 7 taps)
     UPDATE_TAG = "update"
     head_bias = "output.bias"
@@ -126,18 +110,14 @@ class CnnRnnClassifierTrainEngine(ClassifierTrainEngine, ConvStack):
         check_supported(model)
         Cn, T = int(model.input_channels), int(model.input_length)
         slope = float(model.conv_pool_block1[1].negative_slope)
-        geo = geometry(Cn, T, model.lstm1.hidden_size)
-        self.w1, self.W, self.Cn = geo["w1"], geo["W"], Cn
+        self._trunk_geometry(Cn, T, model.lstm1.hidden_size)
+        self.Cn = Cn
         # the conv stack sees W sequences per batch element (branch-major: see _forward); three 7-tap stages, the first pooled
         super().__init__(self.W, T, [(C_FIRST, K7, True), (C_A, K7, False), (C_B, K7, False)], slope, C_B)
-        self.t1, self.ta, self.tb, self.tq = geo["t1"], geo["ta"], geo["tb"], geo["tq"]
         assert self.t1 == self.tout1 and self.stages[1].tout == self.tb
-        # rows per sequence: whole hexes for the F(6,3) form of the 7-tap forward, whole quads otherwise (CnnRnnConvEngine's)
-        self.conv7_form = _kernels.conv7_forward()
         # conv7=wino63bwd: the weight and input gradients of the two wide stages on F(6,3) too (_wgrad7 / _dgrad7; needs whole
         # 256-channel tiles of C_in for the transform-free weight-gradient kernel - the model's widths have them)
         self.conv7_bwd = _kernels.get("conv7") == "wino63bwd"
-        self.Tp = (self.t1 + 5) // 6 * 6 if self.conv7_form == "wino63" else (self.t1 + 3) // 4 * 4
         self.tp1 = self.Tp
         for st in self.stages:
             st.tp_in = st.tp_out = self.Tp
@@ -153,8 +133,6 @@ class CnnRnnClassifierTrainEngine(ClassifierTrainEngine, ConvStack):
             ["output.bias", "output.weight"] + [k for k in names if k.startswith("lstm2.")]
             + [k for k in names if k.startswith("conv_block3.")][::-1]
             + [k for k in names if k.startswith("conv_pool_block")] + [k for k in names if k.startswith("lstm1.")]))
-        self._updates = 0                  # optimiser steps taken: part of the key of every weight pack
-        self._packs: Dict[str, tuple] = {}
 
     # ------------------------------------------------------------------ buffers
     def _alloc_rows(self):
@@ -166,12 +144,7 @@ class CnnRnnClassifierTrainEngine(ClassifierTrainEngine, ConvStack):
         self.P = {1: z(rows + 8, C_FIRST), 2: z(rows + 8, C_A), 3: z(rows, C_B)}
         self.bits = {1: zi(rows, C_FIRST // 32)}
         self.sbits = {1: zi(rows, C_FIRST // 32)}
-        self.V7 = None
-        if self.conv7_form == "wino63":
-            # whole 128-hex tiles of the NT kernel (+ 2: its third segment reads one hex on); under conv7=wino63bwd also whole
-            # 6-hex K-steps of the weight-gradient kernel, which the first rounding does not imply (253 hexes: 256 < 258)
-            nh_pad = (rows // 6 + (6 if self.conv7_bwd else 2) + 127) // 128 * 128
-            self.V7 = (z(nh_pad, 8, C_FIRST), z(nh_pad, 8, C_FIRST))
+        self.V7 = self._alloc_v7(rows, 6 if self.conv7_bwd else 2, dev)
         self._v7_of = None                 # (generation, tag) of the transform V7 holds
         self.Y7 = self.D7 = None           # conv7=wino63bwd: Y = A dz, and V0 / V1 of the moved dz (allocated with G)
 
@@ -192,28 +165,14 @@ class CnnRnnClassifierTrainEngine(ClassifierTrainEngine, ConvStack):
         return _Ws(self, B, dev)
 
     # ------------------------------------------------------------------ LSTM
-    def _version(self, *names) -> tuple:
-        """What a pack of these parameters is keyed on: the engine's own update count (FusedNAdam writes through ``data_ptr``
-        and leaves ``_version`` alone) and torch's version / storage of every tensor (``load_state_dict``, ``.to``)."""
-        return (self._updates,) + tuple((self.params[n]._version, self.params[n].data_ptr()) for n in names)
-
     def _lstm_pack(self, l: _Lstm) -> None:
         """The packs of the CURRENT weights: once per weight version (a train step moves it, ``eval_batch`` does not)."""
-        prm = self.params
-        ver = self._version(*(f"{l.name}.{n}" for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")))
-        if l.packed == ver:
-            return
-        l.packed = ver
-        w_ih, w_hh = prm[f"{l.name}.weight_ih_l0"].data, prm[f"{l.name}.weight_hh_l0"].data
-        H, Hp, D, Kp = l.H, l.Hp, l.in_dim, l.Kp
-        if l.padded:
-            self._permute(w_ih, l.wi, (1, 4, Hp, Kp), (0, H * D, D, 1), (1, 4, H, D))
-        self._permute(w_hh, l.whp, (1, Hp, 4, Hp), (0, H, H * H, 1), (1, H, 4, H))
-        self._permute(w_hh, l.whT, (1, Hp, 4, Hp), (0, 1, H * H, H), (1, H, 4, H))
-        l.bs.view(4, Hp)[:, :H] = (prm[f"{l.name}.bias_ih_l0"].data + prm[f"{l.name}.bias_hh_l0"].data).view(4, H)
+        w = tuple(self.params[f"{l.name}.{n}"].detach() for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"))
+        l.wi, l.bs, l.whp, l.whT = self.packs.get(l.name, w, lambda: lstm_pack_buffers(l.in_dim, l.H, w[0].device, train=True),
+                                                  into=lambda packs: lstm_pack(self.lib, packs, *w))
 
     def _w_ih(self, l: _Lstm) -> torch.Tensor:
-        return l.wi if l.padded else self.params[f"{l.name}.weight_ih_l0"].data
+        return l.wi if l.wi is not None else self.params[f"{l.name}.weight_ih_l0"].data      # (lstm2: used where it lies)
 
     def _lstm_forward(self, l: _Lstm, x_rows: torch.Tensor) -> None:
         self._lstm_pack(l)
@@ -269,51 +228,13 @@ class CnnRnnClassifierTrainEngine(ClassifierTrainEngine, ConvStack):
 
     # ------------------------------------------------------------------ the 7-tap stages, forward
     def _conv7(self, tag, src, name, dst, cin, cout, tvalid) -> None:
-        """dst[r] = lrelu(sum_j w[:, :, j] src[r + j] + b) for every row r of the stack; src holds 8 rows more."""
-        rows = self.S * self.Tp
-        st_ = self._stream()
-        w, b = self.params[name + ".weight"].data, self.params[name + ".bias"].data
-        name = name + ".weight"
-        if self.conv7_form == "wino63":
-            # (a narrower layer re-views the storage: its pad hexes are zeroed - "zero hexes appended", tl_conv7_wino63v_nt's contract)
-            V0, V1 = (self._hex_view(v, cin, rows // 6) for v in self.V7)
-            ev = self._tick(tag + "_xform")
-            check(self.lib.tl_wino63_xform2(ptr(src), ptr(V0), ptr(V1), rows, self.Tp, tvalid, cin, src.shape[1], cin, st_),
-                  "tl_wino63_xform2")
-            self._v7_of = (self.generation, tag)
-            hit = self._packs.get(tag)
-            if hit is None or hit[0] != self._version(name):
-                wp = hit[1] if hit is not None else torch.empty(3 * cin // 8, 8, cout, 8, dtype=torch.float32, device=w.device)
-                check(self.lib.tl_wino63_weights7(ptr(w.reshape(cout, cin, K7)), ptr(wp), cout, cin, K7, st_), "tl_wino63_weights7")
-                self._packs[tag] = (self._version(name), wp)
-            wp = self._packs[tag][1]
-            if ev:
-                ev[1].record()
-            self._nt(tag=tag, fn="tl_conv7_wino63v_nt", A=ptr(V0), aux=ptr(V1), A_rows=V0.shape[0], lda=cin, Bw=ptr(wp),
-                     bias=ptr(b), out=ptr(dst), M=rows, N=cout, K=cin, ldb=3 * cin, ldo=dst.shape[1], J=K7, row_shift=0,
-                     Tp=self.Tp, Tvalid=self.Tp, slope=self.slope, loader=LOAD_V, epilogue=EPI_LRELU)
-            return
-        hit = self._packs.get(tag)
-        if hit is None or hit[0] != self._version(name):
-            self._packs[tag] = (self._version(name), self._pack_conv(w, cin, False))     # [J][O][I]
-        wp = self._packs[tag][1]
-        self._nt(tag=tag, A=ptr(src), Bw=ptr(wp), bias=ptr(b), out=ptr(dst), M=rows, A_rows=rows + 8, N=cout, K=cin, lda=cin,
-                 ldb=cin, ldo=cout, J=K7, row_shift=0, Tp=self.Tp, Tvalid=self.Tp, slope=self.slope, loader=LOAD_DIRECT,
-                 epilogue=EPI_LRELU)
+        """``Conv7Trunk._conv7`` over every row of the stack, timed under ``tag``; V7 then holds this stage's transform."""
+        prm = self.params
+        super()._conv7(tag, src, prm[name + ".weight"].detach(), prm[name + ".bias"].data, dst, cin, cout, tvalid,
+                       self.S * self.Tp, tag=tag)
+        self._v7_of = (self.generation, tag)
 
     # ------------------------------------------------------------------ the 7-tap stages, backward on F(6,3) (conv7=wino63bwd)
-    def _hex_view(self, buf: torch.Tensor, c: int, nhex: int) -> torch.Tensor:
-        """``buf`` (hexes, 8, wider) re-viewed for ``c`` channels; the pad hexes of a narrower view overlay data: zeroed - with
-        an odd ``nhex`` the second hex of the last pair too, which no transform kernel writes (the weight-gradient kernel reads
-        whole 6-hex K-steps of BOTH operands: a stale hex of Y against a stale hex of V is a term of the sum)."""
-        if c == buf.shape[2]:
-            return buf
-        v = buf.view(-1)[: buf.shape[0] * 8 * c].view(-1, 8, c)
-        v[(nhex + 1) // 2 * 2:].zero_()
-        if nhex % 2:
-            v.view(-1, c // 8, 8, 2, 8)[nhex // 2, :, :, 1].zero_()          # (pair layout: [hex / 2][c / 8][8][hex % 2][8])
-        return v
-
     def _wgrad7(self, st, gw: torch.Tensor, gb: torch.Tensor) -> None:
         """dW_j = sum_R dz[R] (x) x[R + j] as three 3-tap F(6,3) weight gradients: taps 3 s .. 3 s + 2 see x shifted by 3 s rows =
         V0(x), V1(x) and V0(x) one hex on (``a_hex``), all against Y = A dz (``tl_wino63_ydz`` of G[idx]); the transform-free
@@ -380,13 +301,11 @@ class CnnRnnClassifierTrainEngine(ClassifierTrainEngine, ConvStack):
         ev = self._tick(tag + "_xform")
         check(self.lib.tl_wino63_xform2s(ptr(Gs), ptr(D0), ptr(D1), rows, Tp, st.tout, K7 - 1, cout, Gs.shape[1], cout,
                                          self._stream()), "tl_wino63_xform2s")
-        hit = self._packs.get(tag)
-        if hit is None or hit[0] != self._version(name):
-            wp = hit[1] if hit is not None else torch.empty(3 * cout // 8, 8, cin, 8, dtype=torch.float32, device=w.device)
+        def flipped(wp):
             wf = w.reshape(cout, cin, K7).flip(2).permute(1, 0, 2).contiguous()        # (I, O, 7): wf[i][o][j] = w[o][i][6 - j]
             check(self.lib.tl_wino63_weights7(ptr(wf), ptr(wp), cin, cout, K7, self._stream()), "tl_wino63_weights7")
-            self._packs[tag] = (self._version(name), wp)
-        wp = self._packs[tag][1]
+        wp = self.packs.get(tag, self.params[name], into=flipped,
+                            build=lambda: torch.empty(3 * cout // 8, 8, cin, 8, dtype=torch.float32, device=w.device))
         if ev:
             ev[1].record()
         kw = dict(auxbits=ptr(self.sbits[1]), ld_auxbits=self.sbits[1].shape[1]) if st.idx == 2 else \
@@ -478,10 +397,3 @@ class CnnRnnClassifierTrainEngine(ClassifierTrainEngine, ConvStack):
         self._call("conv1_dgrad", "tl_conv1_dgrad", ptr(self.G[1]), ptr(self.bits[1]), ptr(w2), ptr(l1.dh_last), B * w1, T, K7,
                    C_FIRST, Tp, self.t1, w1, l1.Hp, w1, 1)
         self._lstm_backward(l1, ws.x1, None)
-
-    def _after_update(self) -> None:
-        self._updates += 1
-        super()._after_update()
-        if getattr(self.model, "_hip", None) is not None:    # (made together with ``_hip``: the two LSTM packs are stale too)
-            self.model._hip_lstm1._packed = None
-            self.model._hip_lstm2._packed = None

@@ -1,5 +1,6 @@
 """Launch plumbing shared by the host engines: the only place that fills ``NtParams`` / ``TnParams`` and calls
-``tl_permute_reduce``, plus the HIP-event timers.  Everything launches on torch's current stream."""
+``tl_permute_reduce``, plus the cache of packed weights and the HIP-event timers.  Everything launches on torch's current
+stream."""
 from __future__ import annotations
 
 import ctypes as C
@@ -58,6 +59,29 @@ def permute_reduce(lib, src, dst, dims, strides, lims=None, nz=1, zs=0, src_off=
     l = (C.c_int64 * 4)(*(lims if lims is not None else dims))
     check(lib.tl_permute_reduce(src.data_ptr() + 4 * src_off, dst.data_ptr(), d, s, l, nz, zs, ptr(bias), _stream()),
           "tl_permute_reduce")
+
+
+class PackCache:
+    """Packed copies of weights, each rebuilt when a tensor it was made from was written to or replaced: the key is
+    ``(_version, data_ptr())`` of every one of them.  Torch's in-place operations and ``FusedNAdam`` both move ``_version``
+    (of the parameter and its ``.detach()`` - ``.data`` has a counter of its own and never shows a write), so an engine
+    needs no word from whoever updated the weights."""
+
+    def __init__(self):
+        self._packed = {}
+
+    def get(self, key, params, build, into=None):
+        """The pack ``key`` of ``params`` (a tensor or a tuple of them): ``build()`` makes it; with ``into`` a stale pack is
+        kept and ``into(pack)`` fills it again (``build()`` then only allocates: ``into`` fills the first one too)."""
+        params = params if isinstance(params, tuple) else (params,)
+        ver = tuple((p._version, p.data_ptr()) for p in params)
+        hit = self._packed.get(key)
+        if hit is None or hit[0] != ver:
+            pack = build() if hit is None or into is None else hit[1]
+            if into is not None:
+                into(pack)
+            hit = self._packed[key] = (ver, pack)
+        return hit[1]
 
 
 class LaunchTimers:

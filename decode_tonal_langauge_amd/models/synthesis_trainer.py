@@ -438,7 +438,8 @@ class SynthesisTrainer:
     def _graph_fingerprint(self) -> tuple:
         """Everything a captured step has frozen into its kernel arguments besides the batch: storage of the parameters,
         of their gradients and NAdam moments, the optimiser's hyper-parameters, the dropout rate and the classifiers'
-        weights (their packed copies are rebuilt when a weight's version changes).  A replay is only valid while this tuple
+        weights (their packed copies are rebuilt when a weight's version changes - and ``FusedNAdam`` moves ``_version`` like
+        torch's own in-place writes, so a classifier trained on the fused path between two steps is seen here).  A replay is only valid while this tuple
         is what it was at capture: ``optimizer.load_state_dict`` (new moment tensors), an edited ``param_groups`` entry, a
         re-loaded classifier or a re-assigned ``.data`` would otherwise leave the graph reading freed or stale buffers."""
         opt = self.optimizer

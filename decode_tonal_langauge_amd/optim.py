@@ -74,6 +74,20 @@ class FusedNAdam(torch.optim.Optimizer):
             raise RuntimeError("FusedNAdam: the row shard of a parameter cannot change between steps")
         return st
 
+    def _advance(self, group, params) -> tuple:
+        """The one place a schedule moves: ``params`` (all at the same point of it) go one step on and are marked as written
+        (the kernels write through ``data_ptr``; the version counter is what packed copies of a weight and saved autograd
+        tensors are checked against).  Call it once every argument check of the update has passed.  Returns
+        (coef_grad, coef_mom, bias_corr2) of the step."""
+        st0 = self.state[params[0]]
+        cg, cm, bc2, mu_product = self._scalars(st0["step"] + 1, st0["mu_product"], group)
+        for p in params:
+            st = self.state[p]
+            st["step"] += 1
+            st["mu_product"] = mu_product
+        torch.autograd.graph.increment_version(params)
+        return cg, cm, bc2
+
     LOWRANK_MAX = 64          # largest factor rank tl_nadam_lowrank takes
 
     @torch.no_grad()
@@ -85,15 +99,14 @@ class FusedNAdam(torch.optim.Optimizer):
         ``dh = (slab (n, U, cols), U, row_tiles)`` (one parameter only): the same pass writes the partial sums of
         ``fa[0:U] . p_old`` - the product of the factor's first U rows with the parameter as it was BEFORE this update
         (``tl_nadam_lowrank_dh``: the label LSTM's last BPTT step rides in the W_hh update); ``slab.sum(0)`` is the product."""
-        stream = torch.cuda.current_stream().cuda_stream
         if dh is not None and len(lowrank) != 1:
             raise RuntimeError("FusedNAdam.step_lowrank: the fused product takes exactly one parameter")
         for group in self.param_groups:
             for p in group["params"]:
                 if p in lowrank:
-                    self._step_lowrank(p, group, lowrank[p], grad_scale, stream, dh)
+                    self._step_lowrank(p, group, lowrank[p], grad_scale, dh)
 
-    def _step_lowrank(self, p, group, spec, grad_scale, stream, dh=None) -> None:
+    def _step_lowrank(self, p, group, spec, grad_scale, dh=None) -> None:
         b1, b2 = group["betas"]
         fa, fb = spec[0], spec[1]
         shard = (int(spec[2]), int(spec[3])) if len(spec) > 2 else None
@@ -106,10 +119,6 @@ class FusedNAdam(torch.optim.Optimizer):
         if kr and (fa.shape[1] != rows or fb.shape[1] != p.shape[1] or fb.shape[0] != kr
                    or fa.stride(1) != 1 or fb.stride(1) != 1):
             raise RuntimeError("FusedNAdam: low-rank factors do not match the parameter")
-        _lib.require_gpu(p, "FusedNAdam.step")
-        st = self._state_for(p, shard)
-        st["step"] += 1
-        cg, cm, bc2, st["mu_product"] = self._scalars(st["step"], st["mu_product"], group)
         if dh is not None:
             slab, U, row_tiles = dh
             nslab = -(-(-(-rows // 32)) // row_tiles)
@@ -117,6 +126,11 @@ class FusedNAdam(torch.optim.Optimizer):
                     or slab.dtype != torch.float32):
                 raise RuntimeError("FusedNAdam: the fused product needs the whole parameter, U <= rank and a contiguous fp32 slab "
                                    f"({nslab}, {U}, {p.shape[1]})")
+        _lib.require_gpu(p, "FusedNAdam.step")
+        st = self._state_for(p, shard)
+        cg, cm, bc2 = self._advance(group, [p])
+        stream = torch.cuda.current_stream().cuda_stream
+        if dh is not None:
             check(self._lib.tl_nadam_lowrank_dh(p.data_ptr(), ptr(st["exp_avg"]), ptr(st["exp_avg_sq"]), ptr(fa), ptr(fb), kr, rows,
                                                 p.shape[1], fa.stride(0), fb.stride(0), cg, cm, b1, b2, bc2, group["eps"],
                                                 group["weight_decay"], grad_scale, ptr(slab), U, row_tiles, stream),
@@ -139,13 +153,12 @@ class FusedNAdam(torch.optim.Optimizer):
         [row0, row0 + n) of the parameter (a data-parallel rank that owns a row shard of it).
         ``skip``: parameters already updated this step through ``step_lowrank``."""
         loss = closure() if closure is not None else None
-        stream = torch.cuda.current_stream().cuda_stream
         dense = {}
         for group in self.param_groups:
             b1, b2 = group["betas"]
             for p in group["params"]:
                 if lowrank is not None and p in lowrank:
-                    self._step_lowrank(p, group, lowrank[p], grad_scale, stream)
+                    self._step_lowrank(p, group, lowrank[p], grad_scale)
                     continue
                 if skip is not None and p in skip:
                     continue
@@ -156,22 +169,22 @@ class FusedNAdam(torch.optim.Optimizer):
                 if not (p.is_contiguous() and g.is_contiguous()):
                     raise RuntimeError("FusedNAdam needs contiguous parameters and gradients")
                 st = self._state_for(p)
-                st["step"] += 1
                 dense.setdefault((st["step"], st["mu_product"]), []).append((p, g, st))
             # tensors at the same point of the schedule (normally all of them) share one launch
-            for (step_no, mu_prod), items in dense.items():
-                cg, cm, bc2, mu_prod = self._scalars(step_no, mu_prod, group)
-                for _, _, st in items:
-                    st["mu_product"] = mu_prod
-                if len(items) == 1 or not self.multi_tensor:
-                    for p, g, st in items:
-                        check(self._lib.tl_nadam(ptr(p), ptr(g), ptr(st["exp_avg"]), ptr(st["exp_avg_sq"]), p.numel(), cg,
-                                                 cm, b1, b2, bc2, group["eps"], group["weight_decay"], grad_scale, stream),
-                              "tl_nadam")
+            stream = torch.cuda.current_stream().cuda_stream if dense else None
+            for items in dense.values():
+                multi = len(items) > 1 and self.multi_tensor
+                if multi:
+                    table, blocks = self._table(items)
+                cg, cm, bc2 = self._advance(group, [p for p, _, _ in items])
+                if multi:
+                    check(self._lib.tl_nadam_multi(ptr(table), len(items), blocks, cg, cm, b1, b2, bc2, group["eps"],
+                                                   group["weight_decay"], grad_scale, stream), "tl_nadam_multi")
                     continue
-                table, blocks = self._table(items)
-                check(self._lib.tl_nadam_multi(ptr(table), len(items), blocks, cg, cm, b1, b2, bc2, group["eps"],
-                                               group["weight_decay"], grad_scale, stream), "tl_nadam_multi")
+                for p, g, st in items:
+                    check(self._lib.tl_nadam(ptr(p), ptr(g), ptr(st["exp_avg"]), ptr(st["exp_avg_sq"]), p.numel(), cg,
+                                             cm, b1, b2, bc2, group["eps"], group["weight_decay"], grad_scale, stream),
+                          "tl_nadam")
             dense.clear()
         return loss
 
@@ -202,19 +215,18 @@ class FusedNAdam(torch.optim.Optimizer):
 
     def advance_scalars(self, params) -> tuple:
         """Advance the schedule of ``params`` (all at the same point of it) by one step on the host and return
-        (coef_grad, coef_mom, bias_corr2) of that step - what ``step`` would have passed by value."""
+        (coef_grad, coef_mom, bias_corr2) of that step - what ``step`` would have passed by value.  This is also where the
+        parameters of a graph-captured step are marked as written: it runs at every replay, ``step_graph`` at capture only."""
         out = None
         for group in self.param_groups:
-            b1, b2 = group["betas"]
             for p in group["params"]:
                 if p not in params:
                     continue
-                st = self._state_for(p)
-                st["step"] += 1
-                cg, cm, bc2, st["mu_product"] = self._scalars(st["step"], st["mu_product"], group)
-                if out is not None and out != (cg, cm, bc2):
+                self._state_for(p)
+                now = self._advance(group, [p])
+                if out is not None and out != now:
                     raise RuntimeError("FusedNAdam.advance_scalars: parameters at different points of the schedule")
-                out = (cg, cm, bc2)
+                out = now
         return out
 
     def _table(self, items):

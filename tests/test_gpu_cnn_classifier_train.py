@@ -304,6 +304,41 @@ def test_inference_after_fused_training_uses_the_updated_weights():
     assert torch.equal(eng.predict_batch(xd).cpu(), s.argmax(1))
 
 
+@pytest.mark.parametrize("kind", ["cnn", "cnnrnn"])
+def test_a_direct_fused_update_reaches_the_inference_packs(kind):
+    """``FusedNAdam`` driven directly - no train engine that could tell the inference engines: forward (the packs are built),
+    one step, forward again.  The second output is, bit for bit, that of a copy of the updated model with fresh engines and
+    fresh packs, and it is not the first one (2e-4: what the tests above take for "moved")."""
+    from decode_tonal_langauge_amd.optim import FusedNAdam
+    from tests import cnnrnn_classifier_ref as rref
+    r = cref if kind == "cnn" else rref
+    shape, seed = r.SHAPES[0]
+    model, x, _ = r.build(shape, seed)
+    model = model.to(DEV).eval()
+    xd = x.to(DEV)
+    with torch.no_grad():
+        first = model(xd).clone()
+    engines = {k: v for k, v in vars(model).items() if k.startswith("_hip") and k != "_hip_cfg"}
+    assert engines["_hip"] is not None
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    grads = {p: torch.randn(p.shape, device=DEV, generator=g) * 1e-2 for p in model.parameters()}
+    versions = [p._version for p in model.parameters()]
+    FusedNAdam(model.parameters()).step(grads=grads)
+    assert all(p._version > v for p, v in zip(model.parameters(), versions))
+    with torch.no_grad():
+        second = model(xd).clone()
+    assert all(getattr(model, k) is v for k, v in engines.items())          # the engines (and their caches) of the first pass
+    for k in engines:                          # the copy: everything but the engines, which it then makes for itself
+        setattr(model, k, None)
+    fresh = copy.deepcopy(model)
+    with torch.no_grad():
+        want = fresh(xd)
+    moved = float((second - first).abs().max())
+    print(f"[direct_update] {kind}: scores moved by {moved:.3e} in one step")
+    assert torch.equal(second, want)
+    assert moved > 2e-4
+
+
 # ---------------------------------------------------------------------------------------------- 7. trainer and pipeline
 def test_fused_trainer_fits_a_cnn_classifier(tmp_path):
     from decode_tonal_langauge_amd._cnn_classifier_train_engine import CnnClassifierTrainEngine

@@ -287,7 +287,7 @@ def test_flipped_packs_follow_the_update(monkeypatch):
     eng.model.train()
     xd, yd = x.to(DEV), y.to(DEV)
     first = {k: g.detach().clone() for k, g in eng.backward_only(xd, yd).items()}
-    packs0 = {k: v[1].clone() for k, v in eng._packs.items() if k.endswith("_dgrad")}
+    packs0 = {k: v[1].clone() for k, v in eng.packs._packed.items() if k.endswith("_dgrad")}
     assert set(packs0) == {"conv2_dgrad", "conv3_dgrad"}
     for _ in range(2):
         eng.train_batch(xd, yd)
@@ -299,5 +299,5 @@ def test_flipped_packs_follow_the_update(monkeypatch):
     for k in moved:
         assert torch.equal(moved[k], fresh[k]), k
     for k, old in packs0.items():
-        assert not torch.equal(eng._packs[k][1], old), k                         # the packs were rebuilt from the moved weights
+        assert not torch.equal(eng.packs._packed[k][1], old), k                         # the packs were rebuilt from the moved weights
     assert not torch.equal(first["conv_pool_block1.0.weight"], moved["conv_pool_block1.0.weight"])

@@ -657,8 +657,58 @@ def test_lowrank_nadam_pass_also_yields_the_last_bptt_product(dev):
             ref = fa[:U].double() @ old.double()
             got = slab.double().sum(0)
             assert float((got - ref).abs().max()) < 1e-5 * float(ref.abs().max()), (rows, cols, kr, U, row_tiles)
+    before = (ob.state[pb]["step"], ob.state[pb]["mu_product"], pb._version, pb.detach().clone())
     with pytest.raises(RuntimeError):           # U above the factor rank / a slab of the wrong shape
         ob.step_lowrank({pb: (fa[:2], fb[:2])}, dh=(torch.empty(1, 5, cols, device=dev), 5, 2))
+    # ... and the rejected call left the schedule, the version and the parameter where they were (it used to advance ``step``)
+    assert (ob.state[pb]["step"], ob.state[pb]["mu_product"], pb._version) == before[:3]
+    assert torch.equal(pb.detach(), before[3])
+
+
+def test_fused_nadam_moves_the_version_of_what_it_wrote_and_nothing_else(dev):
+    """Every route of ``FusedNAdam`` bumps ``_version`` of the parameters it updated, once per step or more, and of no other:
+    not of a parameter without a gradient, not of one in ``skip``."""
+    from decode_tonal_langauge_amd.optim import FusedNAdam
+    g = torch.Generator(device=dev).manual_seed(3)
+    rnd = lambda *s: torch.randn(*s, device=dev, generator=g)
+
+    def fresh():
+        ps = [torch.nn.Parameter(rnd(8, 12)), torch.nn.Parameter(rnd(16, 4)), torch.nn.Parameter(rnd(12))]
+        return ps, FusedNAdam(ps, lr=1e-2), [p.detach().clone() for p in ps]
+
+    def check_moved(ps, old, before, written):
+        for i, p in enumerate(ps):
+            if i in written:
+                assert p._version > before[i] and not torch.equal(p.detach(), old[i]), i
+            else:
+                assert p._version == before[i] and torch.equal(p.detach(), old[i]), i
+
+    for multi in (True, False):                                   # dense: the multi-tensor launch, then one launch per tensor
+        ps, opt, old = fresh()
+        opt.multi_tensor = multi
+        for written, kw in (((0, 2), dict(grads={ps[0]: rnd(8, 12), ps[2]: rnd(12)})),                    # ps[1]: no gradient
+                            ((1, 2), dict(grads={p: torch.randn_like(p) for p in ps}, skip={ps[0]}))):   # ps[0]: skipped
+            before = [p._version for p in ps]
+            old = [p.detach().clone() for p in ps]
+            opt.step(**kw)
+            check_moved(ps, old, before, written)
+    ps, opt, old = fresh()                                        # low-rank, through step and through step_lowrank
+    for call in (lambda: opt.step(grads={}, lowrank={ps[0]: (rnd(3, 8), rnd(3, 12))}),
+                 lambda: opt.step_lowrank({ps[0]: (rnd(3, 8), rnd(3, 12))})):
+        before = [p._version for p in ps]
+        old = [p.detach().clone() for p in ps]
+        call()
+        check_moved(ps, old, before, (0,))
+    ps, opt, old = fresh()                                        # the graph form, outside a capture
+    scalars = torch.zeros(4, device=dev)
+    for _ in range(2):
+        before = [p._version for p in ps]
+        old = [p.detach().clone() for p in ps]
+        grads = {ps[0]: rnd(8, 12), ps[2]: rnd(12)}
+        scalars[:3] = torch.tensor(opt.advance_scalars(set(grads)), dtype=torch.float32)
+        opt.step_graph(grads, scalars)
+        check_moved(ps, old, before, (0, 2))
+    assert [opt.state[p].get("step", 0) for p in ps] == [2, 0, 2]
 
 
 def test_recurrent_gradient_stream_matches_float64(dev):

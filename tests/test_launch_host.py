@@ -88,3 +88,68 @@ def test_classifier_engine_is_a_conv_stack_without_the_synthesis_parts(monkeypat
             assert hasattr(syn, name) and not hasattr(clf, name), name
     assert CnnEngine not in CnnClassifierEngine.__mro__ and ConvStack in CnnClassifierEngine.__mro__
     assert issubclass(CnnEngine, ConvStack)
+
+
+def test_pack_cache_rebuilds_when_a_tensor_it_was_built_from_changed():
+    """``PackCache``: one build while every ``(_version, data_ptr())`` stands; a bumped version of any one tensor of a tuple, or
+    a tensor at another address in its place, is a rebuild; with ``into`` the rebuild lands in the previous pack's storage."""
+    import torch
+    bump = torch.autograd.graph.increment_version
+    cache, builds = _launch.PackCache(), []
+
+    def pack_of(*ts):
+        def build():
+            builds.append(len(builds))
+            return sum(t.detach().sum() for t in ts).reshape(1)
+        return build
+
+    a, b, c = (torch.nn.Parameter(torch.full((4,), float(i))) for i in (1, 2, 3))
+    first = cache.get("abc", (a, b, c), pack_of(a, b, c))
+    assert cache.get("abc", (a, b, c), pack_of(a, b, c)) is first and builds == [0]
+    assert cache.get("abc", (a, b.detach(), c), pack_of(a, b, c)) is first and builds == [0]     # .detach() shares the counter
+    for n, p in enumerate((a, b, c), start=1):                    # any one of the tuple
+        bump(p)
+        assert cache.get("abc", (a, b, c), pack_of(a, b, c)) is not first and builds == list(range(n + 1))
+        assert cache.get("abc", (a, b, c), pack_of(a, b, c)) is cache.get("abc", (a, b, c), pack_of(a, b, c))
+        assert builds == list(range(n + 1))
+    # a single tensor is its own tuple; another key is another pack
+    one = cache.get("a", a, pack_of(a))
+    assert float(one) == 4.0 and cache.get("a", a, pack_of(a)) is one and len(builds) == 5
+    # the parameter replaced by a tensor at another address (same version: both fresh)
+    a2 = torch.nn.Parameter(a.detach().clone() * 2)
+    torch.autograd.graph.increment_version([a2] * a._version)
+    assert a2._version == a._version and a2.data_ptr() != a.data_ptr()
+    two = cache.get("a", a2, pack_of(a2))
+    assert float(two) == 8.0 and two is not one and len(builds) == 6
+    # into: build() allocates once, into(pack) fills - the first time and every rebuild, in the same storage
+    fills = []
+
+    def fill(pack):
+        fills.append(pack.data_ptr())
+        pack.copy_(a2.detach() + 1)
+
+    alloc = lambda: builds.append("alloc") or torch.empty(4)
+    p0 = cache.get("into", a2, alloc, into=fill)
+    assert builds.count("alloc") == 1 and len(fills) == 1 and torch.equal(p0, a2.detach() + 1)
+    assert cache.get("into", a2, alloc, into=fill) is p0 and len(fills) == 1
+    with torch.no_grad():
+        a2.add_(1.0)                                              # torch's own in-place write moves the version too
+    p1 = cache.get("into", a2, alloc, into=fill)
+    assert p1.data_ptr() == p0.data_ptr() and builds.count("alloc") == 1 and len(fills) == 2
+    assert torch.equal(p1, a2.detach() + 1)
+
+
+def test_rejected_lowrank_update_leaves_schedule_and_version_alone():
+    """Factors of the wrong shape are refused by the shape check, which stands before the device check - so this runs on the
+    CPU - and before the schedule moves: no advanced ``step``, the parameter's ``_version`` as it was."""
+    import torch
+    from decode_tonal_langauge_amd.optim import FusedNAdam
+    p = torch.nn.Parameter(torch.ones(6, 8))
+    opt = FusedNAdam([p])
+    version, value = p._version, p.detach().clone()
+    for call in (lambda: opt.step(lowrank={p: (torch.ones(2, 5), torch.ones(2, 8))}),         # fa: 5 columns for 6 rows
+                 lambda: opt.step_lowrank({p: (torch.ones(2, 6), torch.ones(3, 8))})):         # fb: another rank
+        with pytest.raises(RuntimeError, match="do not match the parameter"):
+            call()
+        assert opt.state[p].get("step", 0) == 0 and opt.state[p].get("mu_product", 1.0) == 1.0
+        assert p._version == version and torch.equal(p.detach(), value)
