@@ -8,6 +8,7 @@ Schemas:
                            (reference channel_selection_main.py:86-88)
   * ``config.json``        ``{mel_kwargs, n_syllables, n_tones, tone_dynamic_mapping}`` (reference train_synthesizer.py:171-177)
   * ``B<block>_<modality>.npz``  ``data (C, T)``, ``sf`` (reference preprocess/io/tdt_blocks.py:33-34)
+  * ``HS<subject>-<block>/<modality>.npz``  ``data (C, T)``, ``sf``: a raw block as ``preprocess/io/npz_blocks.py`` reads it
   * ``B<block>.TextGrid``  one interval tier whose reading intervals are marked ``<tone digit><syllable character>``
                            (read by data_loading/text_align.py)
 
@@ -80,6 +81,35 @@ def write_raw_block(root: str, block: int = 1, modality: str = "ecog", n_channel
     path = os.path.join(root, f"B{block}_{modality}.npz")
     np.savez(path, data=data, sf=sf)
     return path
+
+
+def write_raw_tree(root: str, blocks: Dict, n_channels: int = 6, ecog_sf: float = 1017.25, audio_sf: float = 2000.5,
+                   audio_samples: Optional[int] = None, seed: int = 0, subject_dir: str = "Sub{subject}/raw",
+                   stray: Sequence[str] = ()) -> Dict:
+    """A raw tree for the preprocess stage with ``preprocess.io.npz_blocks``: ``<root>/<subject_dir>/HS<subject>-<block>/``
+    holding ``ecog.npz`` (``data (n_channels, int(seconds * ecog_sf)) float32``, ``sf``) and ``audio.npz``
+    (``data (1, audio_samples or int(seconds * audio_sf)) float32``, ``sf``).  ``blocks`` is ``{subject: {block: seconds}}``;
+    the data of (subject, block) are drawn from ``default_rng([seed, subject, block])``, and the default ECoG rate is not an
+    integer, as a TDT rate is not.  Every name in ``stray`` becomes an empty directory beside each subject's blocks (the
+    pipeline skips what does not parse as a block).  Returns ``{"root_dir", "subject_dirs", "subject_ids", "blocks":
+    {(subject, block): block directory}}`` - the first three are the pipeline's parameters."""
+    out = {"root_dir": root, "subject_dirs": [], "subject_ids": [], "blocks": {}}
+    for subject, lengths in blocks.items():
+        rel = subject_dir.format(subject=subject)
+        out["subject_dirs"].append(rel)
+        out["subject_ids"].append(subject)
+        for name in stray:
+            os.makedirs(os.path.join(root, rel, name), exist_ok=True)
+        for block, seconds in lengths.items():
+            rng = np.random.default_rng([seed, int(subject), int(block)])
+            path = os.path.join(root, rel, f"HS{subject}-{block}")
+            os.makedirs(path, exist_ok=True)
+            ecog = (rng.standard_normal((n_channels, int(seconds * ecog_sf))) * 30.0 + 5.0).astype(np.float32)
+            audio = rng.standard_normal((1, audio_samples or int(seconds * audio_sf))).astype(np.float32)
+            np.savez(os.path.join(path, "ecog.npz"), data=ecog, sf=ecog_sf)
+            np.savez(os.path.join(path, "audio.npz"), data=audio, sf=audio_sf)
+            out["blocks"][(subject, block)] = path
+    return out
 
 
 def write_block_annotations(root: str, block: int, events: Sequence, tier: str = "words", seconds: Optional[float] = None,

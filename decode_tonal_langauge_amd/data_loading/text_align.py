@@ -147,15 +147,17 @@ def merge_tone_labels(per_block: List[np.ndarray]) -> np.ndarray:
 def extract_ecog_audio(intervals: Dict[int, pd.DataFrame], recording_dir: Optional[str], syllables: List[str],
                        length: float = 1.0, output_path: Optional[str] = None,
                        rest_period: Optional[Tuple[float, float]] = None, recording_format: str = "npz",
-                       recordings: Optional[Mapping] = None, to_host: bool = True) -> dict:
+                       recordings: Optional[Mapping] = None, to_host: bool = True, announce: bool = False) -> dict:
     """The samples of one subject: ``ecog (n, C, L)``, ``ecog_sf``, ``audio (n, S)``, ``audio_sf``, ``syllable (n,)``,
     ``tone (n,)`` and, with ``rest_period``, ``ecog_rest (m, C, L)``; saved with ``np.savez`` when ``output_path`` is given.
 
     ``recording_dir`` holds ``B<block>...ecog...npz`` and ``B<block>...sound...npz`` files with the keys ``data (C, T)`` and
-    ``sf``.  ``recordings`` is used instead when given: a mapping ``block -> {"ecog": (data, sf), "sound": (data, sf)}`` of
-    NumPy arrays or CUDA tensors, visited in the mapping's order.  ``to_host=False`` leaves ``ecog`` / ``audio`` /
-    ``ecog_rest`` as CUDA tensors (the channel selectors take them as they are); with CUDA recordings nothing then crosses
-    to the host and the host never waits for the device.
+    ``sf``; a file named ``...audio...`` is a sound recording too (the preprocess stage writes ``B<block>_audio.npz``: the
+    reference's two stages disagree on the word).  ``recordings`` is used instead when given: a mapping
+    ``block -> {"ecog": (data, sf), "sound": (data, sf)}`` of NumPy arrays or CUDA tensors, visited in the mapping's order
+    and, within a block, in the entry's (``announce=True`` prints the recording-length line the file walk prints for each).
+    ``to_host=False`` leaves ``ecog`` / ``audio`` / ``ecog_rest`` as CUDA tensors (the channel selectors take them as they
+    are); with CUDA recordings nothing then crosses to the host and the host never waits for the device.
 
     Kept from the reference on purpose:
       * a window is ``[int(start * sf), int(start * sf) + int(length * sf))`` in the float64 arithmetic of the reference; a
@@ -214,13 +216,18 @@ def extract_ecog_audio(intervals: Dict[int, pd.DataFrame], recording_dir: Option
         for block, entry in recordings.items():
             if block not in intervals:
                 continue
-            if "ecog" in entry:
-                ecog_block(block, *entry["ecog"])
-            if "sound" in entry:
-                sound_block(block, *entry["sound"])
+            for kind in entry:                                      # the entry's order: the file order of a registered block
+                if kind not in ("ecog", "sound"):
+                    continue
+                what, work = ("ECoG", ecog_block) if kind == "ecog" else ("audio", sound_block)
+                data, sf = entry[kind]
+                if announce:
+                    print(f"{what} recording length for block {block}:", data.shape[1] / sf, " s")
+                work(block, data, sf)
     else:
         for file in sorted(os.listdir(recording_dir)):
-            for kword, done, what, work in (("ecog", erp, "ECoG", ecog_block), ("sound", audio, "audio", sound_block)):
+            for kword, done, what, work in (("ecog", erp, "ECoG", ecog_block), ("sound", audio, "audio", sound_block),
+                                            ("audio", audio, "audio", sound_block)):
                 if not match_filename(file, recording_format, [kword]):
                     continue
                 block = extract_block_id(file)

@@ -11,7 +11,12 @@ recordings of every subject -> ``subject_<id>.npz``, the file channel selection 
 The output directory is ``<basename(recording_dir)>__<md5(yaml.dump(stage config, sort_keys=True))[:6]>``; the configuration
 of the earlier stages is carried forward into its ``config.yaml``.  A subject is skipped when its recording directory is
 missing, when its output exists and ``overwrite`` is not set, or when its TextGrid directory is missing.  The window copies
-run on the GPU (``data_loading/text_align.py``)."""
+run on the GPU (``data_loading/text_align.py``).
+
+Resident hand-over: a subject whose ``subject_path`` the preprocess stage of this process registered
+(``preprocess.params.pipeline.params.keep_resident: true``, ``preprocess/handover.py``) is epoched from the blocks that stage
+left in memory - visited in the order of their files in a sorted listing - instead of from the files it wrote; results,
+``subject_<id>.npz`` and the printed lines are those of the file route.  Without a registration nothing changes."""
 from __future__ import annotations
 
 import hashlib
@@ -23,6 +28,7 @@ import numpy as np
 import yaml
 
 from .data_loading.text_align import extract_ecog_audio, handle_textgrids
+from .preprocess import handover
 from .utils.config import dict_to_namespace, load_config, update_configuration
 
 
@@ -69,19 +75,28 @@ def run(config: dict) -> str:
             raise ValueError("No intervals found in the TextGrid files. Check the directory and file naming conventions."
                              f"Target blocks: {blocks if blocks else 'all'}")
         print(f"Extracted intervals from TextGrid files: {len(intervals)} blocks found.")
+        resident = handover.lookup(subject_path)
+        recordings = None
+        if resident:                                     # "B10_" sorts before "B1_": the order of the files
+            recordings = {block: resident[block] for block in sorted(resident, key=lambda block: f"B{block}_")}
         for block_id, table in intervals.items():
             if figures and len(table):
                 plot_block_events(subject_path, subject_id, block_id, table.to_dict("records"),
-                                  os.path.join(figure_root, f"subject_{subject_id}"))
+                                  os.path.join(figure_root, f"subject_{subject_id}"),
+                                  recording=(recordings or {}).get(block_id, {}).get("ecog"))
         extract_ecog_audio(intervals, subject_path, syllables=params.syllable_identifiers,
                            length=subject_params["sample_length"], output_path=subject_output_path,
-                           rest_period=tuple(subject_params["rest_period"]))
+                           rest_period=tuple(subject_params["rest_period"]), recordings=recordings,
+                           announce=recordings is not None)
     return output_dir
 
 
-def plot_block_events(subject_path: str, subject_id, block_id, events: list, fig_dir: str, num_events: int = 3) -> None:
+def plot_block_events(subject_path: str, subject_id, block_id, events: list, fig_dir: str, num_events: int = 3,
+                      recording=None) -> None:
     """Three consecutive events of a block on ``min(5, C)`` random channels, the event spans highlighted (host matplotlib;
-    outside the tested contract).  Nothing is drawn without matplotlib or without ``B<block>_ecog.npz``."""
+    outside the tested contract).  Nothing is drawn without matplotlib or without ``B<block>_ecog.npz``; ``recording``
+    (``(data, sf)``, a NumPy array or a tensor) is drawn instead of the file when given, and only the span that is drawn is
+    copied to the host."""
     try:
         import matplotlib
         matplotlib.use("Agg")
@@ -89,11 +104,14 @@ def plot_block_events(subject_path: str, subject_id, block_id, events: list, fig
     except ImportError:
         warnings.warn("matplotlib is not importable: no event figures")
         return
-    ecog_path = os.path.join(subject_path, f"B{block_id}_ecog.npz")
-    if not os.path.exists(ecog_path):
-        return
-    with np.load(ecog_path) as ecog:
-        signal, sf = ecog["data"], float(ecog["sf"])
+    if recording is not None:
+        signal, sf = recording[0], float(recording[1])
+    else:
+        ecog_path = os.path.join(subject_path, f"B{block_id}_ecog.npz")
+        if not os.path.exists(ecog_path):
+            return
+        with np.load(ecog_path) as ecog:
+            signal, sf = ecog["data"], float(ecog["sf"])
     events = sorted(events, key=lambda e: e["start"])
     if len(events) > num_events:
         first = np.random.randint(0, len(events) - num_events + 1)
@@ -101,12 +119,14 @@ def plot_block_events(subject_path: str, subject_id, block_id, events: list, fig
     channels = np.random.choice(signal.shape[0], size=min(5, signal.shape[0]), replace=False)
     lo = int(max(min(e["start"] for e in events) - 0.5, 0) * sf)
     hi = min(int((max(e["end"] for e in events) + 0.5) * sf), signal.shape[1])
+    n_samples, span = signal.shape[1], signal[:, lo:hi]
+    span = span if isinstance(span, np.ndarray) else span.detach().cpu().numpy()
     fig, axes = plt.subplots(len(channels), 1, figsize=(12, 4 * len(channels)), sharex=True, squeeze=False)
     for ax, ch in zip(axes[:, 0], channels):
-        ax.plot(np.arange(lo, hi) / sf, signal[ch, lo:hi], label="Offset", color="blue", alpha=0.7)
+        ax.plot(np.arange(lo, hi) / sf, span[ch], label="Offset", color="blue", alpha=0.7)
         for k, e in enumerate(events):
-            a, b = int(e["start"] * sf), min(int(e["end"] * sf), signal.shape[1])
-            ax.plot(np.arange(a, b) / sf, signal[ch, a:b], label="Onset" if k == 0 else None, color="orange")
+            a, b = int(e["start"] * sf), min(int(e["end"] * sf), n_samples)
+            ax.plot(np.arange(a, b) / sf, span[ch, a - lo:b - lo], label="Onset" if k == 0 else None, color="orange")
             ax.axvline(e["start"], color="g", linestyle="--", alpha=0.7, label="Event Start" if k == 0 else None)
             ax.axvline(e["end"], color="r", linestyle="--", alpha=0.7, label="Event End" if k == 0 else None)
         ax.set_title(f"Channel {ch}", fontsize=18)

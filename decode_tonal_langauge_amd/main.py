@@ -4,7 +4,8 @@ For every stage of the fixed order below whose config names a ``module``, import
 ``getattr(module, cfg.get("function", "run"))(config)``.  A ``str`` return value is remembered as
 that stage's output directory and offered to later stages through their ``params.io`` block
 (only where the user has not set the key), exactly as the reference wires
-preprocess -> sample_collection -> channel_selection -> training.
+preprocess -> sample_collection -> channel_selection -> training.  Blocks the preprocess stage kept in memory for sample
+collection (``keep_resident``, ``preprocess/handover.py``) are released when that stage is done.
 """
 import importlib
 import sys
@@ -64,6 +65,10 @@ def run_pipeline(config_path: str) -> None:
         result = _resolve(cfg["module"], cfg.get("function", "run"))(config)
         if isinstance(result, str):
             outputs[stage] = result
+        if stage == "sample_collection" and "preprocess" in outputs:
+            # blocks the preprocess stage kept for this stage (pipeline.params.keep_resident): no later stage reads them
+            from .preprocess import handover
+            handover.release(outputs["preprocess"])
 
 
 if __name__ == "__main__":

@@ -34,13 +34,24 @@ _STEPS = ("downsample", "frequency_filter", "channel_zscore", "car_rereference",
           "zscore_rereference")
 
 
-def resolve_step_module(name: str):
-    """Import a step module by the name a config gives it.  ``preprocess.signal.X`` and ``preprocess.X``
-    (reference example_config.yaml:27,31,43) map onto this package; anything else is imported as is."""
+#: modules of the preprocess stage a reference config names from its own root (example_config.yaml:9,16,21)
+_STAGE_MODULES = ("preprocess.pipelines.subject_block", "preprocess.io.tdt_blocks", "preprocess.io.npz_blocks",
+                  "preprocess.preprocessor")
+
+
+def resolve_module(name: str):
+    """Import a module of the preprocess stage by the name a config gives it - the one resolver of the stage.  The step
+    names ``preprocess.signal.X`` and ``preprocess.X`` (reference example_config.yaml:27,31,43) and the pipeline, io and
+    preprocessor names of ``_STAGE_MODULES`` map onto this package; anything else is imported as is (plugin ABI)."""
     tail = name.rsplit(".", 1)[-1]
     if tail in _STEPS and (name.startswith("preprocess.") or name == tail):
         name = f"{_PKG}.signal.{tail}"
+    elif name in _STAGE_MODULES:
+        name = f"{_PKG}.{name.split('.', 1)[1]}"
     return importlib.import_module(name)
+
+
+resolve_step_module = resolve_module                   # the name the step dispatcher has always had
 
 
 # Steps of this package whose output row r depends on input row r only (they may stack band entries along the rows): these
@@ -186,9 +197,11 @@ def _plot_step(before, before_freq, after, after_freq, figure_dir, index, module
     import matplotlib
     matplotlib.use("Agg")
     import matplotlib.pyplot as plt
-    to_np = lambda a: a if isinstance(a, np.ndarray) else a.detach().cpu().numpy()
-    before, after = to_np(before), to_np(after)
     n = min(num_channels, before.shape[0], after.shape[0])
+    # only what is drawn crosses to the host: n channels, ``duration`` seconds - cut on the device, then copied
+    shown = lambda a, fs: a[:n, :max(1, min(a.shape[1], int(duration * fs)))]
+    to_np = lambda a: a if isinstance(a, np.ndarray) else a.detach().cpu().numpy()
+    before, after = to_np(shown(before, before_freq)), to_np(shown(after, after_freq))
     fig, axes = plt.subplots(n, 2, figsize=(10, 2 * n), squeeze=False)
     for c in range(n):
         for ax, arr, fs, title in ((axes[c][0], before, before_freq, "before"), (axes[c][1], after, after_freq, "after")):

@@ -22,6 +22,18 @@ def dict_to_namespace(d, exclude_keys=None):
     return d
 
 
+def namespace_to_dict(obj):
+    """The inverse of ``dict_to_namespace``: plain dicts and lists all the way down, so that ``yaml.dump`` writes a file
+    ``yaml.safe_load`` reads back (``vars(Namespace)`` keeps nested Namespaces, which dump as Python object tags)."""
+    if isinstance(obj, Namespace):
+        obj = vars(obj)
+    if isinstance(obj, dict):
+        return {k: namespace_to_dict(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return [namespace_to_dict(v) for v in obj]
+    return obj
+
+
 def update_configuration(output_path: str, previous_config_path: str, new_module: str, new_module_cfg: dict) -> None:
     if os.path.exists(previous_config_path):
         previous_cfg = load_config(previous_config_path)
