@@ -86,6 +86,14 @@ class ConvStack(LaunchTimers):
             self.stages.append(st)
             cin, tin, tp = cout, st.tout, st.tp_out
         self.gy4 = self._gy_applies()          # (fixed here: _alloc_bwd leaves out the gradient rows this path never stores)
+        # stage 3 on whole-sequence tiles (f63_seq16; TONAL_KERNELS f63_yprod=vd3 switches it off alone): where its valid conv rows fit 16 hexes but a sequence stores
+        # more (the reference shape: 96 rows, 17 hexes), its forward and input-gradient launches compute 16 hexes per sequence
+        # (compact-M mode of tl_conv3_wino63v_nt: a lane owns one sequence) and the input gradient runs on Y3, as stage 2's does on
+        # Y2 - Vd3 then has no reader: conv4's input gradient writes Y3 only, without halo rows or a fix-up pass.  The weight
+        # gradient keeps the stored geometry.
+        st3 = self.stages[1] if len(self.stages) >= 2 else None
+        self.f63_seq16 = bool(self.wino63 and self.f63_yprod and self.f63_yprod3 and self.gy4
+                              and _kernels.get("f63_yprod") == "1" and -(-st3.tc // 6) <= 16 < st3.tp_in // 6)
         self.lat = tin
         self.tp5 = tp
         self.ld5 = r4(conv_channels)
@@ -126,7 +134,8 @@ class ConvStack(LaunchTimers):
         self.Yt = {}           # F(6,3): Y = A dz of stage idx, written by the input gradient of the stage above (f63_yprod)
         self._y_ready = {}
         self.V = {}            # F(4,3) input transforms of P[idx] (quads, 6, channels) for the stages that read them
-        self.Vd = {}           # ... and of the un-pooled dZ of stage idx (the operand of its input-gradient pass)
+        self.Vd = {}           # ... and of the un-pooled dZ of stage idx (the operand of its input-gradient pass; stage 3 on
+                               # whole-sequence tiles reads Y3 instead: Vd[3] is then that tensor, no Vd3 exists)
         self._vd_ready = {}
         self.G = None          # gradient workspaces are allocated lazily on the first backward
         return True
@@ -243,10 +252,21 @@ class ConvStack(LaunchTimers):
         least 24: the weight-gradient kernel prefetches three 6-hex K-steps past the last one it uses)."""
         nh = rows // 6
         nh_pad = (nh + 24 + 127) // 128 * 128
+        if self.f63_seq16 and ((store is self.V and idx == 2) or (store is self.Yt and idx == 3)):
+            # the operands of stage 3's whole-sequence launches: every row tile reads 8 stored sequences (a last tile that
+            # holds fewer reads zero hexes); nothing more where the sequence count is a multiple of 8
+            nh_pad = max(nh_pad, (-(-self.S // 8) * 8 * (self.stages[1].tp_in // 6) + 127) // 128 * 128)
         V = store.get(idx)
         if V is None or V.shape[0] != nh_pad or V.shape[1] != 8 or V.shape[2] != cin:
             V = store[idx] = torch.zeros(nh_pad, 8, cin, dtype=torch.float32, device=self._dev)
         return V
+
+    def _vd3_buffer(self, rows, cin):
+        """Vd3 as a buffer of its own.  On whole-sequence tiles ``Vd[3]`` names Y3 - the operand stage 3's input gradient reads -
+        and no Vd3 is allocated; a producer that does write Vd3 (store_p1, the stand-alone tl_wino63_unpool_yvd) gets a real one."""
+        if self.Vd.get(3) is not None and self.Vd[3] is self.Yt.get(3):
+            del self.Vd[3]
+        return self._v_hex_buffer(self.Vd, 3, rows, cin)
 
     def _halo_buffer(self, key, ntm, cout):
         """The halo rows a V / Vd-writing epilogue leaves for its fix-up kernel: two per row tile."""
@@ -263,10 +283,16 @@ class ConvStack(LaunchTimers):
                                          self._stream()), "tl_wino63_weights")
         return dst
 
-    def f63_issue_factor(self, st) -> float:
+    def _seq16(self, st) -> bool:
+        """Stage ``st`` runs its forward and input gradient on whole-sequence tiles (f63_seq16; _v_hex_buffer sizes their operands)."""
+        return self.f63_seq16 and st.idx == 3
+
+    def f63_issue_factor(self, st, wgrad: bool = False) -> float:
         """MFMA FLOPs the F(6,3) kernels issue per direct-convolution FLOP of the stage (8 products per hex, hexes padded
-        to whole sequences, against 3 MACs per valid conv row)."""
-        return (st.tp_in // 6) * 8.0 / (st.tc * 3.0)
+        to whole sequences, against 3 MACs per valid conv row): of its forward / input-gradient launches, or (``wgrad``) of its
+        weight gradient, which always runs over the stored hexes."""
+        hexes = 16 if (not wgrad and self._seq16(st)) else st.tp_in // 6
+        return hexes * 8.0 / (st.tc * 3.0)
 
     def _stage_forward63(self, st, w, bia) -> None:
         S = self.S
@@ -293,6 +319,9 @@ class ConvStack(LaunchTimers):
             if Pout is None:
                 raise RuntimeError("F(6,3) stage 3 writes pooled rows: its output buffer was not allocated")
             kw.update(epilogue=EPI_POOL, out_tp=st.tp_out)
+            if self._seq16(st):
+                # 16 computed hexes per sequence: the pad rows of the output and their words are never written (zero from allocation)
+                kw.update(M=S * 96, Tp=96, a_hps_extra=st.tp_in // 6 - 16)
             self._nt(tag="conv3_fwd", fn="tl_conv3_wino63v_nt", **kw)
 
     def _stage_wgrad63(self, st, gw, gb) -> None:
@@ -311,7 +340,7 @@ class ConvStack(LaunchTimers):
             # (Y3, Vd3), and the weight gradient below runs without a transform like stage 2's
             Gs = self.G[3]
             Y3 = self._v_hex_buffer(self.Yt, 3, rows_in, nd)
-            Vd3 = self._v_hex_buffer(self.Vd, 3, rows_in, nd)
+            Vd3 = self._vd3_buffer(rows_in, nd)
             ev = self._tick("conv3_yvd")
             check(self.lib.tl_wino63_unpool_yvd(ptr(Gs), ptr(self.bits[3]), ptr(Y3), ptr(Vd3), rows_in, Gs.shape[0], st.tp_in,
                                                 st.tp_out, 2 * st.tout, nd, Gs.shape[1], st.cout // 32, nd, self._stream()),
@@ -385,16 +414,22 @@ class ConvStack(LaunchTimers):
         check(self.lib.tl_wino63_weights1(ptr(w), ptr(taps), st.cout, st.cin, st.cout, self._stream()), "tl_wino63_weights1")
         rows3 = S * below.tp_in                                  # conv rows of the stage below: six per hex of ITS geometry
         Y3 = self._v_hex_buffer(self.Yt, below.idx, rows3, below.cout)
-        Vd3 = self._v_hex_buffer(self.Vd, below.idx, rows3, below.cout)
+        # with stage 3's input gradient on Y3 (f63_seq16) Vd3 has no reader: Y only, no halo rows, no fix-up pass
+        # (store_p1 keeps it: Vd2 comes out of the Vd form of stage 3's input gradient alone)
+        y_only = self._seq16(below) and not self.store_p1
+        Vd3 = None if y_only else self._vd3_buffer(rows3, below.cout)
+        if y_only:
+            self.Vd[below.idx] = Y3                              # the operand of stage 3's input-gradient pass IS Y3 here
         ntm = -(-rows // self._nt63_rows())
-        halo = self._halo_buffer("d3", ntm, below.cout)
+        halo = None if y_only else self._halo_buffer("d3", ntm, below.cout)
         self._nt(tag=None, fn="tl_conv1_wino63v_dgrad_nt", A=ptr(A), A_rows=A.shape[0], lda=A.shape[2], loader=LOAD_V,
                  Bw=ptr(taps), M=rows, N=st.cin, K=st.cout, ldb=st.cout, ldo=st.cin, J=1, row_shift=0, Tp=tpg, slope=self.slope,
                  auxbits=ptr(self.sbits[below.idx]), ld_auxbits=self.sbits[below.idx].shape[1], abits=ptr(self.bits[below.idx]),
                  ld_abits=below.cout // 32, out_tp=below.tp_out, Tvalid_in=2 * below.tout, epilogue=EPI_GY, out=None,
                  vout=ptr(Y3), vout2=ptr(Vd3), vhalo=ptr(halo), vout_quads=Y3.shape[0], ld_vout=Y3.shape[2])
-        check(self.lib.tl_wino63_vd_fixup(ptr(Vd3), ptr(halo), rows // 3, ntm, below.tp_in // 6, below.cout, Vd3.shape[2],
-                                          self._stream()), "tl_wino63_vd_fixup")
+        if not y_only:
+            check(self.lib.tl_wino63_vd_fixup(ptr(Vd3), ptr(halo), rows // 3, ntm, below.tp_in // 6, below.cout, Vd3.shape[2],
+                                              self._stream()), "tl_wino63_vd_fixup")
         if ev:
             ev[1].record()
         self._y_ready[below.idx] = self.generation
@@ -404,13 +439,15 @@ class ConvStack(LaunchTimers):
     def _stage_dgrad63(self, st, w):
         S = self.S
         rows_in = S * st.tp_in
-        # _vd_ready[idx]: the operand of this pass is there - Vd of the stage, or (stage 2 with f63_yprod) Y2
+        # _vd_ready[idx]: the operand of this pass is there - Vd of the stage, or (stage 2 with f63_yprod; stage 3 with
+        # f63_seq16) its Y
         if self._vd_ready.get(st.idx) != self.generation:
             raise RuntimeError("F(6,3) input gradient: its operand (Vd from the stage's weight-gradient pass, or Y2 from the "
                                "input gradient of stage 3) must be written first")
         self._vd_ready[st.idx] = -1
-        on_y = st.idx == 2 and self.f63_yprod              # hex H of Y2 yields rows 6 H .. 6 H + 7 (tonal_wino63_epi.h)
-        Vd = self.Yt[2] if on_y else self.Vd[st.idx]
+        seq16 = self._seq16(st)
+        on_y = (st.idx == 2 and self.f63_yprod) or seq16   # hex H of Y yields rows 6 H .. 6 H + 7 (tonal_wino63_epi.h)
+        Vd = self.Yt[st.idx] if on_y else self.Vd[st.idx]
         if on_y:
             wd = torch.empty(8, st.cin, st.cout, dtype=torch.float32, device=w.device)
             check(self.lib.tl_wino63_weights_y(ptr(w), ptr(wd), st.cout, st.cin, st.cout, self._stream()), "tl_wino63_weights_y")
@@ -419,6 +456,29 @@ class ConvStack(LaunchTimers):
         kw = dict(A=ptr(Vd), A_rows=Vd.shape[0], lda=Vd.shape[2], loader=LOAD_V, Bw=ptr(wd), M=rows_in, N=st.cin,
                   K=st.cout, ldb=st.cout, ldo=st.cin, J=3, row_shift=0 if on_y else -2, Tp=st.tp_in, slope=self.slope,
                   auxbits=ptr(self.sbits[st.idx - 1]), ld_auxbits=self.sbits[st.idx - 1].shape[1])
+        if seq16:
+            # whole-sequence tiles on Y3: rows 0 .. 97 of a sequence's gradient from its 16 hexes, Y2 only (hexes 0 .. 32 of the 34)
+            below = self.stages[0]
+            Y2 = self._v_hex_buffer(self.Yt, 2, S * below.tp_in, below.cout)
+            kw.update(M=S * 96, Tp=96, a_hps_extra=st.tp_in // 6 - 16)
+            self._nt(tag="conv3_dgrad", fn="tl_conv3_wino63v_nt", epilogue=EPI_MASKY, out=None, vout=ptr(Y2), vout2=None, vhalo=None,
+                     vout_quads=Y2.shape[0], ld_vout=Y2.shape[2], abits=ptr(self.bits[2]), ld_abits=below.cout // 32,
+                     Tvalid_in=2 * below.tout, **kw)
+            if self.store_p1:
+                # (tests) Vd2 beside Y2: only the Vd form's epilogue writes it - that launch as well, its Y into a scratch buffer
+                Vd3, Vd2 = self.Vd[3], self._v_hex_buffer(self.Vd, 2, S * below.tp_in, below.cout)
+                ntm = -(-rows_in // self._nt63_rows())
+                halo = self._halo_buffer("d2", ntm, below.cout)
+                kw.update(A=ptr(Vd3), A_rows=Vd3.shape[0], lda=Vd3.shape[2], Bw=ptr(self._pack_wino63(w, False)), M=rows_in,
+                          Tp=st.tp_in, a_hps_extra=0, row_shift=-2)
+                self._nt(fn="tl_conv3_wino63v_nt", epilogue=EPI_MASKY, out=None, vout=ptr(torch.empty_like(Y2)), vout2=ptr(Vd2),
+                         vhalo=ptr(halo), vout_quads=Y2.shape[0], ld_vout=Y2.shape[2], abits=ptr(self.bits[2]),
+                         ld_abits=below.cout // 32, Tvalid_in=2 * below.tout, **kw)
+                check(self.lib.tl_wino63_vd_fixup(ptr(Vd2), ptr(halo), rows_in // 3, ntm, below.tp_in // 6, below.cout,
+                                                  Vd2.shape[2], self._stream()), "tl_wino63_vd_fixup")
+            self._y_ready[2] = self.generation
+            self._vd_ready[2] = self.generation
+            return None
         if st.idx == 3 and self.f63_yprod:
             below = self.stages[0]
             rows2 = S * below.tp_in                              # conv rows of stage 2: six per hex = three of this GEMM's rows
@@ -509,7 +569,7 @@ class ConvStack(LaunchTimers):
     def wgrad_issue_factor(self, st) -> float:
         """MFMA FLOPs the weight-gradient kernel of a stage issues per direct-convolution FLOP."""
         if self._f63(st):
-            return self.f63_issue_factor(st)
+            return self.f63_issue_factor(st, wgrad=True)
         return 0.5 if self._v43(st) else 1.0
 
     def kernel_families(self):
@@ -519,27 +579,36 @@ class ConvStack(LaunchTimers):
             self._fam_share = {}
             st2, st3 = self.stages[0], self.stages[1]
             f6 = "Winograd F(6,3) on pre-transformed operands, LDS-DMA"
+            seq16 = self._seq16(st3)
+            s16 = f"; 16 of the {st3.tp_in // 6} stored hexes per sequence" if seq16 else ""
             tn = "wino63v_tn4_kernel<true>" if st3.cin % 256 == 0 and st3.tp_in >= 12 else "wino63v_tn_kernel<true>"
             tn2 = "wino63v_tn4_kernel<true>" if st2.cin % 256 == 0 else "wino63v_tn_kernel<true>"
             fams = {f"wino63v_nt_kernel<POOLV> (conv2 forward, {f6}; writes V of its pooled output for conv3)": ["conv2_fwd"],
-                    f"wino63v_nt_kernel<POOL> (conv3 forward, {f6})": ["conv3_fwd"],
+                    f"wino63v_nt_kernel<POOL> (conv3 forward, {f6}{s16})": ["conv3_fwd"],
                     f"wino63v_nt_kernel<C1WGRAD> (conv2 input gradient + conv1 weight gradient, {f6})": ["conv2_dgrad"],
                     }
             if self.f63_yprod3:
                 gy = self.gy4
                 src = "the epilogue of conv4's input gradient" if gy else "wino63_unpool_yvd_kernel"
-                fams[f"wino63v_tn4y_kernel (conv3 weight gradient, {f6}: both operands by LDS-DMA, no transform in the kernel; Y3 / Vd3 "
+                ops = "Y3" if seq16 else "Y3 / Vd3"
+                fams[f"wino63v_tn4y_kernel (conv3 weight gradient, {f6}: both operands by LDS-DMA, no transform in the kernel; {ops} "
                      f"from {src})"] = ["conv3_wgrad"]
             else:
                 fams[f"{tn} (conv3 weight gradient, {f6}; also writes Vd)"] = ["conv3_wgrad"]
-            if self.f63_yprod:
+            if seq16:
+                fams[f"wino63v_nt_kernel<MASKY_SEQ> (conv3 input gradient on Y3, {f6}{s16}; writes Y of conv2 instead of the gradient "
+                     "rows)"] = ["conv3_dgrad"]
+                fams[f"wino63v_tn4y_kernel (conv2 weight gradient, {f6}: both operands by LDS-DMA, no transform in the kernel)"] = ["conv2_wgrad"]
+            elif self.f63_yprod:
                 both = "Y and Vd" if self.store_p1 else "Y"
                 fams[f"wino63v_nt_kernel<MASKY> (conv3 input gradient, {f6}; writes {both} of conv2 instead of the gradient rows)"] = ["conv3_dgrad"]
                 fams[f"wino63v_tn4y_kernel (conv2 weight gradient, {f6}: both operands by LDS-DMA, no transform in the kernel)"] = ["conv2_wgrad"]
             else:
                 fams[f"wino63v_nt_kernel<MASK> (conv3 input gradient, {f6})"] = ["conv3_dgrad"]
                 fams[f"{tn2} (conv2 weight gradient, {f6}; also writes Vd)"] = ["conv2_wgrad"]
-            issued = {k: self.f63_issue_factor(st2 if "conv2" in k else st3) for k in fams}
+            # (by the launch's timer tag: the labels name their neighbours too)
+            issued = {k: self.f63_issue_factor(st2 if tags[0].startswith("conv2") else st3, wgrad=tags[0].endswith("_wgrad"))
+                      for k, tags in fams.items()}
             return fams, issued
         self._fam_share = {}         # family -> share of its stages' algorithmic FLOPs it computes (default 1)
         if not all(self._v43(st) for st in self.stages[:2]):

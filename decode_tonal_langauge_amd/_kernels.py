@@ -35,9 +35,12 @@ KEYS: Dict[str, Tuple[str, _Allowed, str, str]] = {
     "wino": ("TONAL_WINO", frozenset({"6", "4", "0"}), "6",
              "conv2 / conv3: 6 Winograd F(6,3) on pre-transformed operands (F(4,3) V form where the stack does not allow it), "
              "4 the F(4,3) V form, 0 direct MFMA kernels (also the fallback for every shape neither form covers)"),
-    "f63_yprod": ("TONAL_F63_YPROD", _B, "1", "F(6,3): the backward operands of stages 2 and 3 (Y2 for both passes of stage 2; Y3 / Vd3) come "
-                                              "pre-transformed out of the input-gradient epilogue of the stage above (0: the weight-gradient "
-                                              "kernels un-pool and transform the gradient rows themselves and write Vd)"),
+    "f63_yprod": ("TONAL_F63_YPROD", frozenset({"0", "1", "vd3"}), "1",
+                  "F(6,3): the backward operands of stages 2 and 3 (Y2 for both passes of stage 2; Y3) come pre-transformed out of the "
+                  "input-gradient epilogue of the stage above; where conv3's valid rows fit 16 hexes of a longer stored sequence, its "
+                  "forward and input gradient run on whole-sequence tiles (16 hexes computed), the input gradient on Y3 (vd3: conv3 "
+                  "keeps the stored geometry and its input gradient runs on Vd3, which conv4's input gradient writes beside Y3; 0: the "
+                  "weight-gradient kernels un-pool and transform the gradient rows themselves and write Vd)"),
     "conv4_dgrad": ("TONAL_CONV4_DGRAD", frozenset({"nt63", "gemm"}), "nt63",
                     "F(6,3): the one-tap stage behind conv3 - nt63: its input gradient on the NT63 kernel, writing Y3 / Vd3 "
                     "(no gradient rows, no tl_wino63_unpool_yvd); gemm: one-tap GEMM + tl_wino63_unpool_yvd"),

@@ -32,7 +32,7 @@ class NtParams(C.Structure):
         ("slope", C.c_float),
         ("loader", C.c_int), ("epilogue", C.c_int),
         ("splitk", C.c_int), ("slab_stride", C.c_int64),
-        ("bm", C.c_int),
+        ("bm", C.c_int), ("a_hps_extra", C.c_int),
         ("osign", C.c_void_p), ("auxbits", C.c_void_p), ("ld_auxbits", C.c_int),
         ("c1x", C.c_void_p), ("c1bits", C.c_void_p), ("c1partial", C.c_void_p), ("c1T", C.c_int), ("c1kt", C.c_int),
         ("vout", C.c_void_p), ("vhalo", C.c_void_p), ("vout_quads", C.c_int64), ("ld_vout", C.c_int),

@@ -302,7 +302,7 @@ __global__ __launch_bounds__(512, 2) void wino63v_nt_kernel(const tl_nt_params p
   constexpr bool SEG3 = EPI == W_EPI_LRELU || EPI == W6_EPI_MASK7 || EPI == W6_EPI_MASK7F;
   // EPI == GY (tl_conv1_wino63v_dgrad_nt): transforms 6, 7 of both operands are zero - the six-batch K loop (V6K6_*: half-set H =
   // transforms 4, 5; 24 MFMAs per K-step), and waves 6, 7 fetch through empty resources (their planes are never read)
-  constexpr bool SIX = EPI == W_EPI_GY;
+  constexpr bool SIX = EPI == W_EPI_GY || EPI == W6_EPI_GY_Y;
   const int kseg = p.K / V6_BK;                            // K-steps per segment (host-checked: K % 8 == 0)
   const int nsteps = SEG3 ? 3 * kseg : kseg;               // host-checked: >= 5
   // Accumulators and fragments live in FIXED registers (tonal_wino63_kloop.h: v0 - v127, v128 - v191): every K-step is one asm
@@ -325,9 +325,16 @@ __global__ __launch_bounds__(512, 2) void wino63v_nt_kernel(const tl_nt_params p
   const int hex_of_row = (prow & 3) | ((prow >> 3) << 2) | (((prow >> 2) & 1) << 4);
   // sources: V in the pair layout (K-step s = its 8-channel chunk s: + 512 B), taps chunk-major (+ 256 N bytes per step)
   const int kc8 = p.lda >> 3;
+  // compact-M mode (tl_nt_params.a_hps_extra = x > 0; host-checked: 16 computed hexes per sequence): V stores 16 + x hexes per
+  // sequence, hex c of a tile lies at storage hex c + (c / 16) x - a per-lane constant like the offsets themselves - and a
+  // tile (eight sequences) starts 8 (16 + x) hexes behind the one before.  x = 0: the offsets and the tile step as they were.
+  const int hx = p.a_hps_extra;
   unsigned avoff[4], bv_lane[2];
 #pragma unroll
-  for (int t = 0; t < 4; ++t) avoff[t] = (unsigned)(v6_at(t * 32 + hex_of_row, wave, src_chunk * 4, kc8) * 4);
+  for (int t = 0; t < 4; ++t) {
+    const int c = t * 32 + hex_of_row;
+    avoff[t] = (unsigned)(v6_at(c + (c >> 4) * hx, wave, src_chunk * 4, kc8) * 4);
+  }
   unsigned avoff1[4];                                      // the same pieces one hex on (SEG3, third segment)
 #pragma unroll
   for (int t = 0; t < 4; ++t) avoff1[t] = SEG3 ? (unsigned)(v6_at(t * 32 + hex_of_row + 1, wave, src_chunk * 4, kc8) * 4) : avoff[t];
@@ -343,7 +350,7 @@ __global__ __launch_bounds__(512, 2) void wino63v_nt_kernel(const tl_nt_params p
     v6_i32x4 rsA, rsA1;
     unsigned bvoff[2];
   };
-  const long long a_tile_bytes = (long long)V6_BH * 8 * p.lda * 4, a_total_bytes = p.A_rows * 8LL * p.lda * 4;
+  const long long a_tile_bytes = (long long)(V6_BH + 8 * hx) * 8 * p.lda * 4, a_total_bytes = p.A_rows * 8LL * p.lda * 4;
   auto place = [&](tile_t& t, long long tm, int tn) {
     t.tm = tm;
     t.R0 = tm * V6_ROWS;
@@ -435,6 +442,7 @@ __global__ __launch_bounds__(512, 2) void wino63v_nt_kernel(const tl_nt_params p
   // M0 initialisation the compiler makes for a consumer of its own is never assumed to survive one of them;
   // clang remarks that M0 is a reserved register - the clobber is recorded all the same and the generated code is unchanged,
   // profiles/r05_kernel_resources.md - hence the diagnostic pragma)
+#pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"
 #define V6K_STMT_R(REGS, TEXT, tl_, step, dst, wimm)                                                                     \
   do {                                                                                                                   \
@@ -470,7 +478,8 @@ __global__ __launch_bounds__(512, 2) void wino63v_nt_kernel(const tl_nt_params p
       else if constexpr (EPI == W_EPI_MASK || EPI == W6_EPI_MASK7) return v6_prefetch_mask(p, cur.R0, cur.n0, wm, wn, lr, lh);
       else if constexpr (EPI == W6_EPI_MASK7F) return v6_pre_mask{{0u, 0u, 0u}};      // (float rows: read by the epilogue itself)
       else if constexpr (EPI == W_EPI_MASKY || EPI == W6_EPI_MASKY_Y) return v6_prefetch_masky(p, cur.R0, cur.n0, wm, wn, lr, lh);
-      else if constexpr (EPI == W_EPI_GY) return v6_prefetch_masky<true>(p, cur.R0, cur.n0, wm, wn, lr, lh);
+      else if constexpr (EPI == W_EPI_GY || EPI == W6_EPI_GY_Y) return v6_prefetch_masky<true>(p, cur.R0, cur.n0, wm, wn, lr, lh);
+      else if constexpr (EPI == W6_EPI_MASKY_SEQ) return v6_prefetch_masky_seq(p, cur.tm, cur.n0, wm, wn, lr, lh);
       else return v6_prefetch_c1w(p, cur.R0, cur.n0, wm, wn, lr, lh);
     };
     decltype(prefetch()) pre;
@@ -550,6 +559,12 @@ __global__ __launch_bounds__(512, 2) void wino63v_nt_kernel(const tl_nt_params p
       float* xch = reinterpret_cast<float*>(lds + 3 * V6_STAGE);
       if (full) v6_epilogue_masky<true, true>(p, acc, pre, xch, done.R0, done.n0, wm, wn, lr, lh, done.tm);
       else v6_epilogue_masky<false, true>(p, acc, pre, xch, done.R0, done.n0, wm, wn, lr, lh, done.tm);
+    } else if constexpr (EPI == W6_EPI_GY_Y) {
+      if (full) v6_epilogue_masky<true, true, false>(p, acc, pre, nullptr, done.R0, done.n0, wm, wn, lr, lh, done.tm);
+      else v6_epilogue_masky<false, true, false>(p, acc, pre, nullptr, done.R0, done.n0, wm, wn, lr, lh, done.tm);
+    } else if constexpr (EPI == W6_EPI_MASKY_SEQ) {
+      if (full) v6_epilogue_masky_seq<true>(p, acc, pre, done.n0, wm, wn, lr, lh, done.tm);
+      else v6_epilogue_masky_seq<false>(p, acc, pre, done.n0, wm, wn, lr, lh, done.tm);
     } else {
       v6_epilogue_c1w<EPI == W6_EPI_C1W_Y>(p, acc, pre, reinterpret_cast<float*>(lds + 3 * V6_STAGE) + wave * 512, scratch, done.R0,
                                            done.n0, wm, wn, lr, lh, done.tm);
@@ -561,6 +576,7 @@ __global__ __launch_bounds__(512, 2) void wino63v_nt_kernel(const tl_nt_params p
       __builtin_amdgcn_s_waitcnt((n & 15) | (7 << 4) | (15 << 8) | ((n >> 4) << 14));
     }
   }
+#pragma clang diagnostic pop
 }
 
 
@@ -1907,6 +1923,7 @@ extern "C" int tl_conv7_wino63v_nt(const tl_nt_params* pp, void* stream) {
   const long long nwg = ntm * ((p.N + V6_BN - 1) / V6_BN);
   TL_REQUIRE(nwg < (1LL << 31), "conv7_wino63: grid too large");
   TL_REQUIRE(p.A_rows >= ntm * V6_BH, "conv7_wino63: V0 / V1 must hold whole 128-hex tiles (pad them with zero hexes)");
+  TL_REQUIRE(p.a_hps_extra == 0, "conv7_wino63: no compact-M mode (a_hps_extra must be 0)");
   const long long ngrid = nwg < 256 ? nwg : 256;
   hipLaunchKernelGGL((wino63v_nt_kernel<W_EPI_LRELU>), dim3((unsigned)ngrid), dim3(512), 0, (hipStream_t)stream, p);
   return check_launch("conv7_wino63");
@@ -1936,6 +1953,7 @@ extern "C" int tl_conv7_wino63v_dgrad_nt(const tl_nt_params* pp, void* stream) {
   const long long nwg = ntm * ((p.N + V6_BN - 1) / V6_BN);
   TL_REQUIRE(nwg < (1LL << 31), "conv7_wino63_dgrad: grid too large");
   TL_REQUIRE(p.A_rows >= ntm * V6_BH, "conv7_wino63_dgrad: V0 / V1 must hold whole 128-hex tiles (pad them with zero hexes)");
+  TL_REQUIRE(p.a_hps_extra == 0, "conv7_wino63_dgrad: no compact-M mode (a_hps_extra must be 0)");
   const long long ngrid = nwg < 256 ? nwg : 256;
   if (p.auxbits != nullptr) hipLaunchKernelGGL((wino63v_nt_kernel<W6_EPI_MASK7>), dim3((unsigned)ngrid), dim3(512), 0, (hipStream_t)stream, p);
   else hipLaunchKernelGGL((wino63v_nt_kernel<W6_EPI_MASK7F>), dim3((unsigned)ngrid), dim3(512), 0, (hipStream_t)stream, p);
@@ -1967,7 +1985,18 @@ extern "C" int tl_conv3_wino63v_nt(const tl_nt_params* pp, void* stream) {
   TL_REQUIRE(nwg < (1LL << 31), "wino63v_nt: grid too large");
   TL_REQUIRE(p.N % 32 == 0 && p.M + V6_ROWS < (1LL << 31), "wino63v_nt: N %% 32 == 0 and M < 2^31 - 768 needed");
   TL_REQUIRE(p.slope >= 0.f && p.slope <= 1.f, "wino63v_nt: LeakyReLU slope must lie in [0, 1]");
-  TL_REQUIRE(p.A_rows >= ntm * V6_BH, "wino63v_nt: V must hold whole 128-hex tiles (pad it with zero hexes)");
+  if (p.a_hps_extra != 0) {
+    // compact-M mode: M / Tp / Tvalid are the computed geometry, V stores a_hps_extra more hexes per sequence
+    TL_REQUIRE(p.a_hps_extra > 0 && p.a_hps_extra <= 16, "wino63v_nt: compact M: a_hps_extra must lie in [0, 16]");
+    TL_REQUIRE(p.epilogue == W_EPI_POOL || p.epilogue == W_EPI_MASKY, "wino63v_nt: compact M: POOL epilogue or epilogue 6 only");
+    TL_REQUIRE(V6_BH % (p.Tp / 6) == 0, "wino63v_nt: compact M: tiles must start on sequence boundaries (128 %% (Tp / 6) == 0)");
+    TL_REQUIRE(p.Tp == 96, "wino63v_nt: compact M: 16 computed hexes per sequence (Tp == 96) needed - a lane owns one sequence");
+    TL_REQUIRE((128LL + 8 * p.a_hps_extra) * 8 * p.lda * 4 + 4LL * p.K < (1LL << 31), "wino63v_nt: compact M: tile span too large");
+    TL_REQUIRE(p.A_rows >= ntm * 8 * (16 + p.a_hps_extra),
+               "wino63v_nt: compact M: V must hold 8 (16 + a_hps_extra) hexes for every tile (pad it with zero hexes)");
+  } else {
+    TL_REQUIRE(p.A_rows >= ntm * V6_BH, "wino63v_nt: V must hold whole 128-hex tiles (pad it with zero hexes)");
+  }
   hipStream_t st = (hipStream_t)stream;
   const long long ngrid = nwg < 256 ? nwg : 256;          // one workgroup per CU (144 - 160 KB of LDS each)
   if (p.epilogue == W_EPI_POOL) {
@@ -1990,6 +2019,18 @@ extern "C" int tl_conv3_wino63v_nt(const tl_nt_params* pp, void* stream) {
     TL_REQUIRE(p.row_shift == -2 && p.ldo >= p.N, "wino63v_nt: input gradient needs row_shift -2");
     TL_REQUIRE(p.auxbits != nullptr, "wino63v_nt: MASK needs auxbits (the sign bits of the stage input)");
     hipLaunchKernelGGL((wino63v_nt_kernel<W_EPI_MASK>), dim3((unsigned)ngrid), dim3(512), 0, st, p);
+  } else if (p.epilogue == W_EPI_MASKY && p.a_hps_extra != 0) {
+    // whole-sequence tiles: the operand is Y of the stage (row_shift 0, taps of tl_wino63_weights_y), Y of the stage below is all
+    // that is written; the bit arrays and vout count 6 / 2 (16 + a_hps_extra) rows / hexes per sequence
+    const long long hps2 = 2LL * (16 + p.a_hps_extra);
+    TL_REQUIRE(p.row_shift == 0 && p.auxbits != nullptr && p.abits != nullptr, "wino63v_nt: epilogue 6, compact M: needs row_shift 0 (operand Y), auxbits and abits");
+    TL_REQUIRE(p.ld_abits * 32 >= p.N && p.ld_auxbits * 32 >= p.N && p.Tvalid_in >= 0 && p.Tvalid_in % 2 == 0 && p.Tvalid_in <= 2 * (p.Tp + 2),
+               "wino63v_nt: epilogue 6, compact M: bad abits / auxbits / Tvalid_in (at most 2 (Tp + 2))");
+    TL_REQUIRE(p.vout && p.ld_vout >= p.N && p.ld_vout % 8 == 0 && p.vout_quads >= (p.M / p.Tp) * hps2 && p.vout_quads % 2 == 0,
+               "wino63v_nt: epilogue 6, compact M: needs vout (>= 2 (16 + a_hps_extra) hexes per sequence, whole pairs, ld_vout %% 8 == 0)");
+    TL_REQUIRE(p.vout2 == nullptr && p.vhalo == nullptr, "wino63v_nt: epilogue 6, compact M: writes Y only (no vout2 / vhalo)");
+    TL_REQUIRE(128LL * 8 * p.ld_vout * 4 < (1LL << 31), "wino63v_nt: ld_vout too large");
+    hipLaunchKernelGGL((wino63v_nt_kernel<W6_EPI_MASKY_SEQ>), dim3((unsigned)ngrid), dim3(512), 0, st, p);
   } else if (p.epilogue == W_EPI_MASKY) {
     TL_REQUIRE(p.row_shift == -2 && p.auxbits != nullptr && p.abits != nullptr, "wino63v_nt: epilogue 6 needs row_shift -2, auxbits and abits");
     TL_REQUIRE(p.ld_abits * 32 >= p.N && p.Tvalid_in % 2 == 0 && p.Tvalid_in <= 2 * p.Tp, "wino63v_nt: epilogue 6: bad abits / Tvalid_in");
@@ -2061,14 +2102,18 @@ extern "C" int tl_conv1_wino63v_dgrad_nt(const tl_nt_params* pp, void* stream) {
   TL_REQUIRE(p.N % 32 == 0 && p.M + V6_ROWS < (1LL << 31), "conv1_wino63v_dgrad_nt: N %% 32 == 0 and M < 2^31 - 768 needed");
   TL_REQUIRE(p.slope >= 0.f && p.slope <= 1.f, "conv1_wino63v_dgrad_nt: LeakyReLU slope must lie in [0, 1]");
   TL_REQUIRE(p.A_rows >= ntm * V6_BH, "conv1_wino63v_dgrad_nt: A must hold whole 128-hex tiles (pad it with zero hexes)");
+  TL_REQUIRE(p.a_hps_extra == 0, "conv1_wino63v_dgrad_nt: no compact-M mode (a_hps_extra must be 0)");
   TL_REQUIRE(p.auxbits != nullptr && p.abits != nullptr, "conv1_wino63v_dgrad_nt: needs auxbits (sign) and abits (arg-max) of the stage below");
   TL_REQUIRE(p.out_tp > 0 && p.out_tp <= p.Tp && 2 * p.out_tp >= p.Tvalid_in, "conv1_wino63v_dgrad_nt: out_tp = rows per sequence of the bit arrays (0 < out_tp <= Tp, covering Tvalid_in / 2)");
   TL_REQUIRE(p.ld_abits * 32 >= p.N && p.ld_auxbits * 32 >= p.N && p.Tvalid_in % 2 == 0 && p.Tvalid_in <= 2 * p.Tp, "conv1_wino63v_dgrad_nt: bad abits / auxbits / Tvalid_in");
-  TL_REQUIRE(p.vout && p.vout2 && p.vhalo && p.ld_vout >= p.N && p.ld_vout % 8 == 0 && p.vout_quads >= p.M / 3 && p.vout_quads % 2 == 0,
-             "conv1_wino63v_dgrad_nt: needs vout / vout2 (>= M / 3 hexes, whole pairs, ld_vout %% 8 == 0) and vhalo");
+  TL_REQUIRE(p.vout && p.ld_vout >= p.N && p.ld_vout % 8 == 0 && p.vout_quads >= p.M / 3 && p.vout_quads % 2 == 0,
+             "conv1_wino63v_dgrad_nt: needs vout (>= M / 3 hexes, whole pairs, ld_vout %% 8 == 0)");
+  TL_REQUIRE((p.vout2 == nullptr) == (p.vhalo == nullptr),
+             "conv1_wino63v_dgrad_nt: takes vout2 and vhalo together (Y and Vd) or neither (Y only: the stage below runs its input gradient on Y)");
   TL_REQUIRE(128LL * 8 * p.ld_vout * 4 < (1LL << 31), "conv1_wino63v_dgrad_nt: ld_vout too large");
   const long long ngrid = nwg < 256 ? nwg : 256;
-  hipLaunchKernelGGL((wino63v_nt_kernel<W_EPI_GY>), dim3((unsigned)ngrid), dim3(512), 0, (hipStream_t)stream, p);
+  if (p.vout2 != nullptr) hipLaunchKernelGGL((wino63v_nt_kernel<W_EPI_GY>), dim3((unsigned)ngrid), dim3(512), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL((wino63v_nt_kernel<W6_EPI_GY_Y>), dim3((unsigned)ngrid), dim3(512), 0, (hipStream_t)stream, p);
   return check_launch("conv1_wino63v_dgrad_nt");
 }
 

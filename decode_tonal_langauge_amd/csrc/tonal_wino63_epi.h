@@ -17,7 +17,9 @@ namespace tl {
 // the parameters have: epilogue 6 without vout2 / vhalo (Y only, no Vd), epilogue 4 with row_shift 0 (the operand is Y, not Vd)
 // (10, 11: the MASK epilogue behind the three-segment K loop of a 7-tap convolution, tl_conv7_wino63v_dgrad_nt - the mask from
 // the sign words auxbits / from the float rows `mask`)
-enum { W6_EPI_MASKY_Y = 8, W6_EPI_C1W_Y = 9, W6_EPI_MASK7 = 10, W6_EPI_MASK7F = 11 };
+// (12: epilogue 6 in compact-M mode - the operand is Y of the stage on whole-sequence tiles, v6_epilogue_masky_seq; 13: epilogue 7
+// without vout2 / vhalo - Y only)
+enum { W6_EPI_MASKY_Y = 8, W6_EPI_C1W_Y = 9, W6_EPI_MASK7 = 10, W6_EPI_MASK7F = 11, W6_EPI_MASKY_SEQ = 12, W6_EPI_GY_Y = 13 };
 
 constexpr unsigned V6_DROP = 0x80000000u;     // added to any in-range byte offset (< 2^31) it stays past every resource
 constexpr unsigned long long V6_HI = 0xffffffff00000000ull;
@@ -371,7 +373,7 @@ template <int EPI>
 constexpr int v6_stores() {
   return EPI == W_EPI_POOL ? 52 : EPI == W_EPI_POOLV ? 70
          : (EPI == W_EPI_MASK || EPI == W_EPI_LRELU || EPI == W6_EPI_MASK7 || EPI == W6_EPI_MASK7F) ? 96
-         : (EPI == W_EPI_MASKY || EPI == W6_EPI_MASKY_Y || EPI == W_EPI_GY) ? 63 : 0;
+         : (EPI == W_EPI_MASKY || EPI == W6_EPI_MASKY_Y || EPI == W_EPI_GY || EPI == W6_EPI_MASKY_SEQ || EPI == W6_EPI_GY_Y) ? 63 : 0;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -684,6 +686,128 @@ __device__ __forceinline__ void v6_epilogue_masky(const tl_nt_params& p, const f
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, po), rsH, ho, (unsigned)p.N * 4u, 0);
   }
   }  // VD
+}
+
+// ------------------------------------------------------------------------------------------
+// Epilogue 6 on whole-sequence tiles (W6_EPI_MASKY_SEQ): the input gradient of a stage taken from ITS Y (row_shift 0, taps of
+// tl_wino63_weights_y, as v6_epilogue_c1w<true> does for the stage below) in the compact-M mode of the kernel - 16 computed
+// hexes per sequence (p.Tp = 96), so a lane half owns exactly ONE sequence: wave-tile half (wm, lh) of tile tm is sequence
+// 8 tm + 2 wm + lh.  Hex e yields the EIGHT gradient rows 6 e .. 6 e + 7 = B m (wino63_b); rows 6, 7 are rows 0, 1 of hex e + 1 of
+// the same lane: the carry never leaves the lane (no exchange, no barrier, no halo rows, no fix-up pass).  The two rows left
+// behind the 16th element are rows 96, 97 of the sequence: hex 32 of the stage below.  That stage stores
+// hps2 = 2 (16 + p.a_hps_extra) hexes per sequence (34), so every destination is affine: the wave's Y starts at hex
+// hps2 (8 tm + 2 wm), the second lane half's pairs hps2 / 2 pairs on, element e is pair e, rows 96, 97 pair 16 - whose second hex
+// is written as zeros (no valid row reaches it: Tvalid_in / 2 <= 98, host-checked).  Writes Y only (Y = A dz of the stage below,
+// dz = the rows un-pooled with abits and zeroed from Tvalid_in conv rows on); the bit arrays keep 6 (16 + a_hps_extra) rows per
+// sequence, the geometry of the stage below.
+// ------------------------------------------------------------------------------------------
+struct v6_pre_masky_seq {
+  uint32_t s[4], a[4];         // sign / arg-max words of the sequence's rows lr, 32 + lr, 64 + lr, 96 + lr (the last: lr < 2)
+};
+__device__ __forceinline__ v6_pre_masky_seq v6_prefetch_masky_seq(const tl_nt_params& p, long long tm, int n0, int wm, int wn, int lr,
+                                                                  int lh) {
+  const int colbase = n0 + wn * 32;
+  const long long seq = tm * 8 + wm * 2 + lh, nseq = p.M / p.Tp;
+  const int tps = p.Tp + 6 * p.a_hps_extra;                 // rows per sequence of the bit arrays
+  v6_pre_masky_seq r;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    r.s[k] = r.a[k] = 0u;
+    const int t = lr + 32 * k;
+    if (colbase < p.N && seq < nseq && t < p.Tp + 2) {
+      const long long row = seq * tps + t;
+      r.s[k] = p.auxbits[row * (long long)p.ld_auxbits + (colbase >> 5)];
+      r.a[k] = p.abits[row * (long long)p.ld_abits + (colbase >> 5)];
+    }
+  }
+  return r;
+}
+template <bool FULL>
+__device__ __forceinline__ void v6_epilogue_masky_seq(const tl_nt_params& p, const f32x16 (&acc)[8], const v6_pre_masky_seq& pre, int n0,
+                                                      int wm, int wn, int lr_in, int lh, long long tm) {
+  int lr = lr_in;                                           // (opaque copy: see v6_epilogue_c1w)
+  asm volatile("" : "+v"(lr));
+  const int colbase = n0 + wn * 32;
+  const bool colok = colbase < p.N;
+  const long long seq0 = tm * 8 + wm * 2, nseq = p.M / p.Tp;   // lane half lh owns sequence seq0 + lh
+  const int hps2 = 2 * (16 + p.a_hps_extra);                // hexes of the stage below per sequence
+  const int vt = p.Tvalid_in >> 1;                          // gradient rows of a sequence that count (host-checked: <= 98)
+  // per row a bit of a word this lane holds (v6_epilogue_masky): we / wo = the row counts and its arg-max bit is clear / set
+  uint32_t we[4], wo[4], sT[4];
+  {
+    const bool sok = seq0 + lh < nseq;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int n = vt - 32 * k;
+      const uint32_t okw = (!sok || n <= 0) ? 0u : (n >= 32 ? ~0u : (1u << n) - 1u);
+      sT[k] = bit_transpose32(pre.s[k], lr);
+      const uint32_t aT = bit_transpose32(pre.a[k], lr);
+      we[k] = okw & ~aT;
+      wo[k] = okw & aT;
+    }
+  }
+  const long long Hb = seq0 * hps2;                         // first hex (of the stage below) of the wave
+  const unsigned pair4 = (unsigned)p.ld_vout * 64u;        // bytes per hex pair (pair layout, tonal_wino63.hip)
+  const __amdgpu_buffer_rsrc_t rsY = rsrc_of(p.vout + Hb * 8 * (long long)p.ld_vout, (p.vout_quads - Hb) * 8 * (long long)p.ld_vout * 4);
+  // after v6_pair_swap all 64 lanes of the first register pair carry lane-half 0's sequence, of the second lane-half 1's
+  // (a dropped store carries V6_DROP: only where !FULL, and then no immediate is added to it - v6_store_at)
+  const unsigned offP = v6_pair_offset(colbase, lr, lh);
+  const unsigned vvA = (colok && (FULL || seq0 < nseq)) ? offP : V6_DROP;
+  const unsigned vvB = (colok && (FULL || seq0 + 1 < nseq)) ? (unsigned)(hps2 >> 1) * pair4 + offP : V6_DROP;
+  auto andf = [](float x, uint32_t m) { return __uint_as_float(__float_as_uint(x) & m); };
+  // Y = A dz of one hex of the stage below (the arithmetic of v6_epilogue_masky, wino63_unpool_yvd_kernel)
+  auto ydz = [](const float* d6, float (&Y)[8]) {
+    const float ev1 = (d6[0] + d6[2]) + d6[4], od1 = (d6[1] + d6[3]) + d6[5];
+    const float ev2 = fmaf(16.f, d6[4], fmaf(4.f, d6[2], d6[0])), od2 = fmaf(32.f, d6[5], fmaf(8.f, d6[3], 2.f * d6[1]));
+    const float ev3 = fmaf(0.0625f, d6[4], fmaf(0.25f, d6[2], d6[0])), od3 = fmaf(0.03125f, d6[5], fmaf(0.125f, d6[3], 0.5f * d6[1]));
+    Y[0] = d6[0];
+    Y[1] = ev1 + od1;
+    Y[2] = ev1 - od1;
+    Y[3] = ev2 + od2;
+    Y[4] = ev2 - od2;
+    Y[5] = ev3 + od3;
+    Y[6] = ev3 - od3;
+    Y[7] = d6[5];
+  };
+  // gradient row r of the sequence (a compile-time index after unrolling), un-pooled: the two conv rows of the stage below
+  auto unpool = [&](float g, int r, float& ze, float& zo) {
+    const float t = g * selbit(sT[r >> 5], r & 31, 1.f, p.slope);
+    ze = andf(t, (uint32_t)__builtin_amdgcn_sbfe((int)we[r >> 5], r & 31, 1));
+    zo = andf(t, (uint32_t)__builtin_amdgcn_sbfe((int)wo[r >> 5], r & 31, 1));
+  };
+  float c6 = 0.f, c7 = 0.f;                                 // rows 6, 7 of the hex in front (none in front of element 0)
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    float m[8], d[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) m[i] = acc[i][e];
+    wino63_b(m, d);
+    if (e > 0) {
+      d[0] += c6;
+      d[1] += c7;
+    }
+    c6 = d[6];
+    c7 = d[7];
+    float dzr[12];                                          // the six gradient rows of accumulator element e, un-pooled
+#pragma unroll
+    for (int h = 0; h < 6; ++h) unpool(d[h], 6 * e + h, dzr[2 * h], dzr[2 * h + 1]);
+    float Yp[2][8];                                         // hexes 2 e, 2 e + 1 of the sequence: pair e
+    ydz(dzr, Yp[0]);
+    ydz(dzr + 6, Yp[1]);
+    v6_store_hex_pair<FULL>(Yp[0], Yp[1], rsY, vvA, vvA + 1024u, vvB, vvB + 1024u, (unsigned)e * pair4);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  {
+    // rows 96, 97: hex 32 of the sequence (its third gradient row and hex 33 hold no valid row)
+    float dzr[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    unpool(c6, 96, dzr[0], dzr[1]);
+    unpool(c7, 97, dzr[2], dzr[3]);
+    float Yp[2][8];
+    ydz(dzr, Yp[0]);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) Yp[1][i] = 0.f;
+    v6_store_hex_pair<FULL>(Yp[0], Yp[1], rsY, vvA, vvA + 1024u, vvB, vvB + 1024u, 16u * pair4);
+  }
 }
 
 // ------------------------------------------------------------------------------------------

@@ -67,6 +67,13 @@ typedef struct {
   int loader, epilogue;
   int splitk; int64_t slab_stride;
   int bm;             /* row-tile height: 256 (8 waves, large M), 128 (default) or 32 (skinny M) */
+  /* tl_conv3_wino63v_nt, compact-M mode (in the four bytes that padded `bm`: no offset moves).  A stores a_hps_extra more
+   * hexes per sequence than the launch computes: M, Tp and Tvalid describe the COMPUTED geometry (Tp / 6 = 16 hexes per
+   * sequence: a lane owns one whole sequence, a 128-hex tile eight), hex c of a tile is read from storage hex
+   * c + (c / 16) a_hps_extra and a tile's operand starts 8 (16 + a_hps_extra) hexes behind the one before;
+   * A_rows >= ceil(M / 768) * 8 * (16 + a_hps_extra).  The trailing hexes of every sequence (padding behind the last
+   * valid conv row) are never fetched or multiplied.  0: off.                                                          */
+  int a_hps_extra;
   /* 1 bit per element, rows x ceil(cols/32) words like abits/obits: the POOL epilogue also writes
    * "pooled output > 0" to osign (leading dimension ld_obits, may be null); the MASK epilogue reads
    * its LeakyReLU' mask from auxbits (leading dimension ld_auxbits) instead of the floats in aux

@@ -17,7 +17,11 @@ F6 = "Winograd F(6,3) on pre-transformed operands, LDS-DMA"
 FAMILIES = {
     # round 4: the F(6,3) kernels (tonal_wino63.hip), the default
     "wino63v_nt_kernel<5>": f"wino63v_nt_kernel<POOLV> (conv2 forward, {F6}; writes V of its pooled output for conv3)",
-    "wino63v_nt_kernel<2>": f"wino63v_nt_kernel<POOL> (conv3 forward, {F6})",
+    # (the default path at the timed shape: conv3 on whole-sequence tiles, f63_seq16 - instantiations 2 in compact-M mode, 12, 13)
+    "wino63v_nt_kernel<2>": f"wino63v_nt_kernel<POOL> (conv3 forward, {F6}; 16 of the 17 stored hexes per sequence)",
+    "wino63v_nt_kernel<12>": f"wino63v_nt_kernel<MASKY_SEQ> (conv3 input gradient on Y3, {F6}; 16 of the 17 stored hexes per sequence; writes Y of "
+                             "conv2 instead of the gradient rows)",
+    "wino63v_nt_kernel<13>": "wino63v_nt_kernel<GY_Y> (conv4 input gradient as six batched GEMMs of the NT63 kernel; writes Y of conv3 instead of the gradient rows)",
     "wino63v_nt_kernel<4>": f"wino63v_nt_kernel<C1WGRAD> (conv2 input gradient + conv1 weight gradient, {F6})",
     "wino63v_nt_kernel<6>": f"wino63v_nt_kernel<MASKY> (conv3 input gradient, {F6}; writes Y and Vd of conv2 instead of the gradient rows)",
     # instantiations 8 / 9: epilogue 6 without Vd, epilogue 4 on Y (the default path; tonal_wino63_epi.h)
@@ -52,7 +56,7 @@ FAMILIES = {
 # the two launches of wino63v_tn4y_kernel per step (conv3's, then conv2's: same kernel, same grid) are told apart by duration and
 # ALSO reported under the names CnnEngine.kernel_families() gives them, so that bench.py finds its dominant kernel here
 TN4Y = {"long": f"wino63v_tn4y_kernel (conv2 weight gradient, {F6}: both operands by LDS-DMA, no transform in the kernel)",
-        "short": f"wino63v_tn4y_kernel (conv3 weight gradient, {F6}: both operands by LDS-DMA, no transform in the kernel; Y3 / Vd3 "
+        "short": f"wino63v_tn4y_kernel (conv3 weight gradient, {F6}: both operands by LDS-DMA, no transform in the kernel; Y3 "
                  "from the epilogue of conv4's input gradient)"}
 
 
