@@ -176,7 +176,7 @@ __global__ __launch_bounds__(nt_cfg<BM>::NTHR, 2) void nt_window_group_kernel(tl
 // closes a step.  LDS rows are 64 B (unpadded, as the DMA requires a lane-linear image); the 16-B
 // chunk index is XOR-swizzled with (row >> 2) & 3 on the per-lane SOURCE address and on the
 // fragment read, which makes the ds_read_b128 of 16 consecutive rows conflict-free.
-// Preconditions (host-checked): DIRECT loader, row_shift == 0, K % 16 == 0.
+// Preconditions (host-checked): DIRECT loader, row_shift == 0, K % 16 == 0, no tap window past A_rows (J == 1 or A_rows >= M + J - 1).
 // ------------------------------------------------------------------------------------------
 constexpr int GK = 16;                 // K depth of a stage
 constexpr int G_AROWS = 144;           // 130 staged rows, 9 DMA pieces of 16 rows
@@ -850,9 +850,12 @@ static bool nt_glds_on() {
 }
 
 // does tl_gemm_nt_window run these (checked) parameters on the direct-to-LDS kernel?
+// (its DMA cannot zero-fill: a row from A_rows on is read as row A_rows - 1, which is harmless only where no output row's tap
+// window reaches that far - one tap, or J - 1 rows behind row M - 1.  With fewer rows behind the end, rows M - J + 1 .. M - 1
+// would take the last row's values where the contract says zero: the register-staged kernel runs those.)
 static bool nt_takes_glds(const tl_nt_params& p) {
   return nt_glds_on() && p.J <= 3 && p.bm == 128 && p.loader == tl::LOAD_DIRECT && p.row_shift == 0 && (p.K % tl::GK) == 0 &&
-         p.A_rows > 0;
+         p.A_rows > 0 && (p.J == 1 || p.A_rows >= p.M + p.J - 1);
 }
 
 extern "C" int tl_gemm_nt_window(const tl_nt_params* pp, void* stream) {
