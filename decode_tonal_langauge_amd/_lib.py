@@ -186,6 +186,23 @@ SIGNATURES = {
     "tl_head_bwd_group": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P]),
     "tl_head_bwd_act_group": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _L, _L, _L, _L, _L, _L, _P, _P]),
     "tl_gemm_nt_window_group": (_I, [C.POINTER(NtParams), _I, _L, _L, _L, _L, _P, _P]),
+    "tl_gemm_nt_window_group_fc": (_I, [C.POINTER(NtParams), _I, _L, _L, _L, _L, _L, _P, _P]),
+    "tl_gemm_tn_window_group": (_I, [C.POINTER(TnParams), _I, _L, _L, _L, _L, _P, _P]),
+    "tl_lite_conv_fwd_group": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _L, _L, _L, _L, _P, _P]),
+    "tl_lite_bn_finalize_group": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _L, _I, _F, _F, _I, _P, _L, _L, _L, _L, _P, _P]),
+    "tl_lite_bn_act_pool_fwd_group": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _L, _L, _L, _L, _P, _P]),
+    "tl_lite_bn_act_pool_bwd_group": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _L, _L, _L, _L, _L, _L,
+                                           _L, _P, _P]),
+    "tl_lite_conv_bwd_group": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _L, _L, _L, _L, _L, _P, _P]),
+    "tl_colsum_group": (_I, [_P, _P, _I, _L, _I, _I, _I, _I, _I, _L, _L, _P, _P]),
+    "tl_sum_slabs2_group": (_I, [_P, _P, _L, _P, _P, _L, _I, _I, _L, _L, _L, _L, _P, _P]),
+    "tl_lite_lstm_fwd_group": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _L, _L, _L, _L, _L, _P, _P]),
+    "tl_lite_lstm_bwd_group": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P]),
+    "tl_lstm_ih_grad_group": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P]),
+    "tl_lite_cat_group": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _L, _L, _L, _P, _P]),
+    "tl_lite_uncat_group": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _L, _L, _L, _P, _P]),
+    "tl_splitk_bias_lrelu_group": (_I, [_P, _P, _P, _I, _L, _I, _F, _I, _L, _L, _L, _L, _P, _P]),
+    "tl_l1_mcd_group": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _L, _L, _L, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -143,6 +143,7 @@ struct nt_cfg {
 struct nt_group {
   long long s_A, s_Bw, s_bias, s_out;   // member strides, elements
   const int32_t* active;                // M words or null; 0: the member's workgroups return at once
+  long long s_aux;                      // ... of aux (the MASK epilogue of tl_gemm_nt_window_group_fc)
 };
 
 // member blockIdx.z's parameters; false: the member is masked out (uniform over the workgroup - before any load or barrier)
@@ -151,7 +152,8 @@ __device__ __forceinline__ bool nt_member(tl_nt_params& p, const nt_group& g) {
   if (g.active != nullptr && g.active[mem] == 0) return false;
   p.A += mem * g.s_A;
   p.Bw += mem * g.s_Bw;
-  p.bias += mem * g.s_bias;
+  if (p.bias != nullptr) p.bias += mem * g.s_bias;
+  if (p.aux != nullptr) p.aux += mem * g.s_aux;
   p.out += mem * g.s_out;
   return true;
 }
@@ -908,7 +910,7 @@ extern "C" int tl_gemm_nt_window_group(const tl_nt_params* pp, int M, int64_t s_
   TL_REQUIRE(M == 1 || s_out >= p.M * (int64_t)p.ldo,
              "nt_window_group: member stride of out shorter than the M x ldo elements of a member");
   hipStream_t st = (hipStream_t)stream;
-  const nt_group g = {(long long)s_A, (long long)s_Bw, (long long)s_bias, (long long)s_out, active};
+  const nt_group g = {(long long)s_A, (long long)s_Bw, (long long)s_bias, (long long)s_out, active, 0};
   const bool glds = nt_takes_glds(p), narrow = glds && p.N <= 64;
   const int bn = narrow ? 64 : BN;
   const long long nwg = ((p.M + 127) / 128) * ((p.N + bn - 1) / bn);
@@ -924,6 +926,60 @@ extern "C" int tl_gemm_nt_window_group(const tl_nt_params* pp, int M, int64_t s_
   return check_launch("nt_window_group");
 }
 
+// The group form of the two Linear layers of SynthesisLite and of their input gradients (_lite_ensemble_engine.py): the plain
+// GEMM (J = 1, DIRECT, row_shift 0) on 32- or 128-row tiles, epilogue STORE - split-K on grid.y as in the single launch, every
+// member with splitk slabs of its own - or MASK with aux at a member stride.  The kernel is chosen as tl_gemm_nt_window chooses
+// it for *pp, its body is that kernel's, the member sits on grid.z.
+template <int EPI>
+static int launch_nt_group_fc(const tl_nt_params& p, const tl::nt_group& g, int M, hipStream_t st) {
+  using namespace tl;
+  const bool glds = nt_takes_glds(p), narrow = glds && p.N <= 64;
+  const int bn = narrow ? 64 : BN, bm = glds ? 128 : p.bm;
+  const long long nwg = ((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn);
+  if (nwg <= 0) return TL_OK;
+  TL_REQUIRE(nwg < (1LL << 31), "nt_window_group_fc: grid too large");
+  const dim3 grid((unsigned)nwg, (unsigned)p.splitk, (unsigned)M);
+  if (narrow)
+    hipLaunchKernelGGL((nt_glds_group_kernel<EPI, 1>), grid, dim3(256), 0, st, p, g);
+  else if (glds)
+    hipLaunchKernelGGL((nt_glds_group_kernel<EPI, 2>), grid, dim3(256), 0, st, p, g);
+  else if (p.bm == 128)
+    hipLaunchKernelGGL((nt_window_group_kernel<128, LOAD_DIRECT, EPI>), grid, dim3(nt_cfg<128>::NTHR), 0, st, p, g);
+  else
+    hipLaunchKernelGGL((nt_window_group_kernel<32, LOAD_DIRECT, EPI>), grid, dim3(nt_cfg<32>::NTHR), 0, st, p, g);
+  return check_launch("nt_window_group_fc");
+}
+
+extern "C" int tl_gemm_nt_window_group_fc(const tl_nt_params* pp, int M, int64_t s_A, int64_t s_Bw, int64_t s_bias, int64_t s_aux,
+                                          int64_t s_out, const int32_t* active, void* stream) {
+  using namespace tl;
+  TL_REQUIRE(pp != nullptr, "nt_window_group_fc: null params");
+  tl_nt_params p = *pp;
+  TL_REQUIRE_MEMBERS("nt_window_group_fc", M);
+  TL_REQUIRE(p.J == 1 && p.loader == LOAD_DIRECT && p.row_shift == 0,
+             "nt_window_group_fc: only the plain GEMM has a group form (J = 1, DIRECT loader, row_shift = 0; got J %d, loader %d, "
+             "row_shift %d)", p.J, p.loader, p.row_shift);
+  TL_REQUIRE(p.bm == 32 || p.bm == 128, "nt_window_group_fc: bm must be 32 or 128 (got %d)", p.bm);
+  TL_REQUIRE(p.epilogue == EPI_STORE || p.epilogue == EPI_MASK,
+             "nt_window_group_fc: only the STORE and MASK epilogues have this group form (got %d)", p.epilogue);
+  TL_REQUIRE(!p.auxbits && !p.abits && !p.obits && !p.osign && !p.vout && !p.vout2 && !p.vhalo && !p.c1x && !p.c1bits &&
+                 !p.c1partial && !p.mask && (p.epilogue == EPI_MASK || !p.aux),
+             "nt_window_group_fc: auxbits / abits / obits / osign / vout / c1 / mask pointers (and aux without the MASK epilogue) "
+             "have no member stride: pass null");
+  TL_REQUIRE(p.epilogue != EPI_MASK || p.aux != nullptr, "nt_window_group_fc: the MASK epilogue needs aux");
+  if (const int rc = nt_check(p)) return rc;
+  TL_REQUIRE(s_A >= 0 && s_Bw >= 0 && s_bias >= 0 && s_aux >= 0 && s_A % 4 == 0 && s_Bw % 4 == 0,
+             "nt_window_group_fc: the member strides of A and Bw must be non-negative multiples of 4 elements (16-byte aligned "
+             "members), those of bias and aux non-negative");
+  TL_REQUIRE(p.splitk == 1 || p.slab_stride >= p.M * (int64_t)p.ldo,
+             "nt_window_group_fc: slab_stride shorter than the M x ldo elements of a slab");
+  TL_REQUIRE(M == 1 || s_out >= (p.splitk > 1 ? (int64_t)p.splitk * p.slab_stride : p.M * (int64_t)p.ldo),
+             "nt_window_group_fc: member stride of out shorter than a member's extent (M x ldo elements, or splitk x slab_stride)");
+  const nt_group g = {(long long)s_A, (long long)s_Bw, (long long)s_bias, (long long)s_out, active, (long long)s_aux};
+  hipStream_t st = (hipStream_t)stream;
+  return p.epilogue == EPI_STORE ? launch_nt_group_fc<EPI_STORE>(p, g, M, st) : launch_nt_group_fc<EPI_MASK>(p, g, M, st);
+}
+
 namespace tl {
 // Short reductions (a few hundred rows: the weight gradients of SynthesisLite's Linear / LSTM layers at batch 64): the MFMA
 // kernels' 128 x 128 tiles leave a handful of workgroups with a short K loop of dependent latency (17 - 30 us).  Here a
@@ -931,108 +987,85 @@ namespace tl {
 // arithmetic of the chunk in front of it, 40 KB of LDS), plain FMAs on a 4 x 4 patch per thread, rows in order
 // (deterministic); masked rows ((R % Tp) >= Tvalid) are zero-filled, not read.
 constexpr int TS_K = 64, TS_M = 32, TS_N = 128;
+// (the body is a file of statements included into the single and the group kernel, as with the NT kernels above)
 __global__ __launch_bounds__(256) void tn_short_kernel(const tl_tn_params p) {
-  __shared__ __attribute__((aligned(16))) float As[TS_K * TS_M];
-  __shared__ __attribute__((aligned(16))) float Bs[TS_K * TS_N];
-  const int tid = threadIdx.x, tn = tid & 31, tm = tid >> 5;
-  const int ntn = (p.Ndim + TS_N - 1) / TS_N;
-  const int mt = (int)(blockIdx.x / ntn) * TS_M, nt = (int)(blockIdx.x % ntn) * TS_N;
-  const int kall = (int)(p.Krows < p.A_rows ? (p.Krows < p.B_rows ? p.Krows : p.B_rows) : (p.A_rows < p.B_rows ? p.A_rows : p.B_rows));
-  // reduction split blockIdx.y: rows [kb, kr) = whole 64-row chunks (slab blockIdx.y; the caller sums the splitk slabs)
-  const int per = ((kall + (int)gridDim.y - 1) / (int)gridDim.y + TS_K - 1) / TS_K * TS_K;
-  const int kb = (int)blockIdx.y * per;
-  const int kr = kb + per < kall ? kb + per : kall;
-  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-  // a chunk: A 64 rows x 8 float4, B 64 rows x 32 float4 (Mdim, Ndim % 4 == 0: a float4 is whole or absent)
-  f32x4 ra[2], rb[8];
-  // (every load is issued, from a clamped address, and zeroed afterwards: predicated loads come out as one exec-masked
-  // region each, with the latencies in series)
-  int ta[2], tb[8];                                          // (row offset in the chunk) % Tp: the division is done once
-#pragma unroll
-  for (int i = 0; i < 2; ++i) ta[i] = ((tid + i * 256) >> 3) % p.Tp;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) tb[i] = ((tid + i * 256) >> 5) % p.Tp;
-  const int kstep_mod = TS_K % p.Tp;
-  int r0m = kb % p.Tp;                                       // r0 % Tp of the chunk being fetched
-  auto fetch = [&](int r0) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int idx = tid + i * 256, R = r0 + (idx >> 3), c = mt + (idx & 7) * 4;
-      int t = ta[i] + r0m;
-      t = t >= p.Tp ? t - p.Tp : t;
-      const bool ok = R < kr && t < p.Tvalid && c < p.Mdim;
-      const f32x4 v = *reinterpret_cast<const f32x4*>(p.A + (long long)(R < kall ? R : kall - 1) * p.lda + (c < p.Mdim ? c : p.Mdim - 4));
-      ra[i] = ok ? v : zero;
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int idx = tid + i * 256, R = r0 + (idx >> 5), c = nt + (idx & 31) * 4;
-      int t = tb[i] + r0m;
-      t = t >= p.Tp ? t - p.Tp : t;
-      const bool ok = R < kr && t < p.Tvalid && c < p.Ndim;
-      const f32x4 v = *reinterpret_cast<const f32x4*>(p.B + (long long)(R < kall ? R : kall - 1) * p.ldb + (c < p.Ndim ? c : p.Ndim - 4));
-      rb[i] = ok ? v : zero;
-    }
-    r0m += kstep_mod;
-    r0m = r0m >= p.Tp ? r0m - p.Tp : r0m;
-  };
-  f32x4 acc[4] = {zero, zero, zero, zero};
-  // optional column sums of A (the bias gradient of a Linear layer rides along): the workgroups of the first column tile,
-  // threads 0..31, one column each, rows in order
-  const bool do_cs = p.colsum != nullptr && nt == 0 && gridDim.y == 1 && tid < TS_M;
-  float csum = 0.f;
-  fetch(kb);
-  for (int r0 = kb; r0 < kr; r0 += TS_K) {
-    __syncthreads();                                       // the chunk in front has been consumed
-#pragma unroll
-    for (int i = 0; i < 2; ++i) *reinterpret_cast<f32x4*>(As + ((tid + i * 256) >> 3) * TS_M + ((tid + i * 256) & 7) * 4) = ra[i];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) *reinterpret_cast<f32x4*>(Bs + ((tid + i * 256) >> 5) * TS_N + ((tid + i * 256) & 31) * 4) = rb[i];
-    __syncthreads();
-    if (r0 + TS_K < kr) fetch(r0 + TS_K);
-    if (do_cs) {
-#pragma unroll 8
-      for (int R = 0; R < TS_K; ++R) csum += As[R * TS_M + tid];
-    }
-#pragma unroll 8
-    for (int R = 0; R < TS_K; ++R) {
-      const f32x4 av = *reinterpret_cast<const f32x4*>(As + R * TS_M + tm * 4);
-      const f32x4 bv = *reinterpret_cast<const f32x4*>(Bs + R * TS_N + tn * 4);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) acc[i] += av[i] * bv;
-    }
-  }
-  const int m0 = mt + tm * 4, n0 = nt + tn * 4;
-  if (m0 < p.Mdim && n0 < p.Ndim) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      *reinterpret_cast<f32x4*>(p.slab + (long long)blockIdx.y * p.slab_stride + (long long)(m0 + i) * p.ldc + n0) = acc[i];
-  }
-  if (do_cs && mt + tid < p.Mdim) p.colsum[mt + tid] = csum;
+#include "tonal_gemm_tn_short_body.h"
+}
+struct tn_group {
+  long long s_A, s_B, s_slab, s_colsum;   // member strides, elements
+  const int32_t* active;                  // M words or null; 0: the member's workgroups return at once
+};
+__global__ __launch_bounds__(256) void tn_short_group_kernel(tl_tn_params p, const tn_group g) {
+  const int mem = blockIdx.z;
+  if (g.active != nullptr && g.active[mem] == 0) return;        // uniform over the workgroup, before any load or barrier
+  p.A += mem * g.s_A;
+  p.B += mem * g.s_B;
+  p.slab += mem * g.s_slab;
+  if (p.colsum != nullptr) p.colsum += mem * g.s_colsum;
+#include "tonal_gemm_tn_short_body.h"
 }
 }  // namespace tl
+
+// the shared argument checks of tl_gemm_tn_window and tl_gemm_tn_window_group; fills in the default of splitk
+static int tn_check(tl_tn_params& p, const char* what) {
+  using namespace tl;
+  if (p.splitk < 1) p.splitk = 1;
+  TL_REQUIRE(p.A && p.B && p.slab, "%s: null A/B/slab", what);
+  TL_REQUIRE(p.Krows > 0 && p.Mdim > 0 && p.Ndim > 0, "%s: bad sizes", what);
+  TL_REQUIRE(p.Krows + 64 < (1LL << 31), "%s: more than 2^31 reduction rows", what);
+  TL_REQUIRE(p.Mdim % 4 == 0 && p.Ndim % 4 == 0 && p.lda % 4 == 0 && p.ldb % 4 == 0, "%s: dims/ld must be multiples of 4", what);
+  TL_REQUIRE(p.J >= 1 && p.J <= 7, "%s: J must be 1..7", what);
+  TL_REQUIRE(p.Tp > 0, "%s: Tp must be positive", what);
+  TL_REQUIRE(p.splitk <= 65535, "%s: splitk too large", what);
+  return TL_OK;
+}
+// does tl_gemm_tn_window run these (checked) parameters on the short-reduction kernel?
+static bool tn_takes_short(const tl_tn_params& p) {
+  return p.J == 1 && p.loader == tl::LOAD_DIRECT && p.Krows <= 8 * tl::TS_K && p.splitk <= 8 &&
+         (long long)p.Mdim * p.Ndim <= (1 << 20) && (p.splitk == 1 || p.slab_stride >= (long long)p.Mdim * p.ldc) && p.ldc % 4 == 0;
+}
+
+// tl_gemm_tn_window for M members of equal shape, for the parameters the single entry sends to tn_short_kernel (the weight
+// gradients of SynthesisLite's Linear / LSTM layers): that kernel's body with the member on grid.z.
+extern "C" int tl_gemm_tn_window_group(const tl_tn_params* pp, int M, int64_t s_A, int64_t s_B, int64_t s_slab, int64_t s_colsum,
+                                       const int32_t* active, void* stream) {
+  using namespace tl;
+  TL_REQUIRE(pp != nullptr, "tn_window_group: null params");
+  tl_tn_params p = *pp;
+  TL_REQUIRE_MEMBERS("tn_window_group", M);
+  if (const int rc = tn_check(p, "tn_window_group")) return rc;
+  TL_REQUIRE(tn_takes_short(p),
+             "tn_window_group: only the short-reduction kernel has a group form (J = 1, DIRECT loader, Krows <= 512, splitk <= 8, "
+             "Mdim * Ndim <= 2^20, ldc %% 4 == 0, slab_stride >= Mdim * ldc under split-K; got J %d, loader %d, Krows %lld, splitk %d, "
+             "Mdim %d, Ndim %d, ldc %d)", p.J, p.loader, (long long)p.Krows, p.splitk, p.Mdim, p.Ndim, p.ldc);
+  TL_REQUIRE(!p.bbits && !p.vd, "tn_window_group: bbits / vd have no member stride: pass null");
+  TL_REQUIRE(p.lda >= p.Mdim && p.ldb >= p.Ndim && p.ldc >= p.Ndim, "tn_window_group: lda / ldb / ldc smaller than the row they stride");
+  TL_REQUIRE(p.A_rows > 0 && p.B_rows > 0, "tn_window_group: A_rows and B_rows must be positive");
+  TL_REQUIRE(s_A >= 0 && s_B >= 0 && s_A % 4 == 0 && s_B % 4 == 0 && s_slab % 4 == 0,
+             "tn_window_group: the member strides of A, B and slab must be non-negative multiples of 4 elements (16-byte aligned members)");
+  TL_REQUIRE(s_slab >= 0 && (M == 1 || s_slab >= (p.splitk > 1 ? (int64_t)p.splitk * p.slab_stride : (int64_t)p.Mdim * p.ldc)),
+             "tn_window_group: member stride of slab shorter than a member's extent (Mdim x ldc elements, or splitk x slab_stride)");
+  TL_REQUIRE(p.colsum == nullptr || (s_colsum >= 0 && (M == 1 || s_colsum >= p.Mdim)),
+             "tn_window_group: member stride of colsum shorter than the Mdim elements of a member");
+  const long long nwg = (long long)((p.Mdim + TS_M - 1) / TS_M) * ((p.Ndim + TS_N - 1) / TS_N);
+  const tn_group g = {(long long)s_A, (long long)s_B, (long long)s_slab, (long long)s_colsum, active};
+  hipLaunchKernelGGL(tn_short_group_kernel, dim3((unsigned)nwg, (unsigned)p.splitk, (unsigned)M), dim3(256), 0, (hipStream_t)stream,
+                     p, g);
+  return check_launch("tn_short_group");
+}
 
 extern "C" int tl_gemm_tn_window(const tl_tn_params* pp, void* stream) {
   using namespace tl;
   TL_REQUIRE(pp != nullptr, "tn_window: null params");
   tl_tn_params p = *pp;
-  if (p.splitk < 1) p.splitk = 1;
-  TL_REQUIRE(p.A && p.B && p.slab, "tn_window: null A/B/slab");
-  TL_REQUIRE(p.Krows > 0 && p.Mdim > 0 && p.Ndim > 0, "tn_window: bad sizes");
-  TL_REQUIRE(p.Krows + 64 < (1LL << 31), "tn_window: more than 2^31 reduction rows");
-  TL_REQUIRE(p.Mdim % 4 == 0 && p.Ndim % 4 == 0 && p.lda % 4 == 0 && p.ldb % 4 == 0, "tn_window: dims/ld must be multiples of 4");
-  TL_REQUIRE(p.J >= 1 && p.J <= 7, "tn_window: J must be 1..7");
-  TL_REQUIRE(p.Tp > 0, "tn_window: Tp must be positive");
-  TL_REQUIRE(p.splitk <= 65535, "tn_window: splitk too large");
+  if (const int rc = tn_check(p, "tn_window")) return rc;
   if (p.loader == LOAD_UNPOOL) {
     TL_REQUIRE(p.bbits != nullptr, "tn_window: UNPOOL loader needs bbits");
     TL_REQUIRE(p.Tp % 2 == 0 && p.Tvalid % 2 == 0, "tn_window: UNPOOL needs even Tp/Tvalid");
     TL_REQUIRE(p.ld_bbits * 32 >= p.Ndim, "tn_window: bbits row too short");
   }
   hipStream_t st = (hipStream_t)stream;
-  if (p.J == 1 && p.loader == LOAD_DIRECT && p.Krows <= 8 * TS_K && p.splitk <= 8 && (long long)p.Mdim * p.Ndim <= (1 << 20) &&
-      (p.splitk == 1 || p.slab_stride >= (long long)p.Mdim * p.ldc) &&
-      p.ldc % 4 == 0) {                                             // short reduction, small output: latency-bound
+  if (tn_takes_short(p)) {                                           // short reduction, small output: latency-bound
     const long long nwg = (long long)((p.Mdim + TS_M - 1) / TS_M) * ((p.Ndim + TS_N - 1) / TS_N);
     hipLaunchKernelGGL(tn_short_kernel, dim3((unsigned)nwg, (unsigned)p.splitk), dim3(256), 0, st, p);
     return check_launch("tn_short");

@@ -11,14 +11,25 @@ namespace tl {
 
 constexpr int LT = 64;   // time tile of the direct conv kernels
 
+// Group launches (tl_lite_*_group, include/tonal_hip.h "group launches"): every kernel below takes the member from blockIdx.z,
+// moves its pointers the member strides (elements) behind member 0's and returns at once - before any load, store or barrier -
+// when the member's `active` word is 0.  The single entries launch the same kernels with one member and zero strides.
+#define TL_LITE_MEMBER()                                     \
+  const int mem = blockIdx.z;                                \
+  if (active != nullptr && active[mem] == 0) return
+
 // z[b][o][t] = bias[o] + sum_{i,j} w[o][i][j] * x[b][i][t + j - pad]   (zero padding)
 // part[(b*ntile + tile)][o][0..1] = (sum_t z, sum_t (z - tile mean)^2) over the tile: centred per tile, so that a channel
 // whose mean is many standard deviations (a DC offset on the input) keeps its variance instead of losing it to E[z^2] - m^2
 __global__ __launch_bounds__(512) void lite_conv_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                             const float* __restrict__ bias, float* __restrict__ z,
                                                             float* __restrict__ part, int Cin, int Cout, int T, int k,
-                                                            int pad) {
+                                                            int pad, const int32_t* __restrict__ active, long long s_x,
+                                                            long long s_w, long long s_bias, long long s_z, long long s_part) {
   extern __shared__ __attribute__((aligned(16))) float xs[];      // [Cin][LT + k - 1]
+  TL_LITE_MEMBER();
+  x += mem * s_x, w += mem * s_w, bias += mem * s_bias, z += mem * s_z;
+  if (part) part += mem * s_part;
   const int b = blockIdx.y, tile = blockIdx.x, t0 = tile * LT;
   const int W = LT + k - 1;
   for (int i = threadIdx.x; i < Cin * W; i += blockDim.x) {
@@ -92,7 +103,13 @@ __global__ __launch_bounds__(64) void lite_bn_finalize_kernel(const float* __res
                                                               float* __restrict__ rstd, float* __restrict__ run_mean,
                                                               float* __restrict__ run_var, int nparts, int C, long long count,
                                                               int T, float momentum, float eps, int training,
-                                                              long long* __restrict__ tracked) {
+                                                              long long* __restrict__ tracked,
+                                                              const int32_t* __restrict__ active, long long s_part,
+                                                              long long s_stat, long long s_run, long long s_tracked) {
+  TL_LITE_MEMBER();
+  if (part) part += mem * s_part;
+  mean += mem * s_stat, rstd += mem * s_stat, run_mean += mem * s_run, run_var += mem * s_run;
+  if (tracked) tracked += mem * s_tracked;
   const int c = blockIdx.x;                      // one wave per channel, lanes stride over the partials
   const int lane = threadIdx.x;
   const int ntile = (T + LT - 1) / LT;
@@ -130,7 +147,11 @@ __global__ __launch_bounds__(64) void lite_bn_finalize_kernel(const float* __res
 __global__ __launch_bounds__(256) void lite_bn_act_pool_fwd_kernel(const float* __restrict__ z, const float* __restrict__ mean,
                                                                    const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                                    const float* __restrict__ beta, float* __restrict__ y,
-                                                                   long long total, int C, int T, float slope) {
+                                                                   long long total, int C, int T, float slope,
+                                                                   const int32_t* __restrict__ active, long long s_z,
+                                                                   long long s_stat, long long s_gb, long long s_y) {
+  TL_LITE_MEMBER();
+  z += mem * s_z, mean += mem * s_stat, rstd += mem * s_stat, gamma += mem * s_gb, beta += mem * s_gb, y += mem * s_y;
   const int Tp = T / 2;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const int p = (int)(i % Tp);
@@ -149,8 +170,13 @@ __global__ __launch_bounds__(256) void lite_bn_act_pool_bwd_kernel(const float* 
                                                                    const float* __restrict__ mean, const float* __restrict__ rstd,
                                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                    float* __restrict__ dbn, float* __restrict__ part, int C,
-                                                                   int T, float slope) {
+                                                                   int T, float slope, const int32_t* __restrict__ active,
+                                                                   long long s_dy, long long s_z, long long s_stat,
+                                                                   long long s_gb, long long s_dz, long long s_work) {
   __shared__ float r1[256], r2[256];
+  TL_LITE_MEMBER();
+  dy += mem * s_dy, z += mem * s_z, mean += mem * s_stat, rstd += mem * s_stat, gamma += mem * s_gb, beta += mem * s_gb;
+  dbn += mem * s_dz, part += mem * s_work;
   const int b = blockIdx.y, c = blockIdx.x;
   const int Tp = T / 2;
   const float g = gamma[c] * rstd[c], sh = beta[c] - mean[c] * g;
@@ -197,8 +223,13 @@ __global__ __launch_bounds__(256) void lite_bn_dz_kernel(float* __restrict__ dbn
                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
                                                          const float* __restrict__ gamma, const float* __restrict__ part,
                                                          float* __restrict__ dgamma, float* __restrict__ dbeta, int B, int C, int T,
-                                                         long long count, int training) {
+                                                         long long count, int training, const int32_t* __restrict__ active,
+                                                         long long s_z, long long s_stat, long long s_gb, long long s_dz,
+                                                         long long s_dgb, long long s_work) {
   __shared__ float sm[2];
+  TL_LITE_MEMBER();
+  dbn += mem * s_dz, z += mem * s_z, mean += mem * s_stat, rstd += mem * s_stat, gamma += mem * s_gb, part += mem * s_work;
+  dgamma += mem * s_dgb, dbeta += mem * s_dgb;
   const int c = blockIdx.x, b = blockIdx.y;
   if (threadIdx.x < 64) {
     const int lane = threadIdx.x;
@@ -237,8 +268,12 @@ __global__ __launch_bounds__(256) void lite_bn_dz_kernel(float* __restrict__ dbn
 
 // conv backward: dx[b][i][t] = sum_{o,j} dz[b][o][t - j + pad] w[o][i][j];  per-b weight-gradient partials
 __global__ __launch_bounds__(512) void lite_conv_dx_kernel(const float* __restrict__ dz, const float* __restrict__ w,
-                                                           float* __restrict__ dx, int Cin, int Cout, int T, int k, int pad) {
+                                                           float* __restrict__ dx, int Cin, int Cout, int T, int k, int pad,
+                                                           const int32_t* __restrict__ active, long long s_dz, long long s_w,
+                                                           long long s_dx) {
   extern __shared__ __attribute__((aligned(16))) float ds[];      // [Cout][LT + k - 1]
+  TL_LITE_MEMBER();
+  dz += mem * s_dz, w += mem * s_w, dx += mem * s_dx;
   const int b = blockIdx.y, t0 = blockIdx.x * LT;
   const int W = LT + k - 1;
   for (int i = threadIdx.x; i < Cout * W; i += blockDim.x) {
@@ -293,8 +328,12 @@ __global__ __launch_bounds__(512) void lite_conv_dx_kernel(const float* __restri
 // elements touch) are staged in LDS once, so the T-long dot products read LDS instead of 2 T global loads per thread.
 __global__ __launch_bounds__(256) void lite_conv_dw_kernel(const float* __restrict__ dz, const float* __restrict__ x,
                                                            float* __restrict__ dwpart, float* __restrict__ dbpart, int Cin,
-                                                           int Cout, int T, int k, int pad, int use_lds) {
+                                                           int Cout, int T, int k, int pad, int use_lds,
+                                                           const int32_t* __restrict__ active, long long s_dz, long long s_x,
+                                                           long long s_dwpart, long long s_dbpart) {
   extern __shared__ __attribute__((aligned(16))) float sm[];      // xs[Cin][T], dzs[no][T]
+  TL_LITE_MEMBER();
+  dz += mem * s_dz, x += mem * s_x, dwpart += mem * s_dwpart, dbpart += mem * s_dbpart;
   const int b = blockIdx.x;
   const int n = Cout * Cin * k;
   const int e0 = blockIdx.y * blockDim.x;
@@ -362,8 +401,13 @@ __global__ __launch_bounds__(256) void lite_lstm_fwd_kernel(const float* __restr
                                                             const float* __restrict__ w_hh, const float* __restrict__ b_ih,
                                                             const float* __restrict__ b_hh, float* __restrict__ act,
                                                             float* __restrict__ cs, float* __restrict__ hs, int L, int H,
-                                                            int in_dim) {
+                                                            int in_dim, const int32_t* __restrict__ active, long long s_xl,
+                                                            long long s_wih, long long s_whh, long long s_b, long long s_act,
+                                                            long long s_cs) {
   extern __shared__ __attribute__((aligned(16))) float sm[];   // h[H], c[H], gates[4H]
+  TL_LITE_MEMBER();
+  xl += mem * s_xl, w_ih += mem * s_wih, w_hh += mem * s_whh, b_ih += mem * s_b, b_hh += mem * s_b;
+  act += mem * s_act, cs += mem * s_cs, hs += mem * s_cs;
   float* h = sm;
   float* c = sm + H;
   float* gt = sm + 2 * H;
@@ -410,8 +454,12 @@ __global__ __launch_bounds__(256) void lite_lstm_fwd_kernel(const float* __restr
 // BPTT: dh_last (B,H) -> dgates (B,L,4H) (pre-activation gradients)
 __global__ __launch_bounds__(256) void lite_lstm_bwd_kernel(const float* __restrict__ dh_last, const float* __restrict__ w_hh,
                                                             const float* __restrict__ act, const float* __restrict__ cs,
-                                                            float* __restrict__ dgates, int L, int H, int ld_dh) {
+                                                            float* __restrict__ dgates, int L, int H, int ld_dh,
+                                                            const int32_t* __restrict__ active, long long s_dh,
+                                                            long long s_whh, long long s_act, long long s_cs) {
   extern __shared__ __attribute__((aligned(16))) float sm[];   // dh[H], dc[H], dg[4H]
+  TL_LITE_MEMBER();
+  dh_last += mem * s_dh, w_hh += mem * s_whh, act += mem * s_act, cs += mem * s_cs, dgates += mem * s_act;
   float* dh = sm;
   float* dc = sm + H;
   float* dg = sm + 2 * H;
@@ -469,8 +517,12 @@ __global__ __launch_bounds__(256) void lite_lstm_bwd_kernel(const float* __restr
 // feat[b][0:F] = y2[b][:] (flattened conv features), feat[b][F:F+H] = h_L[b]; dropout (fc.0) on all
 __global__ __launch_bounds__(256) void lite_cat_kernel(const float* __restrict__ y2, const float* __restrict__ hs,
                                                        float* __restrict__ feat, int B, int F, int H, int L, int ldf,
-                                                       float p_drop, uint64_t seed, const uint64_t* __restrict__ seed_dev) {
-  if (seed_dev != nullptr) seed = *seed_dev;      // dropout seed in device memory (HIP-graph replays draw new masks)
+                                                       float p_drop, uint64_t seed, const uint64_t* __restrict__ seed_dev,
+                                                       const int32_t* __restrict__ active, long long s_y2, long long s_hs,
+                                                       long long s_feat) {
+  TL_LITE_MEMBER();
+  y2 += mem * s_y2, hs += mem * s_hs, feat += mem * s_feat;
+  if (seed_dev != nullptr) seed = seed_dev[mem];  // dropout seed in device memory (HIP-graph replays draw new masks)
   const long long total = (long long)B * ldf;
   const float ks = p_drop > 0.f ? 1.f / (1.f - p_drop) : 1.f;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -491,8 +543,12 @@ __global__ __launch_bounds__(256) void lite_cat_kernel(const float* __restrict__
 }
 __global__ __launch_bounds__(256) void lite_uncat_kernel(const float* __restrict__ dfeat, float* __restrict__ dy2,
                                                          float* __restrict__ dh, int B, int F, int H, int ldf, float p_drop,
-                                                         uint64_t seed, const uint64_t* __restrict__ seed_dev) {
-  if (seed_dev != nullptr) seed = *seed_dev;
+                                                         uint64_t seed, const uint64_t* __restrict__ seed_dev,
+                                                         const int32_t* __restrict__ active, long long s_dfeat,
+                                                         long long s_dy2, long long s_dh) {
+  TL_LITE_MEMBER();
+  dfeat += mem * s_dfeat, dy2 += mem * s_dy2, dh += mem * s_dh;
+  if (seed_dev != nullptr) seed = seed_dev[mem];
   const long long total = (long long)B * (F + H);
   const float ks = p_drop > 0.f ? 1.f / (1.f - p_drop) : 1.f;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -520,109 +576,277 @@ static inline unsigned lgrid(long long total) {
 }  // namespace tl
 using namespace tl;
 
+// Every entry below has one launch function, used by the single entry (M = 1, strides 0, active null) and by its
+// tl_lite_*_group neighbour: the same kernel, the same grid in x and y, the member on grid.z.
+#define TL_REQUIRE_STRIDE(entry, M, s, need, what)                                                                        \
+  TL_REQUIRE((s) >= 0 && ((M) == 1 || (int64_t)(s) >= (int64_t)(need)), "%s: member stride of %s shorter than a member's extent", \
+             entry, what)
+
+static int conv_fwd_launch(const char* what, const float* x, const float* w, const float* bias, float* z, float* part, int B,
+                           int Cin, int Cout, int T, int k, int pad, void* stream, int M = 1, int64_t s_x = 0, int64_t s_w = 0,
+                           int64_t s_bias = 0, int64_t s_z = 0, int64_t s_part = 0, const int32_t* active = nullptr) {
+  TL_REQUIRE(x && w && bias && z, "%s: null pointer", what);
+  TL_REQUIRE(B > 0 && B <= 65535 && Cin > 0 && Cout > 0 && T > 0 && k >= 1 && 2 * pad == k - 1, "%s: bad sizes (needs 'same' padding)", what);
+  const size_t lds = (size_t)Cin * (LT + k - 1) * 4;
+  TL_REQUIRE(lds <= 64 * 1024, "%s: Cin too large for the LDS tile", what);
+  const int ntile = (T + LT - 1) / LT;
+  TL_REQUIRE(s_x >= 0 && s_w >= 0 && s_bias >= 0, "%s: negative member stride", what);
+  TL_REQUIRE_STRIDE(what, M, s_z, (int64_t)B * Cout * T, "z");
+  if (part) TL_REQUIRE_STRIDE(what, M, s_part, (int64_t)B * ntile * Cout * 2, "part");
+  hipLaunchKernelGGL(lite_conv_fwd_kernel, dim3(ntile, B, M), dim3(512), lds, (hipStream_t)stream, x, w, bias, z, part, Cin, Cout,
+                     T, k, pad, active, (long long)s_x, (long long)s_w, (long long)s_bias, (long long)s_z, (long long)s_part);
+  return check_launch(what);
+}
 extern "C" int tl_lite_conv_fwd(const float* x, const float* w, const float* bias, float* z, float* part, int B, int Cin,
                                 int Cout, int T, int k, int pad, void* stream) {
-  TL_REQUIRE(x && w && bias && z, "lite_conv_fwd: null pointer");
-  TL_REQUIRE(B > 0 && B <= 65535 && Cin > 0 && Cout > 0 && T > 0 && k >= 1 && 2 * pad == k - 1, "lite_conv_fwd: bad sizes (needs 'same' padding)");
-  const size_t lds = (size_t)Cin * (LT + k - 1) * 4;
-  TL_REQUIRE(lds <= 64 * 1024, "lite_conv_fwd: Cin too large for the LDS tile");
-  dim3 grid((T + LT - 1) / LT, B);
-  hipLaunchKernelGGL(lite_conv_fwd_kernel, grid, dim3(512), lds, (hipStream_t)stream, x, w, bias, z, part, Cin, Cout, T, k, pad);
-  return check_launch("lite_conv_fwd");
+  return conv_fwd_launch("lite_conv_fwd", x, w, bias, z, part, B, Cin, Cout, T, k, pad, stream);
+}
+extern "C" int tl_lite_conv_fwd_group(const float* x, const float* w, const float* bias, float* z, float* part, int M, int B,
+                                      int Cin, int Cout, int T, int k, int pad, int64_t s_x, int64_t s_w, int64_t s_bias,
+                                      int64_t s_z, int64_t s_part, const int32_t* active, void* stream) {
+  TL_REQUIRE_MEMBERS("lite_conv_fwd_group", M);
+  return conv_fwd_launch("lite_conv_fwd_group", x, w, bias, z, part, B, Cin, Cout, T, k, pad, stream, M, s_x, s_w, s_bias, s_z,
+                         s_part, active);
+}
+
+static int bn_finalize_launch(const char* what, const float* part, float* mean, float* rstd, float* run_mean, float* run_var,
+                              int nparts, int C, int64_t count, int T, float momentum, float eps, int training, int64_t* tracked,
+                              void* stream, int M = 1, int64_t s_part = 0, int64_t s_stat = 0, int64_t s_run = 0,
+                              int64_t s_tracked = 0, const int32_t* active = nullptr) {
+  TL_REQUIRE(mean && rstd && run_mean && run_var && C > 0 && (part || !training), "%s: bad arguments", what);
+  TL_REQUIRE(!training || (T > 0 && nparts % ((T + LT - 1) / LT) == 0 && count == (int64_t)(nparts / ((T + LT - 1) / LT)) * T),
+             "%s: partials do not match (rows, T)", what);
+  TL_REQUIRE(s_part >= 0, "%s: negative member stride", what);
+  TL_REQUIRE_STRIDE(what, M, s_stat, C, "mean / rstd");
+  TL_REQUIRE_STRIDE(what, M, s_run, C, "running_mean / running_var");
+  if (tracked) TL_REQUIRE_STRIDE(what, M, s_tracked, 1, "num_batches_tracked");
+  hipLaunchKernelGGL(lite_bn_finalize_kernel, dim3(C, 1, M), dim3(64), 0, (hipStream_t)stream, part, mean, rstd, run_mean, run_var,
+                     nparts, C, (long long)count, T, momentum, eps, training, (long long*)tracked, active, (long long)s_part,
+                     (long long)s_stat, (long long)s_run, (long long)s_tracked);
+  return check_launch(what);
 }
 extern "C" int tl_lite_bn_finalize(const float* part, float* mean, float* rstd, float* run_mean, float* run_var,
                                    int nparts, int C, int64_t count, int T, float momentum, float eps, int training,
                                    int64_t* tracked, void* stream) {
-  TL_REQUIRE(mean && rstd && run_mean && run_var && C > 0 && (part || !training), "lite_bn_finalize: bad arguments");
-  TL_REQUIRE(!training || (T > 0 && nparts % ((T + LT - 1) / LT) == 0 && count == (int64_t)(nparts / ((T + LT - 1) / LT)) * T),
-             "lite_bn_finalize: partials do not match (rows, T)");
-  hipLaunchKernelGGL(lite_bn_finalize_kernel, dim3(C), dim3(64), 0, (hipStream_t)stream, part, mean, rstd,
-                     run_mean, run_var, nparts, C, (long long)count, T, momentum, eps, training, (long long*)tracked);
-  return check_launch("lite_bn_finalize");
+  return bn_finalize_launch("lite_bn_finalize", part, mean, rstd, run_mean, run_var, nparts, C, count, T, momentum, eps, training,
+                            tracked, stream);
+}
+extern "C" int tl_lite_bn_finalize_group(const float* part, float* mean, float* rstd, float* run_mean, float* run_var, int M,
+                                         int nparts, int C, int64_t count, int T, float momentum, float eps, int training,
+                                         int64_t* tracked, int64_t s_part, int64_t s_stat, int64_t s_run, int64_t s_tracked,
+                                         const int32_t* active, void* stream) {
+  TL_REQUIRE_MEMBERS("lite_bn_finalize_group", M);
+  return bn_finalize_launch("lite_bn_finalize_group", part, mean, rstd, run_mean, run_var, nparts, C, count, T, momentum, eps,
+                            training, tracked, stream, M, s_part, s_stat, s_run, s_tracked, active);
+}
+
+static int bn_act_pool_fwd_launch(const char* what, const float* z, const float* mean, const float* rstd, const float* gamma,
+                                  const float* beta, float* y, int B, int C, int T, float slope, void* stream, int M = 1,
+                                  int64_t s_z = 0, int64_t s_stat = 0, int64_t s_gb = 0, int64_t s_y = 0,
+                                  const int32_t* active = nullptr) {
+  TL_REQUIRE(z && mean && rstd && gamma && beta && y && T >= 2, "%s: bad arguments", what);
+  const long long total = (long long)B * C * (T / 2);
+  TL_REQUIRE(s_z >= 0 && s_stat >= 0 && s_gb >= 0, "%s: negative member stride", what);
+  TL_REQUIRE_STRIDE(what, M, s_y, total, "y");
+  hipLaunchKernelGGL(lite_bn_act_pool_fwd_kernel, dim3(lgrid(total), 1, M), dim3(256), 0, (hipStream_t)stream, z, mean, rstd,
+                     gamma, beta, y, total, C, T, slope, active, (long long)s_z, (long long)s_stat, (long long)s_gb, (long long)s_y);
+  return check_launch(what);
 }
 extern "C" int tl_lite_bn_act_pool_fwd(const float* z, const float* mean, const float* rstd, const float* gamma,
                                        const float* beta, float* y, int B, int C, int T, float slope, void* stream) {
-  TL_REQUIRE(z && mean && rstd && gamma && beta && y && T >= 2, "lite_bn_act_pool_fwd: bad arguments");
-  const long long total = (long long)B * C * (T / 2);
-  hipLaunchKernelGGL(lite_bn_act_pool_fwd_kernel, dim3(lgrid(total)), dim3(256), 0, (hipStream_t)stream, z, mean, rstd,
-                     gamma, beta, y, total, C, T, slope);
-  return check_launch("lite_bn_act_pool_fwd");
+  return bn_act_pool_fwd_launch("lite_bn_act_pool_fwd", z, mean, rstd, gamma, beta, y, B, C, T, slope, stream);
+}
+extern "C" int tl_lite_bn_act_pool_fwd_group(const float* z, const float* mean, const float* rstd, const float* gamma,
+                                             const float* beta, float* y, int M, int B, int C, int T, float slope, int64_t s_z,
+                                             int64_t s_stat, int64_t s_gb, int64_t s_y, const int32_t* active, void* stream) {
+  TL_REQUIRE_MEMBERS("lite_bn_act_pool_fwd_group", M);
+  return bn_act_pool_fwd_launch("lite_bn_act_pool_fwd_group", z, mean, rstd, gamma, beta, y, B, C, T, slope, stream, M, s_z,
+                                s_stat, s_gb, s_y, active);
+}
+
+static int bn_act_pool_bwd_launch(const char* what, const float* dy, const float* z, const float* mean, const float* rstd,
+                                  const float* gamma, const float* beta, float* dz, float* dgamma, float* dbeta, float* work,
+                                  int B, int C, int T, float slope, int training, void* stream, int M = 1, int64_t s_dy = 0,
+                                  int64_t s_z = 0, int64_t s_stat = 0, int64_t s_gb = 0, int64_t s_dz = 0, int64_t s_dgb = 0,
+                                  int64_t s_work = 0, const int32_t* active = nullptr) {
+  TL_REQUIRE(dy && z && mean && rstd && gamma && beta && dz && dgamma && dbeta && work, "%s: null pointer", what);
+  TL_REQUIRE(B > 0 && B <= 65535 && C > 0 && T >= 2, "%s: bad sizes", what);
+  TL_REQUIRE(s_dy >= 0 && s_z >= 0 && s_stat >= 0 && s_gb >= 0, "%s: negative member stride", what);
+  TL_REQUIRE_STRIDE(what, M, s_dz, (int64_t)B * C * T, "dz");
+  TL_REQUIRE_STRIDE(what, M, s_dgb, C, "dgamma / dbeta");
+  TL_REQUIRE_STRIDE(what, M, s_work, (int64_t)B * C * 2, "work");
+  hipStream_t st = (hipStream_t)stream;
+  float* part = work;                         // [B][C][2]
+  hipLaunchKernelGGL(lite_bn_act_pool_bwd_kernel, dim3(C, B, M), dim3(256), 0, st, dy, z, mean, rstd, gamma, beta, dz, part, C, T,
+                     slope, active, (long long)s_dy, (long long)s_z, (long long)s_stat, (long long)s_gb, (long long)s_dz,
+                     (long long)s_work);
+  hipLaunchKernelGGL(lite_bn_dz_kernel, dim3(C, B, M), dim3(256), 0, st, dz, z, mean, rstd, gamma, part, dgamma, dbeta, B, C, T,
+                     (long long)B * T, training, active, (long long)s_z, (long long)s_stat, (long long)s_gb, (long long)s_dz,
+                     (long long)s_dgb, (long long)s_work);
+  return check_launch(what);
 }
 extern "C" int tl_lite_bn_act_pool_bwd(const float* dy, const float* z, const float* mean, const float* rstd,
                                        const float* gamma, const float* beta, float* dz, float* dgamma, float* dbeta,
                                        float* work, int B, int C, int T, float slope, int training, void* stream) {
-  TL_REQUIRE(dy && z && mean && rstd && gamma && beta && dz && dgamma && dbeta && work, "lite_bn_act_pool_bwd: null pointer");
-  TL_REQUIRE(B > 0 && B <= 65535 && C > 0 && T >= 2, "lite_bn_act_pool_bwd: bad sizes");
-  hipStream_t st = (hipStream_t)stream;
-  float* part = work;                         // [B][C][2]
-  hipLaunchKernelGGL(lite_bn_act_pool_bwd_kernel, dim3(C, B), dim3(256), 0, st, dy, z, mean, rstd, gamma, beta, dz, part, C, T, slope);
-  hipLaunchKernelGGL(lite_bn_dz_kernel, dim3(C, B), dim3(256), 0, st, dz, z, mean, rstd, gamma, part, dgamma, dbeta, B, C, T,
-                     (long long)B * T, training);
-  return check_launch("lite_bn_act_pool_bwd");
+  return bn_act_pool_bwd_launch("lite_bn_act_pool_bwd", dy, z, mean, rstd, gamma, beta, dz, dgamma, dbeta, work, B, C, T, slope,
+                                training, stream);
 }
-extern "C" int tl_lite_conv_bwd(const float* dz, const float* x, const float* w, float* dx, float* dwpart, float* dbpart,
-                                int B, int Cin, int Cout, int T, int k, int pad, void* stream) {
-  TL_REQUIRE(dz && x && w && dwpart && dbpart, "lite_conv_bwd: null pointer");
-  TL_REQUIRE(B > 0 && B <= 65535 && 2 * pad == k - 1, "lite_conv_bwd: bad sizes");
+extern "C" int tl_lite_bn_act_pool_bwd_group(const float* dy, const float* z, const float* mean, const float* rstd,
+                                             const float* gamma, const float* beta, float* dz, float* dgamma, float* dbeta,
+                                             float* work, int M, int B, int C, int T, float slope, int training, int64_t s_dy,
+                                             int64_t s_z, int64_t s_stat, int64_t s_gb, int64_t s_dz, int64_t s_dgb,
+                                             int64_t s_work, const int32_t* active, void* stream) {
+  TL_REQUIRE_MEMBERS("lite_bn_act_pool_bwd_group", M);
+  return bn_act_pool_bwd_launch("lite_bn_act_pool_bwd_group", dy, z, mean, rstd, gamma, beta, dz, dgamma, dbeta, work, B, C, T,
+                                slope, training, stream, M, s_dy, s_z, s_stat, s_gb, s_dz, s_dgb, s_work, active);
+}
+
+static int conv_bwd_launch(const char* what, const float* dz, const float* x, const float* w, float* dx, float* dwpart,
+                           float* dbpart, int B, int Cin, int Cout, int T, int k, int pad, void* stream, int M = 1,
+                           int64_t s_dz = 0, int64_t s_x = 0, int64_t s_w = 0, int64_t s_dx = 0, int64_t s_dwpart = 0,
+                           int64_t s_dbpart = 0, const int32_t* active = nullptr) {
+  TL_REQUIRE(dz && x && w && dwpart && dbpart, "%s: null pointer", what);
+  TL_REQUIRE(B > 0 && B <= 65535 && 2 * pad == k - 1, "%s: bad sizes", what);
+  TL_REQUIRE(s_dz >= 0 && s_x >= 0 && s_w >= 0, "%s: negative member stride", what);
+  if (dx) TL_REQUIRE_STRIDE(what, M, s_dx, (int64_t)B * Cin * T, "dx");
+  TL_REQUIRE_STRIDE(what, M, s_dwpart, (int64_t)B * Cout * Cin * k, "dwpart");
+  TL_REQUIRE_STRIDE(what, M, s_dbpart, (int64_t)B * Cout, "dbpart");
   hipStream_t st = (hipStream_t)stream;
   if (dx) {
     const size_t lds = (size_t)Cout * (LT + k - 1) * 4;
-    TL_REQUIRE(lds <= 64 * 1024, "lite_conv_bwd: Cout too large for the LDS tile");
-    hipLaunchKernelGGL(lite_conv_dx_kernel, dim3((T + LT - 1) / LT, B), dim3(512), lds, st, dz, w, dx, Cin, Cout, T, k, pad);
+    TL_REQUIRE(lds <= 64 * 1024, "%s: Cout too large for the LDS tile", what);
+    hipLaunchKernelGGL(lite_conv_dx_kernel, dim3((T + LT - 1) / LT, B, M), dim3(512), lds, st, dz, w, dx, Cin, Cout, T, k, pad,
+                       active, (long long)s_dz, (long long)s_w, (long long)s_dx);
   }
   const int max_o = (255 + Cin * k - 1) / (Cin * k) + 1;              // output channels a block of 256 elements can touch
   const size_t lds_dw = ((size_t)Cin * T + (size_t)max_o * T) * 4;
   const int use_lds = lds_dw <= 64 * 1024;
-  hipLaunchKernelGGL(lite_conv_dw_kernel, dim3(B, (Cout * Cin * k + 255) / 256), dim3(256), use_lds ? lds_dw : 0, st, dz, x,
-                     dwpart, dbpart, Cin, Cout, T, k, pad, use_lds);
-  return check_launch("lite_conv_bwd");
+  hipLaunchKernelGGL(lite_conv_dw_kernel, dim3(B, (Cout * Cin * k + 255) / 256, M), dim3(256), use_lds ? lds_dw : 0, st, dz, x,
+                     dwpart, dbpart, Cin, Cout, T, k, pad, use_lds, active, (long long)s_dz, (long long)s_x, (long long)s_dwpart,
+                     (long long)s_dbpart);
+  return check_launch(what);
+}
+extern "C" int tl_lite_conv_bwd(const float* dz, const float* x, const float* w, float* dx, float* dwpart, float* dbpart,
+                                int B, int Cin, int Cout, int T, int k, int pad, void* stream) {
+  return conv_bwd_launch("lite_conv_bwd", dz, x, w, dx, dwpart, dbpart, B, Cin, Cout, T, k, pad, stream);
+}
+extern "C" int tl_lite_conv_bwd_group(const float* dz, const float* x, const float* w, float* dx, float* dwpart, float* dbpart,
+                                      int M, int B, int Cin, int Cout, int T, int k, int pad, int64_t s_dz, int64_t s_x,
+                                      int64_t s_w, int64_t s_dx, int64_t s_dwpart, int64_t s_dbpart, const int32_t* active,
+                                      void* stream) {
+  TL_REQUIRE_MEMBERS("lite_conv_bwd_group", M);
+  return conv_bwd_launch("lite_conv_bwd_group", dz, x, w, dx, dwpart, dbpart, B, Cin, Cout, T, k, pad, stream, M, s_dz, s_x, s_w,
+                         s_dx, s_dwpart, s_dbpart, active);
+}
+
+static int lstm_fwd_launch(const char* what, const float* xl, const float* w_ih, const float* w_hh, const float* b_ih,
+                           const float* b_hh, float* act, float* cs, float* hs, int B, int L, int H, int in_dim, void* stream,
+                           int M = 1, int64_t s_xl = 0, int64_t s_wih = 0, int64_t s_whh = 0, int64_t s_b = 0, int64_t s_act = 0,
+                           int64_t s_cs = 0, const int32_t* active = nullptr) {
+  TL_REQUIRE(xl && w_ih && w_hh && b_ih && b_hh && act && cs && hs && B > 0 && L > 0 && H > 0, "%s: bad arguments", what);
+  const size_t lds = (size_t)6 * H * 4;
+  TL_REQUIRE(lds <= 64 * 1024, "%s: hidden size too large", what);
+  TL_REQUIRE(s_xl >= 0 && s_wih >= 0 && s_whh >= 0 && s_b >= 0, "%s: negative member stride", what);
+  TL_REQUIRE_STRIDE(what, M, s_act, (int64_t)B * L * 4 * H, "act");
+  TL_REQUIRE_STRIDE(what, M, s_cs, (int64_t)B * L * H, "cs / hs");
+  hipLaunchKernelGGL(lite_lstm_fwd_kernel, dim3(B, 1, M), dim3(256), lds, (hipStream_t)stream, xl, w_ih, w_hh, b_ih, b_hh, act,
+                     cs, hs, L, H, in_dim, active, (long long)s_xl, (long long)s_wih, (long long)s_whh, (long long)s_b,
+                     (long long)s_act, (long long)s_cs);
+  return check_launch(what);
 }
 extern "C" int tl_lite_lstm_fwd(const float* xl, const float* w_ih, const float* w_hh, const float* b_ih,
                                 const float* b_hh, float* act, float* cs, float* hs, int B, int L, int H, int in_dim,
                                 void* stream) {
-  TL_REQUIRE(xl && w_ih && w_hh && b_ih && b_hh && act && cs && hs && B > 0 && L > 0 && H > 0, "lite_lstm_fwd: bad arguments");
-  const size_t lds = (size_t)6 * H * 4;
-  TL_REQUIRE(lds <= 64 * 1024, "lite_lstm_fwd: hidden size too large");
-  hipLaunchKernelGGL(lite_lstm_fwd_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, xl, w_ih, w_hh, b_ih, b_hh, act, cs,
-                     hs, L, H, in_dim);
-  return check_launch("lite_lstm_fwd");
+  return lstm_fwd_launch("lite_lstm_fwd", xl, w_ih, w_hh, b_ih, b_hh, act, cs, hs, B, L, H, in_dim, stream);
+}
+extern "C" int tl_lite_lstm_fwd_group(const float* xl, const float* w_ih, const float* w_hh, const float* b_ih,
+                                      const float* b_hh, float* act, float* cs, float* hs, int M, int B, int L, int H, int in_dim,
+                                      int64_t s_xl, int64_t s_wih, int64_t s_whh, int64_t s_b, int64_t s_act, int64_t s_cs,
+                                      const int32_t* active, void* stream) {
+  TL_REQUIRE_MEMBERS("lite_lstm_fwd_group", M);
+  return lstm_fwd_launch("lite_lstm_fwd_group", xl, w_ih, w_hh, b_ih, b_hh, act, cs, hs, B, L, H, in_dim, stream, M, s_xl, s_wih,
+                         s_whh, s_b, s_act, s_cs, active);
+}
+
+static int lstm_bwd_launch(const char* what, const float* dh_last, const float* w_hh, const float* act, const float* cs,
+                           float* dgates, int B, int L, int H, int ld_dh, void* stream, int M = 1, int64_t s_dh = 0,
+                           int64_t s_whh = 0, int64_t s_act = 0, int64_t s_cs = 0, const int32_t* active = nullptr) {
+  TL_REQUIRE(dh_last && w_hh && act && cs && dgates && B > 0 && L > 0 && H > 0, "%s: bad arguments", what);
+  const size_t lds = (size_t)(6 * H + 256) * 4;
+  TL_REQUIRE(lds <= 64 * 1024, "%s: hidden size too large", what);
+  TL_REQUIRE(s_dh >= 0 && s_whh >= 0 && s_cs >= 0, "%s: negative member stride", what);
+  TL_REQUIRE_STRIDE(what, M, s_act, (int64_t)B * L * 4 * H, "act / dgates");
+  hipLaunchKernelGGL(lite_lstm_bwd_kernel, dim3(B, 1, M), dim3(256), lds, (hipStream_t)stream, dh_last, w_hh, act, cs, dgates, L,
+                     H, ld_dh, active, (long long)s_dh, (long long)s_whh, (long long)s_act, (long long)s_cs);
+  return check_launch(what);
 }
 extern "C" int tl_lite_lstm_bwd(const float* dh_last, const float* w_hh, const float* act, const float* cs,
                                 float* dgates, int B, int L, int H, int ld_dh, void* stream) {
-  TL_REQUIRE(dh_last && w_hh && act && cs && dgates && B > 0 && L > 0 && H > 0, "lite_lstm_bwd: bad arguments");
-  const size_t lds = (size_t)(6 * H + 256) * 4;
-  TL_REQUIRE(lds <= 64 * 1024, "lite_lstm_bwd: hidden size too large");
-  hipLaunchKernelGGL(lite_lstm_bwd_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, dh_last, w_hh, act, cs, dgates, L,
-                     H, ld_dh);
-  return check_launch("lite_lstm_bwd");
+  return lstm_bwd_launch("lite_lstm_bwd", dh_last, w_hh, act, cs, dgates, B, L, H, ld_dh, stream);
+}
+extern "C" int tl_lite_lstm_bwd_group(const float* dh_last, const float* w_hh, const float* act, const float* cs, float* dgates,
+                                      int M, int B, int L, int H, int ld_dh, int64_t s_dh, int64_t s_whh, int64_t s_act,
+                                      int64_t s_cs, const int32_t* active, void* stream) {
+  TL_REQUIRE_MEMBERS("lite_lstm_bwd_group", M);
+  return lstm_bwd_launch("lite_lstm_bwd_group", dh_last, w_hh, act, cs, dgates, B, L, H, ld_dh, stream, M, s_dh, s_whh, s_act,
+                         s_cs, active);
+}
+
+static int cat_launch(const char* what, const float* y2, const float* hs, float* feat, int B, int F, int H, int L, int ldf,
+                      float p_drop, uint64_t seed, const uint64_t* seed_dev, void* stream, int M = 1, int64_t s_y2 = 0,
+                      int64_t s_hs = 0, int64_t s_feat = 0, const int32_t* active = nullptr) {
+  TL_REQUIRE(y2 && hs && feat && ldf >= F + H && p_drop >= 0.f && p_drop < 1.f, "%s: bad arguments", what);
+  TL_REQUIRE(s_y2 >= 0 && s_hs >= 0, "%s: negative member stride", what);
+  TL_REQUIRE_STRIDE(what, M, s_feat, (int64_t)B * ldf, "feat");
+  hipLaunchKernelGGL(lite_cat_kernel, dim3(lgrid((long long)B * ldf), 1, M), dim3(256), 0, (hipStream_t)stream, y2, hs, feat, B, F,
+                     H, L, ldf, p_drop, seed, seed_dev, active, (long long)s_y2, (long long)s_hs, (long long)s_feat);
+  return check_launch(what);
+}
+static int uncat_launch(const char* what, const float* dfeat, float* dy2, float* dh, int B, int F, int H, int ldf, float p_drop,
+                        uint64_t seed, const uint64_t* seed_dev, void* stream, int M = 1, int64_t s_dfeat = 0, int64_t s_dy2 = 0,
+                        int64_t s_dh = 0, const int32_t* active = nullptr) {
+  TL_REQUIRE(dfeat && dy2 && dh && ldf >= F + H && p_drop >= 0.f && p_drop < 1.f, "%s: bad arguments", what);
+  TL_REQUIRE(s_dfeat >= 0, "%s: negative member stride", what);
+  TL_REQUIRE_STRIDE(what, M, s_dy2, (int64_t)B * F, "dy2");
+  TL_REQUIRE_STRIDE(what, M, s_dh, (int64_t)B * H, "dh");
+  hipLaunchKernelGGL(lite_uncat_kernel, dim3(lgrid((long long)B * (F + H)), 1, M), dim3(256), 0, (hipStream_t)stream, dfeat, dy2,
+                     dh, B, F, H, ldf, p_drop, seed, seed_dev, active, (long long)s_dfeat, (long long)s_dy2, (long long)s_dh);
+  return check_launch(what);
 }
 extern "C" int tl_lite_cat(const float* y2, const float* hs, float* feat, int B, int F, int H, int L, int ldf,
                            float p_drop, uint64_t seed, void* stream) {
-  TL_REQUIRE(y2 && hs && feat && ldf >= F + H && p_drop >= 0.f && p_drop < 1.f, "lite_cat: bad arguments");
-  hipLaunchKernelGGL(lite_cat_kernel, dim3(lgrid((long long)B * ldf)), dim3(256), 0, (hipStream_t)stream, y2, hs, feat, B, F,
-                     H, L, ldf, p_drop, seed, (const uint64_t*)nullptr);
-  return check_launch("lite_cat");
+  return cat_launch("lite_cat", y2, hs, feat, B, F, H, L, ldf, p_drop, seed, nullptr, stream);
 }
 extern "C" int tl_lite_uncat(const float* dfeat, float* dy2, float* dh, int B, int F, int H, int ldf, float p_drop,
                              uint64_t seed, void* stream) {
-  TL_REQUIRE(dfeat && dy2 && dh && ldf >= F + H && p_drop >= 0.f && p_drop < 1.f, "lite_uncat: bad arguments");
-  hipLaunchKernelGGL(lite_uncat_kernel, dim3(lgrid((long long)B * (F + H))), dim3(256), 0, (hipStream_t)stream, dfeat, dy2,
-                     dh, B, F, H, ldf, p_drop, seed, (const uint64_t*)nullptr);
-  return check_launch("lite_uncat");
+  return uncat_launch("lite_uncat", dfeat, dy2, dh, B, F, H, ldf, p_drop, seed, nullptr, stream);
 }
 // the same two with the dropout seed read from device memory (one uint64): the launches can sit in a HIP graph whose
 // replays draw a fresh mask each, the caller updating *seed_dev between replays
 extern "C" int tl_lite_cat_dev(const float* y2, const float* hs, float* feat, int B, int F, int H, int L, int ldf,
                                float p_drop, const uint64_t* seed_dev, void* stream) {
-  TL_REQUIRE(y2 && hs && feat && seed_dev && ldf >= F + H && p_drop >= 0.f && p_drop < 1.f, "lite_cat_dev: bad arguments");
-  hipLaunchKernelGGL(lite_cat_kernel, dim3(lgrid((long long)B * ldf)), dim3(256), 0, (hipStream_t)stream, y2, hs, feat, B, F,
-                     H, L, ldf, p_drop, (uint64_t)0, seed_dev);
-  return check_launch("lite_cat_dev");
+  TL_REQUIRE(seed_dev, "lite_cat_dev: bad arguments");
+  return cat_launch("lite_cat_dev", y2, hs, feat, B, F, H, L, ldf, p_drop, 0, seed_dev, stream);
 }
 extern "C" int tl_lite_uncat_dev(const float* dfeat, float* dy2, float* dh, int B, int F, int H, int ldf, float p_drop,
                                  const uint64_t* seed_dev, void* stream) {
-  TL_REQUIRE(dfeat && dy2 && dh && seed_dev && ldf >= F + H && p_drop >= 0.f && p_drop < 1.f, "lite_uncat_dev: bad arguments");
-  hipLaunchKernelGGL(lite_uncat_kernel, dim3(lgrid((long long)B * (F + H))), dim3(256), 0, (hipStream_t)stream, dfeat, dy2,
-                     dh, B, F, H, ldf, p_drop, (uint64_t)0, seed_dev);
-  return check_launch("lite_uncat_dev");
+  TL_REQUIRE(seed_dev, "lite_uncat_dev: bad arguments");
+  return uncat_launch("lite_uncat_dev", dfeat, dy2, dh, B, F, H, ldf, p_drop, 0, seed_dev, stream);
+}
+// ... for M members: the seeds are a table of M words in device memory, member m draws the mask of the single launch with
+// seed_dev[m]
+extern "C" int tl_lite_cat_group(const float* y2, const float* hs, float* feat, int M, int B, int F, int H, int L, int ldf,
+                                 float p_drop, const uint64_t* seed_dev, int64_t s_y2, int64_t s_hs, int64_t s_feat,
+                                 const int32_t* active, void* stream) {
+  TL_REQUIRE_MEMBERS("lite_cat_group", M);
+  TL_REQUIRE(seed_dev, "lite_cat_group: the seed table is null");
+  return cat_launch("lite_cat_group", y2, hs, feat, B, F, H, L, ldf, p_drop, 0, seed_dev, stream, M, s_y2, s_hs, s_feat, active);
+}
+extern "C" int tl_lite_uncat_group(const float* dfeat, float* dy2, float* dh, int M, int B, int F, int H, int ldf, float p_drop,
+                                   const uint64_t* seed_dev, int64_t s_dfeat, int64_t s_dy2, int64_t s_dh,
+                                   const int32_t* active, void* stream) {
+  TL_REQUIRE_MEMBERS("lite_uncat_group", M);
+  TL_REQUIRE(seed_dev, "lite_uncat_group: the seed table is null");
+  return uncat_launch("lite_uncat_group", dfeat, dy2, dh, B, F, H, ldf, p_drop, 0, seed_dev, stream, M, s_dfeat, s_dy2, s_dh,
+                      active);
 }

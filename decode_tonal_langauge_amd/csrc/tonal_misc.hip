@@ -397,7 +397,14 @@ __global__ __launch_bounds__(256) void permute_reduce_kernel(const float* __rest
 // partials of a convolution's weight and bias gradient (tl_lite_conv_bwd) reduced together
 __global__ __launch_bounds__(256) void sum_slabs2_kernel(const float* __restrict__ srcA, float* __restrict__ dstA, long long nA,
                                                          const float* __restrict__ srcB, float* __restrict__ dstB, long long nB,
-                                                         int nz) {
+                                                         int nz, const int32_t* __restrict__ active, long long s_srcA,
+                                                         long long s_dstA, long long s_srcB, long long s_dstB) {
+  // member blockIdx.y of a group launch (include/tonal_hip.h "group launches"): its pointers lie the member strides behind member
+  // 0's; a member whose active word is 0 returns before its first load.  The single launch is member 0 of a group of one.
+  const int mem = blockIdx.y;
+  if (active != nullptr && active[mem] == 0) return;
+  srcA += mem * s_srcA, dstA += mem * s_dstA;
+  if (nB > 0) srcB += mem * s_srcB, dstB += mem * s_dstB;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < nA + nB; i += (long long)gridDim.x * blockDim.x) {
     const bool second = i >= nA;
     const float* s = second ? srcB + (i - nA) : srcA + i;
@@ -439,8 +446,13 @@ __global__ __launch_bounds__(256) void permute_reduce_zpar_kernel(const float* _
 // columns, 256/(ncols/4) rows per pass, 4 independent row loads in flight per thread, LDS
 // reduction over the row lanes (fixed order -> deterministic).
 __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ G, float* __restrict__ partial,
-                                                     long long rows, int ncols, int ld, int Tp, int Tvalid) {
+                                                     long long rows, int ncols, int ld, int Tp, int Tvalid,
+                                                     const int32_t* __restrict__ members_on, long long s_G, long long s_part) {
   __shared__ f32x4 red[256];
+  // member blockIdx.y of a group launch (tl_colsum_group): G and partial lie s_G, s_part elements behind member 0's; a member
+  // whose word is 0 returns before its first load.  The single launch is member 0 of a group of one.
+  if (members_on != nullptr && members_on[blockIdx.y] == 0) return;
+  G += blockIdx.y * s_G, partial += blockIdx.y * s_part;
   const int tpr = ncols >> 2;                 // threads per row (ncols % 4 == 0, tpr <= 256)
   const int rpb = 256 / tpr;                  // rows per pass
   const int c4 = threadIdx.x % tpr, rl = threadIdx.x / tpr;
@@ -553,7 +565,15 @@ __global__ __launch_bounds__(256) void lstm_cell_bwd_kernel(const float* __restr
 
 __global__ __launch_bounds__(256) void lstm_ih_grad_kernel(const float* __restrict__ dgates, const float* __restrict__ x,
                                                            float* __restrict__ dw_ih, float* __restrict__ db,
-                                                           float* __restrict__ db2, int L, int U, int H, int in_dim) {
+                                                           float* __restrict__ db2, int L, int U, int H, int in_dim,
+                                                           const int32_t* __restrict__ active, long long s_dg, long long s_x,
+                                                           long long s_dw, long long s_db) {
+  // member blockIdx.y of a group launch (include/tonal_hip.h "group launches"): its pointers lie the member strides behind member
+  // 0's; a member whose active word is 0 returns before its first load.  The single launch is member 0 of a group of one.
+  const int mem = blockIdx.y;
+  if (active != nullptr && active[mem] == 0) return;
+  dgates += mem * s_dg, x += mem * s_x, dw_ih += mem * s_dw, db += mem * s_db;
+  if (db2) db2 += mem * s_db;
   const long long r = blockIdx.x * (long long)blockDim.x + threadIdx.x;
   if (r >= 4LL * H) return;
   float accw[MAXKT];
@@ -577,7 +597,15 @@ __global__ __launch_bounds__(256) void lstm_ih_grad_kernel(const float* __restri
 // few gate rows (SynthesisLite: 4H = 256): one wave per row, lanes stride over the (t,u) pairs
 __global__ __launch_bounds__(64) void lstm_ih_grad_wave_kernel(const float* __restrict__ dgates, const float* __restrict__ x,
                                                                float* __restrict__ dw_ih, float* __restrict__ db,
-                                                               float* __restrict__ db2, int LU, int H, int in_dim) {
+                                                               float* __restrict__ db2, int LU, int H, int in_dim,
+                                                               const int32_t* __restrict__ active, long long s_dg,
+                                                               long long s_x, long long s_dw, long long s_db) {
+  // member blockIdx.y of a group launch (include/tonal_hip.h "group launches"): its pointers lie the member strides behind member
+  // 0's; a member whose active word is 0 returns before its first load.  The single launch is member 0 of a group of one.
+  const int mem = blockIdx.y;
+  if (active != nullptr && active[mem] == 0) return;
+  dgates += mem * s_dg, x += mem * s_x, dw_ih += mem * s_dw, db += mem * s_db;
+  if (db2) db2 += mem * s_db;
   const long long r = blockIdx.x;
   const int lane = threadIdx.x;
   float accw[MAXKT];
@@ -810,8 +838,16 @@ __global__ __launch_bounds__(256) void concat_dh_kernel(const float* __restrict_
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void l1_mcd_kernel(const float* __restrict__ out, const float* __restrict__ tgt,
                                                      float* __restrict__ dout, float* __restrict__ stats, int B, int D,
-                                                     int ldd, int trunc_targets, float grad_scale) {
+                                                     int ldd, int trunc_targets, float grad_scale,
+                                                     const int32_t* __restrict__ active, long long s_out, long long s_tgt,
+                                                     long long s_dout) {
   __shared__ float s1[1024], s2[1024];    // (16 waves: a batch of 64 rows is four dependent rounds of loads, not sixteen)
+  // member blockIdx.y of a group launch (include/tonal_hip.h "group launches"): its pointers lie the member strides behind member
+  // 0's; a member whose active word is 0 returns before its first load.  The single launch is member 0 of a group of one.
+  const int mem = blockIdx.y;
+  if (active != nullptr && active[mem] == 0) return;
+  out += mem * s_out, tgt += mem * s_tgt, stats += mem * 4;      // one workgroup per member: each keeps the fixed order
+  if (dout) dout += mem * s_dout;
   float l1 = 0.f, mcd = 0.f;
   const float gs = grad_scale / ((float)B * (float)D);
   // a wave per row, lanes across the D outputs (coalesced), a shuffle tree per row: the row sums are formed in a
@@ -1122,10 +1158,17 @@ __global__ void tone_dynamics_kernel(const long long* __restrict__ tone, const l
 // out[i] = LeakyReLU(sum_z slab[z][i] + bias[i % ncols]): the split-K reduction of a Linear layer with its bias and activation
 __global__ __launch_bounds__(256) void splitk_bias_lrelu_kernel(const float* __restrict__ slab, const float* __restrict__ bias,
                                                                 float* __restrict__ out, int nz, long long n, int ncols,
-                                                                float slope) {
+                                                                float slope, long long zs, const int32_t* __restrict__ active,
+                                                                long long s_slab, long long s_bias, long long s_out) {
+  // member blockIdx.y of a group launch (include/tonal_hip.h "group launches"): its pointers lie the member strides behind member
+  // 0's; a member whose active word is 0 returns before its first load.  The single launch is member 0 of a group of one.
+  const int mem = blockIdx.y;
+  if (active != nullptr && active[mem] == 0) return;
+  slab += mem * s_slab, out += mem * s_out;
+  if (bias) bias += mem * s_bias;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     float acc = 0.f;
-    for (int z = 0; z < nz; ++z) acc += slab[(long long)z * n + i];
+    for (int z = 0; z < nz; ++z) acc += slab[(long long)z * zs + i];     // zs: elements between split-K slabs (n, or M n)
     if (bias) acc += bias[i % ncols];
     out[i] = acc > 0.f ? acc : acc * slope;
   }
@@ -1419,21 +1462,54 @@ extern "C" int tl_permute_reduce(const float* src, float* dst, const int64_t dim
   return check_launch("permute_reduce");
 }
 
+// (the launch functions of this kind serve a single entry - M = 1, strides 0, active null - and its tl_*_group neighbour)
+#define TL_REQUIRE_STRIDE(entry, M, s, need, what)                                                                        \
+  TL_REQUIRE((s) >= 0 && ((M) == 1 || (int64_t)(s) >= (int64_t)(need)), "%s: member stride of %s shorter than a member's extent", \
+             entry, what)
+
+static int sum_slabs2_launch(const char* what, const float* srcA, float* dstA, int64_t nA, const float* srcB, float* dstB,
+                             int64_t nB, int nz, void* stream, int M = 1, int64_t s_srcA = 0, int64_t s_dstA = 0,
+                             int64_t s_srcB = 0, int64_t s_dstB = 0, const int32_t* active = nullptr) {
+  TL_REQUIRE(srcA && dstA && nA > 0 && nz > 0 && nB >= 0 && (nB == 0 || (srcB && dstB)), "%s: bad arguments", what);
+  TL_REQUIRE(s_srcA >= 0 && s_srcB >= 0, "%s: negative member stride", what);
+  TL_REQUIRE_STRIDE(what, M, s_dstA, nA, "dstA");
+  if (nB > 0) TL_REQUIRE_STRIDE(what, M, s_dstB, nB, "dstB");
+  hipLaunchKernelGGL(sum_slabs2_kernel, dim3(grid_for(nA + nB), (unsigned)M), dim3(256), 0, (hipStream_t)stream, srcA, dstA,
+                     (long long)nA, srcB, dstB, (long long)nB, nz, active, (long long)s_srcA, (long long)s_dstA, (long long)s_srcB,
+                     (long long)s_dstB);
+  return check_launch(what);
+}
 extern "C" int tl_sum_slabs2(const float* srcA, float* dstA, int64_t nA, const float* srcB, float* dstB, int64_t nB, int nz,
                              void* stream) {
-  TL_REQUIRE(srcA && dstA && nA > 0 && nz > 0 && nB >= 0 && (nB == 0 || (srcB && dstB)), "sum_slabs2: bad arguments");
-  hipLaunchKernelGGL(sum_slabs2_kernel, dim3(grid_for(nA + nB)), dim3(256), 0, (hipStream_t)stream, srcA, dstA, (long long)nA, srcB,
-                     dstB, (long long)nB, nz);
-  return check_launch("sum_slabs2");
+  return sum_slabs2_launch("sum_slabs2", srcA, dstA, nA, srcB, dstB, nB, nz, stream);
+}
+extern "C" int tl_sum_slabs2_group(const float* srcA, float* dstA, int64_t nA, const float* srcB, float* dstB, int64_t nB, int nz,
+                                   int M, int64_t s_srcA, int64_t s_dstA, int64_t s_srcB, int64_t s_dstB, const int32_t* active,
+                                   void* stream) {
+  TL_REQUIRE_MEMBERS("sum_slabs2_group", M);
+  return sum_slabs2_launch("sum_slabs2_group", srcA, dstA, nA, srcB, dstB, nB, nz, stream, M, s_srcA, s_dstA, s_srcB, s_dstB,
+                           active);
 }
 
+static int colsum_launch(const char* what, const float* G, float* partial, int nblk, int64_t rows, int ncols, int ld, int Tp,
+                         int Tvalid, void* stream, int M = 1, int64_t s_G = 0, int64_t s_part = 0,
+                         const int32_t* active = nullptr) {
+  TL_REQUIRE(G && partial && nblk > 0 && rows > 0 && ncols > 0 && ld >= ncols && Tp > 0, "%s: bad arguments", what);
+  TL_REQUIRE(ncols % 4 == 0 && ncols <= 1024 && ld % 4 == 0, "%s: ncols must be a multiple of 4 and <= 1024", what);
+  TL_REQUIRE(s_G >= 0 && s_G % 4 == 0 && s_part % 4 == 0, "%s: the member strides must be non-negative multiples of 4 elements", what);
+  TL_REQUIRE_STRIDE(what, M, s_part, (int64_t)nblk * ncols, "partial");
+  hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)nblk, (unsigned)M), dim3(256), 0, (hipStream_t)stream, G, partial,
+                     (long long)rows, ncols, ld, Tp, Tvalid, active, (long long)s_G, (long long)s_part);
+  return check_launch(what);
+}
 extern "C" int tl_colsum(const float* G, float* partial, int nblk, int64_t rows, int ncols, int ld, int Tp,
                          int Tvalid, void* stream) {
-  TL_REQUIRE(G && partial && nblk > 0 && rows > 0 && ncols > 0 && ld >= ncols && Tp > 0, "colsum: bad arguments");
-  TL_REQUIRE(ncols % 4 == 0 && ncols <= 1024 && ld % 4 == 0, "colsum: ncols must be a multiple of 4 and <= 1024");
-  hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, G, partial,
-                     (long long)rows, ncols, ld, Tp, Tvalid);
-  return check_launch("colsum");
+  return colsum_launch("colsum", G, partial, nblk, rows, ncols, ld, Tp, Tvalid, stream);
+}
+extern "C" int tl_colsum_group(const float* G, float* partial, int nblk, int64_t rows, int ncols, int ld, int Tp, int Tvalid, int M,
+                               int64_t s_G, int64_t s_part, const int32_t* active, void* stream) {
+  TL_REQUIRE_MEMBERS("colsum_group", M);
+  return colsum_launch("colsum_group", G, partial, nblk, rows, ncols, ld, Tp, Tvalid, stream, M, s_G, s_part, active);
 }
 
 extern "C" int tl_lstm_cell_fwd(const float* hh, const float* x_t, const float* w_ih, const float* b_ih,
@@ -1492,18 +1568,34 @@ extern "C" int tl_lstm_cell_bwd(const float* dh, const float* dh_rec, const floa
   return check_launch("lstm_cell_bwd");
 }
 
+static int lstm_ih_grad_launch(const char* what, const float* dgates, const float* x, float* dw_ih, float* db, float* db2, int L,
+                               int U, int H, int in_dim, void* stream, int M = 1, int64_t s_dg = 0, int64_t s_x = 0,
+                               int64_t s_dw = 0, int64_t s_db = 0, const int32_t* active = nullptr) {
+  TL_REQUIRE(dgates && x && dw_ih && db, "%s: null pointer", what);
+  TL_REQUIRE(in_dim >= 1 && in_dim <= MAXKT, "%s: in_dim must be 1..%d", what, MAXKT);
+  const long long total = 4LL * H;
+  TL_REQUIRE(s_dg >= 0 && s_x >= 0, "%s: negative member stride", what);
+  TL_REQUIRE_STRIDE(what, M, s_dw, total * in_dim, "dw_ih");
+  TL_REQUIRE_STRIDE(what, M, s_db, total, "db");
+  if (total <= 8192 && (long long)L * U >= 64)
+    hipLaunchKernelGGL(lstm_ih_grad_wave_kernel, dim3((unsigned)total, (unsigned)M), dim3(64), 0, (hipStream_t)stream, dgates, x,
+                       dw_ih, db, db2, L * U, H, in_dim, active, (long long)s_dg, (long long)s_x, (long long)s_dw, (long long)s_db);
+  else
+    hipLaunchKernelGGL(lstm_ih_grad_kernel, dim3((unsigned)((total + 255) / 256), (unsigned)M), dim3(256), 0, (hipStream_t)stream,
+                       dgates, x, dw_ih, db, db2, L, U, H, in_dim, active, (long long)s_dg, (long long)s_x, (long long)s_dw,
+                       (long long)s_db);
+  return check_launch(what);
+}
 extern "C" int tl_lstm_ih_grad(const float* dgates, const float* x, float* dw_ih, float* db, float* db2, int L, int U, int H,
                                int in_dim, void* stream) {
-  TL_REQUIRE(dgates && x && dw_ih && db, "lstm_ih_grad: null pointer");
-  TL_REQUIRE(in_dim >= 1 && in_dim <= MAXKT, "lstm_ih_grad: in_dim must be 1..%d", MAXKT);
-  const long long total = 4LL * H;
-  if (total <= 8192 && (long long)L * U >= 64)
-    hipLaunchKernelGGL(lstm_ih_grad_wave_kernel, dim3((unsigned)total), dim3(64), 0, (hipStream_t)stream, dgates, x, dw_ih,
-                       db, db2, L * U, H, in_dim);
-  else
-    hipLaunchKernelGGL(lstm_ih_grad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       dgates, x, dw_ih, db, db2, L, U, H, in_dim);
-  return check_launch("lstm_ih_grad");
+  return lstm_ih_grad_launch("lstm_ih_grad", dgates, x, dw_ih, db, db2, L, U, H, in_dim, stream);
+}
+extern "C" int tl_lstm_ih_grad_group(const float* dgates, const float* x, float* dw_ih, float* db, float* db2, int M, int L, int U,
+                                     int H, int in_dim, int64_t s_dg, int64_t s_x, int64_t s_dw, int64_t s_db,
+                                     const int32_t* active, void* stream) {
+  TL_REQUIRE_MEMBERS("lstm_ih_grad_group", M);
+  return lstm_ih_grad_launch("lstm_ih_grad_group", dgates, x, dw_ih, db, db2, L, U, H, in_dim, stream, M, s_dg, s_x, s_dw, s_db,
+                             active);
 }
 
 extern "C" int tl_concat_pack(const float* O5, const float* h, const int32_t* uid, float* Xc, int B, int C, int Tp,
@@ -1543,12 +1635,26 @@ extern "C" int tl_concat_unpack_bwd(const float* dXc, const float* O5, const int
   return check_launch("concat_dh");
 }
 
+static int l1_mcd_launch(const char* what, const float* out, const float* targets, float* dout, float* stats, int B, int D,
+                         int ldd, int trunc_targets, float grad_scale, void* stream, int M = 1, int64_t s_out = 0,
+                         int64_t s_tgt = 0, int64_t s_dout = 0, const int32_t* active = nullptr) {
+  TL_REQUIRE(out && targets && stats && B > 0 && D > 0 && ldd >= D, "%s: bad arguments", what);
+  TL_REQUIRE(s_out >= 0 && s_tgt >= 0, "%s: negative member stride", what);
+  if (dout) TL_REQUIRE_STRIDE(what, M, s_dout, (int64_t)(B - 1) * ldd + D, "dout");
+  hipLaunchKernelGGL(l1_mcd_kernel, dim3(1, (unsigned)M), dim3(1024), 0, (hipStream_t)stream, out, targets, dout, stats, B, D, ldd,
+                     trunc_targets, grad_scale, active, (long long)s_out, (long long)s_tgt, (long long)s_dout);
+  return check_launch(what);
+}
 extern "C" int tl_l1_mcd(const float* out, const float* targets, float* dout, float* stats, int B, int D, int ldd,
                          int trunc_targets, float grad_scale, void* stream) {
-  TL_REQUIRE(out && targets && stats && B > 0 && D > 0 && ldd >= D, "l1_mcd: bad arguments");
-  hipLaunchKernelGGL(l1_mcd_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, out, targets, dout, stats, B, D, ldd,
-                     trunc_targets, grad_scale);
-  return check_launch("l1_mcd");
+  return l1_mcd_launch("l1_mcd", out, targets, dout, stats, B, D, ldd, trunc_targets, grad_scale, stream);
+}
+extern "C" int tl_l1_mcd_group(const float* out, const float* targets, float* dout, float* stats, int M, int B, int D, int ldd,
+                               int trunc_targets, float grad_scale, int64_t s_out, int64_t s_tgt, int64_t s_dout,
+                               const int32_t* active, void* stream) {
+  TL_REQUIRE_MEMBERS("l1_mcd_group", M);
+  return l1_mcd_launch("l1_mcd_group", out, targets, dout, stats, B, D, ldd, trunc_targets, grad_scale, stream, M, s_out, s_tgt,
+                       s_dout, active);
 }
 
 static int nadam_launch(float* p, const float* g, float* m, float* v, int64_t n, float coef_grad, float coef_mom, float beta1,
@@ -1673,12 +1779,27 @@ extern "C" int tl_nadam_lowrank_dh(float* p, float* m, float* v, const float* fa
                               weight_decay, grad_scale, dh_slab, U, row_tiles, stream);
 }
 
+static int splitk_bias_lrelu_launch(const char* what, const float* slab, const float* bias, float* out, int nz, int64_t n,
+                                    int ncols, float slope, void* stream, int M = 1, int64_t zs = 0, int64_t s_slab = 0,
+                                    int64_t s_bias = 0, int64_t s_out = 0, const int32_t* active = nullptr) {
+  TL_REQUIRE(slab && out && nz > 0 && n > 0 && ncols > 0, "%s: bad arguments", what);
+  TL_REQUIRE(zs >= n, "%s: the slab stride is shorter than the n elements of a slab", what);
+  TL_REQUIRE(s_slab >= 0 && s_bias >= 0, "%s: negative member stride", what);
+  TL_REQUIRE_STRIDE(what, M, s_out, n, "out");
+  hipLaunchKernelGGL(splitk_bias_lrelu_kernel, dim3(grid_for(n), (unsigned)M), dim3(256), 0, (hipStream_t)stream, slab, bias, out,
+                     nz, (long long)n, ncols, slope, (long long)zs, active, (long long)s_slab, (long long)s_bias, (long long)s_out);
+  return check_launch(what);
+}
 extern "C" int tl_splitk_bias_lrelu(const float* slab, const float* bias, float* out, int nz, int64_t n, int ncols, float slope,
                                     void* stream) {
-  TL_REQUIRE(slab && out && nz > 0 && n > 0 && ncols > 0, "splitk_bias_lrelu: bad arguments");
-  hipLaunchKernelGGL(splitk_bias_lrelu_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, slab, bias, out, nz,
-                     (long long)n, ncols, slope);
-  return check_launch("splitk_bias_lrelu");
+  return splitk_bias_lrelu_launch("splitk_bias_lrelu", slab, bias, out, nz, n, ncols, slope, stream, 1, n);
+}
+extern "C" int tl_splitk_bias_lrelu_group(const float* slab, const float* bias, float* out, int nz, int64_t n, int ncols,
+                                          float slope, int M, int64_t zs, int64_t s_slab, int64_t s_bias, int64_t s_out,
+                                          const int32_t* active, void* stream) {
+  TL_REQUIRE_MEMBERS("splitk_bias_lrelu_group", M);
+  return splitk_bias_lrelu_launch("splitk_bias_lrelu_group", slab, bias, out, nz, n, ncols, slope, stream, M, zs, s_slab, s_bias,
+                                  s_out, active);
 }
 
 static int linear_rows_launch(const float* x, const float* w, const float* bias, float* out, int B, int K, int N, int64_t ldx,

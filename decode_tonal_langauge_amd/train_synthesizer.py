@@ -14,6 +14,9 @@ librosa calls of the reference restated with NumPy / SciPy);
 ``channel_file`` JSON {active_channels, tone_discriminative, syllable_discriminative};
 ``config_file`` JSON {mel_kwargs, tone_dynamic_mapping, n_syllables, n_tones[, *_model_kwargs]}.
 ``--resident`` (YAML: ``resident: true``; off by default) keeps the dataset on the GPU and gathers every batch there.
+``--ensemble`` (YAML: ``ensemble: true``; off by default) trains the ``--repeat`` SynthesisLite models side by side in one
+pass (``models/synthesis_ensemble_trainer.py``): every member gets the bits the sequential loop gives it.  It implies the
+resident dataset and needs ``--synthesis_model_name SynthesisLite``, both classifier checkpoints, a CUDA device, one process.
 Output: one CSV row per run with the reference's columns (:369-385).
 """
 from __future__ import annotations
@@ -68,6 +71,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--lr', type=float, default=0.0005)
     p.add_argument('--resident', action='store_true',
                    help="keep the dataset on the GPU and gather every batch there (data_loading/resident.py); CUDA devices only")
+    p.add_argument('--ensemble', action='store_true',
+                   help="train all --repeat SynthesisLite models in one pass (models/synthesis_ensemble_trainer.py); implies "
+                        "--resident; needs both classifier checkpoints, a CUDA device and a single process")
     return p
 
 
@@ -96,10 +102,33 @@ def _mels_from_dataset(dataset, params, mel_kwargs) -> np.ndarray:
     return np.array([audio_to_mel(audio, params.audio_sampling_rate, mel_kwargs=mel_kwargs) for audio in dataset['audio']])
 
 
+ENSEMBLE_NEEDS = ("--ensemble needs --synthesis_model_name SynthesisLite, both classifier checkpoints (--tone_model_path and "
+                  "--syllable_model_path), a CUDA device and a single process (no torchrun / process group)")
+
+
+def check_ensemble(params: Namespace) -> bool:
+    """Is the one-pass ensemble asked for?  Raises ``ValueError`` (stating the conditions) where it cannot run."""
+    if not bool(getattr(params, 'ensemble', False)):
+        return False
+    unmet = []
+    if params.synthesis_model_name != 'SynthesisLite':
+        unmet.append(f"synthesis_model_name is '{params.synthesis_model_name}'")
+    if getattr(params, 'tone_model_path', None) is None or getattr(params, 'syllable_model_path', None) is None:
+        unmet.append("a classifier checkpoint is missing")
+    if 'cuda' not in str(params.device):
+        unmet.append(f"device is '{params.device}'")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1 or parallel.world()[1] > 1:
+        unmet.append("more than one process")
+    if unmet:
+        raise ValueError(f"{'; '.join(unmet)}: {ENSEMBLE_NEEDS}")
+    return True
+
+
 def train(params: Namespace) -> dict:
     """Body of the reference script (:137-400) on the MI355X trainer.  Returns the result row."""
     if not os.path.exists(params.sample_path):
         raise FileNotFoundError(f"Data file '{params.sample_path}' does not exist.")
+    ensemble = check_ensemble(params)
     # data parallel: one process per GPU under torchrun (RANK / LOCAL_RANK / WORLD_SIZE).  The process group
     # is created before any GPU call; rank r trains on cuda:LOCAL_RANK, every rank sees the same loaders
     # (same seeds) and takes its row shard of each batch inside SynthesisTrainer; only rank 0 writes files.
@@ -129,7 +158,7 @@ def train(params: Namespace) -> dict:
     syl_channels, tone_channels = channel_selections['syllable_discriminative'], channel_selections['tone_discriminative']
     # resident: ecog is stored once on the device and read through the three channel lists by the batch gather; the three
     # host copies ecog[:, channels, :] are not made
-    resident = bool(getattr(params, 'resident', False)) and 'cuda' in str(params.device)
+    resident = (bool(getattr(params, 'resident', False)) or ensemble) and 'cuda' in str(params.device)
     if resident:
         n_samples, n_timepoints = ecog.shape[0], ecog.shape[2]
         n_channels, n_syl_channels, n_tone_channels = len(non_disc), len(syl_channels), len(tone_channels)
@@ -170,7 +199,32 @@ def train(params: Namespace) -> dict:
     np.random.seed(params.seed)
     seeds = np.random.randint(0, 10000, params.repeat)
     model = None
-    for i, seed in enumerate(seeds):
+    if ensemble:
+        # every seed in one pass.  The per-seed prologue consumes each seed's random stream in the order of the loop below
+        # (set_seeds, split_dataset, model construction): batches, initial weights and dropout masks are the loop's
+        from .models.synthesis_ensemble_trainer import SynthesisEnsembleTrainer
+        all_loaders, models, entered = [], [], []
+        for seed in seeds:
+            set_seeds(int(seed))
+            all_loaders.append(split_dataset(tds, [params.train_ratio, 1 - params.train_ratio], shuffling=[True, False],
+                                             batch_size=params.batch_size, seed=int(seed), resident=True))
+            models.append(SynthesisLite(output_dim=mels_dim, n_channels=n_channels, n_timepoints=n_timepoints))
+            entered.append(torch.get_rng_state())            # where the seed's ``train`` is entered
+        trainer = SynthesisEnsembleTrainer(models, tone_model, syllable_model, tone_dynamic_mapping,
+                                           seeds=[int(s) for s in seeds], device=params.device, learning_rate=params.lr,
+                                           verbose=chief and params.verbose > 0, train_classifiers=train_classifiers,
+                                           rng_states=entered)
+        if params.verbose > 0:
+            say(f"Training {len(models)} synthesizers in one pass with seeds {seeds.tolist()}...")
+        histories = trainer.train_loaders([lo[0] for lo in all_loaders], params.epochs, verbose=chief and params.verbose > 1)
+        evaluated = trainer.evaluate([lo[1] for lo in all_loaders])
+        for i, (history, (mcd, recon_mels, origin_mels)) in enumerate(zip(histories, evaluated)):
+            mcds.append(mcd)
+            if params.verbose > 0:
+                say(f"Finished trial {i+1} / {params.repeat}. MCD: {mcd:.4f} dB")
+            losses.append([loss for loss, _ in history])
+        model = models[-1]
+    for i, seed in enumerate(() if ensemble else seeds):
         set_seeds(int(seed))
         ratios = [params.train_ratio, 1 - params.train_ratio]
         loaders = split_dataset(tds, ratios, shuffling=[True, False], batch_size=params.batch_size, seed=int(seed),

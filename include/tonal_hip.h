@@ -564,6 +564,81 @@ int tl_head_bwd_group(const float* dlogits, const float* h, const float* W, floa
  * the member on grid.z, so a member's out has the bits of the single launch.                                                */
 int tl_gemm_nt_window_group(const tl_nt_params* p, int M, int64_t s_A, int64_t s_Bw, int64_t s_bias, int64_t s_out,
                             const int32_t* active, void* stream);
+/* A second group form of tl_gemm_nt_window, for the Linear layers of SynthesisLite and their input gradients
+ * (_lite_ensemble_engine.py): J = 1, loader DIRECT, row_shift 0, bm 32 or 128, and
+ *   epilogue STORE, bias optional, split-K on grid.y as in the single launch: member m's slab z is out + m s_out + z slab_stride,
+ *                  so slab_stride >= p->M * ldo and, with M > 1, s_out >= splitk * slab_stride (s_out >= p->M * ldo without split-K);
+ *   epilogue MASK  with aux (never auxbits) at the member stride s_aux.
+ * Everything else is refused.  s_A and s_Bw non-negative multiples of 4, s_bias and s_aux non-negative.  The kernel is chosen as
+ * tl_gemm_nt_window chooses it for *p and runs that kernel's body with the member on grid.z.                                 */
+int tl_gemm_nt_window_group_fc(const tl_nt_params* p, int M, int64_t s_A, int64_t s_Bw, int64_t s_bias, int64_t s_aux,
+                               int64_t s_out, const int32_t* active, void* stream);
+/* tl_gemm_tn_window for M members, for the parameters the single entry runs on its short-reduction kernel only: J = 1, loader
+ * DIRECT, Krows <= 512, splitk <= 8, Mdim * Ndim <= 2^20, ldc % 4 == 0 (and slab_stride >= Mdim * ldc under split-K); Tp / Tvalid
+ * masking and the optional colsum (written without split-K, as by the single launch) included; bbits and vd null.  Member m works
+ * on A + m s_A, B + m s_B, slab + m s_slab and colsum + m s_colsum: s_A, s_B, s_slab non-negative multiples of 4, and with M > 1
+ * s_slab >= splitk * slab_stride (>= Mdim * ldc without split-K), s_colsum >= Mdim.  Everything else is refused.  The member sits
+ * on grid.z and runs the single kernel's body.                                                                            */
+int tl_gemm_tn_window_group(const tl_tn_params* p, int M, int64_t s_A, int64_t s_B, int64_t s_slab, int64_t s_colsum,
+                            const int32_t* active, void* stream);
+
+/* ---- group forms of the SynthesisLite step (see the group launches above; _lite_ensemble_engine.py) ------------------------
+ * Each is its single neighbour's kernel with the member on the grid (grid.z of the tl_lite_* kernels, grid.y of the four
+ * one-dimensional ones); the arguments are the single entry's, then M where stated, the member strides in ELEMENTS of the
+ * pointer they move, `active` and the stream.  A stride shared by several pointers is named once:
+ *   s_stat  mean and rstd            s_run  running_mean and running_var     s_gb   gamma and beta (BatchNorm weight / bias)
+ *   s_dgb   dgamma and dbeta         s_b    bias_ih and bias_hh              s_cs   cs and hs       s_act  act (and dgates)
+ *   s_db    db and db2
+ * The stride of every pointer a member writes must cover the member's extent when M > 1 (TL_EINVAL otherwise); strides of inputs
+ * are non-negative (0 shares one input among the members).                                                                */
+int tl_lite_conv_fwd_group(const float* x, const float* w, const float* bias, float* z, float* part, int M, int B, int Cin,
+                           int Cout, int T, int k, int pad, int64_t s_x, int64_t s_w, int64_t s_bias, int64_t s_z,
+                           int64_t s_part, const int32_t* active, void* stream);
+/* every member has its own mean / rstd, running statistics and num_batches_tracked word (s_tracked, int64 words)              */
+int tl_lite_bn_finalize_group(const float* part, float* mean, float* rstd, float* run_mean, float* run_var, int M, int nparts,
+                              int C, int64_t count, int T, float momentum, float eps, int training, int64_t* tracked,
+                              int64_t s_part, int64_t s_stat, int64_t s_run, int64_t s_tracked, const int32_t* active,
+                              void* stream);
+int tl_lite_bn_act_pool_fwd_group(const float* z, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                                  float* y, int M, int B, int C, int T, float slope, int64_t s_z, int64_t s_stat, int64_t s_gb,
+                                  int64_t s_y, const int32_t* active, void* stream);
+/* work: B * C * 2 floats per member at s_work                                                                                 */
+int tl_lite_bn_act_pool_bwd_group(const float* dy, const float* z, const float* mean, const float* rstd, const float* gamma,
+                                  const float* beta, float* dz, float* dgamma, float* dbeta, float* work, int M, int B, int C,
+                                  int T, float slope, int training, int64_t s_dy, int64_t s_z, int64_t s_stat, int64_t s_gb,
+                                  int64_t s_dz, int64_t s_dgb, int64_t s_work, const int32_t* active, void* stream);
+int tl_lite_conv_bwd_group(const float* dz, const float* x, const float* w, float* dx, float* dwpart, float* dbpart, int M, int B,
+                           int Cin, int Cout, int T, int k, int pad, int64_t s_dz, int64_t s_x, int64_t s_w, int64_t s_dx,
+                           int64_t s_dwpart, int64_t s_dbpart, const int32_t* active, void* stream);
+/* tl_colsum per member: partial (nblk, ncols) per member at s_part, G at s_G (multiples of 4)                                 */
+int tl_colsum_group(const float* G, float* partial, int nblk, int64_t rows, int ncols, int ld, int Tp, int Tvalid, int M,
+                    int64_t s_G, int64_t s_part, const int32_t* active, void* stream);
+int tl_sum_slabs2_group(const float* srcA, float* dstA, int64_t nA, const float* srcB, float* dstB, int64_t nB, int nz, int M,
+                        int64_t s_srcA, int64_t s_dstA, int64_t s_srcB, int64_t s_dstB, const int32_t* active, void* stream);
+int tl_lite_lstm_fwd_group(const float* xl, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, float* act,
+                           float* cs, float* hs, int M, int B, int L, int H, int in_dim, int64_t s_xl, int64_t s_wih,
+                           int64_t s_whh, int64_t s_b, int64_t s_act, int64_t s_cs, const int32_t* active, void* stream);
+/* dgates lies at the stride of act (the two have one shape)                                                                   */
+int tl_lite_lstm_bwd_group(const float* dh_last, const float* w_hh, const float* act, const float* cs, float* dgates, int M, int B,
+                           int L, int H, int ld_dh, int64_t s_dh, int64_t s_whh, int64_t s_act, int64_t s_cs,
+                           const int32_t* active, void* stream);
+int tl_lstm_ih_grad_group(const float* dgates, const float* x, float* dw_ih, float* db, float* db2, int M, int L, int U, int H,
+                          int in_dim, int64_t s_dg, int64_t s_x, int64_t s_dw, int64_t s_db, const int32_t* active, void* stream);
+/* the dropout seed always comes from device memory: seed_dev is a table of M words and member m draws the mask
+ * tl_lite_cat_dev / tl_lite_uncat_dev draw with seed_dev[m]                                                                   */
+int tl_lite_cat_group(const float* y2, const float* hs, float* feat, int M, int B, int F, int H, int L, int ldf, float p_drop,
+                      const uint64_t* seed_dev, int64_t s_y2, int64_t s_hs, int64_t s_feat, const int32_t* active, void* stream);
+int tl_lite_uncat_group(const float* dfeat, float* dy2, float* dh, int M, int B, int F, int H, int ldf, float p_drop,
+                        const uint64_t* seed_dev, int64_t s_dfeat, int64_t s_dy2, int64_t s_dh, const int32_t* active,
+                        void* stream);
+/* zs: elements between two split-K slabs of one member (>= n): n for [M][nz][n] slabs (s_slab = nz n), M n for [nz][M][n]
+ * (s_slab = n); bias (may be null) at s_bias                                                                                 */
+int tl_splitk_bias_lrelu_group(const float* slab, const float* bias, float* out, int nz, int64_t n, int ncols, float slope, int M,
+                               int64_t zs, int64_t s_slab, int64_t s_bias, int64_t s_out, const int32_t* active, void* stream);
+/* stats is (M, 4); one workgroup per member, so each member's sums keep the single launch's order                             */
+int tl_l1_mcd_group(const float* out, const float* targets, float* dout, float* stats, int M, int B, int D, int ldd,
+                    int trunc_targets, float grad_scale, int64_t s_out, int64_t s_tgt, int64_t s_dout, const int32_t* active,
+                    void* stream);
 
 /* ---- training of CNNRNNClassifier (models/deep_classifiers.py:158-343 under models/classifier_trainer.py:72-89) ----------
  * The LSTM pair keeps ROWS TIME-MAJOR (row = t * B + b), so the kept arrays are directly the (T B)-row operands of the
