@@ -62,8 +62,10 @@ KEYS: Dict[str, Tuple[str, _Allowed, str, str]] = {
                 "time-domain kernels with / without Hermitian symmetry, fft the DFT-domain form)"),
     "hilbert_f32": ("TONAL_HILBERT_F32", _B, "0", "float32 recordings: fp32 transforms end to end (default: fp64 math)"),
     "butter": ("TONAL_BUTTER", frozenset({"seq", "scan"}), "seq",
-               "zero-phase Butterworth: seq the sequential recurrence (bit-identical to scipy's loop), scan the time-parallel "
-               "block scan (2e-8 - 5e-8 from it: the size of the reference's own rounding; ~20 x faster)"),
+               "Butterworth: seq the sequential recurrence (bit-identical to scipy's loop), scan the time-parallel block scan - "
+               "zero-phase (up to 9 taps): 2e-8 - 5e-8 from seq, the size of the reference's own rounding, ~20 x faster; "
+               "causal=True (up to 8 sections): the first two blocks bit-equal, the rest within a few times scipy's own distance "
+               "from long double (1e-16 - 1e-11 by design)"),
 }
 _LEGACY = {v[0]: k for k, v in KEYS.items()}
 _cache: Tuple[str, Dict[str, str]] = ("", {})

@@ -166,6 +166,7 @@ SIGNATURES = {
     "tl_filtfilt_f64": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _L, _I, _P]),
     "tl_filtfilt_scan_f64": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _L, _I, _I, _P]),
     "tl_sosfilt_f64": (_I, [_P, _I, _P, _P, _I, _L, _I, _P]),
+    "tl_sosfilt_scan_f64": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _I, _L, _I, _I, _P]),
     "tl_fir_bank": (_I, [_P, _I, _P, _P, _I, _I, _L, _I, _I, _P]),
     "tl_fir_bank_ols": (_I, [_P, _I, _P, _P, _P, _I, _I, _L, _I, _I, _P]),
     "tl_group_moments": (_I, [_P, _I, _L, _L, _P, _I, _P, _I, _P, _P, _P]),

@@ -865,10 +865,11 @@ __global__ __launch_bounds__(64) void filtfilt_scan_block_kernel(const double* _
 // two_sum, the low words of M and all rounding errors in a second accumulator): correctly rounded up to ~1e-31 of the terms.
 // The matrices of all levels sit in LDS (a lane reads its own row), the vectors are exchanged through LDS.
 constexpr int FS_BLK = 128;
+template <int NR = FS_NS>                                  // (NR = 16: the causal cascade's stacked state, further down)
 __device__ __forceinline__ double scan_row(const double* __restrict__ Mrow, const double* __restrict__ u, double v) {
   double s = v, e = 0.0;
 #pragma unroll
-  for (int k = 0; k < FS_NS; ++k) {
+  for (int k = 0; k < NR; ++k) {
     const double mh = Mrow[2 * k], ml = Mrow[2 * k + 1], uk = u[k];
     const double pr = mh * uk;
     const double pe = fma(mh, uk, -pr);                   // two_prod: mh * uk = pr + pe exactly
@@ -976,6 +977,145 @@ __global__ __launch_bounds__(64) void sosfilt_kernel(const void* __restrict__ x,
         v = yv;
       }
     y[cb + i] = v;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// sosfilt, TIME-PARALLEL (opt-in: TONAL_KERNELS=butter=scan with causal=True).  The structure of tl_filtfilt_scan_f64 on the
+// cascade of biquads: the recording goes TIME-MAJOR into `work` ([T][C], filtfilt_build_tiled_kernel with no extension), so a
+// wave's 64 lanes = 64 channels read one 512-B line per time step; (1) every (channel, block of L samples) runs
+// sosfilt_kernel's statements from a ZERO state and keeps the 2 nsec states it ends in - (z0, z1) of section 0, 1, ... - as
+// s_j; (2) the states at the block starts follow z_{j+1} = A^L z_j + s_j, z_0 = 0 (sosfilt has no zi), A the zero-input
+// transition matrix of the stacked cascade state (2 nsec x 2 nsec, lower block-triangular): one workgroup per channel, a
+// thread per (block, state row), a Hillis-Steele scan over chunks of blocks with the host's matrices A^(L 2^m), the carry
+// kept from chunk to chunk; (3) every (channel, block) re-runs the statements from its true start state, in place, and
+// filtfilt_out_kernel transposes back.  Steps (1) and (3) are the sequential kernel's arithmetic, so the first L samples of
+// a channel are its bits; step (2) is where the two differ.  Second-order sections keep the states near the size of the
+// output, yet with plain fp64 matrices the scan drifts to 18 - 20 x scipy's own distance from the same loop in long double
+// on long recordings with a DC level or a very low band edge; with (hi, lo) pairs and the compensated dot product of the
+// zero-phase scan it stays within ~2 x (tests/test_sosfilt_scan_host.py), so the matrices come as pairs.
+// ------------------------------------------------------------------------------------------
+template <bool APPLY>
+__global__ __launch_bounds__(64) void sosfilt_scan_block_kernel(const double* __restrict__ sos, double* work,
+                                                                const double* __restrict__ Z, double* __restrict__ S, int C,
+                                                                long long T, int nsec, int L) {
+#pragma clang fp contract(off)
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (c >= C) return;
+  const long long j = blockIdx.y;
+  const long long n0 = j * L, n1 = (n0 + L < T) ? n0 + L : T;
+  const int ns = 2 * nsec;
+  double s[MAX_SEC][6], z0[MAX_SEC], z1[MAX_SEC];
+#pragma unroll
+  for (int q = 0; q < MAX_SEC; ++q) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) s[q][k] = q < nsec ? sos[q * 6 + k] : (k == 0 || k == 3 ? 1.0 : 0.0);
+    z0[q] = z1[q] = 0.0;
+  }
+  if constexpr (APPLY) {
+#pragma unroll
+    for (int q = 0; q < MAX_SEC; ++q)
+      if (q < nsec) {
+        z0[q] = Z[(j * ns + 2 * q) * C + c];
+        z1[q] = Z[(j * ns + 2 * q + 1) * C + c];
+      }
+  }
+  double* wp = work + c;                                    // read and (APPLY) written in place: sample n by this lane only
+  constexpr int U = 8;
+  double cur[U], nxt[U];
+  long long n = n0;
+  if (n1 - n0 >= U) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) cur[u] = wp[(n0 + u) * C];
+  }
+  for (; n + U <= n1; n += U) {
+    const bool more = n + 2 * U <= n1;
+    if (more) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) nxt[u] = wp[(n + U + u) * C];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      double v = cur[u];
+#pragma unroll
+      for (int q = 0; q < MAX_SEC; ++q)
+        if (q < nsec) {
+          // scipy _sosfilt order: y = b0*x + z0; z0 = (b1*x - a1*y) + z1; z1 = b2*x - a2*y
+          const double yv = __dadd_rn(__dmul_rn(s[q][0], v), z0[q]);
+          z0[q] = __dadd_rn(__dsub_rn(__dmul_rn(s[q][1], v), __dmul_rn(s[q][4], yv)), z1[q]);
+          z1[q] = __dsub_rn(__dmul_rn(s[q][2], v), __dmul_rn(s[q][5], yv));
+          v = yv;
+        }
+      if constexpr (APPLY) wp[(n + u) * C] = v;
+    }
+    if (more) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+    }
+  }
+  for (; n < n1; ++n) {
+    double v = wp[n * C];
+#pragma unroll
+    for (int q = 0; q < MAX_SEC; ++q)
+      if (q < nsec) {
+        const double yv = __dadd_rn(__dmul_rn(s[q][0], v), z0[q]);
+        z0[q] = __dadd_rn(__dsub_rn(__dmul_rn(s[q][1], v), __dmul_rn(s[q][4], yv)), z1[q]);
+        z1[q] = __dsub_rn(__dmul_rn(s[q][2], v), __dmul_rn(s[q][5], yv));
+        v = yv;
+      }
+    if constexpr (APPLY) wp[n * C] = v;
+  }
+  if constexpr (!APPLY) {
+#pragma unroll
+    for (int q = 0; q < MAX_SEC; ++q)
+      if (q < nsec) {
+        S[(j * ns + 2 * q) * C + c] = z0[q];
+        S[(j * ns + 2 * q + 1) * C + c] = z1[q];
+      }
+  }
+}
+
+// One workgroup per channel; a thread per (block, state row): BLK blocks x NR rows = 1024 threads per chunk of blocks
+// (8 rows x 128 blocks up to four sections, 16 x 64 beyond), NLEV = log2 BLK matrix levels in LDS.  M is the host's
+// (nlev, 16, 16, 2) image, zero beyond the 2 nsec live rows and columns: dead rows stay zero and are never stored.
+constexpr int SS_NR = 16;                                   // rows / columns of a matrix level as the host lays it out
+template <int NR, int BLK, int NLEV>
+__global__ __launch_bounds__(NR * BLK) void sosfilt_scan_prefix_kernel(const double* __restrict__ S, double* __restrict__ Z,
+                                                                       const double* __restrict__ M, int C, long long nb,
+                                                                       int ns) {
+  static_assert(NR * BLK == 1024 && (1 << NLEV) == BLK && NR <= SS_NR, "a chunk is 1024 threads, log2 BLK levels");
+  __shared__ __attribute__((aligned(16))) double sm[NLEV * NR * NR * 2];
+  __shared__ __attribute__((aligned(16))) double sv[2][BLK][NR];
+  __shared__ double scar[NR];
+  const int c = blockIdx.x, tid = threadIdx.x, i = tid % NR, jl = tid / NR;
+  for (int q = tid; q < NLEV * NR * NR * 2; q += NR * BLK) {
+    const int p = q & 1, k = (q >> 1) % NR, r = (q >> 1) / NR % NR, lev = (q >> 1) / (NR * NR);
+    sm[q] = M[((lev * SS_NR + r) * SS_NR + k) * 2 + p];
+  }
+  if (tid < NR) scar[tid] = 0.0;                            // sosfilt starts from a zero state
+  __syncthreads();
+  const bool row = i < ns;
+  for (long long chunk0 = 0; chunk0 < nb; chunk0 += BLK) {
+    const long long j = chunk0 + jl;
+    double v = (j < nb && row) ? S[(j * ns + i) * C + c] : 0.0;
+    if (jl == 0) {
+      if (row) Z[(chunk0 * ns + i) * C + c] = scar[i];
+      v = scan_row<NR>(sm + i * NR * 2, scar, v);         // state at the END of the chunk's first block
+    }
+    int buf = 0;
+    const int nact = (nb - chunk0 < BLK) ? (int)(nb - chunk0) : BLK;      // blocks of this chunk (uniform)
+#pragma unroll 1
+    for (int lev = 0, d = 1; d < nact; ++lev, d <<= 1) {
+      sv[buf][jl][i] = v;
+      __syncthreads();
+      if (jl >= d) v = scan_row<NR>(sm + (lev * NR + i) * NR * 2, sv[buf][jl - d], v);
+      buf ^= 1;
+    }
+    // v = row i of the state at the end of block j = at the start of block j + 1
+    if (j + 1 < nb && row) Z[((j + 1) * ns + i) * C + c] = v;
+    __syncthreads();                                       // (scar is still being read by the first block's lanes above)
+    if (jl == nact - 1) scar[i] = v;
+    __syncthreads();
   }
 }
 
@@ -1188,6 +1328,37 @@ extern "C" int tl_sosfilt_f64(const void* x, int x_is_f64, const double* sos, do
   else
     hipLaunchKernelGGL((sosfilt_kernel<float>), grid, dim3(64), 0, st, x, sos, y, C, (long long)T, nsec);
   return check_launch("sosfilt");
+}
+
+extern "C" int tl_sosfilt_scan_f64(const void* x, int x_is_f64, const double* sos, const double* M, int nlev, double* y,
+                                   double* work, double* swork, int C, int64_t T, int nsec, int L, void* stream) {
+  TL_REQUIRE(x && sos && M && y && work && swork, "sosfilt_scan: null pointer");
+  TL_REQUIRE(nsec >= 1 && nsec <= MAX_SEC, "sosfilt: nsec must be 1..%d", MAX_SEC);      // (the sequential entry's words)
+  TL_REQUIRE(C >= 1 && C <= 65535 && T >= 1, "sosfilt_scan: bad sizes (C must be 1..65535, T >= 1)");
+  TL_REQUIRE(L >= 8, "sosfilt_scan: blocks of at least 8 samples (L = %d)", L);
+  const long long nb = ((long long)T + L - 1) / L;
+  TL_REQUIRE(nb <= 65535, "sosfilt_scan: more than 65 535 blocks of %d samples (raise L)", L);
+  const bool small = nsec <= 4;                             // 8 state rows x 128 blocks per chunk; else 16 x 64
+  const int need = small ? 7 : 6;
+  TL_REQUIRE(nlev >= need, "sosfilt_scan: %d matrix levels A^(L 2^m), m < %d, needed (chunks of %d blocks)", need, need, 1 << need);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 tgrid((unsigned)((T + 63) / 64), (unsigned)((C + 63) / 64));
+  if (x_is_f64)
+    hipLaunchKernelGGL((filtfilt_build_tiled_kernel<double>), tgrid, dim3(256), 0, st, x, work, C, (long long)T, 0);
+  else
+    hipLaunchKernelGGL((filtfilt_build_tiled_kernel<float>), tgrid, dim3(256), 0, st, x, work, C, (long long)T, 0);
+  const int ns = 2 * nsec;
+  double* S = swork;
+  double* Z = swork + nb * ns * C;
+  const dim3 grid((unsigned)((C + 63) / 64), (unsigned)nb);
+  hipLaunchKernelGGL((sosfilt_scan_block_kernel<false>), grid, dim3(64), 0, st, sos, work, nullptr, S, C, (long long)T, nsec, L);
+  if (small)
+    hipLaunchKernelGGL((sosfilt_scan_prefix_kernel<8, 128, 7>), dim3((unsigned)C), dim3(1024), 0, st, S, Z, M, C, nb, ns);
+  else
+    hipLaunchKernelGGL((sosfilt_scan_prefix_kernel<16, 64, 6>), dim3((unsigned)C), dim3(1024), 0, st, S, Z, M, C, nb, ns);
+  hipLaunchKernelGGL((sosfilt_scan_block_kernel<true>), grid, dim3(64), 0, st, sos, work, Z, nullptr, C, (long long)T, nsec, L);
+  hipLaunchKernelGGL(filtfilt_out_kernel, tgrid, dim3(256), 0, st, work, y, C, (long long)T, 0);
+  return check_launch("sosfilt_scan");
 }
 
 // overlap-save form of tl_fir_bank (same causal convolution, zero initial state): G (nb, 1024, 2) = FFT_1024 of each band's taps

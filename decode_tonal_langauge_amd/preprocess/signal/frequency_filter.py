@@ -22,6 +22,9 @@ The arithmetic runs in HIP kernels (``csrc/tonal_signal.hip``):
    ``TONAL_HILBERT=sym`` keeps the time-domain kernel, which uses the kernels' Hermitian symmetry;
  * ``filtfilt`` / ``sosfilt`` are fp64 direct-form-II-transposed recurrences, sequential in time exactly like scipy's loop
    (``filtfilt``: the state spread over the lanes of a DPP row per channel, bit-identical; ``sosfilt``: one lane per channel);
+   ``TONAL_KERNELS=butter=scan`` opts into their time-parallel block scans - ``tl_filtfilt_scan_f64`` (up to 9 taps) and, with
+   ``causal=True``, ``tl_sosfilt_scan_f64`` (up to 8 sections: the first two blocks of 128 samples bit-equal to the sequential
+   kernel, the rest within a few times scipy's own distance from the same loop in long double);
  * the FIR bank is a causal convolution with zero initial state (recordings of >= 1024 samples: overlap-save on the same
    LDS FFT as the Hilbert bank, ``tl_fir_bank_ols``).
 Filter *design* (``butter``, ``lfilter_zi``, ``firwin``) stays on scipy: coefficient generation,
@@ -313,6 +316,9 @@ def butter_filter(data, freqs: Union[Tuple[float, float], float], fs: float, ord
         if causal:
             sos = np.ascontiguousarray(butter(order, wn, btype=filter_type, output='sos'), dtype=np.float64)
             coef = (torch.from_numpy(sos).to(x.device), sos.shape[0])
+            if _kernels.get("butter") == "scan" and sos.shape[0] <= _SOS_NS // 2:
+                # (more sections: the sequential entry below refuses them, in its own words)
+                coef = coef + (sos, {_SCAN_L: torch.from_numpy(_sos_scan_matrices(sos, _SCAN_L, _SCAN_LEVELS)).to(x.device)})
         else:
             b, a = butter(order, wn, btype=filter_type)
             ntaps = max(len(a), len(b))
@@ -327,8 +333,25 @@ def butter_filter(data, freqs: Union[Tuple[float, float], float], fs: float, ord
         if len(_BUTTER_CACHE) > 32:
             _BUTTER_CACHE.clear()
         _BUTTER_CACHE[key] = coef
-    if causal:
-        sd, nsec = coef
+    if causal and len(coef) > 2:
+        # opt-in (TONAL_KERNELS=butter=scan): time-parallel form of the same cascade (tl_sosfilt_scan_f64's header comment) -
+        # the first two blocks bit-equal to the sequential kernel, the rest within a few times the reference's own rounding error;
+        # blocks of _SCAN_L samples, longer blocks (their matrices cached beside the first) beyond 65 535 of them
+        sd, nsec, sos, mats = coef
+        _check_rows(C, "butter_filter")
+        L = _SCAN_L
+        while (T + L - 1) // L > 65535:
+            L *= 2
+        md = mats.get(L)
+        if md is None:
+            md = mats[L] = torch.from_numpy(_sos_scan_matrices(sos, L, _SCAN_LEVELS)).to(x.device)
+        nb = (T + L - 1) // L
+        work = torch.empty(T, C, dtype=torch.float64, device=x.device)
+        swork = torch.empty(2, nb, 2 * nsec, C, dtype=torch.float64, device=x.device)
+        check(lib.tl_sosfilt_scan_f64(ptr(x), int(x.dtype == torch.float64), ptr(sd), ptr(md), _SCAN_LEVELS, ptr(y), ptr(work),
+                                      ptr(swork), C, T, nsec, L, _stream()), "tl_sosfilt_scan_f64")
+    elif causal:
+        sd, nsec = coef[:2]
         check(lib.tl_sosfilt_f64(ptr(x), int(x.dtype == torch.float64), ptr(sd), ptr(y), C, T, nsec, _stream()),
               "tl_sosfilt_f64")
     else:
@@ -402,6 +425,63 @@ def _scan_matrices(aa: np.ndarray, L: int, nlev: int) -> np.ndarray:
                 out[m, i, j, 0] = hi
                 out[m, i, j, 1] = float(fr - Fraction(hi))
         P = mul(P, P)
+    return out
+
+
+_SOS_NS = 16             # state rows of the causal scan's matrices: (z0, z1) of up to 8 sections
+
+
+def _sos_scan_matrices(sos: np.ndarray, L: int, nlev: int) -> np.ndarray:
+    """(nlev, 16, 16, 2) double-double pairs of A^(L 2^m), m < nlev, for the time-parallel ``sosfilt``
+    (``tl_sosfilt_scan_f64``).  ``A`` is the one-sample transition matrix of the stacked cascade state (z0, z1 of section 0, 1, ...) for ZERO input, in the statements
+    scipy's ``_sosfilt`` runs: y_q = b0 v_q + z0_q, z0_q <- (b1 v_q - a1 y_q) + z1_q, z1_q <- b2 v_q - a2 y_q, v_{q+1} = y_q,
+    v_0 = 0 - lower block-triangular, zero beyond 2 nsec.  Built from the float64 coefficients as exact rationals, raised in
+    1024-bit fixed point on Python integers like ``_scan_matrices``, every entry rounded ONCE to a (hi, lo) pair.  Pairs, not
+    plain doubles: restated in NumPy the scan with plain fp64 matrices reaches 18 - 20 x scipy's own distance from the same
+    loop in long double at 40 000 samples (very low band edge at a raw rate; high-pass on a DC level), with pairs and the
+    compensated dot product it stays at ~2 x (tests/test_sosfilt_scan_host.py holds it to 20 x)."""
+    from fractions import Fraction
+    F = 1024
+    one = 1 << F
+    sos = np.asarray(sos, dtype=np.float64)
+    nsec = sos.shape[0]
+    ns = 2 * nsec
+    if not 1 <= nsec <= _SOS_NS // 2:
+        raise ValueError(f"sosfilt: nsec must be 1..{_SOS_NS // 2}")
+    A = [[Fraction(0)] * ns for _ in range(ns)]
+    v = [Fraction(0)] * ns                                   # the section's input as a row over the stacked state
+    for q in range(nsec):
+        b0, b1, b2, _a0, a1, a2 = (Fraction(float(c)) for c in sos[q])
+        y = [b0 * vk for vk in v]
+        y[2 * q] += 1
+        for k in range(ns):
+            A[2 * q][k] = b1 * v[k] - a1 * y[k]
+            A[2 * q + 1][k] = b2 * v[k] - a2 * y[k]
+        A[2 * q][2 * q + 1] += 1
+        v = y
+
+    def mul(X, Y):
+        return [[sum(X[i][k] * Y[k][j] for k in range(ns)) >> F for j in range(ns)] for i in range(ns)]
+
+    base = [[(fr.numerator << F) // fr.denominator for fr in row] for row in A]
+    P = [[one if i == j else 0 for j in range(ns)] for i in range(ns)]
+    e = int(L)
+    while e:
+        if e & 1:
+            P = mul(P, base)
+        e >>= 1
+        if e:
+            base = mul(base, base)
+    out = np.zeros((nlev, _SOS_NS, _SOS_NS, 2))
+    for m in range(nlev):
+        for i in range(ns):
+            for j in range(ns):
+                fr = Fraction(P[i][j], one)
+                hi = float(fr)
+                out[m, i, j, 0] = hi
+                out[m, i, j, 1] = float(fr - Fraction(hi))
+        if m + 1 < nlev:
+            P = mul(P, P)
     return out
 
 

@@ -778,6 +778,16 @@ int tl_filtfilt_scan_f64(const void* x, int x_is_f64, const double* b, const dou
 /* causal cascade of biquads (sosfilt), fp64 (frequency_filter.py:223-224)                     */
 int tl_sosfilt_f64(const void* x, int x_is_f64, const double* sos, double* y, int C, int64_t T,
                    int nsec, void* stream);
+/* the same causal cascade evaluated TIME-PARALLEL (opt-in, TONAL_KERNELS=butter=scan): the recording goes time-major into
+ * work, every (channel, block of L samples) runs tl_sosfilt_f64's statements from a zero state, the 2 nsec stacked section
+ * states (z0, z1 of section 0, 1, ...) at the block starts follow from a per-channel scan z_{j+1} = A^L z_j + s_j, z_0 = 0,
+ * with M[m] = A^(L 2^m) (nlev x 16 x 16 x (hi, lo) double-double pairs, row-major, zero beyond 2 nsec; from the host: exact
+ * powers of the cascade's zero-input transition matrix rounded once), and the blocks are re-run from their true start states.  The first L samples
+ * of a channel are bit-equal to tl_sosfilt_f64; the rest agrees to a small multiple of the reference's own rounding error.
+ * nsec 1..8 (the scan takes chunks of 128 blocks, nlev >= 7, for nsec <= 4; chunks of 64, nlev >= 6, beyond), C <= 65 535,
+ * L >= 8, at most 65 535 blocks.  work: C*T doubles; swork: 2 * blocks * 2 nsec * C doubles.                            */
+int tl_sosfilt_scan_f64(const void* x, int x_is_f64, const double* sos, const double* M, int nlev, double* y, double* work,
+                        double* swork, int C, int64_t T, int nsec, int L, void* stream);
 /* causal FIR bank, mean over bands (frequency_filter.py:260-274); taps (nb, ntap) float64      */
 int tl_fir_bank(const void* x, int x_is_f64, const double* taps, void* y, int y_is_f64, int C, int64_t T,
                 int nb, int ntap, void* stream);
