@@ -1,5 +1,6 @@
 """CPU: the shared launch helpers (``_launch.py``) fill the parameter structs exactly as documented and refuse unknown
-field names; the classifier engine is a conv stack without the synthesis model's parts.  No GPU, no kernel launch."""
+field names, the group helpers hand member count, strides, mask and stream on unchanged; the classifier engine is a conv stack
+without the synthesis model's parts.  No GPU, no kernel launch."""
 import ctypes as C
 
 import pytest
@@ -54,6 +55,9 @@ def test_launch_defaults_fields_and_entry_point(launch, struct, defaults, entry)
     assert name == "tl_other_entry" and len(lib.calls) == 2
     want.update(given)
     assert fields_of(p) == want
+    launch(lib, stream=55, **given)                       # a stream the caller has read already; it is no field
+    name, p, stream = lib.calls[2]
+    assert (name, stream) == (entry, 55) and fields_of(p) == want
 
 
 def test_unknown_field_raises_and_launches_nothing():
@@ -65,6 +69,64 @@ def test_unknown_field_raises_and_launches_nothing():
         _launch.launch_tn(lib_t, Tvalidd=1)
     assert lib.calls == [] and lib_t.calls == []
     assert _launch.r4(5) == 8 and _launch.r4(8) == 8
+
+
+class StandInGroupLib(StandInLib):
+    """... and keeps what a ``_group`` entry is handed between the struct and the stream: member count, strides, ``active``."""
+
+    def __getattr__(self, name):
+        def entry(ref, *rest):
+            p = self.struct()
+            C.memmove(C.byref(p), ref, C.sizeof(p))
+            self.calls.append((name, p, rest))
+            return 0
+        return entry
+
+
+class Words:
+    """A stand-in for the device tensor of mask words: the helpers pass its ``data_ptr()``."""
+
+    def data_ptr(self):
+        return 0x7000
+
+
+GROUP_LAUNCHES = [
+    (_launch.launch_nt_group_fc, NtParams, NT_DEFAULTS, "tl_gemm_nt_window_group_fc", (3, 640, 1280, 8, 320, 5120),
+     dict(A=0x1000, aux=0x3000, ldaux=512, M=5, slope=0.25, epilogue=3, splitk=7, slab_stride=1 << 40, bm=32)),
+    (_launch.launch_tn_group, TnParams, TN_DEFAULTS, "tl_gemm_tn_window_group", (3, 640, 1280, 1 << 33, 512),
+     dict(A=0x1000, colsum=0x3000, Krows=511, Tp=5, Tvalid=4, splitk=8, slab_stride=1 << 40)),
+]
+
+
+@pytest.mark.parametrize("launch,struct,defaults,entry,group,given", GROUP_LAUNCHES)
+def test_group_launch_defaults_fields_members_strides_active_and_stream(launch, struct, defaults, entry, group, given):
+    lib = StandInGroupLib(struct)
+    launch(lib, *group, None)
+    name, p, rest = lib.calls[0]
+    assert name == entry and rest == (*group, None, 77)                   # members, strides; active None -> NULL; the stream
+    want = {n: 0 for n, _ in struct._fields_}
+    want.update(defaults)
+    assert fields_of(p) == want and bytes(p) == bytes(struct(**defaults))
+    # given fields arrive unchanged on top of the defaults (M is a field: the member count is positional); the mask's pointer
+    launch(lib, *group, Words(), **given)
+    name, p, rest = lib.calls[1]
+    assert name == entry and rest == (*group, 0x7000, 77) and len(lib.calls) == 2
+    want.update(given)
+    assert fields_of(p) == want
+    # a stream the caller has read already is the one launched on; it is no field
+    launch(lib, *group, None, stream=55, **given)
+    name, p, rest = lib.calls[2]
+    assert name == entry and rest == (*group, None, 55) and fields_of(p) == want
+
+
+@pytest.mark.parametrize("launch,struct,defaults,entry,group,given", GROUP_LAUNCHES)
+def test_group_launch_unknown_field_raises_and_launches_nothing(launch, struct, defaults, entry, group, given):
+    lib = StandInGroupLib(struct)
+    with pytest.raises(TypeError, match=f"{struct.__name__} has no field slab_strid"):
+        launch(lib, *group, None, slab_strid=16, **given)
+    with pytest.raises(TypeError):                                          # the strides and the mask are positional only
+        launch(lib, *group, active=None)
+    assert lib.calls == []
 
 
 def test_classifier_engine_is_a_conv_stack_without_the_synthesis_parts(monkeypatch):
