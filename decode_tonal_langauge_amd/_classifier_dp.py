@@ -2,8 +2,7 @@
 subclasses): one process per GPU, every rank is handed the GLOBAL batch and works on its rows.  The free-standing parts live
 here, the per-step side (``_take`` / ``_exchange`` / ``epoch_stats``) in the base class.
 
-  shard      ``shard_plan``: the rules of ``SynthesisTrainer._shard`` - contiguous ``parallel.shard_rows``; a ragged batch gives
-             unequal shards, each weighted by its share of the rows; a batch with fewer rows than ranks leaves some ranks
+  shard      ``parallel.shard_plan``, as ``SynthesisTrainer._shard`` - contiguous ``parallel.shard_rows``; a ragged batch gives unequal shards, each weighted by its share of the rows; a batch with fewer rows than ranks leaves some ranks
              recomputing row ``rank % B`` with weight 0 so that every rank still takes part in every collective;
   loss       ``grad_scale`` of the CE kernel is 1 / B_global on a live rank (so the SUM over ranks is the global mean's gradient:
              no 1 / N anywhere else) and 0 on a weight-0 rank, whose statistics go to a scratch buffer that nobody reads;
@@ -16,48 +15,13 @@ No collective here runs without an active process group (``parallel.active()``);
 ``ShardPlan(B, 0, B, 1.0)`` on the same launches."""
 from __future__ import annotations
 
-from dataclasses import dataclass
 from typing import List
 
 import torch
 import torch.distributed as dist
 
 from . import parallel
-
-
-@dataclass(frozen=True)
-class ShardPlan:
-    """Rows [row0, row0 + rows) of a global batch of ``B``; ``weight`` = rows / B, or 0 for a rank that only recomputes a row."""
-    B: int
-    row0: int
-    rows: int
-    weight: float
-
-    @property
-    def live(self) -> bool:
-        return self.weight > 0.0
-
-    @property
-    def rows_sent(self) -> int:
-        """Rows of this rank that belong to the global batch (0 on a weight-0 rank)."""
-        return self.rows if self.live else 0
-
-    @property
-    def slice(self) -> slice:
-        return slice(self.row0, self.row0 + self.rows)
-
-
-def shard_plan(B: int, rank: int, world: int) -> ShardPlan:
-    if B < 1 or world < 1 or not 0 <= rank < world:
-        raise ValueError(f"shard_plan: batch {B}, rank {rank} of {world}")
-    if world == 1:
-        return ShardPlan(B, 0, B, 1.0)
-    if B >= world:
-        sl = parallel.shard_rows(B, rank, world)
-        return ShardPlan(B, sl.start, sl.stop - sl.start, (sl.stop - sl.start) / B)
-    if rank < B:
-        return ShardPlan(B, rank, 1, 1.0 / B)
-    return ShardPlan(B, rank % B, 1, 0.0)
+from .parallel import ShardPlan, shard_plan          # noqa: F401 - the shard rule lives beside shard_rows
 
 
 def _group_device(like: torch.Tensor) -> torch.device:

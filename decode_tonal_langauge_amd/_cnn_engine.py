@@ -18,6 +18,13 @@ from ._lib import EPI_LRELU, EPI_MASK, EPI_STORE, LOAD_DIRECT, check, ptr
 
 
 class CnnEngine(ConvStack):
+    whh_factors = None             # (``_lite_engine.TrainEngine``: what the trainer reads)
+    graph_capable = False          # GPU-bound; its W_hh update takes launch-argument scalars
+
+    @property
+    def ran_sharded(self) -> bool:
+        return self._sh is not None
+
     def __init__(self, output_dim: int, n_channels: int, n_timepoints: int, lstm_channels: int,
                  conv_channels: int, dropout: float, negative_slope: float, stage_defs, concat_widths):
         super().__init__(n_channels, n_timepoints, stage_defs, negative_slope, conv_channels)

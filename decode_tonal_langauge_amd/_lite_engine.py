@@ -13,7 +13,7 @@ kernel form here, their member forms in the ensemble) and ``_fc3_sum``, which th
 which pass the dropout seed by value while there is no seed table in device memory (an eager step of one model)."""
 from __future__ import annotations
 
-from typing import Dict
+from typing import Callable, Dict, Optional, Protocol
 
 import torch
 
@@ -27,8 +27,22 @@ MAX_ROWS = 512        # Krows (8 chunks of 64 rows)
 MAX_OUT = 1 << 20     # Mdim * Ndim
 
 
+class TrainEngine(Protocol):
+    """What ``SynthesisTrainer`` reads on ``model._engine`` (``LiteEngine``, ``_cnn_engine.CnnEngine``), besides ``forward`` /
+    ``backward``, ``ldd`` and ``p_drop``.  An engine states what it does not offer as a class-level default."""
+    lowrank_param: Optional[str]      # the parameter whose gradient leaves ``backward`` as factors (the label LSTM's W_hh); only
+    #                                   an engine that names one can shard that LSTM by gate rows
+    whh_factors: Optional[tuple]      # the factors of the last ``backward(whh_factors=True)``, None when it wrote the gradient
+    lstm_shard: Optional[tuple]       # (rank, world) set by the trainer: shard the label LSTM where a step allows it
+    ran_sharded: bool                 # the last forward did run row-sharded (decided per forward)
+    grad_order: Optional[Callable]    # () -> parameter names, first-finished first: the layout of ``parallel.FlatGrads``
+    graph_capable: bool               # the step may be captured into a HIP graph (``seed_dev``: dropout seed in device memory)
+
+
 class LiteEngine:
     NAME = "SynthesisLite"
+    lowrank_param = whh_factors = lstm_shard = grad_order = None
+    ran_sharded, graph_capable = False, True
 
     def __init__(self, output_dim, n_channels, n_timepoints, label_dim, conv_channels, lstm_hidden, dropout,
                  negative_slope, M: int = 1):

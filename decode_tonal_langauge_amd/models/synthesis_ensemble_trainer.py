@@ -19,14 +19,13 @@ Refused (``ValueError``): ``train_classifiers=True`` (classifier dropout makes t
 parallelism, and what ``LiteEnsembleEngine`` refuses.  Evaluation runs member by member through the single path."""
 from __future__ import annotations
 
-import ctypes as C
-import warnings
 from typing import Dict, Iterable, Iterator, List, Optional, Sequence, Tuple
 
 import torch
 
-from .. import _kernels, _lib, parallel
+from .. import _lib, parallel
 from .._lib import check, ptr
+from .._step_graph import StepGraphs, frozen_rows
 from ..data_loading.resident import ResidentDataset, ResidentLoader
 from ..optim import FusedNAdam
 from .classifier_ensemble_trainer import MemberStreams, check_loaders, draw_orders
@@ -85,8 +84,8 @@ class SynthesisEnsembleTrainer:
         self._stats = torch.zeros(M, 4, dtype=torch.float32, device=self.device)
         self._err = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.streams = MemberStreams(M, rng_states)
-        self._graph_enabled = _kernels.get("graph") != "0"
-        self._graphs, self._g_scal = {}, None
+        self._replay = StepGraphs("SynthesisEnsembleTrainer", self.lib, self.optimizer, self.device)
+        self._graphs = self._replay.states
 
     # ------------------------------------------------------------------ one step
     def _labels(self, inputs_tone: torch.Tensor, inputs_syllable: torch.Tensor) -> torch.Tensor:
@@ -109,7 +108,7 @@ class SynthesisEnsembleTrainer:
                                        torch.cuda.current_stream().cuda_stream), "tl_l1_mcd_group")
         eng.backward(dout)
         if graph:
-            self.optimizer.step_graph(self._grads, self._g_scal, grad_scale=1.0)
+            self.optimizer.step_graph(self._grads, self._replay.scalars, grad_scale=1.0)
         else:
             self.optimizer.step(grads=self._grads, grad_scale=1.0)
 
@@ -141,79 +140,34 @@ class SynthesisEnsembleTrainer:
         self._calls_host = [c + 1 for c in now]
         self.tone_model.eval()
         self.syllable_model.eval()
-        if self._graph_ok() and self._graph_step(inputs_non, inputs_syllable, inputs_tone, targets):
+        if self._graph_ok() and self._replay.step((inputs_non, inputs_syllable, inputs_tone, targets), self._stacks,
+                                                  self._graph_fingerprint, self._graph_capture):
             return
         with torch.no_grad():
             inputs_label = self._labels(inputs_tone, inputs_syllable)
         self._step(inputs_non, inputs_label, targets)
 
-    # ------------------------------------------------------------------ HIP-graph replay (SynthesisTrainer._graph_step for M)
+    # ------------------------------------------------------------------ HIP-graph replay (_step_graph.StepGraphs)
     def _graph_ok(self) -> bool:
-        return self._graph_enabled and not self.single._need_check
+        return not self.single._need_check
 
     def _graph_fingerprint(self) -> tuple:
-        """What a captured step has frozen into its kernel arguments besides the batch (``SynthesisTrainer._graph_fingerprint``)."""
-        opt = self.optimizer
-        fp = []
-        for group in opt.param_groups:
-            fp.append((tuple(group["betas"]), group["eps"], group["weight_decay"], group["momentum_decay"]))
-            for p in group["params"]:
-                st = opt.state.get(p) or {}
-                fp.append((p.data_ptr(), self._grads[p].data_ptr(),
-                           None if "exp_avg" not in st else st["exp_avg"].data_ptr(),
-                           None if "exp_avg_sq" not in st else st["exp_avg_sq"].data_ptr()))
-        fp.append((self.engine.p_drop, tuple(b.data_ptr() for b in self.engine.buffers.values()),
-                   None if self.engine.active is None else self.engine.active.data_ptr()))
-        for clf in (self.tone_model, self.syllable_model):
-            fp.append(tuple((q.data_ptr(), q._version) for q in clf.parameters()) + (clf.training,))
-        return tuple(fp)
+        """What a captured step has frozen into its kernel arguments besides the batch (``_step_graph.frozen_rows``)."""
+        eng = self.engine
+        return tuple(frozen_rows(self.optimizer, self._grads.get, (self.tone_model, self.syllable_model))
+                     + [(eng.p_drop, tuple(b.data_ptr() for b in eng.buffers.values()),
+                         None if eng.active is None else eng.active.data_ptr())])
 
-    def _graph_step(self, inputs_non, inputs_syllable, inputs_tone, targets) -> bool:
-        batch = (inputs_non, inputs_syllable, inputs_tone, targets)
-        key = tuple(tuple(t.shape) for t in batch) + tuple(t.dtype for t in batch)
-        st = self._graphs.get(key)
-        if st is None:
-            st = self._graphs[key] = {"warm": 0, "graph": None}
-        if st["graph"] is not None and st["fingerprint"] != self._graph_fingerprint():
-            st.update(graph=None, warm=0, keep=None, fingerprint=None)        # never replay onto freed or stale buffers
-        if st["graph"] is None:
-            if st["warm"] < 3 or len([v for v in self._graphs.values() if v["graph"] is not None]) >= 2:
-                st["warm"] += 1
-                return False                      # eager warm-up steps (and at most two captured shapes)
-            st["in"] = tuple(torch.empty_like(t) for t in batch)
-            if self._g_scal is None:
-                self._g_scal = torch.zeros(4, dtype=torch.float32, device=self.device)
-                self._g_seed = torch.zeros(1, dtype=torch.int64, device=self.device)       # (the single step's seed word: unused)
-            for d, t in zip(st["in"], batch):
-                d.copy_(t)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            calls = self._calls.clone()
-            try:
-                with torch.cuda.graph(g):
-                    with torch.no_grad():
-                        lab = self._labels(st["in"][2], st["in"][1])
-                    self._step(st["in"][0], lab, st["in"][3], graph=True)
-            except Exception as e:      # noqa: BLE001 - capture refused: stay eager for good
-                warnings.warn(f"SynthesisEnsembleTrainer: HIP-graph capture of the train step failed ({e!r}); continuing eagerly")
-                self._calls.copy_(calls)
-                self._graph_enabled = False
-                return False            # nothing was executed during the failed capture: run this step eagerly
-            st["graph"] = g
-            st["keep"] = list(self.optimizer._tables.values())
-            st["fingerprint"] = self._graph_fingerprint()
-            staged = ()
-        else:
-            staged = tuple(zip(st["in"], batch))
-        cg, cm, bc2 = self.optimizer.advance_scalars(set(self._stacks))
-        stream = torch.cuda.current_stream().cuda_stream
-        n = len(staged)
-        src = (C.c_void_p * 4)(*[t.data_ptr() for _, t in staged], *([None] * (4 - n)))
-        dst = (C.c_void_p * 4)(*[d.data_ptr() for d, _ in staged], *([None] * (4 - n)))
-        nby = (C.c_int64 * 4)(*[t.numel() * t.element_size() for _, t in staged], *([0] * (4 - n)))
-        check(self.lib.tl_stage_step(ptr(self._g_scal), ptr(self._g_seed), cg, cm, bc2, 0, src, dst, nby, n, stream), "tl_stage_step")
-        st["graph"].replay()
-        return True
+    def _graph_capture(self, recording, static) -> None:
+        calls = self._calls.clone()
+        try:
+            with recording:
+                with torch.no_grad():
+                    lab = self._labels(static[2], static[1])
+                self._step(static[0], lab, static[3], graph=True)
+        except Exception:
+            self._calls.copy_(calls)
+            raise
 
     # ------------------------------------------------------------------ public API
     def epoch_tables(self, loaders: Sequence[ResidentLoader]) -> Iterator[torch.Tensor]:

@@ -18,17 +18,15 @@ optimizer, :131-137) - ``train_classifiers`` only toggles ``.train()``.
 """
 from __future__ import annotations
 
-import os
-
 from typing import Dict, List, Tuple
 
-import numpy as np
 import torch
 import torch.nn as nn
 from torch.utils.data import DataLoader
 
 from .. import _kernels, _lib, parallel
 from .._lib import check, ptr
+from .._step_graph import StepGraphs, frozen_rows
 from ..optim import FusedNAdam
 from .classifier import ClassifierModel
 from .synthesis_models import SynthesisModel
@@ -45,6 +43,12 @@ def compute_mcd(true_mcc: torch.Tensor, pred_mcc: torch.Tensor) -> float:
     check(_lib.load().tl_l1_mcd(ptr(p), ptr(t.to(p.device)), None, ptr(stats), B, D, D, 0, 1.0,
                                 torch.cuda.current_stream().cuda_stream), "tl_l1_mcd")
     return float(stats[3].item())
+
+
+# with the row-sharded LSTM its dgates - hence the W_ih / bias gradients - already belong to the global batch on every rank:
+# they stay out of the all-reduce
+_LSTM_LOCAL = ("label_lstm.weight_ih_l0", "label_lstm.bias_ih_l0", "label_lstm.bias_hh_l0")
+_EARLY = ("output_layer.weight", "output_layer.bias")       # final before the convolution backward starts (on_grad_ready)
 
 
 class SynthesisTrainer:
@@ -104,17 +108,20 @@ class SynthesisTrainer:
             self._pair_table = torch.stack([syl_col, dyn], dim=2).reshape(n_cls * n_syl, 2, self._L).contiguous() \
                 .to(self.device)
             self._n_syl = int(n_syl)
-        self._pair_ids = None
+        self._pair_ids = None                 # (pair id per row, the label tensor they belong to) of the last label pass
         self._err = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._stats = torch.zeros(4, dtype=torch.float32, device=self.device)
-        self._grads = None
+        self._grads, self._flat, self._last_out = None, None, None
         self.rank, self.world = parallel.world()
         self.dp = parallel.active()
+        self._row0, self._weight = 0, 1.0     # this rank's shard of the current batch (_shard)
         self._whh_dirty = False
-        self._graph_enabled = _kernels.get("graph") != "0"
-        self._graphs, self._g_scal = {}, None
-        eng = getattr(self.model, "_engine", None)
-        if (self.dp and eng is not None and hasattr(eng, "lstm_shard") and self._pair_table is not None
+        self._guard_hooked = False
+        self.exchange_events = self.exchange_wait_events = None          # lists: HIP events around the exchange (bench.py)
+        self._replay = StepGraphs("SynthesisTrainer", self.lib, self.optimizer, self.device)
+        self._graphs = self._replay.states
+        eng = getattr(self.model, "_engine", None)    # None: a plug-in SynthesisModel on torch autograd (_generic_step)
+        if (self.dp and eng is not None and eng.lowrank_param is not None and self._pair_table is not None
                 and _kernels.get("lstm_shard") != "0"):
             eng.lstm_shard = (self.rank, self.world)        # row-sharded label LSTM (parallel.py docstring)
             # Between steps each rank holds current values only for its own rows of weight_hh_l0.  `train` / `evaluate`
@@ -177,27 +184,14 @@ class SynthesisTrainer:
         return labels
 
     def _shard(self, *tensors):
-        """Row shard of a global batch for this rank.  Sets ``self._row0`` (first global row of the shard)
-        and ``self._weight`` = (rows this rank contributes) / (rows of the global batch): the loss is a
-        mean over the GLOBAL batch, so a rank's gradient enters the all-reduce sum with that weight
-        (uneven shards of a ragged last batch included).  A batch with fewer rows than ranks leaves
-        some ranks without rows: they recompute row ``rank % n`` with weight 0, so every rank still
-        takes part in every collective - decided identically everywhere from the global row count."""
-        n = tensors[0].shape[0]
+        """Row shard of a global batch for this rank (``parallel.shard_plan``).  Sets ``self._row0`` (first global row of the
+        shard) and ``self._weight``, the share of the global mean loss this rank's rows carry."""
         if self.world == 1:
             self._row0, self._weight = 0, 1.0
             return tensors
-        if n >= self.world:
-            sl = parallel.shard_rows(n, self.rank, self.world)
-            self._row0, self._weight = sl.start, (sl.stop - sl.start) / n
-        elif self.rank < n:
-            sl = slice(self.rank, self.rank + 1)
-            self._row0, self._weight = self.rank, 1.0 / n
-        else:
-            r = self.rank % n
-            sl = slice(r, r + 1)
-            self._row0, self._weight = r, 0.0
-        return tuple(t[sl] for t in tensors)
+        plan = parallel.shard_plan(tensors[0].shape[0], self.rank, self.world)
+        self._row0, self._weight = plan.row0, plan.weight
+        return tuple(t[plan.slice] for t in tensors)
 
     def _loss_stats(self, out, targets, dout, ldd, trunc: int, stats=None) -> None:
         """``tl_l1_mcd``: loss gradient (scaled by this rank's weight in the global mean) and the
@@ -205,7 +199,7 @@ class SynthesisTrainer:
         same weight so that their sum over ranks is the statistic of the global batch."""
         stats = self._stats if stats is None else stats
         B, D = out.shape
-        w = getattr(self, "_weight", 1.0)
+        w = self._weight
         if not self.dp:
             check(self.lib.tl_l1_mcd(ptr(out), ptr(targets), ptr(dout), ptr(stats), B, D, ldd, trunc, 1.0,
                                      torch.cuda.current_stream().cuda_stream), "tl_l1_mcd")
@@ -218,7 +212,7 @@ class SynthesisTrainer:
 
     def _timed(self, fn):
         """Wrap an exchange-step call with HIP events when ``self.exchange_events`` is a list (bench.py)."""
-        events = getattr(self, "exchange_events", None)
+        events = self.exchange_events
         if events is None:
             return fn
 
@@ -237,15 +231,15 @@ class SynthesisTrainer:
         names = model._pnames
         params = dict(model.named_parameters())
         prm = {k: params[k].detach() for k in names}
-        skip = getattr(eng, "lowrank_param", None)
+        skip = eng.lowrank_param
         if self._grads is None:
             # the low-rank parameter's gradient (5.4 GB at the north-star shape) is only materialised
             # if its rank exceeds what the fused optimiser kernel takes (the engine then allocates it)
-            if self.dp and hasattr(eng, "grad_order"):
+            if self.dp and eng.grad_order is not None:
                 # data parallel: ONE flat buffer in the order the backward pass finishes the gradients - a bucket of the
                 # exchange step is a contiguous slice (no torch.cat in front of the collective, no copy back behind it)
-                sharded = getattr(eng, "lstm_shard", None) is not None and self._pair_table is not None
-                local_only = ("label_lstm.weight_ih_l0", "label_lstm.bias_ih_l0", "label_lstm.bias_hh_l0") if sharded else ()
+                sharded = eng.lstm_shard is not None and self._pair_table is not None
+                local_only = _LSTM_LOCAL if sharded else ()
                 self._flat = parallel.FlatGrads({k: v.shape for k, v in prm.items() if k != skip}, eng.grad_order(),
                                                 prm[names[0]].device, local=local_only)
                 self._grads = self._flat.views
@@ -253,13 +247,13 @@ class SynthesisTrainer:
                 self._grads = {k: torch.empty_like(v) for k, v in prm.items() if k != skip}
         prm.update(model._engine_buffers())
         kw = {}
-        ids = getattr(self, "_pair_ids", None)
-        if ids is not None and ids[1] is inputs_label and getattr(eng, "lowrank_param", None) is not None:
+        ids = self._pair_ids
+        if ids is not None and ids[1] is inputs_label and skip is not None:
             kw = dict(label_ids=ids[0], label_table=self._pair_table)             # CNN engine: skip torch.unique
         # (HIP-graph capture: the engine reads the dropout seed from device memory, the host seed counter is advanced by
         # the caller once per replay)
         out = eng.forward(prm, inputs_non, inputs_label, training=model.training, save=True,
-                          seed=0 if graph else model._next_seed(), row0=getattr(self, "_row0", 0), **kw)
+                          seed=0 if graph else model._next_seed(), row0=self._row0, **kw)
         B, D = out.shape
         self._last_out = out             # the step's outputs (pre-update), for callers that track them (tests)
         # (tl_l1_mcd writes all D columns of a row: the zero fill is only for padding columns)
@@ -274,12 +268,12 @@ class SynthesisTrainer:
             # single process: the W_hh update (33 GB of HBM traffic) is issued as soon as its gradient factors exist, on the
             # stream the LSTM backward runs on - beside the convolution backward instead of behind it.  ``dh``: the engine
             # asks for the last BPTT product out of the same pass (they exist one step early: h_0 = 0)
-            factors = getattr(eng, "whh_factors", None)
+            factors = eng.whh_factors
             if factors is not None and not self.dp:
                 self.optimizer.step_lowrank({params[skip]: factors}, grad_scale=scale, dh=dh)
                 early.append(params[skip])
         on_factors.fuse_dh = not self.dp
-        flat = getattr(self, "_flat", None) if self.dp else None
+        flat = self._flat if self.dp else None
         pending = []
 
         def on_grad_ready(group):
@@ -287,40 +281,15 @@ class SynthesisTrainer:
             # shape) are final before the convolution backward starts - their all-reduce is started here and runs beside
             # that backward pass ("launched as soon as each grad is final"); the optimiser waits for it below
             if flat is not None and group == "output_layer":
-                pending.append(self._timed(parallel.all_reduce_async)(flat.span(["output_layer.weight", "output_layer.bias"])))
+                pending.append(self._timed(parallel.all_reduce_async)(flat.span(_EARLY)))
         bkw = dict(on_grad_ready=on_grad_ready) if flat is not None else {}
         eng.backward(prm, dout, self._grads, gather_whh=gather, whh_factors=skip is not None, reduce_rows=reduce_rows,
                      on_factors=on_factors if skip is not None else None, **bkw)
         if self.dp:
-            sharded = getattr(eng, "_sh", None) is not None
-            # with the row-sharded LSTM its dgates - hence the W_ih / bias gradients - already belong to the global
-            # batch on every rank: they stay out of the all-reduce
-            local_only = ("label_lstm.weight_ih_l0", "label_lstm.bias_ih_l0", "label_lstm.bias_hh_l0") if sharded else ()
-            if flat is not None and tuple(local_only) == tuple(flat.local):
-                rest = [k for k in flat.offsets if k not in ("output_layer.weight", "output_layer.bias") and k not in local_only]
-                if not pending:                              # (an engine that never reported the early group)
-                    rest = [k for k in flat.offsets if k not in local_only]
-                if rest:
-                    pending.append(self._timed(parallel.all_reduce_async)(flat.span(rest)))
-                wait_events = getattr(self, "exchange_wait_events", None)
-                for h in pending:
-                    h.wait(wait_events)
-            else:
-                # The row-sharded LSTM fell back for this step (its shard decision is per forward: (L - 1) U > 64, a gate-row
-                # count the world size does not divide, no label table) or started to shard after the flat layout was fixed:
-                # the flat span no longer matches what must be reduced.  The early bucket (output layer) is already in
-                # flight: wait for it and reduce every OTHER gradient exactly once.
-                wait_events = getattr(self, "exchange_wait_events", None)
-                reduced = set()
-                for h in pending:
-                    h.wait(wait_events)
-                    reduced.update(("output_layer.weight", "output_layer.bias"))
-                self._timed(parallel.allreduce_bucketed)([g for k, g in self._grads.items()
-                                                          if k != skip and k not in local_only and k not in reduced])
-            self._whh_dirty = self._whh_dirty or sharded
-        factors = getattr(eng, "whh_factors", None)
+            self._exchange(eng, flat, pending, skip)
+        factors = eng.whh_factors
         if graph:            # scalars of the step from device memory (advanced by the caller per replay)
-            self.optimizer.step_graph({params[k]: self._grads[k] for k in names}, self._g_scal, grad_scale=scale)
+            self.optimizer.step_graph({params[k]: self._grads[k] for k in names}, self._replay.scalars, grad_scale=scale)
         elif early:            # W_hh is already updated
             self.optimizer.step(grads={params[k]: self._grads[k] for k in names if k != skip}, grad_scale=scale, skip=set(early))
         elif factors is not None:          # the optimiser forms that gradient from its factors on the fly
@@ -329,6 +298,33 @@ class SynthesisTrainer:
         else:
             self.optimizer.step(grads={params[k]: self._grads[k] for k in names}, grad_scale=scale)
 
+    def _exchange(self, eng, flat, pending, skip) -> None:
+        """The data-parallel gradient exchange behind the backward pass: ``pending`` holds the all-reduce of the early bucket
+        when ``on_grad_ready`` started one, ``skip`` names the low-rank parameter (exchanged as factors, inside the backward)."""
+        sharded = eng.ran_sharded
+        local_only = _LSTM_LOCAL if sharded else ()
+        wait_events = self.exchange_wait_events
+        if flat is not None and local_only == tuple(flat.local):
+            rest = [k for k in flat.offsets if k not in _EARLY and k not in local_only]
+            if not pending:                              # (an engine that never reported the early group)
+                rest = [k for k in flat.offsets if k not in local_only]
+            if rest:
+                pending.append(self._timed(parallel.all_reduce_async)(flat.span(rest)))
+            for h in pending:
+                h.wait(wait_events)
+        else:
+            # The row-sharded LSTM fell back for this step (its shard decision is per forward: (L - 1) U > 64, a gate-row
+            # count the world size does not divide, no label table) or started to shard after the flat layout was fixed:
+            # the flat span no longer matches what must be reduced.  The early bucket (output layer) is already in
+            # flight: wait for it and reduce every OTHER gradient exactly once.
+            reduced = set()
+            for h in pending:
+                h.wait(wait_events)
+                reduced.update(_EARLY)
+            self._timed(parallel.allreduce_bucketed)([g for k, g in self._grads.items()
+                                                      if k != skip and k not in local_only and k not in reduced])
+        self._whh_dirty = self._whh_dirty or sharded
+
     def _generic_step(self, inputs_non, inputs_label, targets) -> None:
         """Any other ``SynthesisModel`` subclass: torch autograd for the model, fused NAdam."""
         self.optimizer.zero_grad()
@@ -336,7 +332,7 @@ class SynthesisTrainer:
         tgt = targets.long()
         loss = self.criterion(outputs, tgt)
         if self.dp:
-            (loss * getattr(self, "_weight", 1.0)).backward()
+            (loss * self._weight).backward()
             for p in self.model.parameters():
                 if p.grad is None:
                     p.grad = torch.zeros_like(p)
@@ -366,7 +362,7 @@ class SynthesisTrainer:
         single-process trajectory across a switch (bench.py ``--lstm-shard auto`` switches during warm-up).  The flat gradient
         layout is rebuilt.  Returns whether the LSTM will run sharded (False where the model / label table does not allow it)."""
         eng = getattr(self.model, "_engine", None)
-        if not self.dp or eng is None or not hasattr(eng, "lstm_shard"):
+        if not self.dp or eng is None or eng.lowrank_param is None:
             return False
         self.sync_parameters()
         want = (self.rank, self.world) if (on and self._pair_table is not None and self.world > 1) else None
@@ -388,7 +384,7 @@ class SynthesisTrainer:
                         st[key] = parallel.all_gather_param_rows_(full, r0, rows)
                 st["shard_rows"] = (r0, rows) if want is not None else None
             self._grads, self._flat = None, None
-            if want is not None and not getattr(self, "_guard_hooked", False):
+            if want is not None and not self._guard_hooked:
                 self.model.register_state_dict_pre_hook(self._state_dict_guard)
                 self._guard_hooked = True
         return eng.lstm_shard is not None
@@ -414,115 +410,42 @@ class SynthesisTrainer:
         targets = targets.to(dev, non_blocking=True).float().contiguous()
         inputs_non, inputs_syllable, inputs_tone, targets = self._shard(inputs_non, inputs_syllable, inputs_tone,
                                                                         targets)
-        if self._graph_ok() and self._graph_step(inputs_non, inputs_syllable, inputs_tone, targets):
+        eng = getattr(self.model, "_engine", None)    # None: a plug-in SynthesisModel on torch autograd
+        if self._graph_ok(eng) and self._replay.step((inputs_non, inputs_syllable, inputs_tone, targets), self.model.parameters(),
+                                                     self._graph_fingerprint, self._graph_capture, self.model._next_seed):
             return
         with torch.no_grad():
             inputs_label = self._labels(inputs_tone, inputs_syllable)
-        if getattr(self.model, "_engine", None) is not None and hasattr(self.model._engine, "backward"):
+        if eng is not None:
             self._fused_step(inputs_non.float().contiguous(), inputs_label, targets.contiguous())
         else:
             self._generic_step(inputs_non, inputs_label, targets)
 
-    # ------------------------------------------------------------------ HIP-graph replay of a launch-bound step
-    def _graph_ok(self) -> bool:
-        """The step of a small model (SynthesisLite: ~58 launches of 4-20 us) is bound by launch overhead, not by the GPU:
-        after three eager steps at a batch shape it is captured once into a HIP graph and replayed.  What changes from step
-        to step lives in device memory - the NAdam coefficients (``tl_nadam_multi_dev``) and the dropout seed
-        (``tl_lite_cat_dev`` / ``tl_lite_uncat_dev``) - and is refreshed by two small copies before each replay.  Not under
-        data parallelism (collectives), not with classifiers in train mode (their dropout seed is a launch argument), not
-        for the big model (GPU-bound; its W_hh update takes launch-argument scalars).  TONAL_GRAPH=0 turns it off."""
-        eng = getattr(self.model, "_engine", None)
-        return (self._graph_enabled and eng is not None and hasattr(eng, "seed_dev") and not self.dp
-                and not self.train_classifiers and not self._need_check and self.model.training)
+    # ------------------------------------------------------------------ HIP-graph replay (_step_graph.StepGraphs)
+    def _graph_ok(self, eng) -> bool:
+        """Whether this step may go through a HIP graph.  Not under data parallelism (collectives), not with classifiers in
+        train mode (their dropout seed is a launch argument), not for the big model (GPU-bound; its W_hh update takes
+        launch-argument scalars).  TONAL_GRAPH=0 turns it off."""
+        return (eng is not None and eng.graph_capable and not self.dp and not self.train_classifiers and not self._need_check
+                and self.model.training)
 
     def _graph_fingerprint(self) -> tuple:
-        """Everything a captured step has frozen into its kernel arguments besides the batch: storage of the parameters,
-        of their gradients and NAdam moments, the optimiser's hyper-parameters, the dropout rate and the classifiers'
-        weights (their packed copies are rebuilt when a weight's version changes - and ``FusedNAdam`` moves ``_version`` like
-        torch's own in-place writes, so a classifier trained on the fused path between two steps is seen here).  A replay is only valid while this tuple
-        is what it was at capture: ``optimizer.load_state_dict`` (new moment tensors), an edited ``param_groups`` entry, a
-        re-loaded classifier or a re-assigned ``.data`` would otherwise leave the graph reading freed or stale buffers."""
-        opt = self.optimizer
-        fp = []
+        """What a captured step has frozen into its kernel arguments besides the batch (``_step_graph.frozen_rows``)."""
         name_of = {id(p): k for k, p in self.model.named_parameters()}       # gradient storage is keyed by parameter NAME
-        for group in opt.param_groups:
-            fp.append((tuple(group["betas"]), group["eps"], group["weight_decay"], group["momentum_decay"]))
-            for p in group["params"]:
-                st = opt.state.get(p) or {}
-                g = (self._grads or {}).get(name_of.get(id(p)))
-                fp.append((p.data_ptr(), None if g is None else g.data_ptr(),
-                           None if "exp_avg" not in st else st["exp_avg"].data_ptr(),
-                           None if "exp_avg_sq" not in st else st["exp_avg_sq"].data_ptr()))
-        eng = getattr(self.model, "_engine", None)
-        fp.append((getattr(eng, "p_drop", None), getattr(self.model, "training", None)))
-        for clf in (self.tone_model, self.syllable_model):
-            fp.append(tuple((q.data_ptr(), q._version) for q in clf.parameters()) + (clf.training,))
-        return tuple(fp)
+        grads = self._grads or {}
+        return tuple(frozen_rows(self.optimizer, lambda p: grads.get(name_of.get(id(p))), (self.tone_model, self.syllable_model))
+                     + [(self.model._engine.p_drop, self.model.training)])
 
-    def _graph_step(self, inputs_non, inputs_syllable, inputs_tone, targets) -> bool:
-        key = (tuple(inputs_non.shape), tuple(inputs_syllable.shape), tuple(inputs_tone.shape), tuple(targets.shape),
-               inputs_non.dtype, inputs_syllable.dtype, inputs_tone.dtype)
-        st = self._graphs.get(key)
-        if st is None:
-            st = self._graphs[key] = {"warm": 0, "graph": None}
-        if st["graph"] is not None and st["fingerprint"] != self._graph_fingerprint():
-            # something the capture had frozen was replaced: drop the graph (and the NAdam entry table it pinned), warm
-            # up eagerly again and recapture - never replay onto freed or stale buffers
-            st.update(graph=None, warm=0, params=None, keep=None, fingerprint=None)
-        if st["graph"] is None:
-            if st["warm"] < 3 or len([v for v in self._graphs.values() if v["graph"] is not None]) >= 2:
-                st["warm"] += 1
-                return False                      # eager warm-up steps (and at most two captured shapes)
-            model, eng = self.model, self.model._engine
-            params = [p for _, p in model.named_parameters()]
-            st["in"] = tuple(torch.empty_like(t) for t in (inputs_non, inputs_syllable, inputs_tone, targets))
-            if self._g_scal is None:
-                self._g_scal = torch.zeros(4, dtype=torch.float32, device=self.device)
-                self._g_seed = torch.zeros(1, dtype=torch.int64, device=self.device)
-            eng.seed_dev = self._g_seed
-            for d, t in zip(st["in"], (inputs_non, inputs_syllable, inputs_tone, targets)):
-                d.copy_(t)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            try:
-                with torch.cuda.graph(g):
-                    with torch.no_grad():
-                        lab = self._labels(st["in"][2], st["in"][1])
-                    self._fused_step(st["in"][0].float().contiguous(), lab, st["in"][3].contiguous(), graph=True)
-            except Exception as e:      # noqa: BLE001 - capture refused (e.g. an op that synchronises): stay eager for good
-                import warnings
-                warnings.warn(f"SynthesisTrainer: HIP-graph capture of the train step failed ({e!r}); continuing eagerly")
-                eng.seed_dev = None
-                self._graph_enabled = False
-                return False            # nothing was executed during the failed capture: run this step eagerly
-            eng.seed_dev = None                      # eager steps (other shapes) keep passing the seed by value
-            st["graph"], st["params"] = g, set(params)
-            # the graph holds raw pointers into the optimiser's entry tables: keep those tensors alive with it (the
-            # optimiser's own cache is cleared when it grows), and remember what the capture froze
-            st["keep"] = list(self.optimizer._tables.values())
-            st["fingerprint"] = self._graph_fingerprint()
-            staged = ()
-        else:
-            staged = tuple(zip(st["in"], (inputs_non, inputs_syllable, inputs_tone, targets)))
-        cg, cm, bc2 = self.optimizer.advance_scalars(st["params"])
-        # the values travel as launch arguments (a pinned host buffer would be overwritten by the next step before an
-        # asynchronous copy of this one has read it: the host runs ahead of the stream); the batch goes into the graph's
-        # static input buffers by the same launch
-        if all(t.is_cuda and t.is_contiguous() and t.dtype == d.dtype and t.shape == d.shape for d, t in staged):
-            import ctypes as C
-            n = len(staged)
-            src = (C.c_void_p * 4)(*[t.data_ptr() for _, t in staged])
-            dst = (C.c_void_p * 4)(*[d.data_ptr() for d, _ in staged])
-            nby = (C.c_int64 * 4)(*[t.numel() * t.element_size() for _, t in staged])
-            check(self.lib.tl_stage_step(ptr(self._g_scal), ptr(self._g_seed), cg, cm, bc2, self.model._next_seed(), src, dst, nby, n,
-                                         torch.cuda.current_stream().cuda_stream), "tl_stage_step")
-        else:
-            for d, t in staged:
-                d.copy_(t, non_blocking=True)
-            check(self.lib.tl_set_step_scalars(ptr(self._g_scal), ptr(self._g_seed), cg, cm, bc2, self.model._next_seed(),
-                                               torch.cuda.current_stream().cuda_stream), "tl_set_step_scalars")
-        st["graph"].replay()
-        return True
+    def _graph_capture(self, recording, static) -> None:
+        eng = self.model._engine
+        eng.seed_dev = self._replay.seed         # the captured step reads its dropout seed from device memory
+        try:
+            with recording:
+                with torch.no_grad():
+                    lab = self._labels(static[2], static[1])
+                self._fused_step(static[0].float().contiguous(), lab, static[3].contiguous(), graph=True)
+        finally:
+            eng.seed_dev = None                  # eager steps (other shapes) keep passing the seed by value
 
     # ------------------------------------------------------------------ public API
     def train(self, train_loader: DataLoader, epochs: int, verbose: bool = True) -> List[Tuple[float, float]]:

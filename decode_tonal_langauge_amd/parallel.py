@@ -20,6 +20,7 @@ Windows are independent, so a global batch is sharded by rows (rank r takes rows
 from __future__ import annotations
 
 import os
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -193,6 +194,45 @@ def shard_rows(n: int, rank: int, nranks: int) -> slice:
     start = rank * base + max(0, rank - (nranks - rem)) if rem else rank * base
     size = base + (1 if rem and rank >= nranks - rem else 0)
     return slice(start, start + size)
+
+
+@dataclass(frozen=True)
+class ShardPlan:
+    """Rows [row0, row0 + rows) of a global batch of ``B``; ``weight`` = rows / B, or 0 for a rank that only recomputes a row."""
+    B: int
+    row0: int
+    rows: int
+    weight: float
+
+    @property
+    def live(self) -> bool:
+        return self.weight > 0.0
+
+    @property
+    def rows_sent(self) -> int:
+        """Rows of this rank that belong to the global batch (0 on a weight-0 rank)."""
+        return self.rows if self.live else 0
+
+    @property
+    def slice(self) -> slice:
+        return slice(self.row0, self.row0 + self.rows)
+
+
+def shard_plan(B: int, rank: int, world: int) -> ShardPlan:
+    """The row shard of ``rank`` in a global batch of ``B`` rows, for every trainer and train engine.  The loss is a mean over
+    the GLOBAL batch, so a rank's gradient enters the all-reduce sum with ``weight`` (uneven shards of a ragged last batch
+    included).  A batch with fewer rows than ranks leaves some ranks without rows: they recompute row ``rank % B`` with weight
+    0, so every rank still takes part in every collective - decided identically everywhere from the global row count."""
+    if B < 1 or world < 1 or not 0 <= rank < world:
+        raise ValueError(f"shard_plan: batch {B}, rank {rank} of {world}")
+    if world == 1:
+        return ShardPlan(B, 0, B, 1.0)
+    if B >= world:
+        sl = shard_rows(B, rank, world)
+        return ShardPlan(B, sl.start, sl.stop - sl.start, (sl.stop - sl.start) / B)
+    if rank < B:
+        return ShardPlan(B, rank, 1, 1.0 / B)
+    return ShardPlan(B, rank % B, 1, 0.0)
 
 
 def allreduce_bucketed(tensors: List[torch.Tensor], bucket_bytes: int = 64 << 20) -> None:

@@ -267,6 +267,37 @@ def test_lite_trainer_steps_follow_float64_oracle(dev, graph, monkeypatch):
             assert v < 5e-4, (k, v)
 
 
+def test_lite_trainer_holds_at_most_two_captured_shapes(dev, monkeypatch):
+    """15 ``train_step``s with batch sizes cycling 5, 3, 2: the first two shapes are captured after their three eager steps, the
+    third stays eager while two graphs are held - and the run leaves the bits of the same run with TONAL_GRAPH=0."""
+    from decode_tonal_langauge_amd.models.simple_classifiers import LogisticRegressionClassifier
+    from decode_tonal_langauge_amd.models.synthesis_models import SynthesisLite
+    from decode_tonal_langauge_amd.models.synthesis_trainer import SynthesisTrainer
+    C, T, D = 4, 64, 80
+    gen = torch.Generator().manual_seed(29)
+    data = [(torch.randn(B, C, T, generator=gen), torch.randn(B, 8, T, generator=gen), torch.randn(B, 8, T, generator=gen),
+             10 * torch.randn(B, D, generator=gen)) for B in (5, 3, 2) * 5]
+    res = {}
+    for mode in ("0", "1"):
+        monkeypatch.setenv("TONAL_GRAPH", mode)
+        torch.manual_seed(0)
+        model = SynthesisLite(D, C, T, dropout=0.3)
+        torch.manual_seed(1)
+        tr = SynthesisTrainer(model, LogisticRegressionClassifier(8 * T, 4), LogisticRegressionClassifier(8 * T, 2), gi.TONE_MAP,
+                              device=dev, verbose=False)
+        model.train()
+        for b in data:
+            tr.train_step(*b)
+        torch.cuda.synchronize()
+        held = sorted(k[0][0] for k, v in tr._graphs.items() if v["graph"] is not None)
+        assert held == ([3, 5] if mode == "1" else []), held
+        res[mode] = ({k: v.detach().clone() for k, v in model.state_dict().items()}, tr._stats.clone(), tr._last_out.clone())
+    assert set(res["1"][0]) == set(dict(model.named_parameters())) | set(dict(model.named_buffers()))
+    for k, v in res["1"][0].items():
+        assert torch.equal(v, res["0"][0][k]), k
+    assert torch.equal(res["1"][1], res["0"][1]) and torch.equal(res["1"][2], res["0"][2])
+
+
 @pytest.mark.parametrize("kw,match", [
     (dict(n_channels=241), "240 ECoG channels"),
     (dict(lstm_hidden=6), "multiple of 4"),

@@ -410,6 +410,51 @@ def test_ensemble_train_step_with_graph_equal_single_runs(dev, graph, monkeypatc
     assert captured == (1 if graph == "1" else 0)
 
 
+def test_ensemble_hip_graph_is_dropped_when_what_it_froze_is_replaced(dev, monkeypatch):
+    """The events of ``test_lite_hip_graph_is_dropped_when_what_it_froze_is_replaced`` (tests/test_gpu_parity.py) on the S2 group:
+    ``optimizer.load_state_dict`` (new moment tensors), an edited ``weight_decay`` and a tone classifier re-loaded in place must
+    each invalidate the captured group step; the run keeps the bits of the same run with TONAL_GRAPH=0."""
+    import copy
+    from decode_tonal_langauge_amd.models.simple_classifiers import LogisticRegressionClassifier
+    from decode_tonal_langauge_amd.models.synthesis_ensemble_trainer import SynthesisEnsembleTrainer
+    cfg = S2
+    B, Cn, T, D = cfg[:4]
+    g = torch.Generator().manual_seed(8)
+    batches = [tuple(torch.stack([f(g) for _ in range(M)]) for f in (
+        lambda g: torch.randn(B, Cn, T, generator=g), lambda g: torch.randn(B, 8, T, generator=g),
+        lambda g: torch.randn(B, 8, T, generator=g), lambda g: 10 * torch.randn(B, D, generator=g))) for _ in range(20)]
+    torch.manual_seed(5)
+    other_tone = LogisticRegressionClassifier(8 * T, 4).state_dict()
+    res = {}
+    for mode in ("0", "1"):
+        monkeypatch.setenv("TONAL_GRAPH", mode)
+        tone, syl = classifiers(T)
+        ens = SynthesisEnsembleTrainer(lite_models(cfg), tone, syl, gi.TONE_MAP, seeds=SEEDS, device=dev, verbose=False)
+        captures = []
+        for i, b in enumerate(batches):
+            if i == 6:                                            # moments move to freshly allocated tensors
+                ens.optimizer.load_state_dict(copy.deepcopy(ens.optimizer.state_dict()))
+            if i == 11:                                           # a launch scalar the capture passed by value
+                for gparam in ens.optimizer.param_groups:
+                    gparam["weight_decay"] = 0.01
+            if i == 16:                                           # classifier weights re-loaded in place (version bump)
+                ens.tone_model.load_state_dict({k: v.to(dev) for k, v in other_tone.items()})
+            ens.train_step(*b)
+            captures.append(sum(1 for v in ens._graphs.values() if v["graph"] is not None))
+        torch.cuda.synchronize()
+        if mode == "1":
+            assert captures[5] == 1 and captures[6] == 0 and captures[10] == 1 and captures[11] == 0 and captures[16] == 0 \
+                and captures[-1] == 1, captures
+        else:
+            assert captures == [0] * 20
+        res[mode] = (ens._stats.clone(), [_state(m) for m in ens.models])
+    assert torch.equal(res["1"][0], res["0"][0]), (res["1"][0].tolist(), res["0"][0].tolist())
+    for m in range(M):
+        assert set(res["1"][1][m]) == set(res["0"][1][m])
+        for k, v in res["1"][1][m].items():
+            assert torch.equal(v, res["0"][1][m][k]), (m, k)
+
+
 def test_train_step_after_a_forward_through_a_member_module(dev, monkeypatch):
     """A forward through a member's module between two ``train_step`` calls (evaluation, inference) advances that member's
     dropout call counter on the host only; the next ``train_step`` still draws the masks of the sequential run."""
