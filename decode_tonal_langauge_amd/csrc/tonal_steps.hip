@@ -174,6 +174,158 @@ __global__ __launch_bounds__(256) void rolling_zscore_kernel(const void* __restr
   y[row + t] = out;
 }
 
+// The same quantity in O(1) per output (tl_rolling_zscore_blocked): the window's count, sum S1 and sum of
+// squares S2 - the sums as (hi, lo) pairs, so that n S2 - S1^2 survives its cancellation - plus its minimum and maximum, which
+// decide pandas' flat-window rule exactly.  With W >= RZ_TB every window of output tile j (samples t0 .. t0 + 255) is the
+// union of three parts, nothing subtracted:
+//   (a) the tile's prefix up to the output                             - a forward scan over the tile;
+//   (b) the whole tiles k0 .. j-1, k0 = ceil((t0 + 256 - W) / 256)      - rows of the per-tile table rz_tile_moments wrote;
+//   (c) the head: the L <= 510 samples from t0 - W + 1 up to tile k0   - output i takes head[i .. L): a backward scan over
+//       head[0 .. 256) plus all of head[256 .. L).
+// Lane i starts its partial with head[256 + i] and adds the table rows k0 + i, k0 + i + 256, ... in that order; one scan over
+// the partials gives the part M every output of the tile shares.  Output i: ((c_i + M) + a_i).  The order of every sum is
+// fixed by the lane and wave numbers alone: two runs give the same bits.  Samples before t = 0 or past T and NaN samples
+// enter as the identity and are never dereferenced.  tests/rolling_blocked_ref.py restates all of this in NumPy.
+struct RzMom {
+  int n;
+  double s1h, s1l, s2h, s2l, mn, mx;
+};
+__device__ __forceinline__ void rz_two_sum(double a, double b, double& s, double& e) {   // a + b = s + e exactly
+  s = __dadd_rn(a, b);
+  const double bv = __dsub_rn(s, a);
+  e = __dadd_rn(__dsub_rn(a, __dsub_rn(s, bv)), __dsub_rn(b, bv));
+}
+__device__ __forceinline__ void rz_fast_two_sum(double a, double b, double& s, double& e) {   // the same for |a| >= |b|
+  s = __dadd_rn(a, b);
+  e = __dsub_rn(b, __dsub_rn(s, a));
+}
+__device__ __forceinline__ void rz_dd_add(double ah, double al, double bh, double bl, double& h, double& l) {
+  double s, e, t, f, s2, e2;
+  rz_two_sum(ah, bh, s, e);
+  rz_two_sum(al, bl, t, f);
+  rz_fast_two_sum(s, __dadd_rn(e, t), s2, e2);
+  rz_fast_two_sum(s2, __dadd_rn(e2, f), h, l);
+}
+// (a b) + c as a pair: a b exactly by fma, the low-order term c added to its error.  Every product of this route is an
+// rz_mul: it rounds on its own whatever contraction the file is compiled with (the additions are __dadd_rn / __dsub_rn).
+__device__ __forceinline__ double rz_mul(double a, double b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ void rz_prod_plus(double a, double b, double c, double& h, double& l) {
+  const double p = rz_mul(a, b);
+  const double e = __fma_rn(a, b, -p);
+  rz_fast_two_sum(p, __dadd_rn(e, c), h, l);
+}
+__device__ __forceinline__ RzMom rz_identity() {
+  return {0, 0.0, 0.0, 0.0, 0.0, __longlong_as_double(0x7ff0000000000000LL), __longlong_as_double(0xfff0000000000000LL)};
+}
+__device__ __forceinline__ RzMom rz_sample(double v) {
+  if (v != v) return rz_identity();
+  RzMom m = {1, v, 0.0, 0.0, 0.0, v, v};
+  rz_prod_plus(v, v, 0.0, m.s2h, m.s2l);
+  return m;
+}
+template <typename T>
+__device__ __forceinline__ RzMom rz_load(const void* __restrict__ x, long long row, long long Tn, long long t) {
+  return (t >= 0 && t < Tn) ? rz_sample(ldd<T>(x, row + t)) : rz_identity();
+}
+__device__ __forceinline__ RzMom rz_combine(const RzMom& a, const RzMom& b) {   // a's samples, then b's
+  RzMom r;
+  r.n = a.n + b.n;
+  rz_dd_add(a.s1h, a.s1l, b.s1h, b.s1l, r.s1h, r.s1l);
+  rz_dd_add(a.s2h, a.s2l, b.s2h, b.s2l, r.s2h, r.s2l);
+  r.mn = fmin(a.mn, b.mn);
+  r.mx = fmax(a.mx, b.mx);
+  return r;
+}
+template <bool REV>
+__device__ __forceinline__ RzMom rz_shfl(const RzMom& m, int off) {
+  RzMom r;
+#define RZ_SH(f) r.f = REV ? __shfl_down(m.f, off) : __shfl_up(m.f, off)
+  RZ_SH(n); RZ_SH(s1h); RZ_SH(s1l); RZ_SH(s2h); RZ_SH(s2l); RZ_SH(mn); RZ_SH(mx);
+#undef RZ_SH
+  return r;
+}
+__device__ __forceinline__ void rz_put(double* p, const RzMom& m) {
+  p[0] = (double)m.n; p[1] = m.s1h; p[2] = m.s1l; p[3] = m.s2h; p[4] = m.s2l; p[5] = m.mn; p[6] = m.mx; p[7] = 0.0;
+}
+__device__ __forceinline__ RzMom rz_get(const double* p) { return {(int)p[0], p[1], p[2], p[3], p[4], p[5], p[6]}; }
+// Inclusive scan over the block's 256 lanes in lane order (REV: from lane 255 down): Hillis-Steele inside each 64-lane
+// wave, then the totals of the waves before (REV: after) this one, added nearest wave last, go in front.  red: [4][8].
+template <bool REV>
+__device__ __forceinline__ RzMom rz_block_scan(RzMom m, double* red) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int off = 1; off < 64; off <<= 1) {
+    const RzMom o = rz_shfl<REV>(m, off);
+    if (REV ? lane + off < 64 : lane >= off) m = REV ? rz_combine(m, o) : rz_combine(o, m);
+  }
+  __syncthreads();                                               // red may still be read from the scan before
+  if (lane == (REV ? 0 : 63)) rz_put(red + 8 * wave, m);
+  __syncthreads();
+  if (REV) {
+    if (wave < 3) {
+      RzMom p = rz_get(red + 8 * 3);
+      for (int w = 2; w > wave; --w) p = rz_combine(rz_get(red + 8 * w), p);
+      m = rz_combine(m, p);
+    }
+  } else if (wave > 0) {
+    RzMom p = rz_get(red);
+    for (int w = 1; w < wave; ++w) p = rz_combine(p, rz_get(red + 8 * w));
+    m = rz_combine(p, m);
+  }
+  return m;
+}
+
+// work[c][j][0..8) = (count, S1 hi, S1 lo, S2 hi, S2 lo, min, max, 0) of tile j of channel c
+template <typename T>
+__global__ __launch_bounds__(256) void rz_tile_moments(const void* __restrict__ x, double* __restrict__ work, long long Tn) {
+  __shared__ double red[32];
+  const long long row = (long long)blockIdx.y * Tn;
+  const RzMom m = rz_block_scan<false>(rz_load<T>(x, row, Tn, (long long)blockIdx.x * RZ_TB + threadIdx.x), red);
+  if (threadIdx.x == RZ_TB - 1) rz_put(work + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 8, m);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void rolling_zscore_blocked_kernel(const void* __restrict__ x, const double* __restrict__ work,
+                                                                     double* __restrict__ y, long long Tn, int W, int zero_nans) {
+  __shared__ double red[32];
+  __shared__ double shared_m[8];
+  const long long row = (long long)blockIdx.y * Tn;
+  const int j = blockIdx.x, i = threadIdx.x;
+  const long long t0 = (long long)j * RZ_TB, t = t0 + i;
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  const double xv = t < Tn ? ldd<T>(x, row + t) : nan;
+  const RzMom a = rz_block_scan<false>(rz_sample(xv), red);                        // (a)
+  // W >= 256, so k0 <= j; a head that lies before t = 0 altogether is empty
+  const long long k0u = (t0 + RZ_TB - W + (RZ_TB - 1)) >> 8;                       // ceil: the numerator is > -2^31
+  const int k0 = t0 + RZ_TB - W > 0 ? (int)k0u : 0;
+  const long long h0 = t0 - W + 1;
+  const int L = t0 + RZ_TB - W > 0 ? (int)((long long)k0 * RZ_TB - h0) : 0;
+  RzMom c = rz_block_scan<true>(i < L ? rz_load<T>(x, row, Tn, h0 + i) : rz_identity(), red);   // (c), head[i .. 256)
+  RzMom p = RZ_TB + i < L ? rz_load<T>(x, row, Tn, h0 + RZ_TB + i) : rz_identity();
+  const double* tab = work + (long long)blockIdx.y * gridDim.x * 8;
+  for (int k = k0 + i; k < j; k += RZ_TB) p = rz_combine(p, rz_get(tab + (long long)k * 8));   // (b)
+  p = rz_block_scan<false>(p, red);
+  if (i == RZ_TB - 1) rz_put(shared_m, p);
+  __syncthreads();
+  if (t >= Tn) return;
+  const RzMom w = rz_combine(rz_combine(c, rz_get(shared_m)), a);
+  double out = nan;
+  if (xv == xv && w.n >= 2 && w.mn != w.mx) {
+    const double n = (double)w.n;
+    double ah, al, bh, bl, qh, ql, dh, dl;
+    rz_prod_plus(n, w.s2h, rz_mul(n, w.s2l), ah, al);                              // n S2
+    rz_prod_plus(w.s1h, w.s1h, rz_mul(2.0, rz_mul(w.s1h, w.s1l)), bh, bl);         // S1^2
+    rz_dd_add(ah, al, -bh, -bl, qh, ql);                                           // n q = n S2 - S1^2
+    rz_prod_plus(n, xv, 0.0, ah, al);                                              // n x_t
+    rz_dd_add(ah, al, -w.s1h, -w.s1l, dh, dl);                                     // n d = n x_t - S1
+    out = (__dadd_rn(dh, dl) / n) / sqrt((__dadd_rn(qh, ql) / n) / (double)(w.n - 1));
+  }
+  if (zero_nans && out != out) out = 0.0;
+  y[row + t] = out;
+}
+
 
 // ------------------------------------------------------------------------------------------
 // FFT resampling (scipy.signal.resample as used by preprocess/signal/downsample.py:21-27): the DFT of
@@ -366,6 +518,30 @@ extern "C" int tl_rolling_zscore(const void* x, int is_f64, double* y, int C, in
   else
     hipLaunchKernelGGL((rolling_zscore_kernel<float>), grid, dim3(256), lds, st, x, y, (long long)T, W, zero_nans);
   return check_launch("rolling_zscore");
+}
+
+extern "C" int tl_rolling_zscore_blocked(const void* x, int is_f64, double* y, double* work, int64_t work_elems, int C, int64_t T,
+                                         int window, int zero_nans, void* stream) {
+  TL_REQUIRE(x && y && work, "rolling_zscore_blocked: null pointer");
+  TL_REQUIRE(C > 0 && C <= 65535 && T > 0, "rolling_zscore_blocked: C must lie in [1, 65535] and T must be positive");
+  TL_REQUIRE(window > 1, "rolling_zscore_blocked: window_size must be greater than 1.");
+  TL_REQUIRE(T <= INT32_MAX - RZ_TB, "rolling_zscore_blocked: recording too long");
+  const int W = window < T ? window : (int)T;                    // as in tl_rolling_zscore
+  TL_REQUIRE(W >= RZ_TB, "rolling_zscore_blocked: min(window, T) = %d is below %d; such windows run on the window kernel "
+             "(tl_rolling_zscore)", W, RZ_TB);
+  const int64_t tiles = (T + RZ_TB - 1) / RZ_TB;
+  TL_REQUIRE(work_elems >= 8 * (int64_t)C * tiles, "rolling_zscore_blocked: the workspace holds %lld doubles, 8 * C * "
+             "ceil(T / 256) = %lld are needed", (long long)work_elems, (long long)(8 * (int64_t)C * tiles));
+  dim3 grid((unsigned)tiles, (unsigned)C);
+  hipStream_t st = (hipStream_t)stream;
+  if (is_f64) {
+    hipLaunchKernelGGL((rz_tile_moments<double>), grid, dim3(256), 0, st, x, work, (long long)T);
+    hipLaunchKernelGGL((rolling_zscore_blocked_kernel<double>), grid, dim3(256), 0, st, x, work, y, (long long)T, W, zero_nans);
+  } else {
+    hipLaunchKernelGGL((rz_tile_moments<float>), grid, dim3(256), 0, st, x, work, (long long)T);
+    hipLaunchKernelGGL((rolling_zscore_blocked_kernel<float>), grid, dim3(256), 0, st, x, work, y, (long long)T, W, zero_nans);
+  }
+  return check_launch("rolling_zscore_blocked");
 }
 
 // in-place power-of-two FFT of `buf` (C, m2) complex128 with scratch `tmp`; result ends in `buf`

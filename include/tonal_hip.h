@@ -805,6 +805,14 @@ int tl_row_zscore(const void* x, int is_f64, void* y, double* stats, int C, int6
 int tl_car(const void* x, int is_f64, const int32_t* include, void* y, int C, int64_t T, int n_inc, void* stream);
 /* pandas rolling(window, min_periods=1) z-score, sample std (rolling_zscore.py:36-49); y float64   */
 int tl_rolling_zscore(const void* x, int is_f64, double* y, int C, int64_t T, int window, int zero_nans, void* stream);
+/* the same quantity in O(1) per sample, for min(window, T) >= 256: per-tile moments (count, sum and sum of squares as (hi, lo)
+ * pairs, minimum, maximum) of the 256-sample tiles go to `work`, at least 8 * C * ceil(T / 256) doubles owned by the caller
+ * (work_elems says how many it holds); every window is then the sum of a head, whole tiles and a tile prefix.  Agrees with
+ * the exact value to a few ulp, not with tl_rolling_zscore bit for bit.  TL_EINVAL, before any launch, on a
+ * null pointer, C outside [1, 65535], window <= 1, T > INT32_MAX - 256, min(window, T) < 256 (use tl_rolling_zscore) or a
+ * workspace that is too small.                                                                                           */
+int tl_rolling_zscore_blocked(const void* x, int is_f64, double* y, double* work, int64_t work_elems, int C, int64_t T,
+                              int window, int zero_nans, void* stream);
 
 /* ---- channel selection: one-way ANOVA at every (channel, timepoint) column (channel_selection/active.py:58-76,
  * channel_selection/discriminative.py:171-180 run scipy.stats.f_oneway per channel).  x is (n_rows, cols) row-major with
