@@ -3,7 +3,9 @@
 ``get_max_length`` / ``find_significant_channels`` are host NumPy with the reference's behaviour.  ``anova_oneway`` is the
 low-level entry to the kernels of ``csrc/tonal_anova.hip``: a one-way ANOVA (``scipy.stats.f_oneway`` along axis 0) at every
 trailing position of the samples, F and p computed on the device in float64.  ``max_run_below`` is the device form of
-``get_max_length`` over the rows of a p-value array.  No CPU fallback: without a GPU both raise."""
+``get_max_length`` over the rows of a p-value array.  ``permutation_table`` / ``permutation_runs`` / ``permutation_p_values``
+are the label-permutation test of the longest significant run (``tl_perm_exceed``, ``tl_perm_runs``).  No CPU fallback:
+without a GPU the device entries raise."""
 from __future__ import annotations
 
 import ctypes as C
@@ -149,6 +151,166 @@ def max_run_below(p, threshold: float):
         check(_lib.load().tl_max_run_below(ptr(p), p.shape[0], p.shape[1], float(threshold), ptr(out[0]), ptr(out[1]),
                                            stream_ptr()), "tl_max_run_below")
     return out[0], out[1]
+
+
+# ---- label-permutation test ----------------------------------------------------------------------------------------
+#: samples per LDS stage of tl_perm_exceed (PX_KC of csrc/tonal_anova.hip): the tests place sample counts around it
+PERM_SAMPLE_CHUNK = 32
+#: the exceedance mask of one chunk of relabellings stays below this many bytes (one byte per relabelling and column)
+_PERM_MASK_BYTES = 64 << 20
+
+
+def permutation_table(group_index, n_permutations: int, seed: int = 0) -> np.ndarray:
+    """``(1 + n_permutations, N)`` uint8, on the host: row 0 is the observed labelling ``group_index`` (integers in
+    [0, k), k <= 64), rows 1.. are ``np.random.default_rng(seed).permutation(group_index)`` drawn in order."""
+    g = np.asarray(group_index)
+    if g.ndim != 1 or g.size < 1 or not np.issubdtype(g.dtype, np.integer):
+        raise ValueError("permutation_table: group_index must be a non-empty 1D integer array")
+    if g.min() < 0 or g.max() >= 64:
+        raise ValueError("permutation_table: group indices must lie in [0, 64)")
+    if n_permutations < 0:
+        raise ValueError("permutation_table: n_permutations must not be negative")
+    g = g.astype(np.uint8)
+    rng = np.random.default_rng(seed)
+    table = np.empty((1 + int(n_permutations), g.size), dtype=np.uint8)
+    table[0] = g
+    for r in range(1, table.shape[0]):
+        table[r] = rng.permutation(g)
+    return table
+
+
+def critical_values(p_threshold: float, k: int, n: int) -> Tuple[float, float]:
+    """``(f_crit, theta)`` of the cell level ``p_threshold``: ``p < p_threshold`` is ``F > f_crit`` is
+    ``ssb > theta * sst`` with ``theta = f_crit dfb / (dfw + f_crit dfb)``; ``scipy.stats.f.isf`` once, on the host."""
+    from scipy import stats
+    dfb, dfw = k - 1, n - k
+    if dfw < 1:
+        raise ValueError(f"permutation test: {n} samples in {k} groups leave no degrees of freedom within the groups")
+    if not 0.0 < p_threshold < 1.0:
+        raise ValueError(f"permutation test: the cell level must lie in (0, 1), got {p_threshold}")
+    f_crit = float(stats.f.isf(p_threshold, dfb, dfw))
+    return f_crit, f_crit * dfb / (dfw + f_crit * dfb)
+
+
+def _perm_apply(arrays, table, counts, p_threshold, perm_chunk, make_out, consume):
+    """The work shared by ``permutation_runs`` and ``permutation_exceedances``: ``out = make_out(P, C, T)``, then
+    ``consume(out, p0, p1, mask)`` per chunk of relabellings with ``mask`` (p1 - p0, C * T) uint8 on the device.  Returns
+    ``(out, f_crit, theta)``."""
+    import torch
+    from .. import _lib
+    from .._lib import check, ptr, stream_ptr
+    arrays = list(arrays)
+    if not 1 <= len(arrays) <= 2:
+        raise ValueError("permutation test: one or two sample arrays")
+    x0 = arrays[0]
+    for a in arrays:
+        _lib.require_gpu(a, "permutation test")
+        if a.dim() != 3 or a.shape[1:] != x0.shape[1:] or a.dtype != x0.dtype or a.device != x0.device:
+            raise ValueError("permutation test: arrays must be (n, C, T) of one trailing shape, dtype and device")
+    if x0.dtype not in (torch.float32, torch.float64):
+        raise ValueError("permutation test: float32 or float64 samples")
+    arrays = [a.contiguous() for a in arrays]
+    x0 = arrays[0]
+    Cn, T = int(x0.shape[1]), int(x0.shape[2])
+    cols = Cn * T
+    N = sum(int(a.shape[0]) for a in arrays)
+    table = np.array(table, dtype=np.uint8, order="C")                      # a copy: the upload needs a writable array
+    counts = [int(c) for c in counts]
+    k = len(counts)
+    if table.ndim != 2 or table.shape[0] < 1 or table.shape[1] != N:
+        raise ValueError(f"permutation test: the table must be (P, {N}), got {table.shape}")
+    if not 2 <= k <= 64 or min(counts) < 1 or sum(counts) != N or cols < 1:
+        raise ValueError("permutation test: between 2 and 64 groups of at least one sample each, adding up to the samples")
+    f_crit, theta = critical_values(p_threshold, k, N)
+    P = table.shape[0]
+    if perm_chunk is None:
+        perm_chunk = max(1, _PERM_MASK_BYTES // cols)
+        if perm_chunk >= 128:
+            perm_chunk -= perm_chunk % 128                   # whole blocks of relabellings for both kernel forms
+    perm_chunk = int(perm_chunk)
+    if perm_chunk < 1:
+        raise ValueError("permutation test: perm_chunk must be at least 1")
+    perm_chunk = min(perm_chunk, P)
+    lib = _lib.load()
+    is_f64 = int(x0.dtype == torch.float64)
+    with torch.cuda.device(x0.device):
+        # total and sst of the observed data: one tl_group_moments pass over all samples, in the frame of sample 0
+        shift = x0[0].reshape(cols)
+        S = torch.zeros(cols, dtype=torch.float64, device=x0.device)
+        Q = torch.zeros(cols, dtype=torch.float64, device=x0.device)
+        for a in arrays:
+            n = int(a.shape[0])
+            splits = _splits(cols, n)
+            sums = torch.empty(2, splits, cols, dtype=torch.float64, device=x0.device)
+            idx = torch.arange(n, dtype=torch.int32, device=x0.device)
+            check(lib.tl_group_moments(ptr(a), is_f64, n, cols, ptr(idx), n, ptr(shift), splits, ptr(sums[0]), ptr(sums[1]),
+                                       stream_ptr()), "tl_group_moments")
+            S += sums[0].sum(dim=0)
+            Q += sums[1].sum(dim=0)
+        mean_sq = S * S / N
+        tau = (theta * (Q - mean_sq) + mean_sq).contiguous()          # theta sst + total^2 / N
+        labels = torch.from_numpy(table).to(x0.device)
+        cnt = (C.c_int32 * k)(*counts)
+        x1 = arrays[1] if len(arrays) == 2 else None
+        out = make_out(P, Cn, T)
+        mask = torch.empty(perm_chunk, cols, dtype=torch.uint8, device=x0.device)
+        for p0 in range(0, P, perm_chunk):
+            p1 = min(P, p0 + perm_chunk)
+            check(lib.tl_perm_exceed(ptr(x0), x0.shape[0], ptr(x1), 0 if x1 is None else x1.shape[0], is_f64, cols, ptr(shift),
+                                     labels.data_ptr() + p0 * N, p1 - p0, cnt, k, ptr(tau), ptr(mask), stream_ptr()),
+                  "tl_perm_exceed")
+            consume(out, p0, p1, mask[:p1 - p0])
+    return out, f_crit, theta
+
+
+def permutation_runs(arrays: Sequence, table, counts: Sequence[int], p_threshold: float, perm_chunk: Optional[int] = None):
+    """``(runs, f_crit, theta)``: ``runs (P, C)`` int32 on the device is, per row of ``table`` (``permutation_table``) and
+    channel, the longest run of timepoints at which the one-way ANOVA under that labelling has ``p < p_threshold``
+    (the CELL level - a selector divides its ``p_threshold`` by T first).
+
+    ``arrays`` is one CUDA tensor (N, C, T) or two, (n0, C, T) and (n1, C, T), whose samples follow each other (rest, then
+    ERP); ``counts`` the k group sizes of the observed labelling.  No p-value is evaluated: a relabelling keeps the group
+    sizes, so ``p < p_threshold`` is ``sum_g S_g^2 / n_g > theta sst + total^2 / N`` with one host ``scipy.stats.f.isf``.
+    The relabellings go through ``tl_perm_exceed`` / ``tl_perm_runs`` in chunks of ``perm_chunk`` (default: a mask of at
+    most 64 MiB); the result does not depend on the chunking."""
+    import torch
+    from .. import _lib
+    from .._lib import check, ptr, stream_ptr
+    lib = _lib.load()
+    device = arrays[0].device
+
+    def consume(runs, p0, p1, mask):
+        Cn = runs.shape[1]
+        check(lib.tl_perm_runs(ptr(mask), (p1 - p0) * Cn, mask.shape[1] // Cn, ptr(runs[p0:p1]), stream_ptr()), "tl_perm_runs")
+    return _perm_apply(arrays, table, counts, p_threshold, perm_chunk,
+                       lambda P, Cn, T: torch.empty(P, Cn, dtype=torch.int32, device=device), consume)
+
+
+def permutation_exceedances(arrays: Sequence, table, counts: Sequence[int], p_threshold: float,
+                            perm_chunk: Optional[int] = None):
+    """The boolean ``(P, C, T)`` CUDA mask behind ``permutation_runs`` (same arguments): where ``p < p_threshold`` under
+    each labelling.  P * C * T bytes: for tests and small inputs."""
+    import torch
+    device = arrays[0].device
+
+    def consume(out, p0, p1, mask):
+        out[p0:p1] = mask.reshape(out[p0:p1].shape) != 0
+    return _perm_apply(arrays, table, counts, p_threshold, perm_chunk,
+                       lambda P, Cn, T: torch.empty(P, Cn, T, dtype=torch.bool, device=device), consume)[0]
+
+
+def permutation_p_values(runs):
+    """``(p_channel, p_max)``, both (C,) float64 NumPy, from ``runs (P, C)`` with the observed labelling in row 0:
+    ``p_channel[c] = (1 + #{pi >= 1: runs[pi, c] >= runs[0, c]}) / P`` and ``p_max[c]`` the same count against the
+    relabelling's maximum over the channels (family-wise)."""
+    r = runs.detach().cpu().numpy() if hasattr(runs, "detach") else np.asarray(runs)
+    if r.ndim != 2 or r.shape[0] < 1:
+        raise ValueError("permutation_p_values: runs must be (P, C)")
+    P = r.shape[0]
+    obs, null = r[0], r[1:]
+    p_channel = (1 + (null >= obs[None, :]).sum(axis=0)) / P
+    p_max = (1 + (null.max(axis=1, initial=0)[:, None] >= obs[None, :]).sum(axis=0)) / P
+    return p_channel.astype(np.float64), p_max.astype(np.float64)
 
 
 def device_recording(data, name: str, what: str):

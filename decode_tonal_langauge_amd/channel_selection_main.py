@@ -7,8 +7,8 @@ selections listed under ``params.selections`` (``module``, ``selection_name``, `
 ``subject_<id>.json`` as ``{selection_name: [channel indices]}`` - the file train_classifier / train_synthesizer read -
 and returns the output directory.
 
-Module names of the reference layout (``channel_selection.active``, ``channel_selection.discriminative``) resolve to this
-package's GPU selectors; any other name is imported as it is (the plugin ABI).  A subject's recordings are uploaded once
+Module names of the reference layout (``channel_selection.active``, ``channel_selection.discriminative``) and
+``channel_selection.permutation`` resolve to this package's GPU selectors; any other name is imported as it is (the plugin ABI).  A subject's recordings are uploaded once
 and shared by that subject's selections."""
 from __future__ import annotations
 
@@ -24,11 +24,11 @@ import numpy as np
 from .utils.config import dict_to_namespace, generate_hash_name_from_config, load_config, update_configuration
 
 _PKG = __name__.rsplit(".", 1)[0]
-_SELECTORS = ("active", "discriminative")
+_SELECTORS = ("active", "discriminative", "permutation")
 
 
 def resolve_selection_module(name: str):
-    """``channel_selection.active`` / ``channel_selection.discriminative`` map onto this package; anything else is
+    """``channel_selection.active`` / ``.discriminative`` / ``.permutation`` map onto this package; anything else is
     imported as is."""
     tail = name.rsplit(".", 1)[-1]
     if tail in _SELECTORS and name == f"channel_selection.{tail}":

@@ -208,6 +208,180 @@ __global__ __launch_bounds__(256) void max_run_below_kernel(const double* __rest
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// label-permutation test: where does the ANOVA of a RELABELLED recording pass the threshold?  A relabelling keeps the group
+// sizes, so the total sum of squares and the degrees of freedom are those of the observed labelling and p < alpha' is
+// sum_g S_g^2 / n_g > tau[col] (tau = theta sst + total^2 / N, formed once by the caller; S_g the shifted column sum of group
+// g).  The group sums of all relabellings are one fp64 product, onehot (P k x N) times (x - shift) (N x cols), on
+// v_mfma_f64_16x16x4_f64:
+//   A (16 rows x 4 samples): row r = q + 4 reg is (relabelling q + 4 (reg / GR), group gbase + reg % GR) of the tile, so the GR
+//     groups of a relabelling are registers of ONE lane in the f64 C/D layout (row = (lane >> 4) + 4 reg, col = lane & 15) and
+//     sum_g S_g^2 / n_g needs no lane movement.  GR = 2 for two groups (8 relabellings per tile), else 4; more than GR groups
+//     are further passes over the samples, each adding its groups' share.  The 0/1 operand is formed in registers from label
+//     bytes held in LDS - a compare, never an index: a label >= k matches no row.
+//   B (4 samples x 16 columns): the samples widened and shifted, staged through LDS from coalesced row loads, PX_KC samples a
+//     stage; the next stage's loads are in flight while the MFMAs of this one run.
+// A wave owns PX_MT x PX_NT tiles (every B value feeds PX_MT MFMAs, every A value PX_NT), a block 4 waves on the same columns.
+// ------------------------------------------------------------------------------------------
+#define PX_KC 32                 // samples per LDS stage
+#define PX_CB 64                 // columns per block = 16 PX_NT
+#define PX_LD 80                 // row stride of the staged samples in doubles: rows s and s + 1 fall into different bank halves
+#define PX_MT 4
+#define PX_NT 4
+
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+struct PermWeights { double inv_n[64]; };
+
+template <typename T, int GR>
+__global__ __launch_bounds__(256) void perm_exceed_kernel(const T* __restrict__ x0, long long n0, const T* __restrict__ x1,
+                                                          long long N, long long cols, const T* __restrict__ shift,
+                                                          const uint8_t* __restrict__ labels, int P, int k, PermWeights wts,
+                                                          const double* __restrict__ tau, uint8_t* __restrict__ exceed) {
+  constexpr int PT = 16 / GR;                                  // relabellings per 16-row tile
+  constexpr int PW = PX_MT * PT;                               // per wave
+  constexpr int PB = 4 * PW;                                   // per block
+  constexpr int LPT = PB * PX_KC / 256;                        // label bytes a thread stages
+  constexpr int XPT = PX_KC * PX_CB / 256;                     // samples a thread stages
+  __shared__ double xs[PX_KC * PX_LD];
+  __shared__ unsigned long long ls[PB * PX_KC / 8];            // [relabelling][sample & 3][sample >> 2] bytes
+  uint8_t* lsb = reinterpret_cast<uint8_t*>(ls);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int npb = (P + PB - 1) / PB;
+  const int pbase = (int)(blockIdx.x % (unsigned)npb) * PB;    // relabelling blocks of one column block are neighbours in the grid
+  const long long col0 = (long long)(blockIdx.x / (unsigned)npb) * PX_CB;
+  const int sc = tid & 63, sr = tid >> 6;                      // staged column, first staged row
+  const long long scol = col0 + sc;
+  const bool col_ok = scol < cols;
+  const double sh = col_ok ? (double)shift[scol] : 0.0;
+  const int arow = lane & 15, kq = lane >> 4;                  // A row of this lane, its sample within a 4-sample step
+  const int a_rel = (arow & 3) + 4 * ((arow >> 2) / GR), a_grp = (arow >> 2) % GR;
+
+  // staging addresses without a multiply in the loop: row i of the samples lies cols * i past (i < n0 ? x0 : x1 - n0 cols), the
+  // label of relabelling p and sample i at labels + p N + i; xo / lo are those offsets for the stage being fetched
+  const long long xstep = 4 * cols, x1_back = n0 * cols, lstep = 8 * N;
+  const int lp0 = pbase + (tid >> 5), ls0 = tid & 31;
+  T xr[XPT];
+  uint8_t lr[LPT];
+  auto fetch = [&](long long i0, long long xo, long long lo) {
+#pragma unroll
+    for (int j = 0; j < XPT; ++j) {
+      const long long i = i0 + sr + 4 * j, o = xo + j * xstep;
+      T v = (T)0;
+      if (col_ok && i < N) v = *(i < n0 ? x0 + o : x1 + (o - x1_back));
+      xr[j] = v;
+    }
+    const bool s_ok = i0 + ls0 < N;
+#pragma unroll
+    for (int j = 0; j < LPT; ++j) lr[j] = (s_ok && lp0 + 8 * j < P) ? labels[lo + j * lstep] : (uint8_t)255;
+  };
+
+  double stat[PX_MT][PX_NT][4 / GR];
+#pragma unroll
+  for (int m = 0; m < PX_MT; ++m)
+#pragma unroll
+    for (int n = 0; n < PX_NT; ++n)
+#pragma unroll
+      for (int j = 0; j < 4 / GR; ++j) stat[m][n][j] = 0.0;
+
+  for (int gbase = 0; gbase < k; gbase += GR) {
+    const unsigned long long gsel = gbase + a_grp < k ? (unsigned long long)(gbase + a_grp) : 0x100ull;   // 0x100: no byte equals it
+    f64x4 acc[PX_MT][PX_NT];
+#pragma unroll
+    for (int m = 0; m < PX_MT; ++m)
+#pragma unroll
+      for (int n = 0; n < PX_NT; ++n) acc[m][n] = (f64x4){0.0, 0.0, 0.0, 0.0};
+    long long xo = (long long)sr * cols + scol, lo = (long long)lp0 * N + ls0;
+    fetch(0, xo, lo);
+    for (long long i0 = 0; i0 < N; i0 += PX_KC) {
+      __syncthreads();                                         // the previous stage has been read by every wave
+#pragma unroll
+      for (int j = 0; j < XPT; ++j) {
+        const int r = sr + 4 * j;
+        xs[r * PX_LD + sc] = (col_ok && i0 + r < N) ? (double)xr[j] - sh : 0.0;
+      }
+#pragma unroll
+      for (int j = 0; j < LPT; ++j) {
+        const int e = tid + 256 * j, s = e & 31;
+        lsb[(e >> 5) * PX_KC + (s & 3) * 8 + (s >> 2)] = lr[j];
+      }
+      __syncthreads();
+      xo += PX_KC * cols;
+      lo += PX_KC;
+      if (i0 + PX_KC < N) fetch(i0 + PX_KC, xo, lo);
+      unsigned long long lw[PX_MT];                            // byte kk: the label of sample i0 + 4 kk + kq
+#pragma unroll
+      for (int m = 0; m < PX_MT; ++m) lw[m] = ls[(wave * PW + m * PT + a_rel) * (PX_KC / 8) + kq];
+      double b[2][PX_NT];                                      // the next step's B values are read while this step's MFMAs run
+#pragma unroll
+      for (int n = 0; n < PX_NT; ++n) b[0][n] = xs[kq * PX_LD + n * 16 + arow];
+#pragma unroll
+      for (int kk = 0; kk < PX_KC / 4; ++kk) {
+        if (kk + 1 < PX_KC / 4) {
+#pragma unroll
+          for (int n = 0; n < PX_NT; ++n) b[(kk + 1) & 1][n] = xs[(4 * (kk + 1) + kq) * PX_LD + n * 16 + arow];
+        }
+#pragma unroll
+        for (int m = 0; m < PX_MT; ++m) {
+          const double a = ((lw[m] >> (8 * kk)) & 0xffull) == gsel ? 1.0 : 0.0;
+#pragma unroll
+          for (int n = 0; n < PX_NT; ++n) acc[m][n] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[kk & 1][n], acc[m][n], 0, 0, 0);
+        }
+      }
+    }
+    // C/D of the f64 form: register reg of lane l is row (l >> 4) + 4 reg, column l & 15
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const int g = gbase + reg % GR;
+      if (g < k) {
+        const double w = wts.inv_n[g];
+#pragma unroll
+        for (int m = 0; m < PX_MT; ++m)
+#pragma unroll
+          for (int n = 0; n < PX_NT; ++n) stat[m][n][reg / GR] = fma(acc[m][n][reg] * acc[m][n][reg], w, stat[m][n][reg / GR]);
+      }
+    }
+  }
+#pragma unroll
+  for (int n = 0; n < PX_NT; ++n) {
+    const long long c = col0 + n * 16 + arow;
+    if (c >= cols) continue;
+    const double t = tau[c];
+#pragma unroll
+    for (int m = 0; m < PX_MT; ++m)
+#pragma unroll
+      for (int j = 0; j < 4 / GR; ++j) {
+        const int p = pbase + wave * PW + m * PT + kq + 4 * j;
+        if (p < P) exceed[(long long)p * cols + c] = stat[m][n][j] > t ? 1 : 0;        // false for NaN
+      }
+  }
+}
+
+// longest run of set cells per row of a byte mask: one wave per row, 64 cells a step (coalesced); the step's cells are one
+// ballot word, reduced to a RunSeg with bit operations (the same in every lane) and appended to the row's segment
+__global__ __launch_bounds__(256) void perm_runs_kernel(const uint8_t* __restrict__ mask, long long rows, long long T,
+                                                        int32_t* __restrict__ maxrun) {
+  const int lane = threadIdx.x & 63;
+  const long long row = blockIdx.x * 4LL + (threadIdx.x >> 6);
+  if (row >= rows) return;                                     // whole waves leave
+  const uint8_t* mr = mask + row * T;
+  RunSeg s = {0, 0, 0, 0, 0};
+  for (long long t0 = 0; t0 < T; t0 += 64) {
+    const long long t = t0 + lane;
+    const unsigned long long w = __ballot(t < T && mr[t] != 0);
+    const int len = T - t0 < 64 ? (int)(T - t0) : 64;
+    const unsigned long long nw = ~w, nwl = ~(w << (64 - len));   // cells past len are clear: nwl != 0 whenever len < 64
+    RunSeg r;
+    r.len = len;
+    r.cnt = __popcll(w);
+    r.pre = nw ? __ffsll((long long)nw) - 1 : 64;
+    r.suf = nwl ? __clzll((long long)nwl) : 64;
+    r.best = 0;
+    for (unsigned long long v = w; v; v &= v << 1) ++r.best;
+    s = run_combine(s, r);
+  }
+  if (lane == 0) maxrun[row] = s.best;
+}
+
 }  // namespace tl
 using namespace tl;
 
@@ -256,4 +430,47 @@ extern "C" int tl_max_run_below(const double* p, int C, int64_t T, double thr, i
   hipLaunchKernelGGL(max_run_below_kernel, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p, C, (long long)T, thr,
                      count, maxrun);
   return check_launch("max_run_below");
+}
+
+extern "C" int tl_perm_exceed(const void* x0, int64_t n0, const void* x1, int64_t n1, int is_f64, int64_t cols, const void* shift,
+                              const uint8_t* labels, int P, const int32_t* counts, int k, const double* tau, uint8_t* exceed,
+                              void* stream) {
+  TL_REQUIRE(x0 && shift && labels && counts && tau && exceed, "perm_exceed: null pointer");
+  TL_REQUIRE(n0 >= 1 && n1 >= 0 && (x1 || n1 == 0), "perm_exceed: n0 must be at least 1, and n1 zero unless x1 is given");
+  TL_REQUIRE(cols >= 1 && P >= 1, "perm_exceed: cols and P must be at least 1");
+  TL_REQUIRE(k >= 2 && k <= 64, "perm_exceed: the number of groups k must lie in [2, 64]");
+  const long long N = (long long)n0 + n1;
+  TL_REQUIRE(n0 <= 0x7fffffffLL && n1 <= 0x7fffffffLL && N <= 0x7fffffffLL, "perm_exceed: too many samples");
+  PermWeights w = {};
+  long long total = 0;
+  for (int g = 0; g < k; ++g) {
+    TL_REQUIRE(counts[g] >= 1, "perm_exceed: every group needs at least one sample");
+    w.inv_n[g] = 1.0 / (double)counts[g];
+    total += counts[g];
+  }
+  TL_REQUIRE(total == N, "perm_exceed: the group sizes must add up to n0 + n1 (got %lld and %lld)", total, N);
+  const int pb = 4 * PX_MT * (k == 2 ? 8 : 4);                 // relabellings per block
+  const long long blocks = ((cols + PX_CB - 1) / PX_CB) * (((long long)P + pb - 1) / pb);
+  TL_REQUIRE(blocks <= 0x7fffffffLL, "perm_exceed: too many blocks (P times cols too large for one launch)");
+  hipStream_t st = (hipStream_t)stream;
+#define TL_PERM_LAUNCH(T, GR)                                                                                                   \
+  hipLaunchKernelGGL((perm_exceed_kernel<T, GR>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)x0, (long long)n0,       \
+                     (const T*)x1, N, (long long)cols, (const T*)shift, labels, P, k, w, tau, exceed)
+  if (is_f64) {
+    if (k == 2) TL_PERM_LAUNCH(double, 2); else TL_PERM_LAUNCH(double, 4);
+  } else {
+    if (k == 2) TL_PERM_LAUNCH(float, 2); else TL_PERM_LAUNCH(float, 4);
+  }
+#undef TL_PERM_LAUNCH
+  return check_launch("perm_exceed");
+}
+
+extern "C" int tl_perm_runs(const uint8_t* mask, int64_t rows, int64_t T, int32_t* maxrun, void* stream) {
+  TL_REQUIRE(mask && maxrun, "perm_runs: null pointer");
+  TL_REQUIRE(rows >= 1 && T >= 1 && T <= 0x7fffffffLL, "perm_runs: rows and T must be at least 1");
+  const long long blocks = (rows + 3) / 4;
+  TL_REQUIRE(blocks <= 0x7fffffffLL, "perm_runs: too many rows");
+  hipLaunchKernelGGL(perm_runs_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, mask, (long long)rows,
+                     (long long)T, maxrun);
+  return check_launch("perm_runs");
 }

@@ -835,6 +835,25 @@ int tl_anova_finalize(const double* sum, const double* sumsq, const int32_t* cou
 /* per row of p (C, T) float64: count[c] = number of p < thr, maxrun[c] = longest run of consecutive p < thr (NaN is not
  * below) - channel_selection/utils.py:4-30 per channel; one wave per row.  count / maxrun are (C) int32                   */
 int tl_max_run_below(const double* p, int C, int64_t T, double thr, int32_t* count, int32_t* maxrun, void* stream);
+/* label-permutation test of the same ANOVA: for P relabellings of the N = n0 + n1 samples, where does the statistic pass the
+ * threshold?  Sample i is row i of x0 (n0, cols) for i < n0, else row i - n0 of x1 (n1, cols); x1 may be null with n1 = 0
+ * (rest and ERP stay two arrays).  x0, x1 and shift (cols; one data row, as for tl_group_moments) share one dtype (is_f64).
+ * labels is (P, N) uint8, device: the group of every sample under every relabelling; a label >= k belongs to no group (labels
+ * are compared, never used as an index).  counts is a HOST array of the k group sizes (each >= 1, adding up to N): a
+ * relabelling keeps them, so sst and the degrees of freedom are those of the observed labelling and p < alpha' is
+ *   exceed[pi][col] = ( sum_g S_g^2 / counts[g]  >  tau[col] ),   S_g = sum over the samples labelled g of (x - shift),
+ * with tau (cols) float64 = theta sst + total^2 / N formed by the caller (total the shifted column sum of all samples,
+ * theta = F_crit dfb / (dfw + F_crit dfb)).  False where the sum or tau is NaN, like p < thr in tl_max_run_below.  exceed is
+ * (P, cols) bytes, 0 or 1.  The group sums are one fp64 product onehot (P k x N) . (x - shift) on v_mfma_f64_16x16x4_f64;
+ * the samples are staged 32 at a time.  TL_EINVAL, before any launch, on a null pointer, n0 < 1, n1 < 0 or n1 > 0 without
+ * x1, cols or P < 1, k outside [2, 64], a group size < 1, sizes that do not add up to N, or more than 2^31 - 1 blocks
+ * (ceil(cols / 64) * ceil(P / 64), ceil(P / 128) for k = 2)                                                              */
+int tl_perm_exceed(const void* x0, int64_t n0, const void* x1, int64_t n1, int is_f64, int64_t cols, const void* shift,
+                   const uint8_t* labels, int P, const int32_t* counts, int k, const double* tau, uint8_t* exceed,
+                   void* stream);
+/* per row of a byte mask (rows, T), e.g. exceed above read as (P * C, T): maxrun[row] = the longest run of consecutive
+ * non-zero cells (0 if none); one wave per row, 64 cells a step.  maxrun is (rows) int32                                  */
+int tl_perm_runs(const uint8_t* mask, int64_t rows, int64_t T, int32_t* maxrun, void* stream);
 
 /* ---- mel-spectrogram targets of a batch of trials (utils/audio.py audio_to_mel, one trial at a time on the host):
  * STFT -> |X|^power -> mel bank -> dB, two launches, fp64 throughout, float32 at the final store.
