@@ -483,6 +483,126 @@ __global__ __launch_bounds__(256) void gl_overlap_add_kernel(const double* __res
   if (s < length) out[n * length + s] = gl_sample<NFFT>(frames + n * n_frames * NFFT, wsum, s + NFFT / 2, n_frames, hop);
 }
 
+// ---------------------------------------------------------------------------------------------- Welch PSD
+// scipy.signal.welch(axis=1, average='mean') of every row of a (C, T) recording (utils/diagnostics.py welch_psd): the
+// segments of one channel are the frames of mel_power_kernel, but nothing is written per frame - a workgroup owns one
+// (channel, slab of consecutive segments), walks the slab F segments a trip and keeps |X|^2 of its own bins in registers.
+//   gather   the thread's eight samples 2m, 2m + 1 (m = j + r M/4) straight from the row; offsets >= nperseg (the zero padding
+//            up to n_fft) and offsets past T are never read;
+//   detrend  constant: the mean of the segment's nperseg live samples is a reduction over the frame's Q = M/4 threads - an
+//            xor butterfly where a frame fits a wave (Q <= 64), else per-wave sums through LDS added in wave order; every
+//            thread of the frame ends with the same bits.  The raw samples stay in registers;
+//   FFT      mel_fft, then the next trip's samples are requested, then mel_unpack_bin and acc += Xr^2 + Xi^2;
+//   slab     after the last trip the F lanes are added through LDS in lane order -> work (C, n_slabs, M + 1).
+// No atomics; the order of every sum is fixed by thread and slab numbers, so two runs give the same bits.
+template <typename TIN, int Q>
+__device__ __forceinline__ void welch_gather(const void* __restrict__ x, long long row, long long T, long long seg,
+                                             long long seg_end, int step, int nperseg, int j, double (&raw)[8]) {
+  const bool live = seg < seg_end;
+  const long long start = seg * step;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int o = 2 * (j + r * Q);
+    raw[2 * r] = (live && o < nperseg && start + o < T) ? mel_ld<TIN>(x, row + start + o) : 0.0;
+    raw[2 * r + 1] = (live && o + 1 < nperseg && start + o + 1 < T) ? mel_ld<TIN>(x, row + start + o + 1) : 0.0;
+  }
+}
+
+template <typename TIN, int LOG2M>
+__global__ __launch_bounds__(MEL_Q) void welch_accum_kernel(const void* __restrict__ x, long long row_stride, long long T,
+                                                            const mel_d2* __restrict__ window, const mel_d2* __restrict__ tw,
+                                                            double* __restrict__ work, long long n_seg, int trips, int nperseg,
+                                                            int step, int detrend) {
+  constexpr int M = 1 << LOG2M, F = MEL_PTS / M, Q = M / 4, FIN = mel_fin(LOG2M), NB = M + 1;
+  __shared__ __attribute__((aligned(16))) double lds[4 * MEL_PAD];
+  __shared__ double wsum[MEL_Q / 64];
+  double* re[2] = {lds, lds + 2 * MEL_PAD};
+  double* im[2] = {lds + MEL_PAD, lds + 3 * MEL_PAD};
+  const int tid = threadIdx.x, fl = tid >> (LOG2M - 2), j = tid & (Q - 1), fbase = fl * M;
+  const long long row = (long long)blockIdx.y * row_stride;
+  const long long seg0 = (long long)blockIdx.x * trips * F;             // an absent slab (seg0 >= n_seg) writes zeros
+  const long long seg_end = seg0 + (long long)trips * F < n_seg ? seg0 + (long long)trips * F : n_seg;
+
+  MelTwiddles<LOG2M> twd;
+  mel_load_twiddles<LOG2M>(tw, j, twd);
+  mel_d2 wv[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) wv[r] = window[j + r * Q];
+  double raw[8], acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  welch_gather<TIN, Q>(x, row, T, seg0 + fl, seg_end, step, nperseg, j, raw);
+  for (int trip = 0; trip < trips; ++trip) {
+    double mean = 0.0;
+    if (detrend) {                                                       // block-uniform
+      double s = ((raw[0] + raw[1]) + (raw[2] + raw[3])) + ((raw[4] + raw[5]) + (raw[6] + raw[7]));
+      if (Q <= 64) {
+#pragma unroll
+        for (int d = Q / 2; d >= 1; d >>= 1) s += __shfl_xor(s, d);
+      } else {
+        constexpr int WPF = Q > 64 ? Q / 64 : 1;                         // waves per frame
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
+        if ((tid & 63) == 0) wsum[tid >> 6] = s;
+        __syncthreads();                                                 // the next write is behind the barriers of mel_fft
+        const int w0 = (tid >> 6) / WPF * WPF;
+        s = wsum[w0];
+#pragma unroll
+        for (int u = 1; u < WPF; ++u) s += wsum[w0 + u];
+      }
+      mean = s / (double)nperseg;
+    }
+    double xr[4], xi[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int o = 2 * (j + r * Q);
+      xr[r] = o < nperseg ? (raw[2 * r] - mean) * wv[r][0] : 0.0;
+      xi[r] = o + 1 < nperseg ? (raw[2 * r + 1] - mean) * wv[r][1] : 0.0;
+    }
+    mel_fft<LOG2M>(xr, xi, twd, re, im, j, fbase);
+    // the next trip's samples are on their way while this one is unpacked (past the last trip: seg >= seg_end, no load)
+    welch_gather<TIN, Q>(x, row, T, seg0 + (long long)(trip + 1) * F + fl, trip + 1 < trips ? seg_end : 0, step, nperseg, j, raw);
+#pragma unroll
+    for (int u = 0; u < 5; ++u) {
+      const int k = j + u * Q;
+      if (k <= M) {                                                      // u = 4: bin M, thread j = 0 only
+        double Xr, Xi;
+        mel_unpack_bin<LOG2M>(re[FIN], im[FIN], tw, fbase, k, Xr, Xi);
+        acc[u] += fma(Xr, Xr, Xi * Xi);
+      }
+    }
+    __syncthreads();                                                     // the next first pass overwrites image 0
+  }
+  // ---- the F frame lanes, in lane order
+  double* pw = lds;                                                      // [F][M + 1], F (M + 1) <= 1032 doubles
+#pragma unroll
+  for (int u = 0; u < 5; ++u) {
+    const int k = j + u * Q;
+    if (k <= M) pw[fl * NB + k] = acc[u];
+  }
+  __syncthreads();
+  double* dst = work + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * NB;
+  for (int k = tid; k < NB; k += MEL_Q) {
+    double s = pw[k];
+#pragma unroll
+    for (int f = 1; f < F; ++f) s += pw[f * NB + k];
+    dst[k] = s;
+  }
+}
+
+// psd[c][k] = (sum of the slabs in order) / n_seg * scale, doubled but at DC and Nyquist (one-sided)
+__global__ __launch_bounds__(256) void welch_finish_kernel(const double* __restrict__ work, double* __restrict__ psd, long long total,
+                                                           int nb, int n_slabs, double n_seg, double scale) {
+  const long long i = blockIdx.x * 256LL + threadIdx.x;
+  if (i >= total) return;
+  const long long c = i / nb;
+  const int k = (int)(i - c * nb);
+  const double* p = work + c * n_slabs * nb + k;
+  double s = p[0];
+  for (int sl = 1; sl < n_slabs; ++sl) s += p[(long long)sl * nb];
+  s = s / n_seg * scale;
+  psd[i] = (k == 0 || k == nb - 1) ? s : 2.0 * s;
+}
+
+
 }  // namespace tl
 using namespace tl;
 
@@ -560,6 +680,56 @@ extern "C" int tl_mel_finish(const double* mel, const double* rowmax, float* out
   hipLaunchKernelGGL(mel_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, mel, rowmax, out, per, total,
                      in_db);
   return check_launch("mel_finish");
+}
+
+extern "C" int tl_welch_psd(const void* x, int x_is_f64, int64_t row_stride, const double* window, const double* tw, double* work,
+                            int64_t work_elems, double* psd, int C, int64_t T, int n_fft, int nperseg, int noverlap, int detrend,
+                            double scale, int64_t n_seg, int n_slabs, void* stream) {
+  TL_REQUIRE(x && window && tw && work && psd, "welch_psd: null pointer");
+  const int log2m = mel_log2m(n_fft);
+  TL_REQUIRE(log2m, "welch_psd: n_fft must be one of 256, 512, 1024, 2048 (got %d)", n_fft);
+  TL_REQUIRE(nperseg >= 2 && nperseg <= n_fft, "welch_psd: nperseg must lie in [2, n_fft] (got %d)", nperseg);
+  TL_REQUIRE(noverlap >= 0 && nperseg - noverlap >= 1, "welch_psd: step = nperseg - noverlap must be at least 1 and noverlap "
+             "not negative (got nperseg %d, noverlap %d)", nperseg, noverlap);
+  TL_REQUIRE(detrend == 0 || detrend == 1, "welch_psd: detrend must be 0 (none) or 1 (constant)");
+  TL_REQUIRE(C >= 1 && C <= 65535, "welch_psd: C must lie in [1, 65535] (got %d)", C);
+  TL_REQUIRE(T >= nperseg && T <= (1LL << 40) && row_stride >= T, "welch_psd: T = %lld must lie in [nperseg, 2^40] and "
+             "row_stride >= T", (long long)T);
+  const int step = nperseg - noverlap;
+  const long long want = ((long long)T - noverlap) / step;
+  TL_REQUIRE(n_seg == want, "welch_psd: n_seg = %lld disagrees with T, nperseg and noverlap (%lld)", (long long)n_seg, want);
+  const int fpb = tl::MEL_PTS / (n_fft / 2), nb = n_fft / 2 + 1;
+  const long long all_trips = (want + fpb - 1) / fpb;
+  TL_REQUIRE(n_slabs >= 1 && n_slabs <= 0x7fffffff / nb, "welch_psd: n_slabs must be at least 1 (got %d)", n_slabs);
+  TL_REQUIRE(work_elems >= (int64_t)C * n_slabs * nb, "welch_psd: the workspace holds %lld doubles, C * n_slabs * (n_fft / 2 + 1) "
+             "= %lld are needed", (long long)work_elems, (long long)((int64_t)C * n_slabs * nb));
+  const long long trips = (all_trips + n_slabs - 1) / n_slabs;
+  TL_REQUIRE(trips <= 0x7fffffffLL / fpb, "welch_psd: too many segments per slab");
+  hipStream_t st = (hipStream_t)stream;
+  const mel_d2* w2 = reinterpret_cast<const mel_d2*>(window);
+  const mel_d2* t2 = reinterpret_cast<const mel_d2*>(tw);
+  dim3 grid((unsigned)n_slabs, (unsigned)C);
+#define WELCH_LAUNCH(TIN, L2M)                                                                                          \
+  hipLaunchKernelGGL((welch_accum_kernel<TIN, L2M>), grid, dim3(MEL_Q), 0, st, x, (long long)row_stride, (long long)T, w2, t2,    \
+                     work, (long long)n_seg, (int)trips, nperseg, step, detrend)
+#define WELCH_SIZES(TIN)                                                                                                \
+  switch (log2m) {                                                                                                      \
+    case 7: WELCH_LAUNCH(TIN, 7); break;                                                                                \
+    case 8: WELCH_LAUNCH(TIN, 8); break;                                                                                \
+    case 9: WELCH_LAUNCH(TIN, 9); break;                                                                                \
+    default: WELCH_LAUNCH(TIN, 10); break;                                                                              \
+  }
+  if (x_is_f64) {
+    WELCH_SIZES(double)
+  } else {
+    WELCH_SIZES(float)
+  }
+#undef WELCH_SIZES
+#undef WELCH_LAUNCH
+  const long long total = (long long)C * nb;
+  hipLaunchKernelGGL(welch_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, work, psd, total, nb, n_slabs,
+                     (double)n_seg, scale);
+  return check_launch("welch_psd");
 }
 
 // the checks the four entries of the inverse share; 0 = refused

@@ -327,6 +327,73 @@ __global__ __launch_bounds__(256) void rolling_zscore_blocked_kernel(const void*
 }
 
 
+// mean and population std (np.std) of the n_seg consecutive segments of L samples from s0 on, per channel
+// (utils/diagnostics.py segment_mean_std).  Two-pass: the mean, then the sum of (x - mean)^2 over the same samples - never
+// E[x^2] - mean^2, so a DC level costs nothing.  One wave per (channel, segment) up to L = 512, one workgroup beyond; the
+// samples stay in registers (eight a thread) up to L = 512 resp. 2048 and are read a second time, from L2, beyond.  A wave
+// adds by an xor butterfly, a workgroup adds its four wave sums in wave order: the same bits on every run.
+constexpr int SM_REG = 8, SM_WAVE_L = 64 * SM_REG;
+__device__ __forceinline__ double sm_wave_sum(double v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+  return v;
+}
+template <typename T, bool BLOCK>
+__global__ __launch_bounds__(256) void segment_moments_kernel(const void* __restrict__ x, long long row_stride,
+                                                              double* __restrict__ mean, double* __restrict__ sd, long long s0,
+                                                              long long L, long long n_seg, long long total) {
+  __shared__ double red[2][4];
+  constexpr int NT = BLOCK ? 256 : 64;
+  const int t = BLOCK ? (int)threadIdx.x : (int)(threadIdx.x & 63), wave = threadIdx.x >> 6;
+  const long long item = BLOCK ? (long long)blockIdx.x : blockIdx.x * 4LL + wave;
+  const bool live = item < total;                                  // BLOCK: always
+  const long long c = live ? item / n_seg : 0, g = live ? item - c * n_seg : 0;
+  const long long base = c * row_stride + s0 + g * L;
+  const long long len = live ? L : 0;
+  const bool in_regs = L <= (long long)NT * SM_REG;                // uniform
+  double v[SM_REG], s = 0.0;
+  if (in_regs) {
+#pragma unroll
+    for (int u = 0; u < SM_REG; ++u) {
+      const int i = t + u * NT;
+      v[u] = i < len ? ldd<T>(x, base + i) : 0.0;
+      s += v[u];
+    }
+  } else {
+    for (long long i = t; i < len; i += NT) s += ldd<T>(x, base + i);
+  }
+  s = sm_wave_sum(s);
+  if (BLOCK) {
+    if ((threadIdx.x & 63) == 0) red[0][wave] = s;
+    __syncthreads();
+    s = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+  }
+  const double mu = s / (double)L;
+  double q = 0.0;
+  if (in_regs) {
+#pragma unroll
+    for (int u = 0; u < SM_REG; ++u) {
+      const double d = v[u] - mu;
+      if (t + u * NT < len) q = fma(d, d, q);
+    }
+  } else {
+    for (long long i = t; i < len; i += NT) {
+      const double d = ldd<T>(x, base + i) - mu;
+      q = fma(d, d, q);
+    }
+  }
+  q = sm_wave_sum(q);
+  if (BLOCK) {
+    if ((threadIdx.x & 63) == 0) red[1][wave] = q;
+    __syncthreads();
+    q = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+  }
+  if (live && t == 0) {
+    mean[item] = mu;
+    sd[item] = sqrt(q / (double)L);
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // FFT resampling (scipy.signal.resample as used by preprocess/signal/downsample.py:21-27): the DFT of
 // an arbitrary length n is evaluated with Bluestein's chirp-z identity on a power-of-two Stockham
@@ -542,6 +609,34 @@ extern "C" int tl_rolling_zscore_blocked(const void* x, int is_f64, double* y, d
     hipLaunchKernelGGL((rolling_zscore_blocked_kernel<float>), grid, dim3(256), 0, st, x, work, y, (long long)T, W, zero_nans);
   }
   return check_launch("rolling_zscore_blocked");
+}
+
+extern "C" int tl_segment_moments(const void* x, int x_is_f64, int64_t row_stride, double* mean, double* std, int C, int64_t T,
+                                  int64_t s0, int64_t L, int64_t n_seg, void* stream) {
+  TL_REQUIRE(x && mean && std, "segment_moments: null pointer");
+  TL_REQUIRE(C >= 1 && T >= 1 && T <= (1LL << 40) && row_stride >= T, "segment_moments: C and T must be at least 1 and "
+             "row_stride >= T");
+  TL_REQUIRE(s0 >= 0 && L >= 1 && n_seg >= 1, "segment_moments: s0 >= 0, L >= 1 and n_seg >= 1 are required (got %lld, %lld, "
+             "%lld)", (long long)s0, (long long)L, (long long)n_seg);
+  TL_REQUIRE(s0 <= T && n_seg <= (T - s0) / L, "segment_moments: s0 + n_seg * L = %lld + %lld * %lld runs past T = %lld",
+             (long long)s0, (long long)n_seg, (long long)L, (long long)T);
+  const long long total = (long long)C * n_seg;
+  TL_REQUIRE(total <= 0x7fffffffLL, "segment_moments: too many segments for one launch");
+  hipStream_t st = (hipStream_t)stream;
+#define SM_LAUNCH(TIN)                                                                                                  \
+  if (L <= SM_WAVE_L)                                                                                                   \
+    hipLaunchKernelGGL((segment_moments_kernel<TIN, false>), dim3((unsigned)((total + 3) / 4)), dim3(256), 0, st, x,         \
+                       (long long)row_stride, mean, std, (long long)s0, (long long)L, (long long)n_seg, total);               \
+  else                                                                                                                  \
+    hipLaunchKernelGGL((segment_moments_kernel<TIN, true>), dim3((unsigned)total), dim3(256), 0, st, x, (long long)row_stride, \
+                       mean, std, (long long)s0, (long long)L, (long long)n_seg, total)
+  if (x_is_f64) {
+    SM_LAUNCH(double);
+  } else {
+    SM_LAUNCH(float);
+  }
+#undef SM_LAUNCH
+  return check_launch("segment_moments");
 }
 
 // in-place power-of-two FFT of `buf` (C, m2) complex128 with scratch `tmp`; result ends in `buf`

@@ -27,7 +27,13 @@ On the device the stage adds no arithmetic - that is the signal kernels' - but r
   ``shard_channels`` (default false) passed to such a preprocessor.
   ``figures`` (default true)         false: the preprocessor gets ``figure_dir=None`` and draws nothing.
   ``keep_resident`` (default false)  the saved blocks are also kept for the sample-collection stage of the same process
-                                     (``preprocess/handover.py``); the files are written all the same."""
+                                     (``preprocess/handover.py``); the files are written all the same.
+  ``diagnostics`` (default false)    the input of the first step and the output of every step of a modality are summarised on
+                                     the device (``utils/diagnostics.py``: Welch PSD, mean and std per second) and written to
+                                     ``<setup>/diagnostics/subject_<id>/block_<id>/<modality>/step<i>_<module>.npz``
+                                     (``step0_input`` is the input).  Needs a preprocessor whose ``preprocess_modalities`` takes
+                                     ``diagnostics_dir``; refused with ``shard_channels``, as per-step figures are.  Absent or
+                                     false: nothing is computed and no directory is made."""
 from __future__ import annotations
 
 import hashlib
@@ -120,6 +126,11 @@ def run(pipeline_params, io_params, io_module, preprocessor_module, modalities_c
         extra["resident"] = bool(getattr(pipeline_params, "resident", True))
     if _takes(preprocessor_module.preprocess_modalities, "shard_channels"):
         extra["shard_channels"] = bool(getattr(pipeline_params, "shard_channels", False))
+    diagnostics = bool(getattr(pipeline_params, "diagnostics", False))
+    if diagnostics and bool(getattr(pipeline_params, "shard_channels", False)):
+        raise ValueError("subject_block: 'diagnostics' needs the whole recording; not available with shard_channels")
+    if diagnostics and not _takes(preprocessor_module.preprocess_modalities, "diagnostics_dir"):
+        raise ValueError("subject_block: 'diagnostics' needs a preprocessor whose preprocess_modalities takes diagnostics_dir")
 
     for subject_id, block_id, block_path in iter_blocks(io_params.root_dir, pipeline_params.subject_dirs,
                                                         getattr(pipeline_params, "subject_ids", None)):
@@ -131,6 +142,8 @@ def run(pipeline_params, io_params, io_module, preprocessor_module, modalities_c
         os.makedirs(block_figure_dir, exist_ok=True)
         if extra.get("resident"):
             _upload(data_dict, modalities_cfg)
+        if diagnostics:
+            extra["diagnostics_dir"] = os.path.join(setup_dir, "diagnostics", f"subject_{subject_id}", f"block_{block_id}")
         preprocessor_module.preprocess_modalities(data_dict, modalities_cfg, block_params,
                                                   figure_dir=block_figure_dir if figures else None, **extra)
         io_module.save_block(setup_dir, subject_id, block_id, data_dict)

@@ -109,8 +109,15 @@ class _ChannelShards:
 
 
 def preprocess_signal(data, steps: List[Dict], block_params: Namespace, figure_dir: Optional[str] = None,
-                      num_channels: int = 5, duration: float = 1.0, resident: bool = False, shard_channels: bool = False):
-    """Apply the steps in order (reference :39-70).  Returns ``(data, block_params.signal_freq)``."""
+                      num_channels: int = 5, duration: float = 1.0, resident: bool = False, shard_channels: bool = False,
+                      diagnostics_dir: Optional[str] = None):
+    """Apply the steps in order (reference :39-70).  Returns ``(data, block_params.signal_freq)``.
+
+    With ``diagnostics_dir`` the 2-D input of the first step and the output of every step are summarised where they are
+    (``utils/diagnostics.summarise``: Welch PSD and per-second mean / std) and written to ``step0_input.npz``,
+    ``step<i>_<module>.npz`` (i from 1) in that directory; the data and the returned values are untouched."""
+    if diagnostics_dir is not None and shard_channels:
+        raise ValueError("preprocess_signal: step diagnostics need the whole recording; not available with shard_channels")
     was_np = isinstance(data, np.ndarray)
     shards = None
     if shard_channels:
@@ -127,6 +134,8 @@ def preprocess_signal(data, steps: List[Dict], block_params: Namespace, figure_d
     if resident and was_np and shards is None:
         import torch
         data = torch.from_numpy(np.ascontiguousarray(data)).to("cuda")
+    if diagnostics_dir is not None and steps and getattr(data, "ndim", 0) == 2:
+        _write_diagnostics(data, block_params.signal_freq, diagnostics_dir, 0, "input")
     for i, step in enumerate(steps):
         module_name = step['module']
         for key, value in step.get('params', {}).items():
@@ -156,6 +165,8 @@ def preprocess_signal(data, steps: List[Dict], block_params: Namespace, figure_d
         if figure_dir and getattr(data, "ndim", 0) == 2:
             _plot_step(before, before_freq, data, block_params.signal_freq, figure_dir, i, module_name,
                        num_channels, duration)
+        if diagnostics_dir is not None and getattr(data, "ndim", 0) == 2:
+            _write_diagnostics(data, block_params.signal_freq, diagnostics_dir, i + 1, module_name.rsplit(".", 1)[-1])
     if shards is not None:
         data = shards.gather(data)
         if was_np:
@@ -166,9 +177,13 @@ def preprocess_signal(data, steps: List[Dict], block_params: Namespace, figure_d
 
 
 def preprocess_modalities(data_dict: Dict, modalities_cfg: Dict, base_params: Namespace,
-                          figure_dir: Optional[str] = None, resident: bool = False, shard_channels: bool = False) -> Dict:
+                          figure_dir: Optional[str] = None, resident: bool = False, shard_channels: bool = False,
+                          diagnostics_dir: Optional[str] = None) -> Dict:
     """Per modality: copy the base parameters, take ``signal_freq`` from ``<modality>_sf``, run the
-    configured steps, write the data and the new sampling rate back (reference :8-36)."""
+    configured steps, write the data and the new sampling rate back (reference :8-36).  ``diagnostics_dir``: the step
+    summaries of ``preprocess_signal`` go to ``<diagnostics_dir>/<modality>/``."""
+    if diagnostics_dir is not None and shard_channels:
+        raise ValueError("preprocess_modalities: step diagnostics need the whole recording; not available with shard_channels")
     for modality, cfg in modalities_cfg.items():
         mod_type = cfg.get("type")
         mod_fig_dir = os.path.join(figure_dir, modality) if figure_dir else None
@@ -184,11 +199,19 @@ def preprocess_modalities(data_dict: Dict, modalities_cfg: Dict, base_params: Na
             raise ValueError(f"Modality '{modality}': unsupported type '{mod_type}' (only 'signal' is preprocessed)")
         params.signal_freq = data_dict.get(f"{modality}_sf")
         processed, freq = preprocess_signal(data_dict[modality], steps, params, figure_dir=mod_fig_dir,
-                                            resident=resident, shard_channels=shard_channels)
+                                            resident=resident, shard_channels=shard_channels,
+                                            diagnostics_dir=os.path.join(diagnostics_dir, modality) if diagnostics_dir else None)
         if freq is not None:
             data_dict[f"{modality}_sf"] = freq
         data_dict[modality] = processed
     return data_dict
+
+
+def _write_diagnostics(data, signal_freq, diagnostics_dir: str, index: int, name: str) -> None:
+    """One ``step<index>_<name>.npz``: the recording is summarised on the device, only the summary is copied and written."""
+    from ..utils import diagnostics
+    os.makedirs(diagnostics_dir, exist_ok=True)
+    np.savez(os.path.join(diagnostics_dir, f"step{index}_{name}.npz"), **diagnostics.summarise(data, signal_freq))
 
 
 def _plot_step(before, before_freq, after, after_freq, figure_dir, index, module_name, num_channels, duration) -> None:

@@ -801,6 +801,12 @@ int tl_fir_bank_ols(const void* x, int x_is_f64, const double* G, const double* 
  * zscore_rereference.py:66-68 (baseline interval); y has the input dtype; stats (C,2) f64 workspace */
 int tl_row_zscore(const void* x, int is_f64, void* y, double* stats, int C, int64_t T, int64_t t0, int64_t t1,
                   int zero_nans, void* stream);
+/* mean and population std (np.std) of the segments x[c][s0 + i L : s0 + (i + 1) L], i < n_seg, of a (C, T) float32 or
+ * float64 recording with row_stride elements between rows -> mean, std (C, n_seg) float64 (utils/diagnostics.py
+ * segment_mean_std).  Two-pass (the mean, then the squared deviations of the same samples), fp64.  TL_EINVAL on a null
+ * pointer, s0 < 0, L < 1, n_seg < 1, s0 + n_seg L > T or row_stride < T                                              */
+int tl_segment_moments(const void* x, int x_is_f64, int64_t row_stride, double* mean, double* std, int C, int64_t T,
+                       int64_t s0, int64_t L, int64_t n_seg, void* stream);
 /* common-average re-reference over the channels with include[c] != 0 (car_rereference.py:34-39)   */
 int tl_car(const void* x, int is_f64, const int32_t* include, void* y, int C, int64_t T, int n_inc, void* stream);
 /* pandas rolling(window, min_periods=1) z-score, sample std (rolling_zscore.py:36-49); y float64   */
@@ -874,6 +880,23 @@ int tl_mel_power(const void* audio, int audio_is_f64, int64_t row_stride, const 
  * (power_to_db(ref=np.max, top_db=80) per trial)                                                                      */
 int tl_mel_finish(const double* mel, const double* rowmax, float* out, int N, int n_mels, int64_t n_frames, int in_db,
                   void* stream);
+
+/* ---- Welch power spectral density of every row of a recording (utils/diagnostics.py welch_psd; the meaning of
+ * scipy.signal.welch(axis=1, return_onesided=True, average='mean')), on the transform of tl_mel_power, fp64 throughout.
+ *
+ * x is (C, T) float32 or float64 (x_is_f64) with row_stride elements between rows, read in place.  Segment s covers the
+ * samples s * (nperseg - noverlap) + [0, nperseg); it is zero-padded to n_fft in registers (the padding is never read from
+ * memory).  detrend 0 = none, 1 = constant (the segment's mean is removed before windowing).  window (n_fft) float64 = the
+ * nperseg coefficients followed by zeros; tw as for tl_mel_power; scale = 1 / (fs sum w^2) or 1 / (sum w)^2, from the host.
+ * Two launches: every (channel, slab of consecutive segments) adds |X|^2 over its segments into work (C, n_slabs, n_fft/2+1)
+ * float64 (work_elems doubles; a slab past the last segment writes zeros), then psd (C, n_fft/2 + 1) float64 = the slabs
+ * added in order / n_seg * scale, doubled except at DC and Nyquist.  No atomics: two runs give the same bits.
+ * TL_EINVAL, before any launch, on a null pointer, n_fft outside {256, 512, 1024, 2048}, nperseg outside [2, n_fft],
+ * noverlap < 0 or nperseg - noverlap < 1, detrend outside {0, 1}, C outside [1, 65535], T < nperseg, row_stride < T,
+ * n_seg != (T - noverlap) / (nperseg - noverlap), n_slabs < 1 or a workspace that is too small                          */
+int tl_welch_psd(const void* x, int x_is_f64, int64_t row_stride, const double* window, const double* tw, double* work,
+                 int64_t work_elems, double* psd, int C, int64_t T, int n_fft, int nperseg, int noverlap, int detrend,
+                 double scale, int64_t n_seg, int n_slabs, void* stream);
 
 /* ---- the way back (utils/audio.py mel_to_audio, one trial at a time on the host): mel -> linear spectrum -> Griffin-Lim.
  * window, tw, bands, weights are the tables of tl_mel_power; n_fft in {256, 512, 1024, 2048}; every array float64.
