@@ -175,6 +175,8 @@ SIGNATURES = {
     "tl_max_run_below": (_I, [_P, _I, _L, C.c_double, _P, _P, _P]),
     "tl_perm_exceed": (_I, [_P, _L, _P, _L, _I, _L, _P, _P, _I, C.POINTER(C.c_int32), _I, _P, _P, _P]),
     "tl_perm_runs": (_I, [_P, _L, _L, _P, _P]),
+    "tl_rank_columns": (_I, [_P, _L, _P, _L, _I, _L, _P, _P]),
+    "tl_kruskal_finalize": (_I, [_P, _P, C.POINTER(C.c_int32), _I, _I, _L, _P, _P, _P]),
     "tl_mel_power": (_I, [_P, _I, _L, _P, _P, _P, _P, _I, _P, _P, _I, _L, _I, _I, _I, _I, _I, _I, _L, _P]),
     "tl_mel_finish": (_I, [_P, _P, _P, _I, _I, _L, _I, _P]),
     "tl_welch_psd": (_I, [_P, _I, _L, _P, _P, _P, _L, _P, _I, _L, _I, _I, _I, _I, _D, _L, _I, _P]),

@@ -4,7 +4,9 @@ channel_selection/active.py:15-84).
 
 Same keys (``erp_name``, ``rest_name``, ``ecog_sf``, ``p_threshold``, ``active_time_threshold``), same errors and the same
 result dict as the reference.  Rest and ERP are two arrays with their own sample counts: one ``tl_group_moments`` launch
-each, ``tl_anova_finalize``, ``tl_max_run_below``.  No CPU fallback."""
+each, ``tl_anova_finalize``, ``tl_max_run_below``.  One key beyond the reference: ``test``, ``anova`` (the default) or
+``kruskal`` - the Kruskal-Wallis test on the midranks of rest and ERP taken together (``tl_rank_columns``,
+``tl_kruskal_finalize``), for amplitudes with heavy tails.  No CPU fallback."""
 from __future__ import annotations
 
 import os
@@ -14,7 +16,7 @@ from typing import Optional
 
 import numpy as np
 
-from .utils import anova_device, device_recording, lookup, max_run_below
+from .utils import anova_device, check_statistic, device_recording, kruskal_device, lookup, max_run_below
 
 
 def run(data: dict, params: dict) -> dict:
@@ -26,7 +28,9 @@ def run(data: dict, params: dict) -> dict:
     only, not of every channel - ``generate_figures`` downstream relies on that shape.
 
     One check goes beyond the reference: rest and ERP recordings with different numbers of timepoints raise a
-    ``ValueError`` here (the reference fails later, inside scipy, on such a pair)."""
+    ``ValueError`` here (the reference fails later, inside scipy, on such a pair).  ``test: kruskal`` takes the p-values
+    from the Kruskal-Wallis test; any value but ``anova`` / ``kruskal`` raises a ``ValueError``."""
+    test = check_statistic(params.get('test', 'anova'), "test")
     names = {"erp": params.get('erp_name', 'ecog'), "rest": params.get('rest_name', 'ecog_rest')}
     if "ecog_sf" not in data:
         raise ValueError("ECoG sampling frequency (ecog_sf) not found in the data.")
@@ -45,7 +49,11 @@ def run(data: dict, params: dict) -> dict:
     erp = device_recording(data, names["erp"], "channel_selection.active")
     if rest.dtype != erp.dtype:
         rest, erp = rest.double(), erp.double()
-    _, p = anova_device([rest, erp], [np.arange(rest.shape[0], dtype=np.int32), np.arange(erp.shape[0], dtype=np.int32)])
+    n_rest, n_erp = int(rest.shape[0]), int(erp.shape[0])
+    if test == "kruskal":
+        _, p = kruskal_device([rest, erp], [np.arange(n_rest, dtype=np.int32), np.arange(n_rest, n_rest + n_erp, dtype=np.int32)])
+    else:
+        _, p = anova_device([rest, erp], [np.arange(n_rest, dtype=np.int32), np.arange(n_erp, dtype=np.int32)])
     count, longest = max_run_below(p, corrected_p_threshold)
     count, longest = count.cpu().numpy(), longest.cpu().numpy()
     active_channels = [int(ch) for ch in np.flatnonzero((count > 0) & (longest > length_threshold))]

@@ -4,7 +4,9 @@ channel_selection/discriminative.py:16-182).
 
 Same keys (``recording_name``, ``target``, ``p_threshold``, ``active_time_threshold``, ``<recording>_sf``), same errors and
 the same result dict as the reference.  The per-channel ``scipy.stats.f_oneway`` loop is one launch of ``tl_group_moments``
-per class plus ``tl_anova_finalize``; the per-channel run search is ``tl_max_run_below``.  No CPU fallback."""
+per class plus ``tl_anova_finalize``; the per-channel run search is ``tl_max_run_below``.  One key beyond the reference:
+``test``, ``anova`` (the default) or ``kruskal`` - the Kruskal-Wallis test on the midranks (``tl_rank_columns``,
+``tl_kruskal_finalize``), for amplitudes with heavy tails.  No CPU fallback."""
 from __future__ import annotations
 
 import os
@@ -14,12 +16,13 @@ from typing import Dict, Mapping, Optional
 
 import numpy as np
 
-from .utils import anova_device, device_recording, lookup, max_run_below
+from .utils import anova_device, check_statistic, device_recording, kruskal_device, lookup, max_run_below
 
 
 def _anova_on_device(data: Mapping, params: dict):
     """The reference's input checks (:122-164, same messages) and the test itself; returns (F, p) as (C, T) float64 CUDA
-    tensors."""
+    tensors - (H, p) with ``test: kruskal``."""
+    test = check_statistic(params.get('test', 'anova'), "test")
     name = params.get('recording_name', 'ecog')
     target = params['target']
     series = lookup(data, name, "Recording")
@@ -37,14 +40,18 @@ def _anova_on_device(data: Mapping, params: dict):
         raise ValueError(f"Labels for '{target}' must be integers.")
     x = device_recording(data, name, "channel_selection.discriminative")
     classes = [np.flatnonzero(labels == v).astype(np.int32) for v in np.unique(labels)]
+    if test == "kruskal":
+        return kruskal_device([x], classes)
     return anova_device([x] * len(classes), classes)
 
 
 def test_discriminative_power(data: Mapping[str, np.ndarray], params: dict) -> Dict[str, np.ndarray]:
     """``{'f_stat', 'p_value'}``, both (n_channels, n_timepoints) float64 NumPy: the ANOVA of ``data[recording_name]``
-    (n_samples, n_channels, n_timepoints) grouped by the integer labels ``data[target]``."""
+    (n_samples, n_channels, n_timepoints) grouped by the integer labels ``data[target]``.  With ``test: kruskal`` the keys
+    are ``{'h_stat', 'p_value'}``."""
     F, p = _anova_on_device(data, params)
-    return {'f_stat': F.cpu().numpy(), 'p_value': p.cpu().numpy()}
+    stat_key = 'h_stat' if params.get('test', 'anova') == "kruskal" else 'f_stat'
+    return {stat_key: F.cpu().numpy(), 'p_value': p.cpu().numpy()}
 
 
 test_discriminative_power.__test__ = False          # a mirrored name, not a pytest case

@@ -9,7 +9,8 @@ With ``target`` in the parameters it is the labelled form and takes the keys of 
 ``target``, ``p_threshold``); without, it is rest against ERP with the keys of ``active`` (``erp_name``, ``rest_name``,
 ``p_threshold``).  Both run the input checks of their counterpart and raise its errors.  New keys: ``n_permutations`` (1000),
 ``seed`` (0), ``alpha`` (0.05), ``correction`` (``max`` | ``channel``) and ``perm_chunk`` (relabellings per launch; the
-default bounds the mask).  ``active_time_threshold`` is not used.  All relabellings are one float64 product on the device
+default bounds the mask) and ``test`` (``anova`` | ``kruskal``: the statistic at every cell; the rank form ranks the samples once,
+``tl_rank_columns``, and relabels the ranks).  ``active_time_threshold`` is not used.  All relabellings are one float64 product on the device
 (``tl_perm_exceed``) and one run search (``tl_perm_runs``); no p-value is evaluated per relabelling.  No CPU fallback."""
 from __future__ import annotations
 
@@ -19,7 +20,7 @@ from typing import Mapping
 
 import numpy as np
 
-from .utils import device_recording, lookup, permutation_p_values, permutation_runs, permutation_table
+from .utils import check_statistic, device_recording, lookup, permutation_p_values, permutation_runs, permutation_table
 
 _CORRECTIONS = ("max", "channel")
 
@@ -86,8 +87,10 @@ def run(data: dict, params: dict) -> dict:
     observed run of ``p < p_threshold / n_timepoints`` is longer than 0 and its permutation p-value is at most ``alpha``.
     ``max_lengths`` holds the observed run of every kept channel, ``p_values`` (n_channels,) the permutation p-value that
     decided (per channel, or against the maximum over channels), ``null_max_lengths`` (n_permutations,) the maximum over
-    channels of every relabelling and ``f_crit`` the F value of the cell level."""
+    channels of every relabelling and ``f_crit`` the F value of the cell level.  With ``test: kruskal`` the cells are those
+    of the Kruskal-Wallis test: ``chi2_crit`` holds its critical value next to ``f_crit``, which is None."""
     what = "channel_selection.permutation"
+    test = check_statistic(params.get('test', 'anova'), "test")
     if 'target' in params:
         name, series, group_index = _labelled_inputs(data, params)
         n_perm, seed, alpha, correction, perm_chunk, cell = _new_keys(params, series.shape[2])
@@ -102,14 +105,17 @@ def run(data: dict, params: dict) -> dict:
         group_index = np.repeat(np.arange(2), [rest.shape[0], erp.shape[0]])
     counts = np.bincount(group_index).tolist()
     table = permutation_table(group_index, n_perm, seed)
-    runs, f_crit, _ = permutation_runs(arrays, table, counts, cell, perm_chunk)
+    runs, crit, _ = permutation_runs(arrays, table, counts, cell, perm_chunk, statistic=test)
     runs = runs.cpu().numpy()
     p_channel, p_max = permutation_p_values(runs)
     p_used = p_max if correction == "max" else p_channel
     selected = [int(ch) for ch in np.flatnonzero((runs[0] > 0) & (p_used <= alpha))]
     print(f"Found {len(selected)} channels by the permutation test ({n_perm} relabellings, correction '{correction}').")
-    return {"selected_channels": selected, "max_lengths": [int(runs[0, ch]) for ch in selected], "p_values": p_used,
-            "null_max_lengths": runs[1:].max(axis=1), "f_crit": f_crit}
+    result = {"selected_channels": selected, "max_lengths": [int(runs[0, ch]) for ch in selected], "p_values": p_used,
+              "null_max_lengths": runs[1:].max(axis=1), "f_crit": crit}
+    if test == "kruskal":
+        result.update(f_crit=None, chi2_crit=crit)
+    return result
 
 
 def generate_figures(data: dict, results: dict, params: dict, figure_dir: str) -> None:

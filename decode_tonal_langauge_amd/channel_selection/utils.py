@@ -136,6 +136,156 @@ def anova_oneway(groups_or_array, labels=None) -> Tuple:
     return F.cpu().numpy(), p.cpu().numpy()
 
 
+# ---- rank form: Kruskal-Wallis ---------------------------------------------------------------------------------------
+#: most samples tl_rank_columns sorts in one column (RK_MAX_N of csrc/tonal_anova.hip)
+RANK_MAX_SAMPLES = 8192
+#: most LDS of one block of tl_rank_columns (RK_LDS_BYTES), of a tile of several columns (RK_TILE_BYTES), its widest tile (RK_MAX_TW)
+_RANK_LDS_BYTES, _RANK_TILE_BYTES, _RANK_MAX_TILE = 81920, 40960, 64
+STATISTICS = ("anova", "kruskal")
+
+
+def check_statistic(value, key: str = "statistic") -> str:
+    if value not in STATISTICS:
+        raise ValueError(f"Unknown {key} '{value}': expected one of {list(STATISTICS)}.")
+    return value
+
+
+def rank_tile_columns(n: int, is_f64: bool) -> int:
+    """Columns a block of ``tl_rank_columns`` sorts for ``n`` samples: the entry point's rule, restated for tests and the
+    bench script."""
+    npad = max(2, 1 << (int(n) - 1).bit_length())
+    per = npad * (10 if is_f64 else 6)
+    tile = 1
+    while tile < _RANK_MAX_TILE and per * tile * 2 <= _RANK_TILE_BYTES:
+        tile *= 2
+    return tile
+
+
+def rank_columns_device(arrays: Sequence):
+    """Midranks (N, ...) float32 on the device of one CUDA tensor (N, ...) or of two whose samples follow each other."""
+    import torch
+    from .. import _lib
+    from .._lib import check, ptr, stream_ptr
+    arrays = list(arrays)
+    if not 1 <= len(arrays) <= 2:
+        raise ValueError("rank_columns: one or two sample arrays")
+    x0 = arrays[0]
+    for a in arrays:
+        _lib.require_gpu(a, "rank_columns")
+        if a.dim() < 1 or a.shape[1:] != x0.shape[1:] or a.dtype != x0.dtype or a.device != x0.device:
+            raise ValueError("rank_columns: arrays must share trailing shape, dtype and device")
+    if x0.dtype not in (torch.float32, torch.float64):
+        raise ValueError("rank_columns: float32 or float64 samples")
+    n0, n1 = int(x0.shape[0]), int(arrays[1].shape[0]) if len(arrays) == 2 else 0
+    cols = int(np.prod(tuple(x0.shape[1:]), dtype=np.int64))
+    if n0 < 1 or cols < 1 or (len(arrays) == 2 and n1 < 1):
+        raise ValueError("rank_columns: every array needs at least one sample and one column")
+    if n0 + n1 > RANK_MAX_SAMPLES:
+        raise ValueError(f"rank_columns: at most {RANK_MAX_SAMPLES} samples (got {n0 + n1})")
+    arrays = [a.contiguous() for a in arrays]
+    ranks = torch.empty((n0 + n1,) + tuple(x0.shape[1:]), dtype=torch.float32, device=x0.device)
+    with torch.cuda.device(x0.device):
+        check(_lib.load().tl_rank_columns(ptr(arrays[0]), n0, ptr(arrays[1]) if n1 else None, n1,
+                                          int(x0.dtype == torch.float64), cols, ptr(ranks), stream_ptr()), "tl_rank_columns")
+    return ranks
+
+
+def rank_columns(x, x1=None):
+    """``scipy.stats.rankdata(x, method='average', axis=0)`` as float32 (a midrank is a multiple of 0.5): the rank of every
+    sample within its column, ties sharing the mean of their positions.  With ``x1`` the samples of both arrays are ranked
+    as one, ``x`` first.  ``-0.0`` and ``+0.0`` tie, infinities rank as values, a column that holds a NaN is NaN throughout;
+    float64 input is ranked on its float64 values.  At most ``RANK_MAX_SAMPLES`` samples.  NumPy in, NumPy out; CUDA
+    tensors stay on the device."""
+    import torch
+    given = [x] if x1 is None else [x, x1]
+    on_device = all(isinstance(a, torch.Tensor) for a in given)
+    n = sum(int(a.shape[0]) for a in given)
+    if n > RANK_MAX_SAMPLES:                                   # before anything is uploaded
+        raise ValueError(f"rank_columns: at most {RANK_MAX_SAMPLES} samples (got {n})")
+    dev = [to_device(a, "rank_columns") for a in given]
+    if len({d.dtype for d in dev}) > 1:
+        dev = [d.double() for d in dev]
+    ranks = rank_columns_device(dev)
+    return ranks if on_device else ranks.cpu().numpy()
+
+
+def kruskal_device(arrays: Sequence, index_lists: Sequence[np.ndarray]):
+    """H and p (float64 CUDA tensors of the trailing shape) of the Kruskal-Wallis test between the groups ``index_lists``:
+    row numbers into the samples of ``arrays``, one CUDA tensor or two that follow each other.  Every sample belongs to
+    exactly one group.  ``tl_rank_columns`` once, ``tl_group_moments`` per group on the ranks, ``tl_kruskal_finalize``."""
+    import torch
+    from .. import _lib
+    from .._lib import check, ptr, stream_ptr
+    k = len(index_lists)
+    if not 2 <= k <= 64:
+        raise ValueError(f"kruskal_oneway: needs between 2 and 64 groups, got {k}")
+    counts = [int(len(ix)) for ix in index_lists]
+    if min(counts) < 1:
+        raise ValueError("kruskal_oneway: every group needs at least one sample and one column")
+    n = sum(int(a.shape[0]) for a in arrays)
+    members = np.concatenate([np.asarray(ix, dtype=np.int64) for ix in index_lists])
+    if members.size != n or not np.array_equal(np.sort(members), np.arange(n)):
+        raise ValueError("kruskal_oneway: the groups must hold every sample exactly once")
+    ranks = rank_columns_device(arrays)
+    trailing = tuple(ranks.shape[1:])
+    cols = int(np.prod(trailing, dtype=np.int64))
+    lib = _lib.load()
+    splits = _splits(cols, min(counts))
+    sums = torch.empty(2, k, splits, cols, dtype=torch.float64, device=ranks.device)
+    idx = torch.from_numpy(members.astype(np.int32)).to(ranks.device)
+    shift_row = int(index_lists[0][0])                 # one row of the ranks for every group: the sums share a frame
+    off = 0
+    with torch.cuda.device(ranks.device):
+        for g in range(k):
+            check(lib.tl_group_moments(ptr(ranks), 0, n, cols, idx.data_ptr() + 4 * off, counts[g],
+                                       ranks.data_ptr() + shift_row * cols * 4, splits,
+                                       ptr(sums[0, g]), ptr(sums[1, g]), stream_ptr()), "tl_group_moments")
+            off += counts[g]
+        out = torch.empty(2, cols, dtype=torch.float64, device=ranks.device)
+        cnt = (C.c_int32 * k)(*counts)
+        check(lib.tl_kruskal_finalize(ptr(sums[0]), ptr(sums[1]), cnt, k, splits, cols, ptr(out[0]), ptr(out[1]),
+                                      stream_ptr()), "tl_kruskal_finalize")
+    return out[0].reshape(trailing), out[1].reshape(trailing)
+
+
+def kruskal_oneway(groups_or_array, labels=None) -> Tuple:
+    """Kruskal-Wallis H-test along axis 0 at every trailing position: ``(H, p)`` as ``scipy.stats.kruskal`` defines them
+    (tie-corrected H, chi-square tail with k - 1 degrees of freedom), float64.
+
+    The calling forms and return conventions of ``anova_oneway``: one array per group, or one array and a label per
+    sample.  A column whose values are all identical gives NaN (scipy raises there), as does a column that holds a NaN.
+    At most ``RANK_MAX_SAMPLES`` samples in all."""
+    import torch
+    if labels is None:
+        groups = list(groups_or_array)
+        on_device = all(isinstance(g, torch.Tensor) for g in groups)
+        sizes = [int(g.shape[0]) for g in groups]
+        if sum(sizes) > RANK_MAX_SAMPLES:
+            raise ValueError(f"kruskal_oneway: at most {RANK_MAX_SAMPLES} samples (got {sum(sizes)})")
+        dev = [to_device(g, "kruskal_oneway") for g in groups]
+        if len({d.dtype for d in dev}) > 1:
+            dev = [d.double() for d in dev]
+        if len(dev) > 2:
+            dev = [torch.cat(dev)]                     # the ranks are those of the pooled sample
+        starts = np.concatenate(([0], np.cumsum(sizes)))
+        index_lists = [np.arange(starts[g], starts[g + 1], dtype=np.int32) for g in range(len(sizes))]
+    else:
+        on_device = isinstance(groups_or_array, torch.Tensor)
+        if int(groups_or_array.shape[0]) > RANK_MAX_SAMPLES:
+            raise ValueError(f"kruskal_oneway: at most {RANK_MAX_SAMPLES} samples (got {int(groups_or_array.shape[0])})")
+        x = to_device(groups_or_array, "kruskal_oneway")
+        lab = labels.detach().cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+        lab = lab.squeeze()
+        if lab.ndim != 1 or lab.shape[0] != x.shape[0]:
+            raise ValueError(f"kruskal_oneway: {x.shape[0]} samples but labels of shape {lab.shape}")
+        index_lists = [np.flatnonzero(lab == v).astype(np.int32) for v in np.unique(lab)]
+        dev = [x]
+    H, p = kruskal_device(dev, index_lists)
+    if on_device:
+        return H, p
+    return H.cpu().numpy(), p.cpu().numpy()
+
+
 def max_run_below(p, threshold: float):
     """Per row of the CUDA float64 tensor ``p (C, T)``: ``(count, longest_run)`` of ``p < threshold`` as int32 CUDA tensors -
     ``get_max_length(np.where(p[c] < threshold)[0])`` for every channel at once (0 where no point is below)."""
@@ -179,26 +329,39 @@ def permutation_table(group_index, n_permutations: int, seed: int = 0) -> np.nda
     return table
 
 
-def critical_values(p_threshold: float, k: int, n: int) -> Tuple[float, float]:
+def critical_values(p_threshold: float, k: int, n: int, statistic: str = "anova") -> Tuple[float, float]:
     """``(f_crit, theta)`` of the cell level ``p_threshold``: ``p < p_threshold`` is ``F > f_crit`` is
-    ``ssb > theta * sst`` with ``theta = f_crit dfb / (dfw + f_crit dfb)``; ``scipy.stats.f.isf`` once, on the host."""
+    ``ssb > theta * sst`` with ``theta = f_crit dfb / (dfw + f_crit dfb)``; ``scipy.stats.f.isf`` once, on the host.
+
+    ``statistic="kruskal"``: ``(chi2_crit, theta)`` with ``chi2_crit = scipy.stats.chi2.isf(p_threshold, k - 1)`` and
+    ``theta = chi2_crit / (n - 1)``, since ``H = (n - 1) ssb / sst`` of the midranks.  H never exceeds n - 1: a level with
+    ``chi2_crit >= n - 1`` can be passed by no cell and raises a ``ValueError``."""
     from scipy import stats
+    check_statistic(statistic)
     dfb, dfw = k - 1, n - k
     if dfw < 1:
         raise ValueError(f"permutation test: {n} samples in {k} groups leave no degrees of freedom within the groups")
     if not 0.0 < p_threshold < 1.0:
         raise ValueError(f"permutation test: the cell level must lie in (0, 1), got {p_threshold}")
+    if statistic == "kruskal":
+        chi2_crit = float(stats.chi2.isf(p_threshold, dfb))
+        if chi2_crit >= n - 1:
+            raise ValueError(f"permutation test: no cell can reach the level {p_threshold} with {n} samples in {k} groups: "
+                             f"H is at most {n - 1}, the level needs H > {chi2_crit:.6g}")
+        return chi2_crit, chi2_crit / (n - 1)
     f_crit = float(stats.f.isf(p_threshold, dfb, dfw))
     return f_crit, f_crit * dfb / (dfw + f_crit * dfb)
 
 
-def _perm_apply(arrays, table, counts, p_threshold, perm_chunk, make_out, consume):
+def _perm_apply(arrays, table, counts, p_threshold, perm_chunk, make_out, consume, statistic="anova"):
     """The work shared by ``permutation_runs`` and ``permutation_exceedances``: ``out = make_out(P, C, T)``, then
     ``consume(out, p0, p1, mask)`` per chunk of relabellings with ``mask`` (p1 - p0, C * T) uint8 on the device.  Returns
-    ``(out, f_crit, theta)``."""
+    ``(out, f_crit, theta)`` (``critical_values`` of ``statistic``).  ``"kruskal"`` ranks the samples once - a relabelling
+    does not change them - and runs the same launches on the ranks."""
     import torch
     from .. import _lib
     from .._lib import check, ptr, stream_ptr
+    check_statistic(statistic)
     arrays = list(arrays)
     if not 1 <= len(arrays) <= 2:
         raise ValueError("permutation test: one or two sample arrays")
@@ -221,7 +384,10 @@ def _perm_apply(arrays, table, counts, p_threshold, perm_chunk, make_out, consum
         raise ValueError(f"permutation test: the table must be (P, {N}), got {table.shape}")
     if not 2 <= k <= 64 or min(counts) < 1 or sum(counts) != N or cols < 1:
         raise ValueError("permutation test: between 2 and 64 groups of at least one sample each, adding up to the samples")
-    f_crit, theta = critical_values(p_threshold, k, N)
+    f_crit, theta = critical_values(p_threshold, k, N, statistic)
+    if statistic == "kruskal":
+        arrays = [rank_columns_device(arrays)]                              # (N, C, T) float32
+        x0 = arrays[0]
     P = table.shape[0]
     if perm_chunk is None:
         perm_chunk = max(1, _PERM_MASK_BYTES // cols)
@@ -263,7 +429,8 @@ def _perm_apply(arrays, table, counts, p_threshold, perm_chunk, make_out, consum
     return out, f_crit, theta
 
 
-def permutation_runs(arrays: Sequence, table, counts: Sequence[int], p_threshold: float, perm_chunk: Optional[int] = None):
+def permutation_runs(arrays: Sequence, table, counts: Sequence[int], p_threshold: float, perm_chunk: Optional[int] = None,
+                     statistic: str = "anova"):
     """``(runs, f_crit, theta)``: ``runs (P, C)`` int32 on the device is, per row of ``table`` (``permutation_table``) and
     channel, the longest run of timepoints at which the one-way ANOVA under that labelling has ``p < p_threshold``
     (the CELL level - a selector divides its ``p_threshold`` by T first).
@@ -272,7 +439,10 @@ def permutation_runs(arrays: Sequence, table, counts: Sequence[int], p_threshold
     ERP); ``counts`` the k group sizes of the observed labelling.  No p-value is evaluated: a relabelling keeps the group
     sizes, so ``p < p_threshold`` is ``sum_g S_g^2 / n_g > theta sst + total^2 / N`` with one host ``scipy.stats.f.isf``.
     The relabellings go through ``tl_perm_exceed`` / ``tl_perm_runs`` in chunks of ``perm_chunk`` (default: a mask of at
-    most 64 MiB); the result does not depend on the chunking."""
+    most 64 MiB); the result does not depend on the chunking.
+
+    ``statistic="kruskal"``: the Kruskal-Wallis test in place of the ANOVA, ``(runs, chi2_crit, theta)``.  The samples are
+    ranked once (``tl_rank_columns``) and the same path runs on the ranks with ``theta = chi2_crit / (N - 1)``."""
     import torch
     from .. import _lib
     from .._lib import check, ptr, stream_ptr
@@ -283,11 +453,11 @@ def permutation_runs(arrays: Sequence, table, counts: Sequence[int], p_threshold
         Cn = runs.shape[1]
         check(lib.tl_perm_runs(ptr(mask), (p1 - p0) * Cn, mask.shape[1] // Cn, ptr(runs[p0:p1]), stream_ptr()), "tl_perm_runs")
     return _perm_apply(arrays, table, counts, p_threshold, perm_chunk,
-                       lambda P, Cn, T: torch.empty(P, Cn, dtype=torch.int32, device=device), consume)
+                       lambda P, Cn, T: torch.empty(P, Cn, dtype=torch.int32, device=device), consume, statistic)
 
 
 def permutation_exceedances(arrays: Sequence, table, counts: Sequence[int], p_threshold: float,
-                            perm_chunk: Optional[int] = None):
+                            perm_chunk: Optional[int] = None, statistic: str = "anova"):
     """The boolean ``(P, C, T)`` CUDA mask behind ``permutation_runs`` (same arguments): where ``p < p_threshold`` under
     each labelling.  P * C * T bytes: for tests and small inputs."""
     import torch
@@ -296,7 +466,7 @@ def permutation_exceedances(arrays: Sequence, table, counts: Sequence[int], p_th
     def consume(out, p0, p1, mask):
         out[p0:p1] = mask.reshape(out[p0:p1].shape) != 0
     return _perm_apply(arrays, table, counts, p_threshold, perm_chunk,
-                       lambda P, Cn, T: torch.empty(P, Cn, T, dtype=torch.bool, device=device), consume)[0]
+                       lambda P, Cn, T: torch.empty(P, Cn, T, dtype=torch.bool, device=device), consume, statistic)[0]
 
 
 def permutation_p_values(runs):

@@ -116,16 +116,14 @@ struct AnovaCounts { int32_t n[64]; };
 // sum / sumsq (k, splits, cols): the split slabs of a group are added here.  With S_g, Q_g the shifted sums of group g,
 // ssb = sum_g n_g (S_g/n_g - S/N)^2 and ssw = sum_g (Q_g - S_g^2/n_g) - both invariant under the shift; the group sums are
 // read twice rather than kept in an array indexed by g (a dynamic register index).
-__global__ __launch_bounds__(256) void anova_finalize_kernel(const double* __restrict__ sum, const double* __restrict__ sumsq,
-                                                             AnovaCounts cnt, int k, int splits, long long cols, long long N,
-                                                             double* __restrict__ F, double* __restrict__ p) {
-  const long long col = blockIdx.x * 256LL + threadIdx.x;
-  if (col >= cols) return;
+__device__ __forceinline__ void group_ss(const double* __restrict__ sum, const double* __restrict__ sumsq, const AnovaCounts& cnt,
+                                         int k, int splits, long long cols, long long N, long long col, double& ssb, double& ssw) {
   double S = 0.0;
   for (int g = 0; g < k; ++g)
     for (int s = 0; s < splits; ++s) S += sum[((long long)g * splits + s) * cols + col];
   const double mean = S / (double)N;
-  double ssb = 0.0, ssw = 0.0;
+  ssb = 0.0;
+  ssw = 0.0;
   for (int g = 0; g < k; ++g) {
     double Sg = 0.0, Qg = 0.0;
     for (int s = 0; s < splits; ++s) {
@@ -136,6 +134,15 @@ __global__ __launch_bounds__(256) void anova_finalize_kernel(const double* __res
     ssb = fma(ng * d, d, ssb);
     ssw += Qg - Sg * mg;
   }
+}
+
+__global__ __launch_bounds__(256) void anova_finalize_kernel(const double* __restrict__ sum, const double* __restrict__ sumsq,
+                                                             AnovaCounts cnt, int k, int splits, long long cols, long long N,
+                                                             double* __restrict__ F, double* __restrict__ p) {
+  const long long col = blockIdx.x * 256LL + threadIdx.x;
+  if (col >= cols) return;
+  double ssb, ssw;
+  group_ss(sum, sumsq, cnt, k, splits, cols, N, col, ssb, ssw);
   const double dfb = (double)(k - 1), dfw = (double)(N - k);
   double f = __builtin_nan(""), pv = __builtin_nan("");
   if (N > k) {
@@ -144,6 +151,218 @@ __global__ __launch_bounds__(256) void anova_finalize_kernel(const double* __res
   }
   F[col] = f;
   p[col] = pv;
+}
+
+// ------------------------------------------------------------------------------------------
+// Kruskal-Wallis: with its tie correction H is the ANOVA decomposition of the midranks, H = (N - 1) ssb / (ssb + ssw), and
+// p = Q(a, x), a = (k - 1)/2, x = H/2, the regularised upper incomplete gamma function (the chi-square tail): the series of
+// P below a + 1, the continued fraction of Q (modified Lentz) from there on.  The prefactor x^a e^-x / Gamma(a) is the product
+// of exp(-x), whose argument is exact, and exp(a log x - lgamma(a)), whose argument stays below 210 for a <= 31.5 and every
+// x that exp(-x) survives: a p of 1e-100 carries the rounding of an argument of a few units, not of one near -230.
+// ------------------------------------------------------------------------------------------
+__host__ __device__ inline double chi2_survival(double H, double df) {
+  if (H != H || df <= 0.0 || H < 0.0) return __builtin_nan("");
+  if (H == 0.0) return 1.0;
+  const double a = 0.5 * df, x = 0.5 * H;
+  const double pre = exp(-x) * exp(fma(a, log(x), -lgamma(a)));
+  if (x < a + 1.0) {
+    double ap = a, del = 1.0 / a, s = del;
+    for (int n = 1; n <= 2000; ++n) {
+      ap += 1.0;
+      del *= x / ap;
+      s += del;
+      if (del < s * 1e-17) break;
+    }
+    return 1.0 - pre * s;
+  }
+  const double tiny = 1e-300;
+  double b = x + 1.0 - a, c = 1.0 / tiny, d = 1.0 / b, h = d;
+  for (int i = 1; i <= 2000; ++i) {
+    const double an = -i * (i - a);
+    b += 2.0;
+    d = an * d + b;
+    if (fabs(d) < tiny) d = tiny;
+    c = b + an / c;
+    if (fabs(c) < tiny) c = tiny;
+    d = 1.0 / d;
+    const double del = d * c;
+    h *= del;
+    if (fabs(del - 1.0) < 2e-16) break;
+  }
+  return pre * h;
+}
+
+// sum / sumsq as anova_finalize_kernel reads them, taken of the midranks; a column of identical values has sst = 0: NaN
+__global__ __launch_bounds__(256) void kruskal_finalize_kernel(const double* __restrict__ sum, const double* __restrict__ sumsq,
+                                                               AnovaCounts cnt, int k, int splits, long long cols, long long N,
+                                                               double* __restrict__ H, double* __restrict__ p) {
+  const long long col = blockIdx.x * 256LL + threadIdx.x;
+  if (col >= cols) return;
+  double ssb, ssw;
+  group_ss(sum, sumsq, cnt, k, splits, cols, N, col, ssb, ssw);
+  const double sst = ssb + ssw;
+  double h = __builtin_nan(""), pv = __builtin_nan("");
+  if (sst > 0.0) {                                             // false for NaN
+    h = (double)(N - 1) * ssb / sst;
+    pv = chi2_survival(h, (double)(k - 1));
+  }
+  H[col] = h;
+  p[col] = pv;
+}
+
+// ------------------------------------------------------------------------------------------
+// midranks down the sample axis: ranks[i][col] = scipy.stats.rankdata(column col, method='average')[i].  A block owns tw
+// consecutive columns and all N samples.  Every value becomes an unsigned key in the order of the values (-0.0 made +0.0 first,
+// so the two tie; the sign bit flipped for a positive value, every bit for a negative one) next to its sample index; a NaN and
+// the padding up to npad = the next power of two take the largest key.  The image is [position][column]: a row load is
+// coalesced along the columns, and a pass of the bitonic network (rank_pass: up to three steps) touches, per lane group, tw
+// consecutive words per position at ANY stride of the network - no power-of-two stride between the lanes of a group, the bank
+// of a word is its column (tw >= 32; a narrower tile puts 32 / tw positions into a lane group: conflict-free while the threads
+// of the group own neighbouring positions, up to 32 / tw-way in the last pass of a stage, whose threads own neighbouring runs
+// of 2^M positions - the narrow tiles measured faster all the same, see below).  The
+// network is not stable and need not be: tied keys get one rank.  Sorted position s then finds the ends [lo, hi) of its tie run
+// (a neighbour compare; a binary search only inside a run) and writes (lo + hi + 1) / 2 to the row of its index.  A column that
+// holds a NaN has the largest key at position N - 1 and gets NaN in every row.
+// tw is the largest power of two <= RK_MAX_TW with npad * tw * (key bytes + 2) <= RK_TILE_BYTES, and 1 where one column takes
+// more (up to RK_LDS_BYTES): four blocks of 512 threads a CU where the tile allows it - at 480 samples tw = 8 for both dtypes,
+// 24 and 40 KiB.  Measured there against 80 KiB tiles and 256 or 1024 threads (float32 / float64 ms): 256 threads, 80 KiB
+// 1.09 / 1.78; 1024, 80 KiB 0.92 / 1.72; 512, 80 KiB 0.86 / 1.30; 256, 40 KiB 0.90 / 1.22; 512, 40 KiB 0.89 / 1.20.
+// ------------------------------------------------------------------------------------------
+#define RK_THREADS 512
+#define RK_MAX_N 8192                 // 8192 float64 keys with their indices are RK_LDS_BYTES at tw = 1
+#define RK_LDS_BYTES 81920            // most LDS of a block: half of the 160 KiB of a CU
+#define RK_TILE_BYTES 40960           // a tile of more than one column stays within a quarter
+#define RK_MAX_TW 64
+#define RK_LOADS 8
+
+__device__ __forceinline__ uint32_t rank_key(float v) {
+  if (v != v) return 0xffffffffu;
+  if (v == 0.f) v = 0.f;
+  const uint32_t u = __float_as_uint(v);
+  return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+}
+__device__ __forceinline__ uint64_t rank_key(double v) {
+  if (v != v) return ~0ull;
+  if (v == 0.0) v = 0.0;
+  const uint64_t u = (uint64_t)__double_as_longlong(v);
+  return u ^ ((u >> 63) ? ~0ull : 0x8000000000000000ull);
+}
+
+// M consecutive steps of stage k, strides j, j/2, .., low = j >> (M - 1), in one pass over LDS: the 2^M positions
+// base + a low (the M stride bits of the position free, the rest taken from g) only exchange among themselves in those steps,
+// so a thread holds them in registers; one read and one write per element and one barrier where the steps alone take M.
+// The direction bit k lies above every stride of its stage: one direction per thread.
+template <typename K, int M>
+__device__ __forceinline__ void rank_pass(K* keys, uint16_t* idx, int npad, int ltw, int k, int j, int tid) {
+  constexpr int E = 1 << M;
+  const int low = j >> (M - 1), st = low << ltw, items = (npad >> M) << ltw;
+  for (int e = tid; e < items; e += RK_THREADS) {
+    const int g = e >> ltw, base = ((g & ~(low - 1)) << M) | (g & (low - 1));
+    const int a0 = (base << ltw) + (e & ((1 << ltw) - 1));
+    const bool up = (base & k) == 0;
+    K kv[E];
+    uint16_t iv[E];
+#pragma unroll
+    for (int a = 0; a < E; ++a) {
+      kv[a] = keys[a0 + a * st];
+      iv[a] = idx[a0 + a * st];
+    }
+#pragma unroll
+    for (int t = M - 1; t >= 0; --t)
+#pragma unroll
+      for (int a = 0; a < E; ++a)
+        if (!(a & (1 << t))) {
+          const int b = a | (1 << t);
+          const bool sw = (kv[a] > kv[b]) == up;
+          const K ka = kv[a];
+          const uint16_t ia = iv[a];
+          kv[a] = sw ? kv[b] : ka;
+          kv[b] = sw ? ka : kv[b];
+          iv[a] = sw ? iv[b] : ia;
+          iv[b] = sw ? ia : iv[b];
+        }
+#pragma unroll
+    for (int a = 0; a < E; ++a) {
+      keys[a0 + a * st] = kv[a];
+      idx[a0 + a * st] = iv[a];
+    }
+  }
+}
+
+template <typename T, typename K>
+__global__ __launch_bounds__(RK_THREADS) void rank_columns_kernel(const T* __restrict__ x0, long long n0, const T* __restrict__ x1,
+                                                                  int N, long long cols, int npad, int ltw,
+                                                                  float* __restrict__ ranks) {
+  extern __shared__ unsigned long long rk_lds[];
+  const int tw = 1 << ltw, cmask = tw - 1, tid = threadIdx.x;
+  K* keys = reinterpret_cast<K*>(rk_lds);                      // [npad][tw]
+  uint16_t* idx = reinterpret_cast<uint16_t*>(keys + npad * tw);
+  const long long col0 = (long long)blockIdx.x * tw;
+  const K pad = ~(K)0;
+  for (int e0 = tid; e0 < npad * tw; e0 += RK_LOADS * RK_THREADS) {       // RK_LOADS row segments in flight per thread
+    T v[RK_LOADS];
+#pragma unroll
+    for (int u = 0; u < RK_LOADS; ++u) {
+      const int e = e0 + u * RK_THREADS;
+      const long long i = e >> ltw, col = col0 + (e & cmask);
+      v[u] = (T)__builtin_nanf("");                                        // padding takes the key of a NaN
+      if (i < N && col < cols) v[u] = i < n0 ? x0[i * cols + col] : x1[(i - n0) * cols + col];
+    }
+#pragma unroll
+    for (int u = 0; u < RK_LOADS; ++u) {
+      const int e = e0 + u * RK_THREADS;
+      if (e < npad * tw) {
+        keys[e] = rank_key(v[u]);
+        idx[e] = (uint16_t)(e >> ltw);
+      }
+    }
+  }
+  for (int k = 2, steps = 1; k <= npad; k <<= 1, ++steps)      // stage k: steps of stride k/2 .. 1, three to a pass
+    for (int j = k >> 1, left = steps; left > 0;) {
+      __syncthreads();
+      if (left >= 3) {
+        rank_pass<K, 3>(keys, idx, npad, ltw, k, j, tid);
+        j >>= 3;
+        left -= 3;
+      } else if (left == 2) {
+        rank_pass<K, 2>(keys, idx, npad, ltw, k, j, tid);
+        j >>= 2;
+        left -= 2;
+      } else {
+        rank_pass<K, 1>(keys, idx, npad, ltw, k, j, tid);
+        j >>= 1;
+        left -= 1;
+      }
+    }
+  __syncthreads();
+  for (int e = tid; e < (N << ltw); e += RK_THREADS) {
+    const int c = e & cmask, s = e >> ltw;
+    const long long col = col0 + c;
+    if (col >= cols) continue;
+    if (keys[((N - 1) << ltw) + c] == pad) {                   // a NaN in the column: positions below N may hold padding
+      ranks[(long long)s * cols + col] = __builtin_nanf("");
+      continue;
+    }
+    const K key = keys[e];
+    int lo = s, hi = s + 1;
+    if (s > 0 && keys[e - tw] == key) {                        // the first position of the run, in [0, s)
+      int a = 0, b = s - 1;
+      while (a < b) {
+        const int m = (a + b) >> 1;
+        if (keys[(m << ltw) + c] < key) a = m + 1; else b = m;
+      }
+      lo = a;
+    }
+    if (hi < N && keys[e + tw] == key) {                       // one past its last position, in (s + 1, N]
+      int a = s + 2, b = N;
+      while (a < b) {
+        const int m = (a + b) >> 1;
+        if (keys[(m << ltw) + c] <= key) a = m + 1; else b = m;
+      }
+      hi = a;
+    }
+    ranks[(long long)idx[e] * cols + col] = 0.5f * (float)(lo + hi + 1);
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -422,6 +641,66 @@ extern "C" int tl_anova_finalize(const double* sum, const double* sumsq, const i
   hipLaunchKernelGGL(anova_finalize_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, sum, sumsq, cnt, k, splits,
                      (long long)cols, N, F, p);
   return check_launch("anova_finalize");
+}
+
+extern "C" int tl_kruskal_finalize(const double* sum, const double* sumsq, const int32_t* counts, int k, int splits, int64_t cols,
+                                   double* H, double* p, void* stream) {
+  TL_REQUIRE(sum && sumsq && counts && H && p, "kruskal_finalize: null pointer");
+  TL_REQUIRE(k >= 2 && k <= 64, "kruskal_finalize: the number of groups k must lie in [2, 64]");
+  TL_REQUIRE(cols >= 1, "kruskal_finalize: cols must be at least 1");
+  TL_REQUIRE(splits >= 1 && splits <= 1024, "kruskal_finalize: splits must lie in [1, 1024]");
+  const long long blocks = (cols + 255) / 256;
+  TL_REQUIRE(blocks <= 0x7fffffffLL, "kruskal_finalize: too many columns");
+  AnovaCounts cnt = {};
+  long long N = 0;
+  for (int g = 0; g < k; ++g) {
+    TL_REQUIRE(counts[g] >= 1, "kruskal_finalize: every group needs at least one sample");
+    cnt.n[g] = counts[g];
+    N += counts[g];
+  }
+  hipLaunchKernelGGL(kruskal_finalize_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, sum, sumsq, cnt, k, splits,
+                     (long long)cols, N, H, p);
+  return check_launch("kruskal_finalize");
+}
+
+extern "C" int tl_rank_columns(const void* x0, int64_t n0, const void* x1, int64_t n1, int is_f64, int64_t cols, float* ranks,
+                               void* stream) {
+  TL_REQUIRE(x0 && ranks, "rank_columns: null pointer");
+  TL_REQUIRE(n0 >= 1 && n1 >= 0 && (x1 || n1 == 0), "rank_columns: n0 must be at least 1, and n1 zero unless x1 is given");
+  TL_REQUIRE(cols >= 1, "rank_columns: cols must be at least 1");
+  TL_REQUIRE(n0 <= RK_MAX_N && n1 <= RK_MAX_N && n0 + n1 <= RK_MAX_N, "rank_columns: at most %d samples n0 + n1 (got %lld and %lld)",
+             RK_MAX_N, (long long)n0, (long long)n1);
+  const int N = (int)(n0 + n1);
+  int npad = 2, ltw = 0;
+  while (npad < N) npad <<= 1;
+  const size_t per = (size_t)npad * (is_f64 ? 10 : 6);         // bytes of one column: keys and 16-bit sample indices
+  while ((1 << ltw) < RK_MAX_TW && (per << (ltw + 1)) <= RK_TILE_BYTES) ++ltw;
+  const long long blocks = (cols + (1 << ltw) - 1) >> ltw;
+  TL_REQUIRE(blocks <= 0x7fffffffLL, "rank_columns: too many columns");
+  const size_t lds = per << ltw;
+  const void* fn = is_f64 ? reinterpret_cast<const void*>(rank_columns_kernel<double, uint64_t>)
+                          : reinterpret_cast<const void*>(rank_columns_kernel<float, uint32_t>);
+  if (lds > 64 * 1024) {      // more than 64 KB of the CU's 160 KB: raise the per-block limit once
+    static thread_local int raised_on[2] = {-1, -1};
+    int devid = 0;
+    (void)hipGetDevice(&devid);
+    if (raised_on[is_f64 != 0] != devid) {
+      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, RK_LDS_BYTES);
+      if (e != hipSuccess) {
+        set_error("rank_columns: cannot raise the dynamic LDS limit for %d samples: %s", N, hipGetErrorString(e));
+        return TL_ELAUNCH;
+      }
+      raised_on[is_f64 != 0] = devid;
+    }
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (is_f64)
+    hipLaunchKernelGGL((rank_columns_kernel<double, uint64_t>), dim3((unsigned)blocks), dim3(RK_THREADS), lds, st, (const double*)x0,
+                       (long long)n0, (const double*)x1, N, (long long)cols, npad, ltw, ranks);
+  else
+    hipLaunchKernelGGL((rank_columns_kernel<float, uint32_t>), dim3((unsigned)blocks), dim3(RK_THREADS), lds, st, (const float*)x0,
+                       (long long)n0, (const float*)x1, N, (long long)cols, npad, ltw, ranks);
+  return check_launch("rank_columns");
 }
 
 extern "C" int tl_max_run_below(const double* p, int C, int64_t T, double thr, int32_t* count, int32_t* maxrun, void* stream) {

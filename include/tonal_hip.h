@@ -860,6 +860,25 @@ int tl_perm_exceed(const void* x0, int64_t n0, const void* x1, int64_t n1, int i
 /* per row of a byte mask (rows, T), e.g. exceed above read as (P * C, T): maxrun[row] = the longest run of consecutive
  * non-zero cells (0 if none); one wave per row, 64 cells a step.  maxrun is (rows) int32                                  */
 int tl_perm_runs(const uint8_t* mask, int64_t rows, int64_t T, int32_t* maxrun, void* stream);
+/* rank form of the same test (Kruskal-Wallis, scipy.stats.kruskal along axis 0): midranks down the sample axis.  Sample i is
+ * row i of x0 (n0, cols) for i < n0, else row i - n0 of x1 (n1, cols); x1 may be null with n1 = 0.  x0 and x1 share one dtype
+ * (is_f64).  ranks (n0 + n1, cols) float32:  ranks[i][col] = scipy.stats.rankdata(column col, method='average')[i], bit for bit
+ * (a midrank is a multiple of 0.5, exact in float32; tl_group_moments and tl_perm_exceed take the array as float32 input).
+ * Values are ranked on their own bits, float64 on float64; -0.0 and +0.0 tie; +-inf rank as values; a column that holds a
+ * NaN gets NaN in every row.  One block sorts a tile of consecutive columns in LDS (bitonic network on order-preserving keys
+ * with 16-bit sample indices, padded to a power of two); the tile is the largest power of two of at most 64 columns for which
+ * npad * columns * (4 or 8 key bytes + 2) <= 40 KiB, npad = max(2, n0 + n1 rounded up to a power of two), and one column where
+ * a column alone takes more (up to 80 KiB).  TL_EINVAL, before
+ * any launch, on a null pointer, n0 < 1, n1 < 0 or n1 > 0 without x1, cols < 1, n0 + n1 > 8192, or more than 2^31 - 1 tiles  */
+int tl_rank_columns(const void* x0, int64_t n0, const void* x1, int64_t n1, int is_f64, int64_t cols, float* ranks,
+                    void* stream);
+/* Kruskal-Wallis H and p from the sums of k groups of MIDRANKS: sum / sumsq / counts / splits as for tl_anova_finalize.
+ * H = (N - 1) ssb / (ssb + ssw) - the statistic with its tie correction - and p = Q((k - 1)/2, H/2), the chi-square tail with
+ * k - 1 degrees of freedom, evaluated on the device in float64 (series of P below a + 1, continued fraction of Q above;
+ * the power part of the prefactor in log space).  NaN in -> NaN; ssb + ssw = 0 (every value of the column identical, where
+ * scipy raises) -> H = p = NaN.  2 <= k <= 64                                                                            */
+int tl_kruskal_finalize(const double* sum, const double* sumsq, const int32_t* counts, int k, int splits, int64_t cols,
+                        double* H, double* p, void* stream);
 
 /* ---- mel-spectrogram targets of a batch of trials (utils/audio.py audio_to_mel, one trial at a time on the host):
  * STFT -> |X|^power -> mel bank -> dB, two launches, fp64 throughout, float32 at the final store.
