@@ -181,6 +181,7 @@ SIGNATURES = {
     "tl_mel_finish": (_I, [_P, _P, _P, _I, _I, _L, _I, _P]),
     "tl_welch_psd": (_I, [_P, _I, _L, _P, _P, _P, _L, _P, _I, _L, _I, _I, _I, _I, _D, _L, _I, _P]),
     "tl_segment_moments": (_I, [_P, _I, _L, _P, _P, _I, _L, _L, _L, _L, _P]),
+    "tl_yin_f0": (_I, [_P, _I, _L, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _I, _I, _D, _D, _L, _P]),
     "tl_mel_invert": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _L, _I, _D, _I, _P]),
     "tl_gl_synth": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _L, _P]),
     "tl_gl_analyse": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _L, _D, _I, _P]),

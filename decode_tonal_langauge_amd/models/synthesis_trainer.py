@@ -51,6 +51,22 @@ _LSTM_LOCAL = ("label_lstm.weight_ih_l0", "label_lstm.bias_ih_l0", "label_lstm.b
 _EARLY = ("output_layer.weight", "output_layer.bias")       # final before the convolution backward starts (on_grad_ready)
 
 
+def tone_dynamics_table(tone_dynamic_mapping: Dict[str, List[float]]):
+    """(table, L, n_rows): row t of the float32 host table is ``mapping[str(t)]``, NaN where a tone below the largest key has
+    no entry.  Every entry must have the same length L."""
+    keys = sorted(int(k) for k in tone_dynamic_mapping)
+    lens = {len(v) for v in tone_dynamic_mapping.values()}
+    if len(lens) != 1:
+        raise ValueError("every entry of tone_dynamic_mapping must have the same length")
+    L = lens.pop()
+    n_rows = (max(keys) + 1) if keys else 0
+    table = torch.full((max(n_rows, 1), L), float("nan"))
+    for k in keys:
+        if k >= 0:
+            table[k] = torch.tensor(tone_dynamic_mapping[str(k)], dtype=torch.float32)
+    return table, L, n_rows
+
+
 class SynthesisTrainer:
     def __init__(self, synthesize_model: SynthesisModel, tone_model: ClassifierModel, syllable_model: ClassifierModel,
                  tone_dynamic_mapping: Dict[str, List[int]], device: torch.device = torch.device("cpu"),
@@ -78,17 +94,7 @@ class SynthesisTrainer:
             for nm, m in (("tone", self.tone_model), ("syllable", self.syllable_model)):
                 n = sum(p.numel() for p in m.parameters() if p.requires_grad)
                 print(f"Number of trainable parameters in the {nm} model: {n:,}")
-        # tone dynamics table: row t = mapping[str(t)]
-        keys = sorted(int(k) for k in tone_dynamic_mapping)
-        lens = {len(v) for v in tone_dynamic_mapping.values()}
-        if len(lens) != 1:
-            raise ValueError("every entry of tone_dynamic_mapping must have the same length")
-        self._L = lens.pop()
-        self._n_rows = (max(keys) + 1) if keys else 0
-        table = torch.full((max(self._n_rows, 1), self._L), float("nan"))
-        for k in keys:
-            if k >= 0:
-                table[k] = torch.tensor(tone_dynamic_mapping[str(k)], dtype=torch.float32)
+        table, self._L, self._n_rows = tone_dynamics_table(tone_dynamic_mapping)
         self._table_host = table
         n_cls = getattr(self.tone_model, "n_classes", None)
         self._need_check = n_cls is None or any(str(t) not in tone_dynamic_mapping for t in range(n_cls))

@@ -17,6 +17,8 @@ librosa calls of the reference restated with NumPy / SciPy);
 ``--ensemble`` (YAML: ``ensemble: true``; off by default) trains the ``--repeat`` SynthesisLite models side by side in one
 pass (``models/synthesis_ensemble_trainer.py``): every member gets the bits the sequential loop gives it.  It implies the
 resident dataset and needs ``--synthesis_model_name SynthesisLite``, both classifier checkpoints, a CUDA device, one process.
+``--f0_metrics`` (YAML: ``f0_metrics: true``; off by default; needs ``--audio_dir``) tracks F0 on the waveforms written there,
+originals and reconstructions in one ``yin_f0_batch`` call, and writes ``f0_metrics.json`` and ``f0_tracks.npz`` beside them.
 Output: one CSV row per run with the reference's columns (:369-385).
 """
 from __future__ import annotations
@@ -74,6 +76,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--ensemble', action='store_true',
                    help="train all --repeat SynthesisLite models in one pass (models/synthesis_ensemble_trainer.py); implies "
                         "--resident; needs both classifier checkpoints, a CUDA device and a single process")
+    p.add_argument('--f0_metrics', action='store_true',
+                   help="compare the F0 contours of the original and the synthesised waveforms of --audio_dir (utils/audio.py "
+                        "yin_f0_batch, utils/metrics.py compute_f0_metrics); writes f0_metrics.json and f0_tracks.npz there")
     return p
 
 
@@ -124,10 +129,50 @@ def check_ensemble(params: Namespace) -> bool:
     return True
 
 
+#: the F0 range of ``--f0_metrics``, Hz: below the lowest male and above the highest female speaking pitch
+F0_FMIN, F0_FMAX = 60.0, 500.0
+
+
+def check_f0_metrics(params: Namespace) -> bool:
+    """Is ``--f0_metrics`` asked for?  Raises ``ValueError`` naming the flag where there is no ``--audio_dir`` to work in."""
+    if not bool(getattr(params, 'f0_metrics', False)):
+        return False
+    if not getattr(params, 'audio_dir', None):
+        raise ValueError("--f0_metrics needs --audio_dir: it tracks F0 on the waveforms written there")
+    return True
+
+
+def write_f0_metrics(waves: np.ndarray, n_audio: int, params: Namespace, mel_kwargs: dict) -> Optional[dict]:
+    """F0 of the (2 n_audio, samples) waveforms - rows [0, n_audio) the originals, the rest the reconstructions, both out of
+    the same mel inversion, so what differs is the model's - on the frames of the mel front end (``n_fft``, ``hop_length``),
+    60 - 500 Hz; ``compute_f0_metrics`` of the two halves -> ``f0_metrics.json``, the tracks -> ``f0_tracks.npz`` (rows as
+    ``waves``).  On a CUDA device one ``yin_f0_batch`` call, on 'cpu' ``yin_f0`` clip by clip."""
+    from .utils.audio import F0Track, yin_f0, yin_f0_batch
+    from .utils.metrics import compute_f0_metrics
+    if n_audio < 1 or waves.shape[1] < 1:
+        print("f0_metrics: no waveform to track (no audio sample, or mel spectrograms of a single frame)")
+        return None
+    sr = float(params.audio_sampling_rate)
+    kw = dict(frame_length=int(mel_kwargs.get("n_fft", 2048)), hop_length=mel_kwargs.get("hop_length"))
+    if 'cuda' in str(params.device):
+        track = yin_f0_batch(waves, sr, F0_FMIN, F0_FMAX, device=params.device, **kw)
+    else:
+        track = F0Track(*(np.stack(col) for col in zip(*(yin_f0(w, sr, F0_FMIN, F0_FMAX, **kw) for w in waves))))
+    metrics = compute_f0_metrics(F0Track(*(t[:n_audio] for t in track)), F0Track(*(t[n_audio:] for t in track)))
+    np.savez(os.path.join(params.audio_dir, 'f0_tracks.npz'), **track._asdict())
+    with open(os.path.join(params.audio_dir, 'f0_metrics.json'), 'w') as f:
+        json.dump(metrics, f, indent=1)
+    print(f"F0 of the synthesised against the original waveforms ({metrics['n_voiced']} frames voiced in both): "
+          f"RMSE {metrics['f0_rmse_cents']:.1f} cents, correlation {metrics['f0_corr']:.3f}, "
+          f"gross pitch error {metrics['gross_pitch_error']:.3f}, voicing error {metrics['voicing_error']:.3f}")
+    return metrics
+
+
 def train(params: Namespace) -> dict:
     """Body of the reference script (:137-400) on the MI355X trainer.  Returns the result row."""
     if not os.path.exists(params.sample_path):
         raise FileNotFoundError(f"Data file '{params.sample_path}' does not exist.")
+    f0_metrics = check_f0_metrics(params)
     ensemble = check_ensemble(params)
     # data parallel: one process per GPU under torchrun (RANK / LOCAL_RANK / WORLD_SIZE).  The process group
     # is created before any GPU call; rank r trains on cuda:LOCAL_RANK, every rank sees the same loaders
@@ -289,15 +334,21 @@ def train(params: Namespace) -> dict:
                                    np.asarray(recon_mels[:n_audio]).reshape(n_audio, -1)])
             waves = mel_to_audio_batch(both, mel_kwargs['n_mels'], audio_sampling_rate=params.audio_sampling_rate,
                                        device=params.device, **stft_kw)
+        host_waves = [[], []]
         for i in range(n_audio):
             for k, (tag, mel) in enumerate((("origin", origin_mels[i]), ("recon", recon_mels[i]))):
                 wave = waves[k * n_audio + i] if waves is not None else \
                     mel_to_audio(np.asarray(mel), mel_kwargs['n_mels'], audio_sampling_rate=params.audio_sampling_rate, **stft_kw)
+                host_waves[k].append(wave)
                 if wave.size == 0:          # a single mel frame inverts to zero samples (centred STFT)
                     continue
                 path = os.path.join(params.audio_dir, f'{tag}_audio_{i}.wav')
                 write_wave(path, int(params.audio_sampling_rate), wave)
                 print(f"Saved {tag} audio to ", path)
+        if f0_metrics:
+            if waves is None:
+                waves = np.array(host_waves[0] + host_waves[1]).reshape(2 * n_audio, -1) if n_audio else np.zeros((0, 0))
+            write_f0_metrics(np.asarray(waves), n_audio, params, mel_kwargs)
     return results
 
 

@@ -21,7 +21,7 @@ synthesis trainer consumes its output (mel targets), nothing here runs per train
 from __future__ import annotations
 
 import functools
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 from scipy.optimize import nnls
@@ -577,3 +577,163 @@ def mel_to_audio_batch(mels, n_mels: int, audio_sampling_rate: int = 24414, mel_
     mag = mel_invert_batch(p, audio_sampling_rate, n_fft, n_mels, fmin=fmin, fmax=fmax, nnls_iter=nnls_iter, power=int(power))
     wave = griffinlim_batch(mag, n_iter=n_iter, hop_length=hop, win_length=wl, seed=seed, length=length).float()
     return wave if is_tensor else wave.cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------ F0 tracking (YIN)
+# librosa 0.10's ``yin`` restated, like the mel functions above: de Cheveigne & Kawahara's difference function, its
+# cumulative-mean normalisation, the first trough below a threshold (else the global minimum) and a parabolic refinement.
+# The difference function is the direct sum of squared differences - not librosa's E(0) + E(tau) - 2 r(tau) from an FFT
+# autocorrelation, which cancels exactly at the period of a voiced frame - so the host path and ``tl_yin_f0`` state the same
+# arithmetic and every term of every sum is non-negative.
+#: the longest frame ``tl_yin_f0`` keeps in LDS (YIN_MAX_FRAME of csrc/tonal_pitch.hip)
+YIN_MAX_FRAME = 4096
+
+
+class F0Track(NamedTuple):
+    """Per frame: ``f0`` in Hz, ``aperiodicity`` (the CMND value at the pick; small = periodic), ``period_index`` (the pick,
+    counted from ``min_period``) and ``rms`` of the frame's first ``win_length`` samples."""
+    f0: object
+    aperiodicity: object
+    period_index: object
+    rms: object
+
+
+class F0TrackCmnd(NamedTuple):
+    """``F0Track`` plus ``cmnd`` (..., n_frames, max_period - min_period + 1): the whole normalised difference curve."""
+    f0: object
+    aperiodicity: object
+    period_index: object
+    rms: object
+    cmnd: object
+
+
+def yin_geometry(sr: float, fmin: float, fmax: float, frame_length: int = 2048, win_length: Optional[int] = None,
+                 hop_length: Optional[int] = None):
+    """(frame_length, win_length, hop, min_period, max_period) as ``yin_f0`` and ``yin_f0_batch`` derive them."""
+    frame_length = int(frame_length)
+    wl = frame_length // 2 if win_length is None else int(win_length)
+    hop = frame_length // 4 if hop_length is None else int(hop_length)
+    if not sr > 0:
+        raise ValueError(f"sr = {sr} must be positive")
+    if not 0 < fmin < fmax:
+        raise ValueError(f"0 < fmin < fmax is required (got fmin = {fmin}, fmax = {fmax})")
+    if not 1 <= wl < frame_length:
+        raise ValueError(f"win_length = {wl} must lie in [1, frame_length = {frame_length})")
+    if hop < 1:
+        raise ValueError(f"hop_length = {hop} must be at least 1")
+    min_period = max(int(np.floor(sr / fmax)), 1)
+    max_period = min(int(np.ceil(sr / fmin)), frame_length - wl - 1)
+    if max_period < min_period + 1:
+        raise ValueError(f"fmin = {fmin}, fmax = {fmax} at sr = {sr} give the periods [{min_period}, {max_period}] for "
+                         f"frame_length = {frame_length}, win_length = {wl}: at least two lags are needed")
+    return frame_length, wl, hop, min_period, max_period
+
+
+def yin_n_frames(S: int, frame_length: int, hop: int, center: bool) -> int:
+    if center:
+        return 1 + S // hop
+    if S < frame_length:
+        raise ValueError(f"audio of {S} samples is shorter than frame_length = {frame_length}")
+    return 1 + (S - frame_length) // hop
+
+
+def yin_f0(y, sr: float, fmin: float, fmax: float, frame_length: int = 2048, win_length: Optional[int] = None,
+           hop_length: Optional[int] = None, trough_threshold: float = 0.1, center: bool = True, return_cmnd: bool = False):
+    """F0 track of one clip on the host, NumPy float64: the meaning of ``librosa.yin(y, fmin=, fmax=, sr=, frame_length=,
+    win_length=, hop_length=, trough_threshold=, center=, pad_mode='constant')`` with the difference function as a direct sum.
+    Returns ``F0Track`` of (n_frames,) arrays (``F0TrackCmnd`` with ``return_cmnd``).  ``yin_f0_batch`` is the same on the GPU."""
+    y = np.asarray(y, dtype=np.float64)
+    if y.ndim != 1:
+        raise ValueError("Audio input must be a 1D array.")
+    if y.shape[0] < 1:
+        raise ValueError("Audio input holds no sample.")
+    frame_length, W, hop, pmin, pmax = yin_geometry(sr, fmin, fmax, frame_length, win_length, hop_length)
+    if not trough_threshold > 0:
+        raise ValueError(f"trough_threshold = {trough_threshold} must be positive")
+    n_frames = yin_n_frames(y.shape[0], frame_length, hop, center)
+    if center:
+        y = np.pad(y, frame_length // 2, mode="constant")
+    if y.shape[0] < (n_frames - 1) * hop + frame_length:              # a short clip: the frames past its padding read zeros
+        y = np.pad(y, (0, (n_frames - 1) * hop + frame_length - y.shape[0]), mode="constant")
+    nc = pmax - pmin + 1
+    f0, aper, rms = np.empty(n_frames), np.empty(n_frames), np.empty(n_frames)
+    pidx = np.empty(n_frames, dtype=np.int32)
+    cmnd = np.empty((n_frames, nc))
+    tiny = np.finfo(np.float64).tiny
+    taus = np.arange(1, pmax + 1, dtype=np.float64)
+    for f in range(n_frames):
+        x = y[f * hop:f * hop + frame_length]
+        df = x[None, :W] - np.lib.stride_tricks.sliding_window_view(x[:W + pmax], W)          # (pmax + 1, W): row tau
+        d = np.sum(df * df, axis=1)
+        cm = np.cumsum(d[1:]) / taus
+        c = d[pmin:] / (cm[pmin - 1:] + tiny)
+        trough = np.zeros(nc, dtype=bool)
+        trough[0] = c[0] < c[1]
+        trough[1:-1] = (c[1:-1] < c[:-2]) & (c[1:-1] <= c[2:])
+        below = np.flatnonzero(trough & (c < trough_threshold))
+        i = int(below[0]) if below.size else int(np.argmin(c))
+        shift = 0.0
+        if 0 < i < nc - 1:
+            a = c[i + 1] + c[i - 1] - 2.0 * c[i]
+            b = (c[i + 1] - c[i - 1]) / 2.0
+            if abs(b) < abs(a):
+                shift = -b / a
+        f0[f] = sr / (pmin + i + shift)
+        aper[f], pidx[f], cmnd[f] = c[i], i, c
+        rms[f] = np.sqrt(np.mean(x[:W] ** 2))
+    return F0TrackCmnd(f0, aper, pidx, rms, cmnd) if return_cmnd else F0Track(f0, aper, pidx, rms)
+
+
+def yin_f0_batch(audio, sr: float, fmin: float, fmax: float, frame_length: int = 2048, win_length: Optional[int] = None,
+                 hop_length: Optional[int] = None, trough_threshold: float = 0.1, center: bool = True, device=None,
+                 return_cmnd: bool = False):
+    """``yin_f0`` of every row of an (N, S) batch in one kernel launch (``tl_yin_f0``, one workgroup per frame): row n of each
+    (N, n_frames) result is ``yin_f0(audio[n], ...)`` up to fp64 rounding of the sums.  float32 and float64 input is read as it
+    is (float32 widened in registers), anything else becomes float64; a CUDA tensor is read in place, also a view whose rows
+    are strided (unit stride along the samples).  NumPy in -> NumPy out; CUDA tensor in -> CUDA tensors out on its device.
+    ``f0``, ``aperiodicity``, ``rms`` (and ``cmnd`` with ``return_cmnd``) are float64, ``period_index`` int32.
+    ``frame_length`` at most ``YIN_MAX_FRAME``.  No CPU fallback: on the host call ``yin_f0`` per clip."""
+    import torch
+    from .. import _lib
+    is_tensor = isinstance(audio, torch.Tensor)
+    if not is_tensor:
+        audio = np.asarray(audio)
+    if audio.ndim != 2:
+        raise ValueError("Audio input must be a 2D array (clips, samples).")
+    frame_length, W, hop, pmin, pmax = yin_geometry(sr, fmin, fmax, frame_length, win_length, hop_length)
+    if frame_length > YIN_MAX_FRAME:
+        raise ValueError(f"frame_length = {frame_length} is not supported on the GPU (at most {YIN_MAX_FRAME})")
+    if not trough_threshold > 0:
+        raise ValueError(f"trough_threshold = {trough_threshold} must be positive")
+    N, S = int(audio.shape[0]), int(audio.shape[1])
+    if N < 1 or S < 1:
+        raise ValueError("Audio input holds no clip or no sample.")
+    n_frames = yin_n_frames(S, frame_length, hop, bool(center))
+    if is_tensor:
+        _lib.require_gpu(audio, "yin_f0_batch")
+        x = audio if audio.dtype in (torch.float32, torch.float64) else audio.double()
+        if x.stride(1) != 1 or (N > 1 and x.stride(0) < S):
+            x = x.contiguous()
+    else:
+        if not torch.cuda.is_available():
+            raise RuntimeError("yin_f0_batch (MI355X build): no GPU visible; this package has no CPU fallback")
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError(f"yin_f0_batch: device '{dev}' is not a CUDA device; this package has no CPU fallback")
+        if audio.dtype not in (np.float32, np.float64):
+            audio = audio.astype(np.float64)
+        x = torch.from_numpy(np.array(audio, order="C")).to(dev)
+    dev = x.device
+    f0 = torch.empty(N, n_frames, dtype=torch.float64, device=dev)
+    aper, rms = torch.empty_like(f0), torch.empty_like(f0)
+    pidx = torch.empty(N, n_frames, dtype=torch.int32, device=dev)
+    cmnd = torch.empty(N, n_frames, pmax - pmin + 1, dtype=torch.float64, device=dev) if return_cmnd else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().tl_yin_f0(x.data_ptr(), int(x.dtype == torch.float64), x.stride(0) if N > 1 else S,
+                                         f0.data_ptr(), aper.data_ptr(), pidx.data_ptr(), rms.data_ptr(), _lib.ptr(cmnd), N, S,
+                                         frame_length, W, hop, int(bool(center)), pmin, pmax, float(trough_threshold),
+                                         float(sr), n_frames, _lib.stream_ptr()), "tl_yin_f0")
+    out = (f0, aper, pidx, rms) + ((cmnd,) if return_cmnd else ())
+    if not is_tensor:
+        out = tuple(t.cpu().numpy() for t in out)
+    return F0TrackCmnd(*out) if return_cmnd else F0Track(*out)

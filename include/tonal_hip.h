@@ -948,6 +948,28 @@ int tl_gl_analyse(const double* frames, const double* wsum, const double* window
 int tl_gl_overlap_add(const double* frames, const double* wsum, double* out, int N, int n_fft, int win_length, int hop,
                       int64_t n_frames, int64_t length, void* stream);
 
+/* ---- F0 tracking of a batch of clips (utils/audio.py yin_f0, one clip at a time on the host): the YIN estimator with the
+ * steps of librosa 0.10's yin(pad_mode='constant'), one workgroup per frame, fp64 throughout, no atomics (two runs give the
+ * same bits), one launch.
+ *
+ * audio is (N, S) float32 or float64 (audio_is_f64) with row_stride elements between clips, read in place.  Frame f of a clip
+ * covers the samples f*hop - (center ? frame_length/2 : 0) + [0, frame_length); samples outside [0, S) read as zero (no padded
+ * copy).  Per frame x, with W = win_length, pmin = min_period, pmax = max_period:
+ *   d[tau]  = sum_{j<W} (x[j] - x[j+tau])^2, tau <= pmax, as a direct sum (never E(0) + E(tau) - 2 r(tau), which cancels where
+ *             d -> 0);  cm[tau] = (d[1] + ... + d[tau]) / tau;  c[i] = d[pmin+i] / (cm[pmin+i] + DBL_MIN), i <= pmax - pmin;
+ *   troughs: i = 0 iff c[0] < c[1]; interior i iff c[i] < c[i-1] && c[i] <= c[i+1]; the last index never;
+ *   pick i  = the first trough with c[i] < threshold, else the lowest index of the global minimum;
+ *   shift   = -b / a with a = c[i+1] + c[i-1] - 2 c[i], b = (c[i+1] - c[i-1]) / 2 when i is interior and |b| < |a|, else 0.
+ * Writes, each (N, n_frames): f0 = sr / (pmin + i + shift) and aperiodicity = c[i] (float64), period_index = i (int32),
+ * rms = sqrt(mean(x[0:W]^2)) (float64); and, where cmnd is not null, the whole curve c as (N, n_frames, pmax - pmin + 1)
+ * float64.  TL_EINVAL, before any GPU call, on a null required pointer, N < 1, S < 1, win_length outside
+ * [1, frame_length), frame_length > 4096, hop < 1, min_period < 1, max_period outside [min_period + 1, frame_length -
+ * win_length - 1], threshold <= 0, sr <= 0, S < frame_length with center = 0, n_frames != 1 + S / hop (center) resp.
+ * 1 + (S - frame_length) / hop, row_stride < S with N > 1, or more than 2^31 - 1 frames                                   */
+int tl_yin_f0(const void* audio, int audio_is_f64, int64_t row_stride, double* f0, double* aperiodicity,
+              int32_t* period_index, double* rms, double* cmnd, int N, int64_t S, int frame_length, int win_length, int hop,
+              int center, int min_period, int max_period, double threshold, double sr, int64_t n_frames, void* stream);
+
 /* FFT resampling = scipy.signal.resample(x, num, axis=1) (downsample.py:21-27): Bluestein chirp-z on
  * power-of-two FFTs.  Host-prepared coefficient arrays (complex128 interleaved): w1 (nx) / w2 (num)
  * chirps exp(i pi m^2 / n); bf1 (m2a) / bf2 (m2b) spectra of the chirp filters; tw1 (m2a/2) / tw2
