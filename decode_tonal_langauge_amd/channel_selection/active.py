@@ -16,7 +16,7 @@ from typing import Optional
 
 import numpy as np
 
-from .utils import anova_device, check_statistic, device_recording, kruskal_device, lookup, max_run_below
+from .utils import channels_by_run, check_statistic, device_recording, group_test, promote, rest_erp_inputs
 
 
 def run(data: dict, params: dict) -> dict:
@@ -30,34 +30,13 @@ def run(data: dict, params: dict) -> dict:
     One check goes beyond the reference: rest and ERP recordings with different numbers of timepoints raise a
     ``ValueError`` here (the reference fails later, inside scipy, on such a pair).  ``test: kruskal`` takes the p-values
     from the Kruskal-Wallis test; any value but ``anova`` / ``kruskal`` raises a ``ValueError``."""
+    what = "channel_selection.active"
     test = check_statistic(params.get('test', 'anova'), "test")
-    names = {"erp": params.get('erp_name', 'ecog'), "rest": params.get('rest_name', 'ecog_rest')}
-    if "ecog_sf" not in data:
-        raise ValueError("ECoG sampling frequency (ecog_sf) not found in the data.")
+    rest_name, erp_name, rest_samples, _ = rest_erp_inputs(data, params)
     length_threshold = int(params['active_time_threshold'] * data["ecog_sf"])
-    rest_samples = lookup(data, names["rest"], "Recording")
-    erp_samples = lookup(data, names["erp"], "Recording")
-    erp_channels, rest_channels = erp_samples.shape[1:2], rest_samples.shape[1:2]
-    if erp_channels != rest_channels:
-        raise ValueError(f"Shape mismatch between '{names['erp']}' and '{names['rest']}': {erp_channels} vs {rest_channels}.")
-    if erp_samples.shape[2:] != rest_samples.shape[2:]:
-        # beyond the reference, which fails inside scipy on such a pair: refused here before anything is uploaded
-        raise ValueError(f"'{names['erp']}' and '{names['rest']}' must have the same number of timepoints: "
-                         f"{erp_samples.shape[2:]} vs {rest_samples.shape[2:]}.")
     corrected_p_threshold = params['p_threshold'] / rest_samples.shape[2]          # Bonferroni
-    rest = device_recording(data, names["rest"], "channel_selection.active")
-    erp = device_recording(data, names["erp"], "channel_selection.active")
-    if rest.dtype != erp.dtype:
-        rest, erp = rest.double(), erp.double()
-    n_rest, n_erp = int(rest.shape[0]), int(erp.shape[0])
-    if test == "kruskal":
-        _, p = kruskal_device([rest, erp], [np.arange(n_rest, dtype=np.int32), np.arange(n_rest, n_rest + n_erp, dtype=np.int32)])
-    else:
-        _, p = anova_device([rest, erp], [np.arange(n_rest, dtype=np.int32), np.arange(n_erp, dtype=np.int32)])
-    count, longest = max_run_below(p, corrected_p_threshold)
-    count, longest = count.cpu().numpy(), longest.cpu().numpy()
-    active_channels = [int(ch) for ch in np.flatnonzero((count > 0) & (longest > length_threshold))]
-    max_lengths = [int(longest[ch]) for ch in active_channels]
+    _, p = group_test(test, promote([device_recording(data, rest_name, what), device_recording(data, erp_name, what)]))
+    active_channels, max_lengths = channels_by_run(p, corrected_p_threshold, length_threshold)
     print(f"Found {len(active_channels)} active channels.")
     return {"selected_channels": active_channels, "max_lengths": max_lengths, "p_values": p[-1].cpu().numpy()}
 

@@ -16,40 +16,23 @@ from typing import Dict, Mapping, Optional
 
 import numpy as np
 
-from .utils import anova_device, check_statistic, device_recording, kruskal_device, lookup, max_run_below
+from .utils import channels_by_run, check_statistic, device_recording, group_test, labelled_inputs
 
 
-def _anova_on_device(data: Mapping, params: dict):
-    """The reference's input checks (:122-164, same messages) and the test itself; returns (F, p) as (C, T) float64 CUDA
-    tensors - (H, p) with ``test: kruskal``."""
+def _test_on_device(data: Mapping, params: dict, need_sf: bool):
+    """The reference's input checks and the test itself; returns (F, p) as (C, T) float64 CUDA tensors - (H, p) with
+    ``test: kruskal``."""
     test = check_statistic(params.get('test', 'anova'), "test")
-    name = params.get('recording_name', 'ecog')
-    target = params['target']
-    series = lookup(data, name, "Recording")
-    if series.ndim != 3:
-        raise ValueError(f"Recording '{name}' must be a 3D array (n_samples, n_channels, n_timepoints).")
-    labels = np.asarray(lookup(data, target, "Labels")).squeeze()
-    if labels.ndim != 1:
-        raise ValueError(f"Labels '{target}' must be a 1D array (n_samples,) or 2D array with shape (1, n_samples)"
-                         " or (n_samples, 1).")
-    n_labels, n_samples = labels.shape[0], series.shape[0]
-    if n_labels != n_samples:
-        raise ValueError(f"Number of samples in '{target}' ({n_labels}) does not match number of samples in "
-                         f"'{name}' ({n_samples}).")
-    if not np.issubdtype(labels.dtype, np.integer):
-        raise ValueError(f"Labels for '{target}' must be integers.")
+    name, _, labels = labelled_inputs(data, params, need_sf)
     x = device_recording(data, name, "channel_selection.discriminative")
-    classes = [np.flatnonzero(labels == v).astype(np.int32) for v in np.unique(labels)]
-    if test == "kruskal":
-        return kruskal_device([x], classes)
-    return anova_device([x] * len(classes), classes)
+    return group_test(test, [x], [np.flatnonzero(labels == v).astype(np.int32) for v in np.unique(labels)])
 
 
 def test_discriminative_power(data: Mapping[str, np.ndarray], params: dict) -> Dict[str, np.ndarray]:
     """``{'f_stat', 'p_value'}``, both (n_channels, n_timepoints) float64 NumPy: the ANOVA of ``data[recording_name]``
     (n_samples, n_channels, n_timepoints) grouped by the integer labels ``data[target]``.  With ``test: kruskal`` the keys
     are ``{'h_stat', 'p_value'}``."""
-    F, p = _anova_on_device(data, params)
+    F, p = _test_on_device(data, params, need_sf=False)
     stat_key = 'h_stat' if params.get('test', 'anova') == "kruskal" else 'f_stat'
     return {stat_key: F.cpu().numpy(), 'p_value': p.cpu().numpy()}
 
@@ -63,15 +46,9 @@ def run(data: dict, params: dict) -> dict:
     an empty ``max_lengths`` list (as the reference returns it) and the p-values (n_channels, n_timepoints)."""
     p_threshold = params.get('p_threshold', 0.05)
     target = params['target']
-    sf_key = f"{params.get('recording_name', 'ecog')}_sf"
-    if sf_key not in data:
-        raise ValueError("ECoG sampling frequency (ecog_sf) not found in the data.")
-    ecog_sf = data[sf_key]
-    _, p = _anova_on_device(data, params)
-    length_threshold = int(params["active_time_threshold"] * ecog_sf)
-    count, longest = max_run_below(p, p_threshold / p.shape[1])          # Bonferroni, as find_significant_channels
-    count, longest = count.cpu().numpy(), longest.cpu().numpy()
-    significant_channels = [int(ch) for ch in np.flatnonzero((count > 0) & (longest > length_threshold))]
+    _, p = _test_on_device(data, params, need_sf=True)
+    length_threshold = int(params["active_time_threshold"] * data[f"{params.get('recording_name', 'ecog')}_sf"])
+    significant_channels, _ = channels_by_run(p, p_threshold / p.shape[1], length_threshold)       # Bonferroni
     print(f'Found {len(significant_channels)} discriminative channels'
           f' for target "{target}"')
     return {'selected_channels': significant_channels, 'max_lengths': [], 'p_values': p.cpu().numpy()}

@@ -7,7 +7,8 @@ channel``) or against the relabelling's maximum over all channels (``correction:
 
 With ``target`` in the parameters it is the labelled form and takes the keys of ``discriminative`` (``recording_name``,
 ``target``, ``p_threshold``); without, it is rest against ERP with the keys of ``active`` (``erp_name``, ``rest_name``,
-``p_threshold``).  Both run the input checks of their counterpart and raise its errors.  New keys: ``n_permutations`` (1000),
+``p_threshold``).  Both run the input checks of their counterpart (``utils.labelled_inputs``, ``utils.rest_erp_inputs``) and
+raise its errors.  New keys: ``n_permutations`` (1000),
 ``seed`` (0), ``alpha`` (0.05), ``correction`` (``max`` | ``channel``) and ``perm_chunk`` (relabellings per launch; the
 default bounds the mask) and ``test`` (``anova`` | ``kruskal``: the statistic at every cell; the rank form ranks the samples once,
 ``tl_rank_columns``, and relabels the ranks).  ``active_time_threshold`` is not used.  All relabellings are one float64 product on the device
@@ -16,11 +17,11 @@ from __future__ import annotations
 
 import os
 import warnings
-from typing import Mapping
 
 import numpy as np
 
-from .utils import check_statistic, device_recording, lookup, permutation_p_values, permutation_runs, permutation_table
+from .utils import (check_statistic, device_recording, labelled_inputs, permutation_p_values, permutation_runs, permutation_table,
+                    promote, rest_erp_inputs)
 
 _CORRECTIONS = ("max", "channel")
 
@@ -42,46 +43,6 @@ def _new_keys(params: dict, n_timepoints: int):
     return int(n_perm), int(params.get('seed', 0)), float(alpha), correction, params.get('perm_chunk'), float(cell)
 
 
-def _labelled_inputs(data: Mapping, params: dict):
-    """The checks of ``discriminative`` (same messages); returns ``(name, series, group index per sample)``."""
-    name = params.get('recording_name', 'ecog')
-    target = params['target']
-    if f"{name}_sf" not in data:
-        raise ValueError("ECoG sampling frequency (ecog_sf) not found in the data.")
-    series = lookup(data, name, "Recording")
-    if series.ndim != 3:
-        raise ValueError(f"Recording '{name}' must be a 3D array (n_samples, n_channels, n_timepoints).")
-    labels = np.asarray(lookup(data, target, "Labels")).squeeze()
-    if labels.ndim != 1:
-        raise ValueError(f"Labels '{target}' must be a 1D array (n_samples,) or 2D array with shape (1, n_samples)"
-                         " or (n_samples, 1).")
-    n_labels, n_samples = labels.shape[0], series.shape[0]
-    if n_labels != n_samples:
-        raise ValueError(f"Number of samples in '{target}' ({n_labels}) does not match number of samples in "
-                         f"'{name}' ({n_samples}).")
-    if not np.issubdtype(labels.dtype, np.integer):
-        raise ValueError(f"Labels for '{target}' must be integers.")
-    classes, group_index = np.unique(labels, return_inverse=True)
-    if not 2 <= len(classes) <= 64:
-        raise ValueError(f"Labels '{target}' must hold between 2 and 64 classes, got {len(classes)}.")
-    return name, series, group_index.astype(np.int64)
-
-
-def _rest_erp_inputs(data: Mapping, params: dict):
-    """The checks of ``active`` (same messages); returns ``(rest name, ERP name, rest, erp)``."""
-    erp_name, rest_name = params.get('erp_name', 'ecog'), params.get('rest_name', 'ecog_rest')
-    if "ecog_sf" not in data:
-        raise ValueError("ECoG sampling frequency (ecog_sf) not found in the data.")
-    rest = lookup(data, rest_name, "Recording")
-    erp = lookup(data, erp_name, "Recording")
-    if erp.shape[1:2] != rest.shape[1:2]:
-        raise ValueError(f"Shape mismatch between '{erp_name}' and '{rest_name}': {erp.shape[1:2]} vs {rest.shape[1:2]}.")
-    if erp.shape[2:] != rest.shape[2:]:
-        raise ValueError(f"'{erp_name}' and '{rest_name}' must have the same number of timepoints: "
-                         f"{erp.shape[2:]} vs {rest.shape[2:]}.")
-    return rest_name, erp_name, rest, erp
-
-
 def run(data: dict, params: dict) -> dict:
     """``{'selected_channels', 'max_lengths', 'p_values', 'null_max_lengths', 'f_crit'}``.  A channel is kept when its
     observed run of ``p < p_threshold / n_timepoints`` is longer than 0 and its permutation p-value is at most ``alpha``.
@@ -92,16 +53,16 @@ def run(data: dict, params: dict) -> dict:
     what = "channel_selection.permutation"
     test = check_statistic(params.get('test', 'anova'), "test")
     if 'target' in params:
-        name, series, group_index = _labelled_inputs(data, params)
+        name, series, labels = labelled_inputs(data, params)
+        classes, group_index = np.unique(labels, return_inverse=True)
+        if not 2 <= len(classes) <= 64:
+            raise ValueError(f"Labels '{params['target']}' must hold between 2 and 64 classes, got {len(classes)}.")
         n_perm, seed, alpha, correction, perm_chunk, cell = _new_keys(params, series.shape[2])
         arrays = [device_recording(data, name, what)]
     else:
-        rest_name, erp_name, rest, erp = _rest_erp_inputs(data, params)
+        rest_name, erp_name, rest, erp = rest_erp_inputs(data, params)
         n_perm, seed, alpha, correction, perm_chunk, cell = _new_keys(params, rest.shape[2])
-        rest_d, erp_d = device_recording(data, rest_name, what), device_recording(data, erp_name, what)
-        if rest_d.dtype != erp_d.dtype:
-            rest_d, erp_d = rest_d.double(), erp_d.double()
-        arrays = [rest_d, erp_d]
+        arrays = promote([device_recording(data, rest_name, what), device_recording(data, erp_name, what)])
         group_index = np.repeat(np.arange(2), [rest.shape[0], erp.shape[0]])
     counts = np.bincount(group_index).tolist()
     table = permutation_table(group_index, n_perm, seed)

@@ -4,12 +4,13 @@
 low-level entry to the kernels of ``csrc/tonal_anova.hip``: a one-way ANOVA (``scipy.stats.f_oneway`` along axis 0) at every
 trailing position of the samples, F and p computed on the device in float64.  ``max_run_below`` is the device form of
 ``get_max_length`` over the rows of a p-value array.  ``permutation_table`` / ``permutation_runs`` / ``permutation_p_values``
-are the label-permutation test of the longest significant run (``tl_perm_exceed``, ``tl_perm_runs``).  No CPU fallback:
-without a GPU the device entries raise."""
+are the label-permutation test of the longest significant run (``tl_perm_exceed``, ``tl_perm_runs``).  The input checks
+(``rest_erp_inputs``, ``labelled_inputs``), the dispatch on the ``test`` key (``group_test``) and the run rule
+(``channels_by_run``) that the selectors share live here too.  No CPU fallback: without a GPU the device entries raise."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence, Tuple
+from typing import Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -44,6 +45,50 @@ def lookup(data, key: str, kind: str):
     return data[key]
 
 
+# ---- the selectors' input checks: the reference's, with its messages ---------------------------------------------------
+_NO_SF = "ECoG sampling frequency (ecog_sf) not found in the data."
+
+
+def rest_erp_inputs(data: Mapping, params: dict):
+    """The checks of the rest-against-ERP form (reference active.py): ``(rest name, ERP name, rest, erp)``, the recordings
+    as ``data`` holds them.  One check goes beyond the reference, which fails inside scipy on such a pair: recordings with
+    different numbers of timepoints are refused here, before anything is uploaded."""
+    erp_name, rest_name = params.get('erp_name', 'ecog'), params.get('rest_name', 'ecog_rest')
+    if "ecog_sf" not in data:
+        raise ValueError(_NO_SF)
+    rest = lookup(data, rest_name, "Recording")
+    erp = lookup(data, erp_name, "Recording")
+    if erp.shape[1:2] != rest.shape[1:2]:
+        raise ValueError(f"Shape mismatch between '{erp_name}' and '{rest_name}': {erp.shape[1:2]} vs {rest.shape[1:2]}.")
+    if erp.shape[2:] != rest.shape[2:]:
+        raise ValueError(f"'{erp_name}' and '{rest_name}' must have the same number of timepoints: "
+                         f"{erp.shape[2:]} vs {rest.shape[2:]}.")
+    return rest_name, erp_name, rest, erp
+
+
+def labelled_inputs(data: Mapping, params: dict, need_sf: bool = True):
+    """The checks of the labelled form (reference discriminative.py:122-164): ``(recording name, recording, labels)`` with
+    the labels a 1D integer array, one per sample.  ``need_sf`` asks for the key ``<recording>_sf`` first."""
+    name = params.get('recording_name', 'ecog')
+    target = params['target']
+    if need_sf and f"{name}_sf" not in data:
+        raise ValueError(_NO_SF)
+    series = lookup(data, name, "Recording")
+    if series.ndim != 3:
+        raise ValueError(f"Recording '{name}' must be a 3D array (n_samples, n_channels, n_timepoints).")
+    labels = np.asarray(lookup(data, target, "Labels")).squeeze()
+    if labels.ndim != 1:
+        raise ValueError(f"Labels '{target}' must be a 1D array (n_samples,) or 2D array with shape (1, n_samples)"
+                         " or (n_samples, 1).")
+    n_labels, n_samples = labels.shape[0], series.shape[0]
+    if n_labels != n_samples:
+        raise ValueError(f"Number of samples in '{target}' ({n_labels}) does not match number of samples in "
+                         f"'{name}' ({n_samples}).")
+    if not np.issubdtype(labels.dtype, np.integer):
+        raise ValueError(f"Labels for '{target}' must be integers.")
+    return name, series, labels
+
+
 # ---- device side ---------------------------------------------------------------------------------------------------
 def to_device(a, what: str):
     """NumPy array -> CUDA tensor (uploaded, float32 / float64 kept, anything else becomes float64); CUDA tensor -> itself."""
@@ -64,76 +109,97 @@ def to_device(a, what: str):
     return t.contiguous()
 
 
+def device_recording(data, name: str, what: str):
+    """The recording ``data[name]`` on the GPU.  The stage hands the selectors a mapping with a ``device(name)`` method that
+    uploads a recording once per subject; a plain dict / NpzFile is uploaded here."""
+    getter = getattr(data, "device", None)
+    if callable(getter):
+        return getter(name)
+    return to_device(data[name], what)
+
+
+def promote(tensors: Sequence) -> list:
+    """The tensors as they are where their dtypes agree, all of them widened to float64 where not."""
+    tensors = list(tensors)
+    if len({t.dtype for t in tensors}) > 1:
+        tensors = [t.double() for t in tensors]
+    return tensors
+
+
+def _sample_arrays(arrays: Sequence, what: str, ndim: Optional[int] = None) -> list:
+    """One or two CUDA tensors whose samples follow each other, checked and made contiguous: one trailing shape, dtype
+    (float32 or float64) and device.  Any trailing shape passes; ``ndim=3`` asks for (n, C, T)."""
+    import torch
+    from .. import _lib
+    arrays = list(arrays)
+    if not 1 <= len(arrays) <= 2:
+        raise ValueError(f"{what}: one or two sample arrays")
+    x0 = arrays[0]
+    shape = "must share trailing shape" if ndim is None else "must be (n, C, T) of one trailing shape"
+    for a in arrays:
+        _lib.require_gpu(a, what)
+        bad_rank = a.dim() < 1 if ndim is None else a.dim() != ndim
+        if bad_rank or a.shape[1:] != x0.shape[1:] or a.dtype != x0.dtype or a.device != x0.device:
+            raise ValueError(f"{what}: arrays {shape}, dtype and device")
+    if x0.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"{what}: float32 or float64 samples")
+    return [a.contiguous() for a in arrays]
+
+
 def _splits(cols: int, n_min: int) -> int:
     return int(max(1, min(-(-_FILL_COLUMNS // cols), n_min, 1024)))
 
 
-def anova_device(arrays: Sequence, index_lists: Sequence[np.ndarray]):
-    """F and p (float64 CUDA tensors of the trailing shape) of the groups ``arrays[g][index_lists[g]]``.  ``arrays`` are
-    CUDA tensors (n_g_rows, ...) of one dtype and one trailing shape - the same tensor k times for a labelled recording."""
+def _group_counts(what: str, index_lists: Sequence[np.ndarray], trailing: Sequence[int] = ()) -> list:
+    """The sizes of between 2 and 64 groups of at least one sample each, in columns of a non-empty ``trailing`` shape."""
+    k = len(index_lists)
+    if not 2 <= k <= 64:
+        raise ValueError(f"{what}: needs between 2 and 64 groups, got {k}")
+    counts = [int(len(ix)) for ix in index_lists]
+    if min(counts) < 1 or not all(trailing):
+        raise ValueError(f"{what}: every group needs at least one sample and one column")
+    return counts
+
+
+def _group_test(finalize: str, arrays: Sequence, index_lists: Sequence[np.ndarray], counts: Sequence[int]):
+    """``(statistic, p)``, float64 CUDA tensors of the trailing shape: ``tl_group_moments`` once per group ``g`` over the rows
+    ``index_lists[g]`` (``counts[g]`` of them) of ``arrays[g]``, then the entry point ``finalize``.  ``arrays`` are contiguous
+    CUDA tensors (n_g_rows, ...) of one dtype, trailing shape and device."""
     import torch
     from .. import _lib
     from .._lib import check, ptr, stream_ptr
-    k = len(arrays)
-    if not 2 <= k <= 64:
-        raise ValueError(f"anova_oneway: needs between 2 and 64 groups, got {k}")
-    x0 = arrays[0]
+    x0, k = arrays[0], len(counts)
     trailing = tuple(x0.shape[1:])
     cols = int(np.prod(trailing, dtype=np.int64))
-    counts = [int(len(ix)) for ix in index_lists]
-    if min(counts) < 1 or cols < 1:
-        raise ValueError("anova_oneway: every group needs at least one sample and one column")
-    for a in arrays:
-        if tuple(a.shape[1:]) != trailing or a.dtype != x0.dtype or a.device != x0.device:
-            raise ValueError("anova_oneway: groups must share trailing shape, dtype and device")
     lib = _lib.load()
     splits = _splits(cols, min(counts))
     sums = torch.empty(2, k, splits, cols, dtype=torch.float64, device=x0.device)
     idx = torch.from_numpy(np.concatenate([np.asarray(ix, dtype=np.int32) for ix in index_lists])).to(x0.device)
     is_f64 = int(x0.dtype == torch.float64)
-    shift_row = int(index_lists[0][0])                 # one row of the data for every group: the sums share a frame
+    # one row of the first array for every group: the sums share a frame
+    shift = x0.data_ptr() + int(index_lists[0][0]) * cols * x0.element_size()
     off = 0
     with torch.cuda.device(x0.device):
         for g, a in enumerate(arrays):
-            check(lib.tl_group_moments(ptr(a), is_f64, a.shape[0], cols, idx.data_ptr() + 4 * off, counts[g],
-                                       x0.data_ptr() + shift_row * cols * x0.element_size(), splits,
+            check(lib.tl_group_moments(ptr(a), is_f64, a.shape[0], cols, idx.data_ptr() + 4 * off, counts[g], shift, splits,
                                        ptr(sums[0, g]), ptr(sums[1, g]), stream_ptr()), "tl_group_moments")
             off += counts[g]
         out = torch.empty(2, cols, dtype=torch.float64, device=x0.device)
         cnt = (C.c_int32 * k)(*counts)
-        check(lib.tl_anova_finalize(ptr(sums[0]), ptr(sums[1]), cnt, k, splits, cols, ptr(out[0]), ptr(out[1]),
-                                    stream_ptr()), "tl_anova_finalize")
+        check(getattr(lib, finalize)(ptr(sums[0]), ptr(sums[1]), cnt, k, splits, cols, ptr(out[0]), ptr(out[1]), stream_ptr()),
+              finalize)
     return out[0].reshape(trailing), out[1].reshape(trailing)
 
 
-def anova_oneway(groups_or_array, labels=None) -> Tuple:
-    """One-way ANOVA along axis 0 at every trailing position: ``(F, p)`` as ``scipy.stats.f_oneway`` defines them.
-
-    ``anova_oneway([g0, g1, ...])`` takes one array ``(n_g, ...)`` per group; ``anova_oneway(x, labels)`` takes one array
-    ``(n, ...)`` and an integer label per sample (groups in the order of ``np.unique(labels)``).  NumPy arrays are uploaded
-    and the result comes back as NumPy; CUDA tensors are used in place and the result stays on the device.  float32 input
-    is read as it is and widened in registers; every sum and the p-value are float64."""
-    import torch
-    if labels is None:
-        groups = list(groups_or_array)
-        on_device = all(isinstance(g, torch.Tensor) for g in groups)
-        dev = [to_device(g, "anova_oneway") for g in groups]
-        if len({d.dtype for d in dev}) > 1:
-            dev = [d.double() for d in dev]
-        index_lists = [np.arange(d.shape[0], dtype=np.int32) for d in dev]
-    else:
-        on_device = isinstance(groups_or_array, torch.Tensor)
-        x = to_device(groups_or_array, "anova_oneway")
-        lab = labels.detach().cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
-        lab = lab.squeeze()
-        if lab.ndim != 1 or lab.shape[0] != x.shape[0]:
-            raise ValueError(f"anova_oneway: {x.shape[0]} samples but labels of shape {lab.shape}")
-        index_lists = [np.flatnonzero(lab == v).astype(np.int32) for v in np.unique(lab)]
-        dev = [x] * len(index_lists)
-    F, p = anova_device(dev, index_lists)
-    if on_device:
-        return F, p
-    return F.cpu().numpy(), p.cpu().numpy()
+def anova_device(arrays: Sequence, index_lists: Sequence[np.ndarray]):
+    """F and p (float64 CUDA tensors of the trailing shape) of the groups ``arrays[g][index_lists[g]]``.  ``arrays`` are
+    CUDA tensors (n_g_rows, ...) of one dtype and one trailing shape - the same tensor k times for a labelled recording."""
+    counts = _group_counts("anova_oneway", index_lists, tuple(arrays[0].shape[1:]) if len(arrays) else ())
+    x0 = arrays[0]
+    for a in arrays:
+        if a.shape[1:] != x0.shape[1:] or a.dtype != x0.dtype or a.device != x0.device:
+            raise ValueError("anova_oneway: groups must share trailing shape, dtype and device")
+    return _group_test("tl_anova_finalize", arrays, index_lists, counts)
 
 
 # ---- rank form: Kruskal-Wallis ---------------------------------------------------------------------------------------
@@ -166,23 +232,14 @@ def rank_columns_device(arrays: Sequence):
     import torch
     from .. import _lib
     from .._lib import check, ptr, stream_ptr
-    arrays = list(arrays)
-    if not 1 <= len(arrays) <= 2:
-        raise ValueError("rank_columns: one or two sample arrays")
+    arrays = _sample_arrays(arrays, "rank_columns")
     x0 = arrays[0]
-    for a in arrays:
-        _lib.require_gpu(a, "rank_columns")
-        if a.dim() < 1 or a.shape[1:] != x0.shape[1:] or a.dtype != x0.dtype or a.device != x0.device:
-            raise ValueError("rank_columns: arrays must share trailing shape, dtype and device")
-    if x0.dtype not in (torch.float32, torch.float64):
-        raise ValueError("rank_columns: float32 or float64 samples")
     n0, n1 = int(x0.shape[0]), int(arrays[1].shape[0]) if len(arrays) == 2 else 0
     cols = int(np.prod(tuple(x0.shape[1:]), dtype=np.int64))
     if n0 < 1 or cols < 1 or (len(arrays) == 2 and n1 < 1):
         raise ValueError("rank_columns: every array needs at least one sample and one column")
     if n0 + n1 > RANK_MAX_SAMPLES:
         raise ValueError(f"rank_columns: at most {RANK_MAX_SAMPLES} samples (got {n0 + n1})")
-    arrays = [a.contiguous() for a in arrays]
     ranks = torch.empty((n0 + n1,) + tuple(x0.shape[1:]), dtype=torch.float32, device=x0.device)
     with torch.cuda.device(x0.device):
         check(_lib.load().tl_rank_columns(ptr(arrays[0]), n0, ptr(arrays[1]) if n1 else None, n1,
@@ -202,10 +259,7 @@ def rank_columns(x, x1=None):
     n = sum(int(a.shape[0]) for a in given)
     if n > RANK_MAX_SAMPLES:                                   # before anything is uploaded
         raise ValueError(f"rank_columns: at most {RANK_MAX_SAMPLES} samples (got {n})")
-    dev = [to_device(a, "rank_columns") for a in given]
-    if len({d.dtype for d in dev}) > 1:
-        dev = [d.double() for d in dev]
-    ranks = rank_columns_device(dev)
+    ranks = rank_columns_device(promote(to_device(a, "rank_columns") for a in given))
     return ranks if on_device else ranks.cpu().numpy()
 
 
@@ -213,39 +267,64 @@ def kruskal_device(arrays: Sequence, index_lists: Sequence[np.ndarray]):
     """H and p (float64 CUDA tensors of the trailing shape) of the Kruskal-Wallis test between the groups ``index_lists``:
     row numbers into the samples of ``arrays``, one CUDA tensor or two that follow each other.  Every sample belongs to
     exactly one group.  ``tl_rank_columns`` once, ``tl_group_moments`` per group on the ranks, ``tl_kruskal_finalize``."""
-    import torch
-    from .. import _lib
-    from .._lib import check, ptr, stream_ptr
-    k = len(index_lists)
-    if not 2 <= k <= 64:
-        raise ValueError(f"kruskal_oneway: needs between 2 and 64 groups, got {k}")
-    counts = [int(len(ix)) for ix in index_lists]
-    if min(counts) < 1:
-        raise ValueError("kruskal_oneway: every group needs at least one sample and one column")
+    counts = _group_counts("kruskal_oneway", index_lists)
     n = sum(int(a.shape[0]) for a in arrays)
     members = np.concatenate([np.asarray(ix, dtype=np.int64) for ix in index_lists])
     if members.size != n or not np.array_equal(np.sort(members), np.arange(n)):
         raise ValueError("kruskal_oneway: the groups must hold every sample exactly once")
-    ranks = rank_columns_device(arrays)
-    trailing = tuple(ranks.shape[1:])
-    cols = int(np.prod(trailing, dtype=np.int64))
-    lib = _lib.load()
-    splits = _splits(cols, min(counts))
-    sums = torch.empty(2, k, splits, cols, dtype=torch.float64, device=ranks.device)
-    idx = torch.from_numpy(members.astype(np.int32)).to(ranks.device)
-    shift_row = int(index_lists[0][0])                 # one row of the ranks for every group: the sums share a frame
-    off = 0
-    with torch.cuda.device(ranks.device):
-        for g in range(k):
-            check(lib.tl_group_moments(ptr(ranks), 0, n, cols, idx.data_ptr() + 4 * off, counts[g],
-                                       ranks.data_ptr() + shift_row * cols * 4, splits,
-                                       ptr(sums[0, g]), ptr(sums[1, g]), stream_ptr()), "tl_group_moments")
-            off += counts[g]
-        out = torch.empty(2, cols, dtype=torch.float64, device=ranks.device)
-        cnt = (C.c_int32 * k)(*counts)
-        check(lib.tl_kruskal_finalize(ptr(sums[0]), ptr(sums[1]), cnt, k, splits, cols, ptr(out[0]), ptr(out[1]),
-                                      stream_ptr()), "tl_kruskal_finalize")
-    return out[0].reshape(trailing), out[1].reshape(trailing)
+    return _group_test("tl_kruskal_finalize", [rank_columns_device(arrays)] * len(counts), index_lists, counts)
+
+
+def group_test(test: str, arrays: Sequence, classes: Optional[Sequence[np.ndarray]] = None):
+    """``(statistic, p)`` of ``test`` on the device: F of the ANOVA or H of the Kruskal-Wallis test, float64 CUDA tensors of
+    the trailing shape.  Without ``classes`` every CUDA tensor of ``arrays`` is one group (rest and ERP); with them ``arrays``
+    holds one tensor and ``classes`` the row numbers of each of its groups."""
+    import torch
+    arrays = list(arrays)
+    if classes is None:
+        sizes = [int(a.shape[0]) for a in arrays]
+        starts = np.cumsum([0] + sizes[:-1]) if test == "kruskal" else [0] * len(sizes)     # the ranks' rows count through
+        classes = [np.arange(s, s + n, dtype=np.int32) for s, n in zip(starts, sizes)]
+        if test == "kruskal" and len(arrays) > 2:
+            arrays = [torch.cat(arrays)]                   # the ranks are those of the pooled sample
+    elif test == "anova":
+        arrays = arrays * len(classes)
+    return (kruskal_device if test == "kruskal" else anova_device)(arrays, classes)
+
+
+def _oneway(test: str, groups_or_array, labels, limit: Optional[int] = None) -> Tuple:
+    """The two calling forms of ``anova_oneway`` / ``kruskal_oneway``: upload, common dtype, groups, test, and NumPy back
+    unless every sample array came as a tensor.  More than ``limit`` samples are refused before anything is uploaded."""
+    import torch
+    what = f"{test}_oneway"
+    given = list(groups_or_array) if labels is None else [groups_or_array]
+    on_device = all(isinstance(g, torch.Tensor) for g in given)
+    if limit is not None:
+        n = sum(int(g.shape[0]) for g in given)
+        if n > limit:
+            raise ValueError(f"{what}: at most {limit} samples (got {n})")
+    arrays = promote(to_device(g, what) for g in given)
+    classes = None
+    if labels is not None:
+        lab = labels.detach().cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+        lab = lab.squeeze()
+        if lab.ndim != 1 or lab.shape[0] != arrays[0].shape[0]:
+            raise ValueError(f"{what}: {arrays[0].shape[0]} samples but labels of shape {lab.shape}")
+        classes = [np.flatnonzero(lab == v).astype(np.int32) for v in np.unique(lab)]
+    stat, p = group_test(test, arrays, classes)
+    if on_device:
+        return stat, p
+    return stat.cpu().numpy(), p.cpu().numpy()
+
+
+def anova_oneway(groups_or_array, labels=None) -> Tuple:
+    """One-way ANOVA along axis 0 at every trailing position: ``(F, p)`` as ``scipy.stats.f_oneway`` defines them.
+
+    ``anova_oneway([g0, g1, ...])`` takes one array ``(n_g, ...)`` per group; ``anova_oneway(x, labels)`` takes one array
+    ``(n, ...)`` and an integer label per sample (groups in the order of ``np.unique(labels)``).  NumPy arrays are uploaded
+    and the result comes back as NumPy; CUDA tensors are used in place and the result stays on the device.  float32 input
+    is read as it is and widened in registers; every sum and the p-value are float64."""
+    return _oneway("anova", groups_or_array, labels)
 
 
 def kruskal_oneway(groups_or_array, labels=None) -> Tuple:
@@ -255,35 +334,7 @@ def kruskal_oneway(groups_or_array, labels=None) -> Tuple:
     The calling forms and return conventions of ``anova_oneway``: one array per group, or one array and a label per
     sample.  A column whose values are all identical gives NaN (scipy raises there), as does a column that holds a NaN.
     At most ``RANK_MAX_SAMPLES`` samples in all."""
-    import torch
-    if labels is None:
-        groups = list(groups_or_array)
-        on_device = all(isinstance(g, torch.Tensor) for g in groups)
-        sizes = [int(g.shape[0]) for g in groups]
-        if sum(sizes) > RANK_MAX_SAMPLES:
-            raise ValueError(f"kruskal_oneway: at most {RANK_MAX_SAMPLES} samples (got {sum(sizes)})")
-        dev = [to_device(g, "kruskal_oneway") for g in groups]
-        if len({d.dtype for d in dev}) > 1:
-            dev = [d.double() for d in dev]
-        if len(dev) > 2:
-            dev = [torch.cat(dev)]                     # the ranks are those of the pooled sample
-        starts = np.concatenate(([0], np.cumsum(sizes)))
-        index_lists = [np.arange(starts[g], starts[g + 1], dtype=np.int32) for g in range(len(sizes))]
-    else:
-        on_device = isinstance(groups_or_array, torch.Tensor)
-        if int(groups_or_array.shape[0]) > RANK_MAX_SAMPLES:
-            raise ValueError(f"kruskal_oneway: at most {RANK_MAX_SAMPLES} samples (got {int(groups_or_array.shape[0])})")
-        x = to_device(groups_or_array, "kruskal_oneway")
-        lab = labels.detach().cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
-        lab = lab.squeeze()
-        if lab.ndim != 1 or lab.shape[0] != x.shape[0]:
-            raise ValueError(f"kruskal_oneway: {x.shape[0]} samples but labels of shape {lab.shape}")
-        index_lists = [np.flatnonzero(lab == v).astype(np.int32) for v in np.unique(lab)]
-        dev = [x]
-    H, p = kruskal_device(dev, index_lists)
-    if on_device:
-        return H, p
-    return H.cpu().numpy(), p.cpu().numpy()
+    return _oneway("kruskal", groups_or_array, labels, limit=RANK_MAX_SAMPLES)
 
 
 def max_run_below(p, threshold: float):
@@ -301,6 +352,15 @@ def max_run_below(p, threshold: float):
         check(_lib.load().tl_max_run_below(ptr(p), p.shape[0], p.shape[1], float(threshold), ptr(out[0]), ptr(out[1]),
                                            stream_ptr()), "tl_max_run_below")
     return out[0], out[1]
+
+
+def channels_by_run(p, cell_threshold: float, length_threshold: int) -> Tuple[list, list]:
+    """``(channels, lengths)`` on the host: the rows of the CUDA p-values ``p (C, T)`` whose longest run of
+    ``p < cell_threshold`` is strictly longer than ``length_threshold``, and the length of that run for each of them."""
+    count, longest = max_run_below(p, cell_threshold)
+    count, longest = count.cpu().numpy(), longest.cpu().numpy()
+    channels = [int(ch) for ch in np.flatnonzero((count > 0) & (longest > length_threshold))]
+    return channels, [int(longest[ch]) for ch in channels]
 
 
 # ---- label-permutation test ----------------------------------------------------------------------------------------
@@ -353,26 +413,17 @@ def critical_values(p_threshold: float, k: int, n: int, statistic: str = "anova"
     return f_crit, f_crit * dfb / (dfw + f_crit * dfb)
 
 
-def _perm_apply(arrays, table, counts, p_threshold, perm_chunk, make_out, consume, statistic="anova"):
-    """The work shared by ``permutation_runs`` and ``permutation_exceedances``: ``out = make_out(P, C, T)``, then
-    ``consume(out, p0, p1, mask)`` per chunk of relabellings with ``mask`` (p1 - p0, C * T) uint8 on the device.  Returns
-    ``(out, f_crit, theta)`` (``critical_values`` of ``statistic``).  ``"kruskal"`` ranks the samples once - a relabelling
-    does not change them - and runs the same launches on the ranks."""
+def _perm_masks(arrays, table, counts, p_threshold, perm_chunk, statistic):
+    """The work shared by ``permutation_runs`` and ``permutation_exceedances``: the checks, the threshold of every column and
+    the upload of the table.  Returns ``(f_crit, theta, (P, C, T), chunks)`` (``critical_values`` of ``statistic``); ``chunks``
+    yields ``(p0, p1, mask)`` per chunk of relabellings, ``mask`` (p1 - p0, C * T) uint8 on the device, overwritten by the
+    next chunk.  ``"kruskal"`` ranks the samples once - a relabelling does not change them - and runs the same launches on
+    the ranks."""
     import torch
     from .. import _lib
     from .._lib import check, ptr, stream_ptr
     check_statistic(statistic)
-    arrays = list(arrays)
-    if not 1 <= len(arrays) <= 2:
-        raise ValueError("permutation test: one or two sample arrays")
-    x0 = arrays[0]
-    for a in arrays:
-        _lib.require_gpu(a, "permutation test")
-        if a.dim() != 3 or a.shape[1:] != x0.shape[1:] or a.dtype != x0.dtype or a.device != x0.device:
-            raise ValueError("permutation test: arrays must be (n, C, T) of one trailing shape, dtype and device")
-    if x0.dtype not in (torch.float32, torch.float64):
-        raise ValueError("permutation test: float32 or float64 samples")
-    arrays = [a.contiguous() for a in arrays]
+    arrays = _sample_arrays(arrays, "permutation test", ndim=3)
     x0 = arrays[0]
     Cn, T = int(x0.shape[1]), int(x0.shape[2])
     cols = Cn * T
@@ -416,17 +467,19 @@ def _perm_apply(arrays, table, counts, p_threshold, perm_chunk, make_out, consum
         mean_sq = S * S / N
         tau = (theta * (Q - mean_sq) + mean_sq).contiguous()          # theta sst + total^2 / N
         labels = torch.from_numpy(table).to(x0.device)
-        cnt = (C.c_int32 * k)(*counts)
-        x1 = arrays[1] if len(arrays) == 2 else None
-        out = make_out(P, Cn, T)
-        mask = torch.empty(perm_chunk, cols, dtype=torch.uint8, device=x0.device)
-        for p0 in range(0, P, perm_chunk):
-            p1 = min(P, p0 + perm_chunk)
-            check(lib.tl_perm_exceed(ptr(x0), x0.shape[0], ptr(x1), 0 if x1 is None else x1.shape[0], is_f64, cols, ptr(shift),
-                                     labels.data_ptr() + p0 * N, p1 - p0, cnt, k, ptr(tau), ptr(mask), stream_ptr()),
-                  "tl_perm_exceed")
-            consume(out, p0, p1, mask[:p1 - p0])
-    return out, f_crit, theta
+    cnt = (C.c_int32 * k)(*counts)
+    x1 = arrays[1] if len(arrays) == 2 else None
+
+    def chunks():
+        with torch.cuda.device(x0.device):
+            mask = torch.empty(perm_chunk, cols, dtype=torch.uint8, device=x0.device)
+            for p0 in range(0, P, perm_chunk):
+                p1 = min(P, p0 + perm_chunk)
+                check(lib.tl_perm_exceed(ptr(x0), x0.shape[0], ptr(x1), 0 if x1 is None else x1.shape[0], is_f64, cols,
+                                         ptr(shift), labels.data_ptr() + p0 * N, p1 - p0, cnt, k, ptr(tau), ptr(mask),
+                                         stream_ptr()), "tl_perm_exceed")
+                yield p0, p1, mask[:p1 - p0]
+    return f_crit, theta, (P, Cn, T), chunks()
 
 
 def permutation_runs(arrays: Sequence, table, counts: Sequence[int], p_threshold: float, perm_chunk: Optional[int] = None,
@@ -447,13 +500,11 @@ def permutation_runs(arrays: Sequence, table, counts: Sequence[int], p_threshold
     from .. import _lib
     from .._lib import check, ptr, stream_ptr
     lib = _lib.load()
-    device = arrays[0].device
-
-    def consume(runs, p0, p1, mask):
-        Cn = runs.shape[1]
-        check(lib.tl_perm_runs(ptr(mask), (p1 - p0) * Cn, mask.shape[1] // Cn, ptr(runs[p0:p1]), stream_ptr()), "tl_perm_runs")
-    return _perm_apply(arrays, table, counts, p_threshold, perm_chunk,
-                       lambda P, Cn, T: torch.empty(P, Cn, dtype=torch.int32, device=device), consume, statistic)
+    f_crit, theta, (P, Cn, T), chunks = _perm_masks(arrays, table, counts, p_threshold, perm_chunk, statistic)
+    runs = torch.empty(P, Cn, dtype=torch.int32, device=arrays[0].device)
+    for p0, p1, mask in chunks:
+        check(lib.tl_perm_runs(ptr(mask), (p1 - p0) * Cn, T, ptr(runs[p0:p1]), stream_ptr()), "tl_perm_runs")
+    return runs, f_crit, theta
 
 
 def permutation_exceedances(arrays: Sequence, table, counts: Sequence[int], p_threshold: float,
@@ -461,12 +512,11 @@ def permutation_exceedances(arrays: Sequence, table, counts: Sequence[int], p_th
     """The boolean ``(P, C, T)`` CUDA mask behind ``permutation_runs`` (same arguments): where ``p < p_threshold`` under
     each labelling.  P * C * T bytes: for tests and small inputs."""
     import torch
-    device = arrays[0].device
-
-    def consume(out, p0, p1, mask):
+    _, _, shape, chunks = _perm_masks(arrays, table, counts, p_threshold, perm_chunk, statistic)
+    out = torch.empty(shape, dtype=torch.bool, device=arrays[0].device)
+    for p0, p1, mask in chunks:
         out[p0:p1] = mask.reshape(out[p0:p1].shape) != 0
-    return _perm_apply(arrays, table, counts, p_threshold, perm_chunk,
-                       lambda P, Cn, T: torch.empty(P, Cn, T, dtype=torch.bool, device=device), consume, statistic)[0]
+    return out
 
 
 def permutation_p_values(runs):
@@ -481,12 +531,3 @@ def permutation_p_values(runs):
     p_channel = (1 + (null >= obs[None, :]).sum(axis=0)) / P
     p_max = (1 + (null.max(axis=1, initial=0)[:, None] >= obs[None, :]).sum(axis=0)) / P
     return p_channel.astype(np.float64), p_max.astype(np.float64)
-
-
-def device_recording(data, name: str, what: str):
-    """The recording ``data[name]`` on the GPU.  The stage hands the selectors a mapping with a ``device(name)`` method that
-    uploads a recording once per subject; a plain dict / NpzFile is uploaded here."""
-    getter = getattr(data, "device", None)
-    if callable(getter):
-        return getter(name)
-    return to_device(data[name], what)

@@ -136,22 +136,16 @@ __device__ __forceinline__ void group_ss(const double* __restrict__ sum, const d
   }
 }
 
-__global__ __launch_bounds__(256) void anova_finalize_kernel(const double* __restrict__ sum, const double* __restrict__ sumsq,
-                                                             AnovaCounts cnt, int k, int splits, long long cols, long long N,
-                                                             double* __restrict__ F, double* __restrict__ p) {
-  const long long col = blockIdx.x * 256LL + threadIdx.x;
-  if (col >= cols) return;
-  double ssb, ssw;
-  group_ss(sum, sumsq, cnt, k, splits, cols, N, col, ssb, ssw);
-  const double dfb = (double)(k - 1), dfw = (double)(N - k);
-  double f = __builtin_nan(""), pv = __builtin_nan("");
-  if (N > k) {
-    f = (ssb / dfb) / (ssw / dfw);
-    pv = f_survival(f, dfb, dfw);
+// a statistic of group_finalize_kernel: (stat, pv) of a column from its (ssb, ssw), left as they come in (NaN) where undefined
+struct AnovaF {
+  static __device__ __forceinline__ void eval(double ssb, double ssw, long long N, int k, double& stat, double& pv) {
+    const double dfb = (double)(k - 1), dfw = (double)(N - k);
+    if (N > k) {
+      stat = (ssb / dfb) / (ssw / dfw);
+      pv = f_survival(stat, dfb, dfw);
+    }
   }
-  F[col] = f;
-  p[col] = pv;
-}
+};
 
 // ------------------------------------------------------------------------------------------
 // Kruskal-Wallis: with its tie correction H is the ANOVA decomposition of the midranks, H = (N - 1) ssb / (ssb + ssw), and
@@ -192,21 +186,29 @@ __host__ __device__ inline double chi2_survival(double H, double df) {
   return pre * h;
 }
 
-// sum / sumsq as anova_finalize_kernel reads them, taken of the midranks; a column of identical values has sst = 0: NaN
-__global__ __launch_bounds__(256) void kruskal_finalize_kernel(const double* __restrict__ sum, const double* __restrict__ sumsq,
-                                                               AnovaCounts cnt, int k, int splits, long long cols, long long N,
-                                                               double* __restrict__ H, double* __restrict__ p) {
+// (ssb, ssw) taken of the midranks; a column of identical values has sst = 0: NaN
+struct KruskalH {
+  static __device__ __forceinline__ void eval(double ssb, double ssw, long long N, int k, double& stat, double& pv) {
+    const double sst = ssb + ssw;
+    if (sst > 0.0) {                                             // false for NaN
+      stat = (double)(N - 1) * ssb / sst;
+      pv = chi2_survival(stat, (double)(k - 1));
+    }
+  }
+};
+
+// one column per lane: Stat (AnovaF or KruskalH) turns the column's (ssb, ssw) into the statistic and its p
+template <typename Stat>
+__global__ __launch_bounds__(256) void group_finalize_kernel(const double* __restrict__ sum, const double* __restrict__ sumsq,
+                                                       AnovaCounts cnt, int k, int splits, long long cols, long long N,
+                                                       double* __restrict__ stat, double* __restrict__ p) {
   const long long col = blockIdx.x * 256LL + threadIdx.x;
   if (col >= cols) return;
   double ssb, ssw;
   group_ss(sum, sumsq, cnt, k, splits, cols, N, col, ssb, ssw);
-  const double sst = ssb + ssw;
-  double h = __builtin_nan(""), pv = __builtin_nan("");
-  if (sst > 0.0) {                                             // false for NaN
-    h = (double)(N - 1) * ssb / sst;
-    pv = chi2_survival(h, (double)(k - 1));
-  }
-  H[col] = h;
+  double s = __builtin_nan(""), pv = __builtin_nan("");
+  Stat::eval(ssb, ssw, N, k, s, pv);
+  stat[col] = s;
   p[col] = pv;
 }
 
@@ -623,44 +625,35 @@ extern "C" int tl_group_moments(const void* x, int is_f64, int64_t n_rows, int64
   return check_launch("group_moments");
 }
 
-extern "C" int tl_anova_finalize(const double* sum, const double* sumsq, const int32_t* counts, int k, int splits, int64_t cols,
-                                 double* F, double* p, void* stream) {
-  TL_REQUIRE(sum && sumsq && counts && F && p, "anova_finalize: null pointer");
-  TL_REQUIRE(k >= 2 && k <= 64, "anova_finalize: the number of groups k must lie in [2, 64]");
-  TL_REQUIRE(cols >= 1, "anova_finalize: cols must be at least 1");
-  TL_REQUIRE(splits >= 1 && splits <= 1024, "anova_finalize: splits must lie in [1, 1024]");
+template <typename Stat>
+static int finalize(const char* name, const double* sum, const double* sumsq, const int32_t* counts, int k, int splits,
+                    int64_t cols, double* stat, double* p, void* stream) {
+  TL_REQUIRE(sum && sumsq && counts && stat && p, "%s: null pointer", name);
+  TL_REQUIRE(k >= 2 && k <= 64, "%s: the number of groups k must lie in [2, 64]", name);
+  TL_REQUIRE(cols >= 1, "%s: cols must be at least 1", name);
+  TL_REQUIRE(splits >= 1 && splits <= 1024, "%s: splits must lie in [1, 1024]", name);
   const long long blocks = (cols + 255) / 256;
-  TL_REQUIRE(blocks <= 0x7fffffffLL, "anova_finalize: too many columns");
+  TL_REQUIRE(blocks <= 0x7fffffffLL, "%s: too many columns", name);
   AnovaCounts cnt = {};
   long long N = 0;
   for (int g = 0; g < k; ++g) {
-    TL_REQUIRE(counts[g] >= 1, "anova_finalize: every group needs at least one sample");
+    TL_REQUIRE(counts[g] >= 1, "%s: every group needs at least one sample", name);
     cnt.n[g] = counts[g];
     N += counts[g];
   }
-  hipLaunchKernelGGL(anova_finalize_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, sum, sumsq, cnt, k, splits,
-                     (long long)cols, N, F, p);
-  return check_launch("anova_finalize");
+  hipLaunchKernelGGL((group_finalize_kernel<Stat>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, sum, sumsq, cnt, k, splits,
+                     (long long)cols, N, stat, p);
+  return check_launch(name);
+}
+
+extern "C" int tl_anova_finalize(const double* sum, const double* sumsq, const int32_t* counts, int k, int splits, int64_t cols,
+                                 double* F, double* p, void* stream) {
+  return finalize<AnovaF>("anova_finalize", sum, sumsq, counts, k, splits, cols, F, p, stream);
 }
 
 extern "C" int tl_kruskal_finalize(const double* sum, const double* sumsq, const int32_t* counts, int k, int splits, int64_t cols,
                                    double* H, double* p, void* stream) {
-  TL_REQUIRE(sum && sumsq && counts && H && p, "kruskal_finalize: null pointer");
-  TL_REQUIRE(k >= 2 && k <= 64, "kruskal_finalize: the number of groups k must lie in [2, 64]");
-  TL_REQUIRE(cols >= 1, "kruskal_finalize: cols must be at least 1");
-  TL_REQUIRE(splits >= 1 && splits <= 1024, "kruskal_finalize: splits must lie in [1, 1024]");
-  const long long blocks = (cols + 255) / 256;
-  TL_REQUIRE(blocks <= 0x7fffffffLL, "kruskal_finalize: too many columns");
-  AnovaCounts cnt = {};
-  long long N = 0;
-  for (int g = 0; g < k; ++g) {
-    TL_REQUIRE(counts[g] >= 1, "kruskal_finalize: every group needs at least one sample");
-    cnt.n[g] = counts[g];
-    N += counts[g];
-  }
-  hipLaunchKernelGGL(kruskal_finalize_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, sum, sumsq, cnt, k, splits,
-                     (long long)cols, N, H, p);
-  return check_launch("kruskal_finalize");
+  return finalize<KruskalH>("kruskal_finalize", sum, sumsq, counts, k, splits, cols, H, p, stream);
 }
 
 extern "C" int tl_rank_columns(const void* x0, int64_t n0, const void* x1, int64_t n1, int is_f64, int64_t cols, float* ranks,

@@ -158,6 +158,17 @@ def test_cuda_tensors_in_cuda_tensors_out():
     _check_numbers(Fg.cpu().numpy(), pg.cpu().numpy(), ar.scipy_loop(host_groups), ar.closed_form(host_groups), "per_group_form")
     with pytest.raises(RuntimeError, match="no CPU"):
         anova_oneway(torch.from_numpy(x), lab)
+    # two groups of different dtype (4 and 6 samples of the smallest ragged shape): float32 widens exactly, so both tests
+    # return, bit for bit, what they return on the float64 casts
+    from decode_tonal_langauge_amd.channel_selection import kruskal_oneway
+    _, N, C, T, _ = min(_SHAPES, key=lambda s: s[1] * s[2] * s[3])
+    y = np.random.default_rng(100 + N).standard_normal((N, C, T))
+    y[:4] += 0.5
+    mixed = [y[:4].astype(np.float32), y[4:]]
+    for oneway in (anova_oneway, kruskal_oneway):
+        got, want = oneway(mixed), oneway([g.astype(np.float64) for g in mixed])
+        assert got[0].shape == (C, T) and np.isfinite(want[1]).all() and want[1].min() < want[1].max()
+        assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
 
 
 # ---------------------------------------------------------------------------------------------- run lengths

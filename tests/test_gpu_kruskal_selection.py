@@ -191,6 +191,18 @@ def test_active_decisions_equal_the_reference_and_the_anova_is_unchanged():
                      dict(base, active_time_threshold=0.2, test="kruskal"))
     selected, runs, _ = kr.selection(ps, 0.05 / 65, 20)
     assert res["selected_channels"] == selected == [1, 2] and res["max_lengths"] == [runs[c] for c in selected]
+    # mixed dtypes on the same pair: the rest float32, the ERP the same values as float64.  Widening float32 is exact, so
+    # every result equals, bit for bit, that of both given as float64 - in this selector and in the permutation test
+    from decode_tonal_langauge_amd.channel_selection import permutation
+    mixed = {"ecog": erp.astype(np.float64), "ecog_rest": rest.copy(), "ecog_sf": 100}
+    wide = dict(mixed, ecog_rest=rest.astype(np.float64))
+    for test in ("anova", "kruskal"):
+        for selector, prm in ((permutation, {"p_threshold": 0.05, "n_permutations": 40, "test": test}),
+                              (active, dict(base, active_time_threshold=0.2, test=test))):
+            got, want = selector.run(mixed, prm), selector.run(wide, prm)
+            assert got["selected_channels"] == want["selected_channels"] and got["max_lengths"] == want["max_lengths"]
+            assert np.array_equal(got["p_values"], want["p_values"])
+    assert want["selected_channels"] == selected                        # active, rank form: the float32 pair's channels
 
 
 # ---------------------------------------------------------------------------------------------- permutation test
