@@ -263,3 +263,40 @@ def require_gpu(t, what: str) -> None:
         raise RuntimeError(
             f"{what}: tensor is on '{t.device}'. The MI355X path runs HIP kernels only and has no CPU "
             "fallback; move the model and its inputs to a 'cuda' device.")
+
+
+def normalise(t, *, floats: bool = True, rows: str = "contiguous"):
+    """The dtype and layout half of ``to_gpu``, on a tensor of any device.  ``floats``: float32 / float64 are kept, anything
+    else becomes float64.  ``rows="strided"`` keeps a 2-D tensor with unit stride along the last axis and a row stride of at
+    least the row length (one row: any row stride); every other layout, and ``rows="contiguous"``, is made contiguous."""
+    import torch
+    if rows not in ("contiguous", "strided"):
+        raise ValueError(f"rows must be 'contiguous' or 'strided' (got {rows!r})")
+    if floats and t.dtype not in (torch.float32, torch.float64):
+        t = t.double()
+    if rows == "strided" and t.dim() == 2 and t.stride(1) == 1 and not (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        return t
+    return t.contiguous()
+
+
+def to_gpu(a, what: str, *, device=None, floats: bool = True, rows: str = "contiguous"):
+    """``(tensor, was_numpy)``: the package's one input rule.  A CUDA tensor is read in place (a tensor elsewhere draws
+    ``require_gpu``'s refusal); anything else is taken as a NumPy array and uploaded once, to ``device`` or the current one -
+    the caller then answers NumPy with NumPy.  ``floats`` and ``rows`` as in ``normalise``; an array's dtype is converted on the
+    host, and only an array that is not C-contiguous and writable is copied there before the upload.  No CPU fallback."""
+    import numpy as np
+    import torch
+    if isinstance(a, torch.Tensor):
+        require_gpu(a, what)
+        return normalise(a, floats=floats, rows=rows), False
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"{what} (MI355X build): no GPU visible; this package has no CPU fallback")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"{what}: device '{dev}' is not a CUDA device; this package has no CPU fallback")
+    arr = np.asarray(a)
+    if floats and arr.dtype not in (np.float32, np.float64):
+        arr = arr.astype(np.float64)
+    if not (arr.flags.c_contiguous and arr.flags.writeable):
+        arr = np.array(arr, order="C")
+    return normalise(torch.from_numpy(arr).to(dev), floats=floats, rows=rows), True

@@ -92,21 +92,8 @@ def labelled_inputs(data: Mapping, params: dict, need_sf: bool = True):
 # ---- device side ---------------------------------------------------------------------------------------------------
 def to_device(a, what: str):
     """NumPy array -> CUDA tensor (uploaded, float32 / float64 kept, anything else becomes float64); CUDA tensor -> itself."""
-    import torch
     from .. import _lib
-    if isinstance(a, torch.Tensor):
-        _lib.require_gpu(a, what)
-        t = a
-    else:
-        if not torch.cuda.is_available():
-            raise RuntimeError(f"{what} (MI355X build): no GPU visible; this package has no CPU fallback")
-        arr = np.asarray(a)
-        if arr.dtype not in (np.float32, np.float64):
-            arr = arr.astype(np.float64)
-        t = torch.from_numpy(np.ascontiguousarray(arr)).to(torch.device("cuda", torch.cuda.current_device()))
-    if t.dtype not in (torch.float32, torch.float64):
-        t = t.double()
-    return t.contiguous()
+    return _lib.to_gpu(a, what)[0]
 
 
 def device_recording(data, name: str, what: str):

@@ -18,11 +18,19 @@
 // LDS: 4 images of 1024 + 64 doubles = 34 KB -> four workgroups per CU.  The index padding d + (d >> 4) takes the stride-4
 // stores of the first pass off each other's banks (a 16-lane store group then covers 16 different bank pairs).
 //
+// Every kernel of this file that transforms frames (mel_power, gl_synth, gl_analyse, welch_accum) is built from the same pieces,
+// each stated once: MelFrames (the workgroup's frame set-up: LDS images, fl, j, fbase, twiddles; mel_fft and mel_unpack_bin on
+// them) and mel_band_sane (the band-run check, also of mel_invert).  On the host MelArgs holds the checks the entries share
+// (n_fft -> log2 M, win_length, hop, frames per workgroup, the 2^31 launch cap) and mel_dispatch picks the instantiation by size
+// (mel_by_type the sample type, where the rows have one).  The windowed gather of mel_power and gl_analyse stays written out in both: as one function over a sample
+// callable the compiler fused a different product of the first butterfly into its fma in gl_analyse, and bits changed.
+//
 // The way back (utils/audio.py mel_to_audio_batch) is further down: tl_mel_invert (mel -> linear spectrum by FISTA, the whole
 // solve in LDS and registers) and Griffin-Lim as tl_gl_synth / tl_gl_analyse / tl_gl_overlap_add, whose inverse and forward
 // transforms are the mel_fft below (the inverse runs it on the conjugate).
 #include "tonal_common.h"
 #include <math.h>
+#include <type_traits>
 
 namespace tl {
 
@@ -141,6 +149,33 @@ __device__ __forceinline__ void mel_unpack_bin(const double* zr, const double* z
   Xi = ei + fma(orr, w[1], oi * w[0]);
 }
 
+// ---- the set-up of the four frame kernels (mel_power, gl_synth, gl_analyse, welch_accum): thread tid of the MEL_Q owns the points
+// j + r M/4 of frame fl of the workgroup's F = MEL_PTS / M, whose points start at fbase in the ping-pong images re[] / im[] laid
+// over the kernel's own `__shared__ double lds[4 * MEL_PAD]`; the thread's twiddles are requested here.  Which frames of which
+// row a workgroup holds (blockIdx) is each kernel's own business
+template <int LOG2M>
+struct MelFrames {
+  static constexpr int M = 1 << LOG2M, F = MEL_PTS / M, Q = M / 4, FIN = mel_fin(LOG2M);
+  double* re[2];
+  double* im[2];
+  int tid, fl, j, fbase;
+  MelTwiddles<LOG2M> twd;
+  __device__ __forceinline__ explicit MelFrames(double* lds)
+      : re{lds, lds + 2 * MEL_PAD}, im{lds + MEL_PAD, lds + 3 * MEL_PAD}, tid(threadIdx.x), fl(tid >> (LOG2M - 2)),
+        j(tid & (Q - 1)), fbase(fl * M) {}
+  __device__ __forceinline__ void load_twiddles(const mel_d2* tw) { mel_load_twiddles<LOG2M>(tw, j, twd); }
+  __device__ __forceinline__ void fft(double (&xr)[4], double (&xi)[4]) const { mel_fft<LOG2M>(xr, xi, twd, re, im, j, fbase); }
+  __device__ __forceinline__ void unpack_bin(const mel_d2* tw, int k, double& Xr, double& Xi) const {
+    mel_unpack_bin<LOG2M>(re[FIN], im[FIN], tw, fbase, k, Xr, Xi);
+  }
+};
+
+// a band's run [first, last) lies within the nb bins and its weights within the table; the kernels poison a band whose run does
+// not instead of reading out of bounds
+__device__ __forceinline__ bool mel_band_sane(int first, int last, int off, int nb, int n_weights) {
+  return first >= 0 && first <= last && last <= nb && off >= 0 && (long long)off + (last - first) <= n_weights;
+}
+
 // bands (n_mels, 3) int32: first bin, one past the last bin, offset of the band's first weight in `weights`
 template <typename TIN, int LOG2M>
 __global__ __launch_bounds__(MEL_Q) void mel_power_kernel(const void* __restrict__ audio, long long row_stride, long long S,
@@ -149,20 +184,19 @@ __global__ __launch_bounds__(MEL_Q) void mel_power_kernel(const void* __restrict
                                                           int n_weights, double* __restrict__ mel, double* __restrict__ rowmax,
                                                           int blocks_per_trial, long long n_frames, int hop, int center,
                                                           int power, int n_mels) {
-  constexpr int M = 1 << LOG2M, F = MEL_PTS / M, Q = M / 4, FIN = mel_fin(LOG2M);
+  using Fr = MelFrames<LOG2M>;
+  constexpr int M = Fr::M, F = Fr::F, Q = Fr::Q, FIN = Fr::FIN;
   __shared__ __attribute__((aligned(16))) double lds[4 * MEL_PAD];
   __shared__ double wmax[MEL_Q / 64];
-  double* re[2] = {lds, lds + 2 * MEL_PAD};
-  double* im[2] = {lds + MEL_PAD, lds + 3 * MEL_PAD};
-  const int tid = threadIdx.x, fl = tid >> (LOG2M - 2), j = tid & (Q - 1), fbase = fl * M;
+  Fr fr(lds);
+  const int tid = fr.tid, fl = fr.fl, j = fr.j;
   const long long n = blockIdx.x / blocks_per_trial;
   const long long frame0 = (long long)(blockIdx.x % blocks_per_trial) * F;
   const long long frame = frame0 + fl;
   const long long start = frame * hop - (center ? M : 0);
   const long long row = n * row_stride;
 
-  MelTwiddles<LOG2M> twd;
-  mel_load_twiddles<LOG2M>(tw, j, twd);
+  fr.load_twiddles(tw);
   // ---- gather + window + first pass (Ns = 1, no twiddles) straight from registers
   double xr[4], xi[4];
 #pragma unroll
@@ -173,12 +207,12 @@ __global__ __launch_bounds__(MEL_Q) void mel_power_kernel(const void* __restrict
     xr[r] = (frame < n_frames && s0 >= 0 && s0 < S) ? mel_ld<TIN>(audio, row + s0) * w[0] : 0.0;
     xi[r] = (frame < n_frames && s1 >= 0 && s1 < S) ? mel_ld<TIN>(audio, row + s1) * w[1] : 0.0;
   }
-  mel_fft<LOG2M>(xr, xi, twd, re, im, j, fbase);
+  fr.fft(xr, xi);
   // ---- unpack to the M + 1 bins of the real transform, |X|^power into the image nobody reads any more
-  double* pw = re[FIN ^ 1];                                  // [F][M + 1], F (M + 1) <= 1032 doubles
+  double* pw = fr.re[FIN ^ 1];                               // [F][M + 1], F (M + 1) <= 1032 doubles
   for (int k = j; k <= M; k += Q) {
     double Xr, Xi;
-    mel_unpack_bin<LOG2M>(re[FIN], im[FIN], tw, fbase, k, Xr, Xi);
+    fr.unpack_bin(tw, k, Xr, Xi);
     const double p2 = fma(Xr, Xr, Xi * Xi);
     pw[fl * (M + 1) + k] = power == 2 ? p2 : sqrt(p2);
   }
@@ -191,8 +225,7 @@ __global__ __launch_bounds__(MEL_Q) void mel_power_kernel(const void* __restrict
     const bool live = item < total;
     const int f2 = live ? item / n_mels : 0, m = live ? item - f2 * n_mels : 0;
     const int first = bands[3 * m], last = bands[3 * m + 1], off = bands[3 * m + 2];
-    // a table that points outside the spectrum or the weights poisons the band instead of reading out of bounds
-    const bool sane = first >= 0 && first <= last && last <= M + 1 && off >= 0 && (long long)off + (last - first) <= n_weights;
+    const bool sane = mel_band_sane(first, last, off, M + 1, n_weights);
     double acc = 0.0;
     // eight weights in flight per trip (a run is up to ~90 bins at 80 bands: three trips, not twenty-two dependent loads); the
     // padding terms are fma(0, 0, acc) = acc, so the sum is the plain in-order one
@@ -281,7 +314,7 @@ __global__ __launch_bounds__(MEL_Q) void mel_invert_kernel(const double* __restr
   bool bad = false;
   for (int m = tid; m < n_mels; m += MEL_Q) {
     const int first = bands[3 * m], last = bands[3 * m + 1], off = bands[3 * m + 2];
-    const bool sane = first >= 0 && first <= last && last <= NB && off >= 0 && (long long)off + (last - first) <= n_weights;
+    const bool sane = mel_band_sane(first, last, off, NB, n_weights);
     bs[3 * m] = sane ? first : 0;
     bs[3 * m + 1] = sane ? last : 0;
     bs[3 * m + 2] = sane ? off : 0;
@@ -371,19 +404,18 @@ __global__ __launch_bounds__(MEL_Q) void gl_synth_kernel(const double* __restric
                                                          long long angle_stride, const mel_d2* __restrict__ window,
                                                          const mel_d2* __restrict__ tw, mel_d2* __restrict__ frames,
                                                          int blocks_per_trial, long long n_frames) {
-  constexpr int M = 1 << LOG2M, F = MEL_PTS / M, Q = M / 4, FIN = mel_fin(LOG2M);
+  using Fr = MelFrames<LOG2M>;
+  constexpr int M = Fr::M, F = Fr::F, Q = Fr::Q, FIN = Fr::FIN;
   __shared__ __attribute__((aligned(16))) double lds[4 * MEL_PAD];
-  double* re[2] = {lds, lds + 2 * MEL_PAD};
-  double* im[2] = {lds + MEL_PAD, lds + 3 * MEL_PAD};
-  const int tid = threadIdx.x, fl = tid >> (LOG2M - 2), j = tid & (Q - 1), fbase = fl * M;
+  Fr fr(lds);
+  const int fl = fr.fl, j = fr.j, fbase = fr.fbase;
   const long long n = blockIdx.x / blocks_per_trial;
   const long long frame = (long long)(blockIdx.x % blocks_per_trial) * F + fl;
   const bool live = frame < n_frames;
   const double* mg = mag + (n * n_frames + frame) * (M + 1);
   const mel_d2* an = angles + n * angle_stride + frame * (M + 1);
 
-  MelTwiddles<LOG2M> twd;
-  mel_load_twiddles<LOG2M>(tw, j, twd);
+  fr.load_twiddles(tw);
   double xr[4], xi[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -403,7 +435,7 @@ __global__ __launch_bounds__(MEL_Q) void gl_synth_kernel(const double* __restric
     xr[r] = er - oi;                                         // conj Z, Z = E + i O
     xi[r] = -(ei + orr);
   }
-  mel_fft<LOG2M>(xr, xi, twd, re, im, j, fbase);
+  fr.fft(xr, xi);
   if (live) {
     constexpr double inv_m = 1.0 / M;
     mel_d2* dst = frames + (n * n_frames + frame) * M;
@@ -412,8 +444,8 @@ __global__ __launch_bounds__(MEL_Q) void gl_synth_kernel(const double* __restric
       const int m = j + r * Q;
       const mel_d2 w = window[m];
       mel_d2 v;
-      v[0] = re[FIN][mel_idx(fbase + m)] * inv_m * w[0];
-      v[1] = -im[FIN][mel_idx(fbase + m)] * inv_m * w[1];
+      v[0] = fr.re[FIN][mel_idx(fbase + m)] * inv_m * w[0];
+      v[1] = -fr.im[FIN][mel_idx(fbase + m)] * inv_m * w[1];
       dst[m] = v;
     }
   }
@@ -428,33 +460,32 @@ __global__ __launch_bounds__(MEL_Q) void gl_analyse_kernel(const double* __restr
                                                            mel_d2* __restrict__ angles, mel_d2* __restrict__ tprev,
                                                            int blocks_per_trial, long long n_frames, long long length,
                                                            long long re_frames, int hop, double coef, int first) {
-  constexpr int M = 1 << LOG2M, NFFT = 2 * M, F = MEL_PTS / M, Q = M / 4, FIN = mel_fin(LOG2M);
+  using Fr = MelFrames<LOG2M>;
+  constexpr int M = Fr::M, NFFT = 2 * M, F = Fr::F, Q = Fr::Q;
   __shared__ __attribute__((aligned(16))) double lds[4 * MEL_PAD];
-  double* re[2] = {lds, lds + 2 * MEL_PAD};
-  double* im[2] = {lds + MEL_PAD, lds + 3 * MEL_PAD};
-  const int tid = threadIdx.x, fl = tid >> (LOG2M - 2), j = tid & (Q - 1), fbase = fl * M;
+  Fr fr(lds);
+  const int j = fr.j;
   const long long n = blockIdx.x / blocks_per_trial;
-  const long long frame = (long long)(blockIdx.x % blocks_per_trial) * F + fl;
+  const long long frame = (long long)(blockIdx.x % blocks_per_trial) * F + fr.fl;
   const bool live = frame < n_frames && frame < re_frames;
   const long long start = frame * hop - M;
-  const double* fr = frames + n * n_frames * NFFT;
+  const double* trial = frames + n * n_frames * NFFT;
 
-  MelTwiddles<LOG2M> twd;
-  mel_load_twiddles<LOG2M>(tw, j, twd);
+  fr.load_twiddles(tw);
   double xr[4], xi[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int m = j + r * Q;
     const long long s0 = start + 2 * m, s1 = s0 + 1;
     const mel_d2 w = window[m];
-    xr[r] = (live && s0 >= 0 && s0 < length) ? gl_sample<NFFT>(fr, wsum, s0 + M, n_frames, hop) * w[0] : 0.0;
-    xi[r] = (live && s1 >= 0 && s1 < length) ? gl_sample<NFFT>(fr, wsum, s1 + M, n_frames, hop) * w[1] : 0.0;
+    xr[r] = (live && s0 >= 0 && s0 < length) ? gl_sample<NFFT>(trial, wsum, s0 + M, n_frames, hop) * w[0] : 0.0;
+    xi[r] = (live && s1 >= 0 && s1 < length) ? gl_sample<NFFT>(trial, wsum, s1 + M, n_frames, hop) * w[1] : 0.0;
   }
-  mel_fft<LOG2M>(xr, xi, twd, re, im, j, fbase);
+  fr.fft(xr, xi);
   if (frame < n_frames)
     for (int k = j; k <= M; k += Q) {
       double Xr, Xi;
-      mel_unpack_bin<LOG2M>(re[FIN], im[FIN], tw, fbase, k, Xr, Xi);
+      fr.unpack_bin(tw, k, Xr, Xi);
       if (k == 0 || k == M) Xi = 0.0;                        // exactly real, as rfft returns them
       const long long idx = (n * n_frames + frame) * (M + 1) + k;
       double ar = Xr, ai = Xi;
@@ -513,18 +544,17 @@ __global__ __launch_bounds__(MEL_Q) void welch_accum_kernel(const void* __restri
                                                             const mel_d2* __restrict__ window, const mel_d2* __restrict__ tw,
                                                             double* __restrict__ work, long long n_seg, int trips, int nperseg,
                                                             int step, int detrend) {
-  constexpr int M = 1 << LOG2M, F = MEL_PTS / M, Q = M / 4, FIN = mel_fin(LOG2M), NB = M + 1;
+  using Fr = MelFrames<LOG2M>;
+  constexpr int M = Fr::M, F = Fr::F, Q = Fr::Q, NB = M + 1;
   __shared__ __attribute__((aligned(16))) double lds[4 * MEL_PAD];
   __shared__ double wsum[MEL_Q / 64];
-  double* re[2] = {lds, lds + 2 * MEL_PAD};
-  double* im[2] = {lds + MEL_PAD, lds + 3 * MEL_PAD};
-  const int tid = threadIdx.x, fl = tid >> (LOG2M - 2), j = tid & (Q - 1), fbase = fl * M;
+  Fr fr(lds);
+  const int tid = fr.tid, fl = fr.fl, j = fr.j;
   const long long row = (long long)blockIdx.y * row_stride;
   const long long seg0 = (long long)blockIdx.x * trips * F;             // an absent slab (seg0 >= n_seg) writes zeros
   const long long seg_end = seg0 + (long long)trips * F < n_seg ? seg0 + (long long)trips * F : n_seg;
 
-  MelTwiddles<LOG2M> twd;
-  mel_load_twiddles<LOG2M>(tw, j, twd);
+  fr.load_twiddles(tw);
   mel_d2 wv[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) wv[r] = window[j + r * Q];
@@ -557,7 +587,7 @@ __global__ __launch_bounds__(MEL_Q) void welch_accum_kernel(const void* __restri
       xr[r] = o < nperseg ? (raw[2 * r] - mean) * wv[r][0] : 0.0;
       xi[r] = o + 1 < nperseg ? (raw[2 * r + 1] - mean) * wv[r][1] : 0.0;
     }
-    mel_fft<LOG2M>(xr, xi, twd, re, im, j, fbase);
+    fr.fft(xr, xi);
     // the next trip's samples are on their way while this one is unpacked (past the last trip: seg >= seg_end, no load)
     welch_gather<TIN, Q>(x, row, T, seg0 + (long long)(trip + 1) * F + fl, trip + 1 < trips ? seg_end : 0, step, nperseg, j, raw);
 #pragma unroll
@@ -565,7 +595,7 @@ __global__ __launch_bounds__(MEL_Q) void welch_accum_kernel(const void* __restri
       const int k = j + u * Q;
       if (k <= M) {                                                      // u = 4: bin M, thread j = 0 only
         double Xr, Xi;
-        mel_unpack_bin<LOG2M>(re[FIN], im[FIN], tw, fbase, k, Xr, Xi);
+        fr.unpack_bin(tw, k, Xr, Xi);
         acc[u] += fma(Xr, Xr, Xi * Xi);
       }
     }
@@ -606,14 +636,64 @@ __global__ __launch_bounds__(256) void welch_finish_kernel(const double* __restr
 }  // namespace tl
 using namespace tl;
 
-static int mel_log2m(int n_fft) {
-  switch (n_fft) {
-    case 256: return 7;
-    case 512: return 8;
-    case 1024: return 9;
-    case 2048: return 10;
-    default: return 0;
+static const mel_d2* mel_d2_ptr(const double* p) { return reinterpret_cast<const mel_d2*>(p); }
+static mel_d2* mel_d2_ptr(double* p) { return reinterpret_cast<mel_d2*>(p); }
+
+// ---- what the entries check in common, each fault refused in `who`'s name with the one text it has
+struct MelArgs {
+  const char* who;
+  int log2m = 0, fpb = 0;                                    // log2 (n_fft / 2); frames per workgroup
+  long long bpt = 0;                                         // workgroups per trial
+
+  int size(int n_fft) {
+    log2m = n_fft == 256 ? 7 : n_fft == 512 ? 8 : n_fft == 1024 ? 9 : n_fft == 2048 ? 10 : 0;
+    TL_REQUIRE(log2m, "%s: n_fft must be one of 256, 512, 1024, 2048 (got %d)", who, n_fft);
+    fpb = tl::MEL_PTS / (n_fft / 2);
+    return TL_OK;
   }
+  int window(int n_fft, int win_length, int hop) const {
+    TL_REQUIRE(win_length >= 1 && win_length <= n_fft, "%s: win_length must lie in [1, n_fft] (got %d)", who, win_length);
+    TL_REQUIRE(hop >= 1, "%s: hop must be at least 1 (got %d)", who, hop);
+    return TL_OK;
+  }
+  // after size(): N trials of n_frames frames in one launch.  The 2^40 test is the inverse entries'; mel_power has bounded S
+  // and checked n_frames against it before it comes here, and at 2^40 frames the launch cap refuses in the same words
+  int frames(int N, int64_t n_frames) {
+    bpt = ((long long)n_frames + fpb - 1) / fpb;
+    TL_REQUIRE(n_frames <= (1LL << 40) && bpt * N <= 0x7fffffffLL, "%s: too many frames for one launch", who);
+    return TL_OK;
+  }
+  int inverse(int N, int n_fft, int64_t n_frames) {          // what the four entries of the way back begin with
+    if (size(n_fft)) return TL_EINVAL;
+    TL_REQUIRE(N >= 1 && n_frames >= 1, "%s: N and n_frames must be at least 1 (got %d, %lld)", who, N, (long long)n_frames);
+    return frames(N, n_frames);
+  }
+  // what istft keeps of n_frames frames after the centre trim: at most n_fft / 2 + hop (n_frames - 1) samples
+  int signal(int n_fft, int win_length, int hop, int64_t n_frames, int64_t length) const {
+    if (window(n_fft, win_length, hop)) return TL_EINVAL;
+    TL_REQUIRE(hop <= win_length, "%s: hop = %d > win_length = %d leaves gaps in the window-square sum", who, hop, win_length);
+    const long long most = n_fft / 2 + (long long)hop * (n_frames - 1);
+    TL_REQUIRE(length >= 1 && length <= most, "%s: length = %lld disagrees with n_frames = %lld, n_fft and hop (1 .. %lld)", who,
+               (long long)length, (long long)n_frames, most);
+    return TL_OK;
+  }
+};
+
+// launch(size) with log2m as a std::integral_constant; the two entries that read float32 or float64 rows pick the sample type
+// inside their launch with mel_by_type
+template <typename Launch>
+static void mel_dispatch(int log2m, Launch launch) {
+  switch (log2m) {
+    case 7: launch(std::integral_constant<int, 7>()); break;
+    case 8: launch(std::integral_constant<int, 8>()); break;
+    case 9: launch(std::integral_constant<int, 9>()); break;
+    default: launch(std::integral_constant<int, 10>()); break;
+  }
+}
+
+template <typename Launch>
+static void mel_by_type(int is_f64, Launch launch) {
+  is_f64 ? launch(double()) : launch(float());
 }
 
 extern "C" int tl_mel_power(const void* audio, int audio_is_f64, int64_t row_stride, const double* window, const double* tw,
@@ -621,10 +701,8 @@ extern "C" int tl_mel_power(const void* audio, int audio_is_f64, int64_t row_str
                             int64_t S, int n_fft, int win_length, int hop, int center, int power, int n_mels, int64_t n_frames,
                             void* stream) {
   TL_REQUIRE(audio && window && tw && bands && weights && mel && rowmax, "mel_power: null pointer");
-  const int log2m = mel_log2m(n_fft);
-  TL_REQUIRE(log2m, "mel_power: n_fft must be one of 256, 512, 1024, 2048 (got %d)", n_fft);
-  TL_REQUIRE(win_length >= 1 && win_length <= n_fft, "mel_power: win_length must lie in [1, n_fft] (got %d)", win_length);
-  TL_REQUIRE(hop >= 1, "mel_power: hop must be at least 1 (got %d)", hop);
+  MelArgs a{"mel_power"};
+  if (a.size(n_fft) || a.window(n_fft, win_length, hop)) return TL_EINVAL;
   TL_REQUIRE(power == 1 || power == 2, "mel_power: power must be 1 or 2 (got %d)", power);
   TL_REQUIRE(n_mels >= 1 && n_mels <= 65536, "mel_power: n_mels must lie in [1, 65536] (got %d)", n_mels);
   TL_REQUIRE(center == 0 || center == 1, "mel_power: center must be 0 or 1");
@@ -634,35 +712,20 @@ extern "C" int tl_mel_power(const void* audio, int audio_is_f64, int64_t row_str
   TL_REQUIRE(padded >= n_fft, "mel_power: S = %lld samples are shorter than n_fft = %d", (long long)S, n_fft);
   const long long want = 1 + (padded - n_fft) / hop;
   TL_REQUIRE(n_frames == want, "mel_power: n_frames = %lld disagrees with S, n_fft, hop and center (%lld)", (long long)n_frames, want);
-  const int fpb = tl::MEL_PTS / (n_fft / 2);
-  const long long bpt = (n_frames + fpb - 1) / fpb;
-  TL_REQUIRE(bpt * N <= 0x7fffffffLL, "mel_power: too many frames for one launch");
+  if (a.frames(N, n_frames)) return TL_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(rowmax, 0, sizeof(double) * (size_t)N, st) != hipSuccess) {
     (void)hipGetLastError();
     tl::set_error("mel_power: clearing rowmax failed");
     return TL_ELAUNCH;
   }
-  const mel_d2* w2 = reinterpret_cast<const mel_d2*>(window);
-  const mel_d2* t2 = reinterpret_cast<const mel_d2*>(tw);
-  dim3 grid((unsigned)(bpt * N));
-#define MEL_LAUNCH(TIN, L2M)                                                                                            \
-  hipLaunchKernelGGL((mel_power_kernel<TIN, L2M>), grid, dim3(MEL_Q), 0, st, audio, (long long)row_stride, (long long)S, w2, t2,  \
-                     bands, weights, n_weights, mel, rowmax, (int)bpt, (long long)n_frames, hop, center, power, n_mels)
-#define MEL_SIZES(TIN)                                                                                                  \
-  switch (log2m) {                                                                                                      \
-    case 7: MEL_LAUNCH(TIN, 7); break;                                                                                  \
-    case 8: MEL_LAUNCH(TIN, 8); break;                                                                                  \
-    case 9: MEL_LAUNCH(TIN, 9); break;                                                                                  \
-    default: MEL_LAUNCH(TIN, 10); break;                                                                                \
-  }
-  if (audio_is_f64) {
-    MEL_SIZES(double)
-  } else {
-    MEL_SIZES(float)
-  }
-#undef MEL_SIZES
-#undef MEL_LAUNCH
+  mel_dispatch(a.log2m, [&](auto size) {
+    mel_by_type(audio_is_f64, [&](auto sample) {
+      hipLaunchKernelGGL((mel_power_kernel<decltype(sample), decltype(size)::value>), dim3((unsigned)(a.bpt * N)), dim3(MEL_Q), 0,
+                         st, audio, (long long)row_stride, (long long)S, mel_d2_ptr(window), mel_d2_ptr(tw), bands, weights,
+                         n_weights, mel, rowmax, (int)a.bpt, (long long)n_frames, hop, center, power, n_mels);
+    });
+  });
   return check_launch("mel_power");
 }
 
@@ -686,8 +749,8 @@ extern "C" int tl_welch_psd(const void* x, int x_is_f64, int64_t row_stride, con
                             int64_t work_elems, double* psd, int C, int64_t T, int n_fft, int nperseg, int noverlap, int detrend,
                             double scale, int64_t n_seg, int n_slabs, void* stream) {
   TL_REQUIRE(x && window && tw && work && psd, "welch_psd: null pointer");
-  const int log2m = mel_log2m(n_fft);
-  TL_REQUIRE(log2m, "welch_psd: n_fft must be one of 256, 512, 1024, 2048 (got %d)", n_fft);
+  MelArgs a{"welch_psd"};
+  if (a.size(n_fft)) return TL_EINVAL;
   TL_REQUIRE(nperseg >= 2 && nperseg <= n_fft, "welch_psd: nperseg must lie in [2, n_fft] (got %d)", nperseg);
   TL_REQUIRE(noverlap >= 0 && nperseg - noverlap >= 1, "welch_psd: step = nperseg - noverlap must be at least 1 and noverlap "
              "not negative (got nperseg %d, noverlap %d)", nperseg, noverlap);
@@ -698,7 +761,7 @@ extern "C" int tl_welch_psd(const void* x, int x_is_f64, int64_t row_stride, con
   const int step = nperseg - noverlap;
   const long long want = ((long long)T - noverlap) / step;
   TL_REQUIRE(n_seg == want, "welch_psd: n_seg = %lld disagrees with T, nperseg and noverlap (%lld)", (long long)n_seg, want);
-  const int fpb = tl::MEL_PTS / (n_fft / 2), nb = n_fft / 2 + 1;
+  const int fpb = a.fpb, nb = n_fft / 2 + 1;
   const long long all_trips = (want + fpb - 1) / fpb;
   TL_REQUIRE(n_slabs >= 1 && n_slabs <= 0x7fffffff / nb, "welch_psd: n_slabs must be at least 1 (got %d)", n_slabs);
   TL_REQUIRE(work_elems >= (int64_t)C * n_slabs * nb, "welch_psd: the workspace holds %lld doubles, C * n_slabs * (n_fft / 2 + 1) "
@@ -706,161 +769,83 @@ extern "C" int tl_welch_psd(const void* x, int x_is_f64, int64_t row_stride, con
   const long long trips = (all_trips + n_slabs - 1) / n_slabs;
   TL_REQUIRE(trips <= 0x7fffffffLL / fpb, "welch_psd: too many segments per slab");
   hipStream_t st = (hipStream_t)stream;
-  const mel_d2* w2 = reinterpret_cast<const mel_d2*>(window);
-  const mel_d2* t2 = reinterpret_cast<const mel_d2*>(tw);
-  dim3 grid((unsigned)n_slabs, (unsigned)C);
-#define WELCH_LAUNCH(TIN, L2M)                                                                                          \
-  hipLaunchKernelGGL((welch_accum_kernel<TIN, L2M>), grid, dim3(MEL_Q), 0, st, x, (long long)row_stride, (long long)T, w2, t2,    \
-                     work, (long long)n_seg, (int)trips, nperseg, step, detrend)
-#define WELCH_SIZES(TIN)                                                                                                \
-  switch (log2m) {                                                                                                      \
-    case 7: WELCH_LAUNCH(TIN, 7); break;                                                                                \
-    case 8: WELCH_LAUNCH(TIN, 8); break;                                                                                \
-    case 9: WELCH_LAUNCH(TIN, 9); break;                                                                                \
-    default: WELCH_LAUNCH(TIN, 10); break;                                                                              \
-  }
-  if (x_is_f64) {
-    WELCH_SIZES(double)
-  } else {
-    WELCH_SIZES(float)
-  }
-#undef WELCH_SIZES
-#undef WELCH_LAUNCH
+  mel_dispatch(a.log2m, [&](auto size) {
+    mel_by_type(x_is_f64, [&](auto sample) {
+      hipLaunchKernelGGL((welch_accum_kernel<decltype(sample), decltype(size)::value>), dim3((unsigned)n_slabs, (unsigned)C),
+                         dim3(MEL_Q), 0, st, x, (long long)row_stride, (long long)T, mel_d2_ptr(window), mel_d2_ptr(tw), work,
+                         (long long)n_seg, (int)trips, nperseg, step, detrend);
+    });
+  });
   const long long total = (long long)C * nb;
   hipLaunchKernelGGL(welch_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, work, psd, total, nb, n_slabs,
                      (double)n_seg, scale);
   return check_launch("welch_psd");
 }
 
-// the checks the four entries of the inverse share; 0 = refused
-static int mel_inverse_args(const char* who, int N, int n_fft, int64_t n_frames, long long* bpt) {
-  const int log2m = mel_log2m(n_fft);
-  if (!log2m) {
-    tl::set_error("%s: n_fft must be one of 256, 512, 1024, 2048 (got %d)", who, n_fft);
-    return 0;
-  }
-  if (N < 1 || n_frames < 1) {
-    tl::set_error("%s: N and n_frames must be at least 1 (got %d, %lld)", who, N, (long long)n_frames);
-    return 0;
-  }
-  const int fpb = tl::MEL_PTS / (n_fft / 2);
-  *bpt = ((long long)n_frames + fpb - 1) / fpb;
-  if (n_frames > (1LL << 40) || *bpt * N > 0x7fffffffLL) {
-    tl::set_error("%s: too many frames for one launch", who);
-    return 0;
-  }
-  return log2m;
-}
-
-#define MEL_BY_SIZE(LAUNCH)   \
-  switch (log2m) {            \
-    case 7: LAUNCH(7); break; \
-    case 8: LAUNCH(8); break; \
-    case 9: LAUNCH(9); break; \
-    default: LAUNCH(10); break; \
-  }
-
 extern "C" int tl_mel_invert(const double* mel_power, const int32_t* bands, const double* weights, int n_weights,
                              const int32_t* bin_bands, const double* bin_weights, const double* momentum, double* out, int N,
                              int n_fft, int n_mels, int64_t n_frames, int nnls_iter, double step, int power, void* stream) {
   TL_REQUIRE(mel_power && bands && weights && bin_bands && bin_weights && momentum && out, "mel_invert: null pointer");
-  long long bpt = 0;
-  const int log2m = mel_inverse_args("mel_invert", N, n_fft, n_frames, &bpt);
-  if (!log2m) return TL_EINVAL;
+  MelArgs a{"mel_invert"};
+  if (a.inverse(N, n_fft, n_frames)) return TL_EINVAL;
   TL_REQUIRE(n_mels >= 1 && n_mels <= tl::INV_MAX_MELS, "mel_invert: n_mels must lie in [1, %d] (got %d)", tl::INV_MAX_MELS, n_mels);
   TL_REQUIRE(n_weights >= 0 && n_weights <= n_fft + 2,
              "mel_invert: n_weights must lie in [0, n_fft + 2]: at most two bands cover a bin (got %d)", n_weights);
   TL_REQUIRE(nnls_iter >= 1, "mel_invert: nnls_iter must be at least 1 (got %d)", nnls_iter);
   TL_REQUIRE(step > 0.0 && step < INFINITY, "mel_invert: step must be positive and finite");
   TL_REQUIRE(power == 1 || power == 2, "mel_invert: power must be 1 or 2 (got %d)", power);
-  dim3 grid((unsigned)(bpt * N));
-#define INV_LAUNCH(L2M)                                                                                                   \
-  hipLaunchKernelGGL((mel_invert_kernel<L2M>), grid, dim3(MEL_Q), 0, (hipStream_t)stream, mel_power, bands, weights, n_weights,  \
-                     bin_bands, bin_weights, momentum, out, (int)bpt, (long long)n_frames, n_mels, nnls_iter, step, power)
-  MEL_BY_SIZE(INV_LAUNCH)
-#undef INV_LAUNCH
+  mel_dispatch(a.log2m, [&](auto size) {
+    hipLaunchKernelGGL((mel_invert_kernel<decltype(size)::value>), dim3((unsigned)(a.bpt * N)), dim3(MEL_Q), 0, (hipStream_t)stream,
+                       mel_power, bands, weights, n_weights, bin_bands, bin_weights, momentum, out, (int)a.bpt,
+                       (long long)n_frames, n_mels, nnls_iter, step, power);
+  });
   return check_launch("mel_invert");
 }
 
 extern "C" int tl_gl_synth(const double* mag, const double* angles, int angles_shared, const double* window, const double* tw,
                            double* frames, int N, int n_fft, int64_t n_frames, void* stream) {
   TL_REQUIRE(mag && angles && window && tw && frames, "gl_synth: null pointer");
-  long long bpt = 0;
-  const int log2m = mel_inverse_args("gl_synth", N, n_fft, n_frames, &bpt);
-  if (!log2m) return TL_EINVAL;
+  MelArgs a{"gl_synth"};
+  if (a.inverse(N, n_fft, n_frames)) return TL_EINVAL;
   TL_REQUIRE(angles_shared == 0 || angles_shared == 1, "gl_synth: angles_shared must be 0 or 1");
   const long long stride = angles_shared ? 0 : (long long)n_frames * (n_fft / 2 + 1);
-  dim3 grid((unsigned)(bpt * N));
-#define SYNTH_LAUNCH(L2M)                                                                                              \
-  hipLaunchKernelGGL((gl_synth_kernel<L2M>), grid, dim3(MEL_Q), 0, (hipStream_t)stream, mag,                              \
-                     reinterpret_cast<const mel_d2*>(angles), stride, reinterpret_cast<const mel_d2*>(window),            \
-                     reinterpret_cast<const mel_d2*>(tw), reinterpret_cast<mel_d2*>(frames), (int)bpt, (long long)n_frames)
-  MEL_BY_SIZE(SYNTH_LAUNCH)
-#undef SYNTH_LAUNCH
+  mel_dispatch(a.log2m, [&](auto size) {
+    hipLaunchKernelGGL((gl_synth_kernel<decltype(size)::value>), dim3((unsigned)(a.bpt * N)), dim3(MEL_Q), 0, (hipStream_t)stream,
+                       mag, mel_d2_ptr(angles), stride, mel_d2_ptr(window), mel_d2_ptr(tw), mel_d2_ptr(frames), (int)a.bpt,
+                       (long long)n_frames);
+  });
   return check_launch("gl_synth");
-}
-
-// what istft keeps of n_frames frames after the centre trim: at most n_fft / 2 + hop (n_frames - 1) samples
-static int gl_signal_args(const char* who, int n_fft, int win_length, int hop, int64_t n_frames, int64_t length) {
-  if (win_length < 1 || win_length > n_fft) {
-    tl::set_error("%s: win_length must lie in [1, n_fft] (got %d)", who, win_length);
-    return 0;
-  }
-  if (hop < 1) {
-    tl::set_error("%s: hop must be at least 1 (got %d)", who, hop);
-    return 0;
-  }
-  if (hop > win_length) {
-    tl::set_error("%s: hop = %d > win_length = %d leaves gaps in the window-square sum", who, hop, win_length);
-    return 0;
-  }
-  const long long most = n_fft / 2 + (long long)hop * (n_frames - 1);
-  if (length < 1 || length > most) {
-    tl::set_error("%s: length = %lld disagrees with n_frames = %lld, n_fft and hop (1 .. %lld)", who, (long long)length,
-                  (long long)n_frames, most);
-    return 0;
-  }
-  return 1;
 }
 
 extern "C" int tl_gl_analyse(const double* frames, const double* wsum, const double* window, const double* tw, double* angles,
                              double* tprev, int N, int n_fft, int win_length, int hop, int64_t n_frames, int64_t length,
                              double momentum, int first, void* stream) {
   TL_REQUIRE(frames && wsum && window && tw && angles && tprev, "gl_analyse: null pointer");
-  long long bpt = 0;
-  const int log2m = mel_inverse_args("gl_analyse", N, n_fft, n_frames, &bpt);
-  if (!log2m) return TL_EINVAL;
-  if (!gl_signal_args("gl_analyse", n_fft, win_length, hop, n_frames, length)) return TL_EINVAL;
+  MelArgs a{"gl_analyse"};
+  if (a.inverse(N, n_fft, n_frames) || a.signal(n_fft, win_length, hop, n_frames, length)) return TL_EINVAL;
   TL_REQUIRE(momentum >= 0.0 && momentum < INFINITY, "gl_analyse: momentum must be finite and not negative");
   TL_REQUIRE(first == 0 || first == 1, "gl_analyse: first must be 0 or 1");
   const double coef = momentum / (1.0 + momentum);
   const long long re_frames = 1 + length / hop;
-  dim3 grid((unsigned)(bpt * N));
-#define ANA_LAUNCH(L2M)                                                                                                \
-  hipLaunchKernelGGL((gl_analyse_kernel<L2M>), grid, dim3(MEL_Q), 0, (hipStream_t)stream, frames, wsum,                   \
-                     reinterpret_cast<const mel_d2*>(window), reinterpret_cast<const mel_d2*>(tw),                        \
-                     reinterpret_cast<mel_d2*>(angles), reinterpret_cast<mel_d2*>(tprev), (int)bpt, (long long)n_frames,  \
-                     (long long)length, re_frames, hop, coef, first)
-  MEL_BY_SIZE(ANA_LAUNCH)
-#undef ANA_LAUNCH
+  mel_dispatch(a.log2m, [&](auto size) {
+    hipLaunchKernelGGL((gl_analyse_kernel<decltype(size)::value>), dim3((unsigned)(a.bpt * N)), dim3(MEL_Q), 0, (hipStream_t)stream,
+                       frames, wsum, mel_d2_ptr(window), mel_d2_ptr(tw), mel_d2_ptr(angles), mel_d2_ptr(tprev), (int)a.bpt,
+                       (long long)n_frames, (long long)length, re_frames, hop, coef, first);
+  });
   return check_launch("gl_analyse");
 }
 
 extern "C" int tl_gl_overlap_add(const double* frames, const double* wsum, double* out, int N, int n_fft, int win_length, int hop,
                                  int64_t n_frames, int64_t length, void* stream) {
   TL_REQUIRE(frames && wsum && out, "gl_overlap_add: null pointer");
-  long long bpt = 0;
-  const int log2m = mel_inverse_args("gl_overlap_add", N, n_fft, n_frames, &bpt);
-  if (!log2m) return TL_EINVAL;
-  if (!gl_signal_args("gl_overlap_add", n_fft, win_length, hop, n_frames, length)) return TL_EINVAL;
+  MelArgs a{"gl_overlap_add"};
+  if (a.inverse(N, n_fft, n_frames) || a.signal(n_fft, win_length, hop, n_frames, length)) return TL_EINVAL;
   TL_REQUIRE(N <= 65535, "gl_overlap_add: at most 65535 trials per launch (got %d)", N);
   const long long blocks = ((long long)length + 255) / 256;
   TL_REQUIRE(blocks <= 0x7fffffffLL, "gl_overlap_add: length too large for one launch");
-  dim3 grid((unsigned)blocks, (unsigned)N);
-#define OLA_LAUNCH(L2M)                                                                                                 \
-  hipLaunchKernelGGL((gl_overlap_add_kernel<(2 << L2M)>), grid, dim3(256), 0, (hipStream_t)stream, frames, wsum, out,       \
-                     (long long)n_frames, (long long)length, hop)
-  MEL_BY_SIZE(OLA_LAUNCH)
-#undef OLA_LAUNCH
+  mel_dispatch(a.log2m, [&](auto size) {
+    hipLaunchKernelGGL((gl_overlap_add_kernel<(2 << decltype(size)::value)>), dim3((unsigned)blocks, (unsigned)N), dim3(256), 0,
+                       (hipStream_t)stream, frames, wsum, out, (long long)n_frames, (long long)length, hop);
+  });
   return check_launch("gl_overlap_add");
 }

@@ -43,23 +43,13 @@ def plan_starts(times: Sequence[float], sf, length_s: float, n_samples: Optional
 def to_recording(recording, what: str = "extract_windows"):
     """A (C, T) recording as a CUDA tensor whose last dimension is contiguous: a NumPy array is uploaded once, a CUDA tensor
     is taken as it is (any row stride)."""
-    import torch
-    if isinstance(recording, torch.Tensor):
-        _lib.require_gpu(recording, what)
-        rec = recording
-    else:
-        arr = np.asarray(recording)
-        if not torch.cuda.is_available():
-            raise RuntimeError(f"{what} (MI355X build): no GPU visible; this package has no CPU fallback")
-        rec = torch.from_numpy(np.ascontiguousarray(arr)).to(torch.device("cuda", torch.cuda.current_device()))
+    rec, _ = _lib.to_gpu(recording, what, floats=False, rows="strided")
     if rec.dim() != 2:
         raise ValueError(f"{what}: the recording must be (n_channels, n_timepoints), got shape {tuple(rec.shape)}")
     if rec.element_size() not in (1, 2, 4, 8) or rec.is_complex():
         raise ValueError(f"{what}: dtype {rec.dtype} is not a 1-, 2-, 4- or 8-byte element")
     if rec.shape[0] < 1 or rec.shape[1] < 1:
         raise ValueError(f"{what}: empty recording of shape {tuple(rec.shape)}")
-    if rec.shape[1] > 1 and rec.stride(1) != 1 or rec.shape[0] > 1 and rec.stride(0) < rec.shape[1]:
-        rec = rec.contiguous()
     return rec
 
 

@@ -45,7 +45,8 @@ import torch
 from scipy.signal import butter, firwin, lfilter_zi
 
 from ... import _kernels, _lib
-from ..._lib import check, ptr
+from ..._lib import check, ptr, stream_ptr
+from ._common import ret, to_device
 
 _MAX_TAPS_LDS = 7169      # (1024 + ntap - 1) * 8 B <= 64 KiB
 _OLS_N = 1024             # FFT length of the overlap-save path (tl_hilbert_ols)
@@ -55,39 +56,6 @@ _MAX_ROWS = 65535         # channels per call of the time-domain and overlap-sav
 def _check_rows(C: int, what: str) -> None:
     if C > _MAX_ROWS:
         raise ValueError(f"{what}: {C} channels; the band kernels take at most {_MAX_ROWS} per call (split the recording by rows)")
-
-
-def _device() -> torch.device:
-    if not torch.cuda.is_available():
-        raise RuntimeError("frequency_filter (MI355X build): no GPU visible; this package has no CPU fallback")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _to_device(data) -> Tuple[torch.Tensor, bool]:
-    """(C,T) float32/float64 device tensor and whether the caller passed a NumPy array."""
-    if isinstance(data, torch.Tensor):
-        _lib.require_gpu(data, "frequency_filter")
-        t = data
-        was_np = False
-    else:
-        arr = np.asarray(data)
-        if arr.dtype not in (np.float32, np.float64):
-            arr = arr.astype(np.float64)
-        t = torch.from_numpy(np.ascontiguousarray(arr)).to(_device())
-        was_np = True
-    if t.dtype not in (torch.float32, torch.float64):
-        t = t.double()
-    if t.dim() != 2:
-        raise ValueError("expected data of shape (n_channels, n_timepoints)")
-    return t.contiguous(), was_np
-
-
-def _ret(t: torch.Tensor, was_np: bool):
-    return t.cpu().numpy() if was_np else t
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def gaussian_bank(freq_ranges, sampling_rate, f0=0.018, octspace=1 / 7, filterbank_bias=math.log10(0.39),
@@ -248,7 +216,7 @@ def _hilbert_dft(x: torch.Tensor, sampling_rate, cfs, sds, envelope: bool) -> to
     for c0 in range(0, C, chunk):
         n = min(chunk, C - c0)
         check(lib.tl_hilbert_fft(ptr(x[c0:c0 + n]), int(x.dtype == torch.float64), ptr(y[c0:c0 + n]), n, T, ptr(kd),
-                                 len(cfs), ptr(w), ptr(bf), ptr(tw), m2, int(envelope), ptr(work), _stream()),
+                                 len(cfs), ptr(w), ptr(bf), ptr(tw), m2, int(envelope), ptr(work), stream_ptr()),
               "tl_hilbert_fft")
     return y
 
@@ -258,18 +226,18 @@ def hilbert_filter(data, sampling_rate: int, freq_ranges: Union[List[Tuple[float
                    filterbank_slope: float = 0.5, envelope: bool = True):
     """Gaussian Hilbert filter bank, mean over bands; float64 out (reference :80-184)."""
     cfs, sds = gaussian_bank(freq_ranges, sampling_rate, f0, octspace, filterbank_bias, filterbank_slope)
-    x, was_np = _to_device(data)
+    x, was_np = to_device(data, "frequency_filter")
     C, T = x.shape
     if len(cfs) == 0:
         # the reference's mean over an empty band axis yields NaN
-        return _ret(torch.full((C, T), float("nan"), dtype=torch.float64, device=x.device), was_np)
+        return ret(torch.full((C, T), float("nan"), dtype=torch.float64, device=x.device), was_np)
     mode = _kernels.get("hilbert")
     tp, ntap, half, sym, ols = (None, 0, 0, None, None) if mode == "fft" else _device_taps(T, sampling_rate, cfs, sds, x.device)
     if mode == "fft" or ntap > _MAX_TAPS_LDS:
         if mode in ("taps", "sym"):
             raise ValueError(f"hilbert_filter: the band kernels need {ntap} taps at this sampling rate; the time-domain "
                              f"kernel supports up to {_MAX_TAPS_LDS} (TONAL_KERNELS hilbert={mode} forbids the DFT-domain path)")
-        return _ret(_hilbert_dft(x, sampling_rate, cfs, sds, bool(envelope)), was_np)
+        return ret(_hilbert_dft(x, sampling_rate, cfs, sds, bool(envelope)), was_np)
     _check_rows(C, "hilbert_filter")
     y = torch.empty(C, T, dtype=torch.float64, device=x.device)
     # hilbert = auto: the first form below that the bank / recording allows; ols, ols_full, sym, taps force one
@@ -281,19 +249,19 @@ def hilbert_filter(data, sampling_rate: int, freq_ranges: Union[List[Tuple[float
         # instead of ~0.16 ms at 256 x 24 000; ~1e-6 relative, golden G6 hilbert_f32_odd holds it to 1e-5)
         mode_x = 1 if x.dtype == torch.float64 else (0 if _kernels.get("hilbert_f32") == "1" else 2)
         check(_lib.load().tl_hilbert_ols_bl(ptr(x), mode_x, ptr(ols[3][0]), ptr(ols[3][1]), ptr(ols[1]), ptr(y),
-                                            C, T, len(cfs), half, ols[2], int(bool(envelope)), _stream()), "tl_hilbert_ols_bl")
-        return _ret(y, was_np)
+                                            C, T, len(cfs), half, ols[2], int(bool(envelope)), stream_ptr()), "tl_hilbert_ols_bl")
+        return ret(y, was_np)
     if ols is not None and mode in ("auto", "ols", "ols_full"):          # overlap-save with all 1024 bins per band
         check(_lib.load().tl_hilbert_ols(ptr(x), int(x.dtype == torch.float64), ptr(ols[0]), ptr(ols[1]), ptr(y), C, T, len(cfs),
-                                         half, ols[2], int(bool(envelope)), _stream()), "tl_hilbert_ols")
-        return _ret(y, was_np)
+                                         half, ols[2], int(bool(envelope)), stream_ptr()), "tl_hilbert_ols")
+        return ret(y, was_np)
     if sym is not None and mode != "taps":                               # Hermitian-symmetric time-domain kernel
         check(_lib.load().tl_gauss_envelope_sym(ptr(x), int(x.dtype == torch.float64), ptr(sym), ptr(y), C, T, len(cfs), half,
-                                                int(bool(envelope)), _stream()), "tl_gauss_envelope_sym")
-        return _ret(y, was_np)
+                                                int(bool(envelope)), stream_ptr()), "tl_gauss_envelope_sym")
+        return ret(y, was_np)
     check(_lib.load().tl_gauss_envelope(ptr(x), int(x.dtype == torch.float64), ptr(tp), ptr(y), C, T, len(cfs), ntap,
-                                        half, int(bool(envelope)), _stream()), "tl_gauss_envelope")
-    return _ret(y, was_np)
+                                        half, int(bool(envelope)), stream_ptr()), "tl_gauss_envelope")
+    return ret(y, was_np)
 
 
 def butter_filter(data, freqs: Union[Tuple[float, float], float], fs: float, order: int = 4, causal: bool = False,
@@ -305,7 +273,7 @@ def butter_filter(data, freqs: Union[Tuple[float, float], float], fs: float, ord
     if not isinstance(data, torch.Tensor) and np.asarray(data).ndim == 1:
         data = np.asarray(data)[None, :]
         squeeze = True
-    x, was_np = _to_device(data)
+    x, was_np = to_device(data, "frequency_filter")
     C, T = x.shape
     lib = _lib.load()
     y = torch.empty(C, T, dtype=torch.float64, device=x.device)
@@ -349,10 +317,10 @@ def butter_filter(data, freqs: Union[Tuple[float, float], float], fs: float, ord
         work = torch.empty(T, C, dtype=torch.float64, device=x.device)
         swork = torch.empty(2, nb, 2 * nsec, C, dtype=torch.float64, device=x.device)
         check(lib.tl_sosfilt_scan_f64(ptr(x), int(x.dtype == torch.float64), ptr(sd), ptr(md), _SCAN_LEVELS, ptr(y), ptr(work),
-                                      ptr(swork), C, T, nsec, L, _stream()), "tl_sosfilt_scan_f64")
+                                      ptr(swork), C, T, nsec, L, stream_ptr()), "tl_sosfilt_scan_f64")
     elif causal:
         sd, nsec = coef[:2]
-        check(lib.tl_sosfilt_f64(ptr(x), int(x.dtype == torch.float64), ptr(sd), ptr(y), C, T, nsec, _stream()),
+        check(lib.tl_sosfilt_f64(ptr(x), int(x.dtype == torch.float64), ptr(sd), ptr(y), C, T, nsec, stream_ptr()),
               "tl_sosfilt_f64")
     else:
         bd, ad, zd, ntaps = coef[:4]
@@ -371,12 +339,12 @@ def butter_filter(data, freqs: Union[Tuple[float, float], float], fs: float, ord
             nb = (T + 2 * edge + L - 1) // L
             swork = torch.empty(2, nb, 8, C, dtype=torch.float64, device=x.device)
             check(lib.tl_filtfilt_scan_f64(ptr(x), int(x.dtype == torch.float64), ptr(bd), ptr(ad), ptr(zd), ptr(md), _SCAN_LEVELS,
-                                           ptr(y), ptr(work), ptr(swork), C, T, ntaps, L, _stream()), "tl_filtfilt_scan_f64")
-            out = _ret(y, was_np)
+                                           ptr(y), ptr(work), ptr(swork), C, T, ntaps, L, stream_ptr()), "tl_filtfilt_scan_f64")
+            out = ret(y, was_np)
             return out[0] if squeeze else out
         check(lib.tl_filtfilt_f64(ptr(x), int(x.dtype == torch.float64), ptr(bd), ptr(ad), ptr(zd), ptr(y), ptr(work),
-                                  C, T, ntaps, _stream()), "tl_filtfilt_f64")
-    out = _ret(y, was_np)
+                                  C, T, ntaps, stream_ptr()), "tl_filtfilt_f64")
+    out = ret(y, was_np)
     return out[0] if squeeze else out
 
 
@@ -492,7 +460,7 @@ def fir_bandpass_filter(data, fs: float, order: int, center_frequencies: List[fl
     if not isinstance(data, torch.Tensor) and np.asarray(data).ndim == 1:
         data = np.asarray(data)[None, :]
         squeeze = True
-    x, was_np = _to_device(data)
+    x, was_np = to_device(data, "frequency_filter")
     C, T = x.shape
     _check_rows(C, "fir_bandpass_filter")
     use_ols = T >= _OLS_N                      # (shorter recordings: the time-domain kernel, tl_fir_bank)
@@ -503,13 +471,13 @@ def fir_bandpass_filter(data, fs: float, order: int, center_frequencies: List[fl
         # the same causal convolution by overlap-save on the LDS-resident FFT (tl_fir_bank_ols): ~5 x fewer fp64 operations
         # at 391 taps
         check(_lib.load().tl_fir_bank_ols(ptr(x), int(x.dtype == torch.float64), ptr(coef), ptr(_ols_twiddles(x.device)), ptr(y),
-                                          int(y.dtype == torch.float64), C, T, nb, ntap, _stream()),
+                                          int(y.dtype == torch.float64), C, T, nb, ntap, stream_ptr()),
               "tl_fir_bank_ols")
     else:
         check(_lib.load().tl_fir_bank(ptr(x), int(x.dtype == torch.float64), ptr(coef), ptr(y),
-                                      int(y.dtype == torch.float64), C, T, nb, ntap, _stream()),
+                                      int(y.dtype == torch.float64), C, T, nb, ntap, stream_ptr()),
               "tl_fir_bank")
-    out = _ret(y, was_np)
+    out = ret(y, was_np)
     return out[0] if squeeze else out
 
 

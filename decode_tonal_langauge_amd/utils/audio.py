@@ -24,7 +24,6 @@ import functools
 from typing import NamedTuple, Optional
 
 import numpy as np
-from scipy.optimize import nnls
 
 
 # ------------------------------------------------------------------------------------------ mel scale (Slaney)
@@ -64,13 +63,18 @@ def _hann(n: int) -> np.ndarray:
     return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n) / n)          # periodic ("fftbins=True")
 
 
+def _padded_window(n_fft: int, win_length: int) -> np.ndarray:
+    """The Hann window of ``win_length`` samples centred in ``n_fft``, zeros around it."""
+    win = np.zeros(n_fft)
+    off = (n_fft - win_length) // 2
+    win[off:off + win_length] = _hann(win_length)
+    return win
+
+
 def stft(y: np.ndarray, n_fft: int = 2048, hop_length: Optional[int] = None, win_length: Optional[int] = None,
          center: bool = True) -> np.ndarray:
     hop = n_fft // 4 if hop_length is None else int(hop_length)
-    wl = n_fft if win_length is None else int(win_length)
-    win = np.zeros(n_fft)
-    off = (n_fft - wl) // 2
-    win[off:off + wl] = _hann(wl)
+    win = _padded_window(n_fft, n_fft if win_length is None else int(win_length))
     y = np.asarray(y, dtype=np.float64)
     if center:
         y = np.pad(y, n_fft // 2, mode="constant")
@@ -85,10 +89,7 @@ def istft(S: np.ndarray, hop_length: Optional[int] = None, win_length: Optional[
           length: Optional[int] = None) -> np.ndarray:
     n_fft = 2 * (S.shape[0] - 1)
     hop = n_fft // 4 if hop_length is None else int(hop_length)
-    wl = n_fft if win_length is None else int(win_length)
-    win = np.zeros(n_fft)
-    off = (n_fft - wl) // 2
-    win[off:off + wl] = _hann(wl)
+    win = _padded_window(n_fft, n_fft if win_length is None else int(win_length))
     frames = np.fft.irfft(S, n=n_fft, axis=0) * win[:, None]
     n_frames = S.shape[1]
     out = np.zeros(n_fft + hop * (n_frames - 1))
@@ -170,13 +171,16 @@ def _upload(a: np.ndarray, device):
 
 
 @functools.lru_cache(maxsize=8)
-def _stft_batch_tables(device: str, n_fft: int, win_length: int):
-    """Device copies of the window (as ``stft`` builds it) and the full-circle twiddles (cos, -sin)."""
-    win = np.zeros(n_fft)
-    off = (n_fft - win_length) // 2
-    win[off:off + win_length] = _hann(win_length)
+def _stft_twiddles(device: str, n_fft: int):
+    """Device copy of the full-circle twiddles (cos, -sin)(2 pi i / n_fft) every kernel of csrc/tonal_mel.hip reads."""
     ang = 2.0 * np.pi * np.arange(n_fft) / n_fft
-    return _upload(win, device), _upload(np.stack([np.cos(ang), -np.sin(ang)], axis=1), device)
+    return _upload(np.stack([np.cos(ang), -np.sin(ang)], axis=1), device)
+
+
+@functools.lru_cache(maxsize=8)
+def _stft_batch_tables(device: str, n_fft: int, win_length: int):
+    """Device copies of the window (as ``stft`` builds it) and the twiddles."""
+    return _upload(_padded_window(n_fft, win_length), device), _stft_twiddles(device, n_fft)
 
 
 @functools.lru_cache(maxsize=8)
@@ -203,18 +207,9 @@ def audio_to_mel_batch(audio, audio_sampling_rate: int, mel_in_db: bool = True, 
     if audio.ndim != 2:
         raise ValueError("Audio input must be a 2D array (trials, samples).")
     stft_kw, power, mel_kw = _split_kwargs(mel_kwargs)
-    n_fft = stft_kw.get("n_fft", 2048)
-    if n_fft not in MEL_BATCH_N_FFT:
-        raise ValueError(f"n_fft = {n_fft} is not supported on the GPU (supported: {', '.join(map(str, MEL_BATCH_N_FFT))})")
-    n_fft = int(n_fft)
-    hop = n_fft // 4 if stft_kw.get("hop_length") is None else int(stft_kw["hop_length"])
-    wl = n_fft if stft_kw.get("win_length") is None else int(stft_kw["win_length"])
+    n_fft, hop, wl = _check_stft_args(stft_kw.get("n_fft", 2048), stft_kw.get("hop_length"), stft_kw.get("win_length"))
     center = bool(stft_kw.get("center", True))
     n_mels = int(mel_kw.get("n_mels", 128))
-    if not 1 <= wl <= n_fft:
-        raise ValueError(f"win_length = {wl} must lie in [1, n_fft = {n_fft}]")
-    if hop < 1:
-        raise ValueError(f"hop_length = {hop} must be at least 1")
     if power not in (1, 2):
         raise ValueError(f"power = {power} is not supported on the GPU (supported: 1, 2)")
     if n_mels < 1:
@@ -227,20 +222,7 @@ def audio_to_mel_batch(audio, audio_sampling_rate: int, mel_in_db: bool = True, 
         raise ValueError(f"audio of {padded} samples is shorter than n_fft = {n_fft}")
     n_frames = 1 + (padded - n_fft) // hop
 
-    if is_tensor:
-        _lib.require_gpu(audio, "audio_to_mel_batch")
-        x = audio if audio.dtype in (torch.float32, torch.float64) else audio.double()
-        if x.stride(1) != 1 or (N > 1 and x.stride(0) < S):
-            x = x.contiguous()
-    else:
-        if not torch.cuda.is_available():
-            raise RuntimeError("audio_to_mel_batch (MI355X build): no GPU visible; this package has no CPU fallback")
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"audio_to_mel_batch: device '{dev}' is not a CUDA device; this package has no CPU fallback")
-        if audio.dtype not in (np.float32, np.float64):
-            audio = audio.astype(np.float64)
-        x = torch.from_numpy(np.array(audio, order="C")).to(dev)          # a copy: read-only arrays upload without a warning
+    x, _ = _lib.to_gpu(audio, "audio_to_mel_batch", device=device, rows="strided")
     dev = x.device
     fmax = mel_kw.get("fmax")
     win, tw, bands, weights, n_weights = _mel_batch_tables(
@@ -357,22 +339,28 @@ def griffinlim(mag: np.ndarray, n_iter: int = 32, hop_length: Optional[int] = No
     return istft(mag * angles, hop_length=hop_length, win_length=win_length, length=length)
 
 
+def _inverse_kwargs(kwargs: dict, **extra) -> dict:
+    """The keywords of ``mel_to_audio`` (and ``extra``: name = default) with their defaults; any other is a ``TypeError``."""
+    defaults = dict(n_fft=2048, hop_length=None, win_length=None, power=2.0, n_iter=32, length=None, seed=0, fmin=0.0,
+                    fmax=None, **extra)
+    kw = {k: kwargs.pop(k, d) for k, d in defaults.items()}
+    if kwargs:
+        raise TypeError(f"unsupported keyword(s) {sorted(kwargs)}")
+    return kw
+
+
 def mel_to_audio(mel: np.ndarray, n_mels: int, audio_sampling_rate: int = 24414, mel_in_db: bool = True, **kwargs) -> np.ndarray:
     """Waveform from a flattened mel spectrogram by NNLS mel inversion + Griffin-Lim - reference utils/audio.py:46-87."""
     mel = np.asarray(mel, dtype=np.float64).reshape(n_mels, -1)
     if mel_in_db:
         mel = db_to_power(mel, ref=0.0001)
-    n_fft = kwargs.pop("n_fft", 2048)
-    hop_length, win_length = kwargs.pop("hop_length", None), kwargs.pop("win_length", None)
-    power, n_iter = kwargs.pop("power", 2.0), kwargs.pop("n_iter", 32)
-    length, seed = kwargs.pop("length", None), kwargs.pop("seed", 0)
-    fb_kw = {k: kwargs.pop(k) for k in ("fmin", "fmax") if k in kwargs}
-    if kwargs:
-        raise TypeError(f"unsupported keyword(s) {sorted(kwargs)}")
-    fb = mel_filterbank(audio_sampling_rate, n_fft, n_mels=n_mels, **fb_kw).astype(np.float64)
+    from scipy.optimize import nnls                  # here, its one use: importing this module (utils/diagnostics.py does) stays light
+    kw = _inverse_kwargs(kwargs)
+    fb = mel_filterbank(audio_sampling_rate, kw["n_fft"], n_mels=n_mels, fmin=kw["fmin"], fmax=kw["fmax"]).astype(np.float64)
     lin = np.stack([nnls(fb, mel[:, t])[0] for t in range(mel.shape[1])], axis=1)      # power (or magnitude^power) spectrum
-    mag = np.power(np.maximum(lin, 0.0), 1.0 / power)
-    return griffinlim(mag, n_iter=n_iter, hop_length=hop_length, win_length=win_length, seed=seed, length=length).astype(np.float32)
+    mag = np.power(np.maximum(lin, 0.0), 1.0 / kw["power"])
+    return griffinlim(mag, n_iter=kw["n_iter"], hop_length=kw["hop_length"], win_length=kw["win_length"], seed=kw["seed"],
+                      length=kw["length"]).astype(np.float32)
 
 
 # ------------------------------------------------------------------------------------------ the way back, a batch on the GPU
@@ -413,19 +401,14 @@ def _batch_on_gpu(a, device, what: str):
     """``a`` (NumPy array or tensor) as a contiguous float64 CUDA tensor, by the container rules of ``audio_to_mel_batch``."""
     import torch
     from .. import _lib
-    if isinstance(a, torch.Tensor):
-        _lib.require_gpu(a, what)
-        return a.double().contiguous()
-    if not torch.cuda.is_available():
-        raise RuntimeError(f"{what} (MI355X build): no GPU visible; this package has no CPU fallback")
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError(f"{what}: device '{dev}' is not a CUDA device; this package has no CPU fallback")
-    return torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev)
+    if not isinstance(a, torch.Tensor):
+        a = np.asarray(a, dtype=np.float64)
+    return _lib.to_gpu(a, what, device=device)[0].double()
 
 
-def _check_stft_args(n_fft, hop_length, win_length):
-    """(n_fft, hop, win_length) as ints, refused with the messages of ``audio_to_mel_batch``."""
+def _check_stft_args(n_fft, hop_length, win_length, inverse: bool = False):
+    """(n_fft, hop, win_length) as ints, or the refusal every batch entry gives; ``inverse`` also refuses a hop that leaves
+    gaps between the windows."""
     if n_fft not in MEL_BATCH_N_FFT:
         raise ValueError(f"n_fft = {n_fft} is not supported on the GPU (supported: {', '.join(map(str, MEL_BATCH_N_FFT))})")
     n_fft = int(n_fft)
@@ -435,7 +418,7 @@ def _check_stft_args(n_fft, hop_length, win_length):
         raise ValueError(f"win_length = {wl} must lie in [1, n_fft = {n_fft}]")
     if hop < 1:
         raise ValueError(f"hop_length = {hop} must be at least 1")
-    if hop > wl:
+    if inverse and hop > wl:
         raise ValueError(f"hop_length = {hop} > win_length = {wl} leaves gaps in the window-square sum of the inverse STFT")
     return n_fft, hop, wl
 
@@ -456,7 +439,7 @@ def griffinlim_batch(mag, n_iter: int = 32, hop_length: Optional[int] = None, wi
     if mag.ndim != 3:
         raise ValueError("Magnitude input must be a 3D array (trials, bins, frames).")
     N, n_bins, T = (int(v) for v in mag.shape)
-    n_fft, hop, wl = _check_stft_args(2 * (n_bins - 1), hop_length, win_length)
+    n_fft, hop, wl = _check_stft_args(2 * (n_bins - 1), hop_length, win_length, inverse=True)
     if N < 1 or T < 1:
         raise ValueError("Magnitude input holds no trial or no frame.")
     if n_iter < 0:
@@ -472,10 +455,7 @@ def griffinlim_batch(mag, n_iter: int = 32, hop_length: Optional[int] = None, wi
         win, tw = _stft_batch_tables(str(dev), n_fft, wl)
         phases = np.exp(2j * np.pi * np.random.default_rng(seed).random((n_bins, T)))      # as griffinlim draws them
         phase0 = _upload(np.ascontiguousarray(phases.T).view(np.float64).reshape(T, n_bins, 2), dev)
-        w2 = np.zeros(n_fft)
-        off = (n_fft - wl) // 2
-        w2[off:off + wl] = _hann(wl)
-        w2 = w2 ** 2
+        w2 = _padded_window(n_fft, wl) ** 2
         wsum_host = np.zeros(n_fft + hop * (T - 1))
         for t in range(T):                                                                 # the additions of istft, in its order
             wsum_host[t * hop:t * hop + n_fft] += w2
@@ -546,15 +526,9 @@ def mel_to_audio_batch(mels, n_mels: int, audio_sampling_rate: int = 24414, mel_
         mels = np.asarray(mels)
     if mels.ndim != 2:
         raise ValueError("Mel input must be a 2D array (trials, n_mels * frames).")
-    n_fft = kwargs.pop("n_fft", 2048)
-    hop_length, win_length = kwargs.pop("hop_length", None), kwargs.pop("win_length", None)
-    power, n_iter = kwargs.pop("power", 2.0), kwargs.pop("n_iter", 32)
-    length, seed = kwargs.pop("length", None), kwargs.pop("seed", 0)
-    nnls_iter = kwargs.pop("nnls_iter", NNLS_ITER_DEFAULT)
-    fmin, fmax = kwargs.pop("fmin", 0.0), kwargs.pop("fmax", None)
-    if kwargs:
-        raise TypeError(f"unsupported keyword(s) {sorted(kwargs)}")
-    n_fft, hop, wl = _check_stft_args(n_fft, hop_length, win_length)
+    kw = _inverse_kwargs(kwargs, nnls_iter=NNLS_ITER_DEFAULT)
+    power, nnls_iter = kw["power"], kw["nnls_iter"]
+    n_fft, hop, wl = _check_stft_args(kw["n_fft"], kw["hop_length"], kw["win_length"], inverse=True)
     if power not in (1, 2):
         raise ValueError(f"power = {power} is not supported on the GPU (supported: 1, 2)")
     n_mels = int(n_mels)
@@ -574,8 +548,9 @@ def mel_to_audio_batch(mels, n_mels: int, audio_sampling_rate: int = 24414, mel_
     p = x.reshape(N, n_mels, T)
     if mel_in_db:
         p = 0.0001 * torch.pow(10.0, 0.1 * p)                                              # db_to_power(., ref=1e-4)
-    mag = mel_invert_batch(p, audio_sampling_rate, n_fft, n_mels, fmin=fmin, fmax=fmax, nnls_iter=nnls_iter, power=int(power))
-    wave = griffinlim_batch(mag, n_iter=n_iter, hop_length=hop, win_length=wl, seed=seed, length=length).float()
+    mag = mel_invert_batch(p, audio_sampling_rate, n_fft, n_mels, fmin=kw["fmin"], fmax=kw["fmax"], nnls_iter=nnls_iter,
+                           power=int(power))
+    wave = griffinlim_batch(mag, n_iter=kw["n_iter"], hop_length=hop, win_length=wl, seed=kw["seed"], length=kw["length"]).float()
     return wave if is_tensor else wave.cpu().numpy()
 
 
@@ -709,20 +684,7 @@ def yin_f0_batch(audio, sr: float, fmin: float, fmax: float, frame_length: int =
     if N < 1 or S < 1:
         raise ValueError("Audio input holds no clip or no sample.")
     n_frames = yin_n_frames(S, frame_length, hop, bool(center))
-    if is_tensor:
-        _lib.require_gpu(audio, "yin_f0_batch")
-        x = audio if audio.dtype in (torch.float32, torch.float64) else audio.double()
-        if x.stride(1) != 1 or (N > 1 and x.stride(0) < S):
-            x = x.contiguous()
-    else:
-        if not torch.cuda.is_available():
-            raise RuntimeError("yin_f0_batch (MI355X build): no GPU visible; this package has no CPU fallback")
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"yin_f0_batch: device '{dev}' is not a CUDA device; this package has no CPU fallback")
-        if audio.dtype not in (np.float32, np.float64):
-            audio = audio.astype(np.float64)
-        x = torch.from_numpy(np.array(audio, order="C")).to(dev)
+    x, _ = _lib.to_gpu(audio, "yin_f0_batch", device=device, rows="strided")
     dev = x.device
     f0 = torch.empty(N, n_frames, dtype=torch.float64, device=dev)
     aper, rms = torch.empty_like(f0), torch.empty_like(f0)

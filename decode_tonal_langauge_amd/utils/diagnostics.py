@@ -9,16 +9,18 @@ that no channel is dead or drifting, without downloading the recording.
 ``summarise``          both, at their defaults, as the dict the preprocess stage writes per step (``diagnostics_dir``).
 
 NumPy in (uploaded once) -> NumPy out; CUDA tensor in (read in place, a row-strided view included) -> CUDA tensors out on the
-input's device - the convention of ``preprocess/signal/_common.py``.  There is no CPU fallback."""
+input's device - the rule of ``_lib.to_gpu``.  There is no CPU fallback."""
 from __future__ import annotations
 
-import functools
 from typing import Optional, Tuple
 
 import numpy as np
 
-#: the transform sizes ``tl_welch_psd`` is instantiated for
-WELCH_N_FFT = (256, 512, 1024, 2048)
+from .audio import MEL_BATCH_N_FFT, _hann, _stft_twiddles
+
+#: the transform sizes ``tl_welch_psd`` is instantiated for: those of the mel front end
+WELCH_N_FFT = MEL_BATCH_N_FFT
+
 _SUPPORTED = ("supported: average='mean'; detrend='constant' or False; window 'hann', 'boxcar' or an array of nperseg "
               f"coefficients; scaling 'density' or 'spectrum'; even nfft in {WELCH_N_FFT}; one-sided output of real input")
 
@@ -48,7 +50,7 @@ def window_coefficients(window, nperseg: int) -> np.ndarray:
     analysis; ``'boxcar'``) or as an array of that length (``np.hanning(256)`` is matplotlib's)."""
     if isinstance(window, str):
         if window == "hann":
-            return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(nperseg) / nperseg)
+            return _hann(nperseg)
         if window == "boxcar":
             return np.ones(nperseg)
         raise ValueError(f"welch_psd: window '{window}' is not supported ({_SUPPORTED})")
@@ -58,38 +60,18 @@ def window_coefficients(window, nperseg: int) -> np.ndarray:
     return w
 
 
-@functools.lru_cache(maxsize=8)
-def _twiddles(device: str, n_fft: int):
-    import torch
-    ang = 2.0 * np.pi * np.arange(n_fft) / n_fft
-    return torch.from_numpy(np.stack([np.cos(ang), -np.sin(ang)], axis=1)).to(device)
-
-
 def _on_device(data, what: str):
     """(C, T) float32 / float64 CUDA tensor with unit column stride and row stride >= T (kept as it is when it already is
     one), and whether the input was NumPy."""
     import torch
     from .. import _lib
-    if isinstance(data, torch.Tensor):
-        if data.dim() != 2:
-            raise ValueError(f"{what}: expected data of shape (n_channels, n_timepoints)")
-        if data.is_complex():
-            raise ValueError(f"{what}: complex input is not supported ({_SUPPORTED})")
-        _lib.require_gpu(data, what)
-        x = data if data.dtype in (torch.float32, torch.float64) else data.double()
-        if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
-            x = x.contiguous()
-        return x, False
-    arr = np.asarray(data)
-    if arr.ndim != 2:
+    if not isinstance(data, torch.Tensor):
+        data = np.asarray(data)
+    if data.ndim != 2:
         raise ValueError(f"{what}: expected data of shape (n_channels, n_timepoints)")
-    if np.iscomplexobj(arr):
+    if np.iscomplexobj(data) if isinstance(data, np.ndarray) else data.is_complex():
         raise ValueError(f"{what}: complex input is not supported ({_SUPPORTED})")
-    if not torch.cuda.is_available():
-        raise RuntimeError(f"{what} (MI355X build): no GPU visible; this package has no CPU fallback")
-    if arr.dtype not in (np.float32, np.float64):
-        arr = arr.astype(np.float64)
-    return torch.from_numpy(np.array(arr, order="C")).to(torch.device("cuda", torch.cuda.current_device())), True
+    return _lib.to_gpu(data, what, rows="strided")
 
 
 def _row_stride(x) -> int:
@@ -156,7 +138,7 @@ def welch_psd(data, fs: float = 1.0, window="hann", nperseg: int = 256, noverlap
     win = np.zeros(nfft)
     win[:nperseg] = w
     win_d = torch.from_numpy(win).to(dev)
-    tw = _twiddles(str(dev), nfft)
+    tw = _stft_twiddles(str(dev), nfft)
     work = torch.empty(C, n_slabs, nb, dtype=torch.float64, device=dev)
     psd = torch.empty(C, nb, dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
